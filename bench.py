@@ -10,9 +10,14 @@ Random-init weights of the exact architectures (no network), synthetic data.
 N > 1: the LLM runs tensor-parallel over N ranks (RCCL all-reduce); tokenizer / Voicebox / vocoder are replicated
 (they do not shard within one utterance) -> strong scaling of ONE utterance; value = RTF of the whole job.
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
-  roofline     : the dominant kernel (decode GEMV, HBM-bound) measured live with HIP events
-  cpu_baseline : the CPU oracle timed on the host cores over a bounded sample, extrapolated (stated in "sample")
+Prints ONE JSON line on rank 0 (measurement contract: BASELINE.md).  A plain run sets up, warms up, times --steps steps and
+reports the headline figures of the timed steps only.  --full adds the measurements that take runs of their own:
+  stage_rooflines : MFMA-bound stages against their peaks (one extra vocoder pass)
+  roofline        : the dominant kernel (decode GEMV, HBM-bound) measured live with HIP events
+  llm_batched_decode, pipeline_throughput : informational batched runs (single-rank runs only)
+  cpu_baseline    : the CPU oracle timed on the host cores over a bounded sample, extrapolated (stated in "sample")
+--dump-outputs DIR writes what the last timed step computed (audio + token ids) as DIR/<name>.npy, so that two builds can be
+compared output for output: every input and weight is generated from fixed seeds.
 """
 import argparse
 import json
@@ -37,12 +42,18 @@ def parse():
     ap.add_argument("--units", type=int, default=500, help="generated unit tokens (50 Hz) in the TTS round")
     ap.add_argument("--text-tokens", type=int, default=32)
     ap.add_argument("--nt", type=int, default=64, help="Voicebox n_timesteps (Heun halves it)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batched", action="store_true", help="skip the informational batched-decode measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure stage rooflines, the decode-GEMV roofline, batched decode / pipeline throughput and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-batched", action="store_true", help="with --full: skip the informational batched-decode measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--vocoder-dtype", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--force-dist", action="store_true",
                     help="debug: run the multi-rank code path (process group, collectives, TP plan segments) on however many ranks there are")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Pipeline:
@@ -180,7 +191,18 @@ class Pipeline:
         self._mark("dec")
         self.prompt_lens = (p1.shape[1], p2.shape[1], p3.shape[1])
         self.n_generated = 2 * a.text_tokens + a.units
+        # what a caller of the path receives (references only: nothing is copied inside the timed step)
+        self.outputs = {"units": units, "llm_asr_tokens": o1[0, p1.shape[1]:], "llm_t2t_tokens": o2[0, p2.shape[1]:],
+                        "llm_tts_tokens": o3[0, p3.shape[1]:], "audio": audio}
         return audio
+
+    def dump_outputs(self, d):
+        """The last step's outputs as d/<name>.npy: audio in float32 (as returned), token ids in float64 (exact)."""
+        import numpy as np
+        os.makedirs(d, exist_ok=True)
+        for name, v in self.outputs.items():
+            v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+            np.save(os.path.join(d, name + ".npy"), v.astype(np.float32 if v.dtype == np.float32 else np.float64))
 
     def stage_ms(self):
         torch.cuda.synchronize()
@@ -577,6 +599,20 @@ def main():
         "stage_ms": {k: round(v, 2) for k, v in stages.items()},
         "model_build_s": round(pipe.build_s, 1),
     }
+    if args.dump_outputs and rank == 0:
+        pipe.dump_outputs(args.dump_outputs)
+    if args.full:
+        full_measurements(args, pipe, res, stages, dev, rank, world, dist_on)
+    if dist_on:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+
+
+def full_measurements(args, pipe, res, stages, dev, rank, world, dist_on):
+    """--full: everything beside the headline figures, each measured in runs of its own after the timed steps."""
     # secondary rooflines (informational): MFMA-bound stages, algorithmic FLOPs from SURVEY.md §8d
     mel = torch.randn(1, 80, pipe.frames, device=dev) * 2.1575 - 5.5419
     pipe.voc(mel)
@@ -613,12 +649,6 @@ def main():
             res["cpu_baseline"] = cpu_baseline(args, dev, pipe)
     elif dist_on:
         measure_gemv_roofline(pipe.llm)  # collectives inside the TP decode need every rank
-    if dist_on:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
