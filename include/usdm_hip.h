@@ -379,6 +379,14 @@ typedef struct usdm_sample_args {
 } usdm_sample_args;
 int usdm_sample_final(const usdm_sample_args* args, const usdm_decode_state* st, const void* embed_table_bf16, int32_t Hd,
                       void* h_out_bf16, usdm_stream_t stream);
+/* The same draw over a row of nseg SEGMENTS (tensor parallelism: the ranks' lm_head shards gathered rank-major): id i (0 <= i < V)
+ * of sequence b is read at logits + (i / seg_len) * seg_stride + b * logits_bs + i % seg_len.  nseg = 1, seg_len >= V is the
+ * contiguous row; the batched tensor-parallel step gathers [rank][sequence][Vloc] and passes nseg = tp, seg_len = logits_bs = Vloc,
+ * seg_stride = batch * Vloc.  Ids >= V are never read (the last rank's padding slots need no fill).  probs_out is contiguous
+ * [batch][V].  Histograms and masses are integer sums, so token, kept set and probs_out are bit-identical with usdm_sample_final
+ * on the same logical row.  Needs 2 <= seg_len <= 2^20 and nseg * seg_len >= V. */
+int usdm_sample_final_seg(const usdm_sample_args* args, int32_t nseg, int64_t seg_stride, int32_t seg_len, const usdm_decode_state* st,
+                          const void* embed_table_bf16, int32_t Hd, void* h_out_bf16, usdm_stream_t stream);
 
 /* out[r][:] = table[ids[r]][:] (bf16 rows; ids == NULL -> single row from *next_token) */
 int usdm_embed_rows(const void* table, const int64_t* ids, const int32_t* next_token, int32_t n, int32_t Hd,
@@ -426,8 +434,10 @@ int usdm_attn_decode(const usdm_attn_decode_args* args, usdm_stream_t stream);
  * the data is its own flag (one aligned 8-byte system-scope store is never torn), so no fence, no counter and no
  * separate flag store are needed; the reader polls its OWN memory.
  *
- *   buffer of one rank:  [256-B header: epoch u32, err u32][parity 2][site n_sites][src rank 8][max_elems] granules
- *   epoch   : device word, starts at 1, +1 per decode step (usdm_argmax_p2p), so a captured hipGraph replays correctly
+ *   buffer of one rank:  [256-B header: epoch u32, err u32, arrivals u32][parity 2][site n_sites][src rank 8][max_elems] granules
+ *   epoch   : device word, starts at 1, +1 per decode step (usdm_argmax_p2p, or usdm_logits_p2p when sampling), so a captured
+ *             hipGraph replays correctly
+ *   arrivals: local word of usdm_logits_p2p's last-arriving workgroup (zero between launches)
  *   parity  : epoch & 1 selects the half; together with the all-to-all of usdm_argmax_p2p once per token no slot is
  *             rewritten before every reader has left it
  *   waits   : every poll is BOUNDED (timeout_ms of the 100 MHz wall clock); on expiry the kernel ORs a code into the
@@ -440,7 +450,8 @@ int usdm_attn_decode(const usdm_attn_decode_args* args, usdm_stream_t stream);
  * ---------------------------------------------------------------------------------------------- */
 enum { USDM_P2P_MAX_RANKS = 8, USDM_P2P_HANDLE_BYTES = 64, USDM_P2P_HEADER_BYTES = 256 };
 enum { USDM_P2P_ERR_TIMEOUT_ROWS = 1, USDM_P2P_ERR_TIMEOUT_PICK = 2, USDM_P2P_ERR_TIMEOUT_REDUCE = 4,
-       USDM_P2P_ERR_PEER = 8 /* set by ANOTHER rank that timed out (with its code): results may have diverged there */ };
+       USDM_P2P_ERR_PEER = 8 /* set by ANOTHER rank that timed out (with its code): results may have diverged there */,
+       USDM_P2P_ERR_TIMEOUT_LOGITS = 16 };
 typedef struct usdm_p2p_dev {          /* device-visible view (device memory, constant after commit) */
   uint64_t base[8];                    /* address of rank r's buffer as mapped in THIS process; base[rank] = local */
   int32_t rank, world, n_sites, max_elems;
@@ -468,6 +479,19 @@ int usdm_allreduce_p2p_reduce(const usdm_p2p_dev* dev, int32_t site, int32_t n_e
 int usdm_argmax_p2p(const float* part_val, const int32_t* part_idx, int32_t nparts, const usdm_decode_state* st,
                     const usdm_p2p_dev* dev, int32_t site, int32_t phase, const void* embed_table_bf16, int32_t Hd,
                     void* h_out_bf16, usdm_stream_t stream);
+/* Logits exchange of the SAMPLED tensor-parallel step (the sampling twin of usdm_argmax_p2p): every rank puts its Vloc ban-masked f32
+ * logits as tagged granules into slot [parity][site0 + j][src = rank] of every rank's buffer (element e of the shard: site
+ * site0 + e / max_elems, granule e % max_elems; one shard spans ceil(Vloc / max_elems) consecutive sites), then waits (bounded) for
+ * every rank's granules and unpacks them into row_out[rank * Vloc + e]: the full [world * Vloc] row in global-id order (v0 = rank *
+ * Vloc), identical on every rank, on which the unchanged usdm_sample_final draws the same token everywhere (same seed, same step).
+ * Epoch += 1 per call, done by the get half's last-arriving workgroup (arrivals word), after every workgroup of the launch has read
+ * the epoch.  The parity argument above still holds: this is the step's one all-to-all, and a rank can only write parity p again
+ * two epochs later, i.e. after it received every peer's granules of the epoch in between, which each peer puts only after its own
+ * get of parity p has finished (stream order) - nothing is rewritten before every reader has left it.  st: only its done word is
+ * read (a finished sequence skips the exchange on every rank alike, epoch unchanged).  phase 0: put + get in one launch (ranks on
+ * different streams / GPUs); 1 / 2: the put half / the get half (split form).  Timeouts set USDM_P2P_ERR_TIMEOUT_LOGITS. */
+int usdm_logits_p2p(const float* logits, int32_t Vloc, const usdm_decode_state* st, const usdm_p2p_dev* dev, int32_t site0,
+                    int32_t phase, float* row_out, usdm_stream_t stream);
 
 /* h = bf16(h + bf16(delta)) : residual add after a tensor-parallel all-reduce of f32 partial sums */
 int usdm_residual_add(void* h_bf16, const float* delta, int32_t n, usdm_stream_t stream);

@@ -9,6 +9,8 @@ typedef unsigned long long p2p_gran;
 
 __device__ __forceinline__ unsigned* p2p_epoch_word(const usdm_p2p_dev* d) { return (unsigned*)d->base[d->rank]; }
 __device__ __forceinline__ unsigned* p2p_err_word(const usdm_p2p_dev* d) { return (unsigned*)d->base[d->rank] + 1; }
+// arrival counter of usdm_logits_p2p's multi-workgroup get half (local use only, zero between launches)
+__device__ __forceinline__ unsigned* p2p_arrive_word(const usdm_p2p_dev* d) { return (unsigned*)d->base[d->rank] + 2; }
 
 // granule n of slot[parity][site][src] inside the buffer of rank `owner`
 __device__ __forceinline__ p2p_gran* p2p_slot(const usdm_p2p_dev* d, int owner, unsigned epoch, int site, int src) {

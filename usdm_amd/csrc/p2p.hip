@@ -194,7 +194,69 @@ __global__ __launch_bounds__(256) void argmax_p2p_kernel(const float* pv, const 
     for (int i = tid; i < Hd / 8; i += 256) dst[i] = src[i];
   }
 }
+
+// logits exchange of the sampled step (see usdm_logits_p2p in the header).  Workgroup w owns shard elements
+// [w * LG_CHUNK, (w + 1) * LG_CHUNK): it puts them to every rank and, in the get half, collects the same elements of every rank, so
+// no workgroup of a launch waits for another workgroup of the same launch.
+constexpr int LG_NT = 256, LG_PER = 4, LG_CHUNK = LG_NT * LG_PER;
+__global__ __launch_bounds__(LG_NT) void logits_p2p_kernel(const float* logits, int Vloc, const int* done, const usdm_p2p_dev* d,
+                                                            int site0, int phase, float* row_out) {
+  if (done && *done) return;
+  const unsigned epoch = p2p_load_epoch(d);
+  const bool failed = p2p_load_err(d) != 0;
+  const int me = d->max_elems, world = d->world, rank = d->rank;
+  const int e0 = blockIdx.x * LG_CHUNK + threadIdx.x;
+  if (site0 + (Vloc - 1) / me >= d->n_sites) {   // the shard does not fit the communicator: flag it, touch no slot
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+      __hip_atomic_fetch_or(p2p_err_word(d), USDM_P2P_ERR_TIMEOUT_LOGITS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return;
+  }
+  if (phase != 2) {
+#pragma unroll
+    for (int k = 0; k < LG_PER; ++k) {
+      const int e = e0 + k * LG_NT;
+      if (e < Vloc) {
+        const float v = logits[e];
+        const int site = site0 + e / me, g = e % me;
+        for (int r = 0; r < world; ++r) p2p_put(p2p_slot(d, r, epoch, site, rank) + g, epoch, v);
+      }
+    }
+  }
+  if (phase == 1) return;
+  for (int r = 0; r < world; ++r) {
+#pragma unroll
+    for (int k = 0; k < LG_PER; ++k) {
+      const int e = e0 + k * LG_NT;
+      const bool want = e < Vloc;
+      const int ec = want ? e : 0;
+      const float v = p2p_get(d, p2p_slot(d, rank, epoch, site0 + ec / me, r) + ec % me, epoch, want, USDM_P2P_ERR_TIMEOUT_LOGITS,
+                              failed);
+      if (want) row_out[(int64_t)r * Vloc + e] = v;
+    }
+  }
+  // the last workgroup to arrive advances the epoch: every workgroup of this launch has read it by then
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const unsigned n = __hip_atomic_fetch_add(p2p_arrive_word(d), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (n == gridDim.x - 1) {
+      __hip_atomic_store(p2p_arrive_word(d), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(p2p_epoch_word(d), epoch + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
 }  // namespace
+
+extern "C" int usdm_logits_p2p(const float* logits, int32_t Vloc, const usdm_decode_state* st, const usdm_p2p_dev* dev, int32_t site0,
+                               int32_t phase, float* row_out, usdm_stream_t stream) {
+  USDM_CHECK_ARG(phase >= 0 && phase <= 2, "usdm_logits_p2p: phase 0 (put + get), 1 (put), 2 (get)");
+  USDM_CHECK_ARG(logits && Vloc > 0 && dev && site0 >= 0 && (phase == 1 || row_out), "usdm_logits_p2p: bad args");
+  USDM_CHECK_ARG(!st || st->batch <= 1, "usdm_logits_p2p: single sequence only");
+  hipLaunchKernelGGL(logits_p2p_kernel, dim3(cdiv(Vloc, LG_CHUNK)), dim3(LG_NT), 0, (hipStream_t)stream, logits, Vloc,
+                     st ? (const int*)st->done : nullptr, dev, site0, phase, row_out);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int usdm_allreduce_p2p_reduce(const usdm_p2p_dev* dev, int32_t site, int32_t n_elems, void* h, const int32_t* skip,
                                          usdm_stream_t stream) {

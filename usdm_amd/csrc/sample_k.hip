@@ -48,8 +48,14 @@ __device__ float block_max(float v, float* sred) {
   return m;
 }
 
+// SEG = false: the row of sequence b is contiguous (usdm_sample_final).  SEG = true: it is made of rank-major segments of seg_len
+// ids, seg_stride elements apart (usdm_sample_final_seg); id i sits at (i / seg_len) * seg_stride + i % seg_len, the quotient by a
+// multiply-high with seg_magic = ceil(2^32 / seg_len) and one correction (exact for i, seg_len < 2^20).  Every sum below is an
+// integer sum and every per-id quantity depends on the id's value only, so both forms give bit-identical results on the same row.
+template <bool SEG>
 __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, usdm_decode_state st, const bf16_t* E, int Hd,
-                                                           bf16_t* h_out) {
+                                                           bf16_t* h_out, int64_t seg_stride, int seg_len, unsigned seg_magic,
+                                                           int64_t probs_bs) {
   __shared__ unsigned long long hist[256];
   __shared__ unsigned long long sscan[NT];
   __shared__ float sred[NT / 64];
@@ -61,7 +67,7 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
   // Philox counter (its own step): a sequence sampled inside a continuous batch gets the tokens it would get alone
   const int b = blockIdx.x;
   a.logits += (int64_t)b * a.logits_bs;
-  if (a.probs_out) a.probs_out += (int64_t)b * a.logits_bs;
+  if (a.probs_out) a.probs_out += (int64_t)b * probs_bs;
   st.next_token += b; st.step += b; st.pos += b; st.out_tokens += (int64_t)b * st.max_out;
   if (st.done) st.done += b;
   h_out += (int64_t)b * Hd;
@@ -74,7 +80,32 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     if (a.top_k < 0) a.top_k = 0;
   }
   const float invT = 1.0f / a.temperature;   // HF divides; x / T and x * (1 / T) differ by <= 1 ulp, below the logits' bf16 grain
-  auto X = [&](int i) { return a.logits[i] * invT; };
+  auto LG = [&](int i) -> float {   // logit of id i (0 <= i < V)
+    if constexpr (SEG) {
+      unsigned q = __umulhi((unsigned)i, seg_magic);
+      if (q * (unsigned)seg_len > (unsigned)i) --q;
+      return a.logits[(int64_t)q * seg_stride + (i - (int)q * seg_len)];
+    } else {
+      return a.logits[i];
+    }
+  };
+  // f(i, logit of i) for i = tid, tid + NT, ... < V.  The segmented form divides once and then walks a pointer, stepping over the
+  // gap between two segments when it crosses one (seg_len >= NT: at most one step per iteration)
+  auto each = [&](auto&& f) {
+    if constexpr (SEG) {
+      unsigned q = __umulhi((unsigned)tid, seg_magic);
+      if (q * (unsigned)seg_len > (unsigned)tid) --q;
+      int r = tid - (int)q * seg_len;
+      const float* ptr = a.logits + (int64_t)q * seg_stride + r;
+      for (int i = tid; i < V; i += NT) {
+        f(i, *ptr);
+        ptr += NT; r += NT;
+        while (r >= seg_len) { r -= seg_len; ptr += seg_stride - seg_len; }
+      }
+    } else {
+      for (int i = tid; i < V; i += NT) f(i, a.logits[i]);
+    }
+  };
 
   // ---- top-k: key of the k-th largest scaled logit (all keys >= it are kept, ties included: `scores < kth` is removed)
   unsigned kth = 0;   // keep everything
@@ -84,10 +115,10 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     for (int shift = 24; shift >= 0; shift -= 8) {
       if (tid < 256) hist[tid] = 0;
       __syncthreads();
-      for (int i = tid; i < V; i += NT) {
-        const unsigned k = fkey(X(i));
+      each([&](int, float lg) {
+        const unsigned k = fkey(lg * invT);
         if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255], 1ull);
-      }
+      });
       __syncthreads();
       if (tid == 0) {
         unsigned long long r = rem;
@@ -107,22 +138,23 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
   }
   // ---- softmax numerators over the top-k survivors
   float m = -INFINITY;
-  for (int i = tid; i < V; i += NT) {
-    const float x = X(i);
+  each([&](int, float lg) {
+    const float x = lg * invT;
     if (fkey(x) >= kth) m = fmaxf(m, x);
-  }
+  });
   m = block_max(m, sred);
-  auto Ei = [&](int i) -> float {   // exp(x - max) of a top-k survivor, 0 otherwise (banned = -inf -> 0)
-    const float x = X(i);
+  auto El = [&](float lg) -> float {   // exp(x - max) of a top-k survivor, 0 otherwise (banned = -inf -> 0)
+    const float x = lg * invT;
     return (fkey(x) >= kth) ? __expf(x - m) : 0.f;
   };
+  auto Ei = [&](int i) -> float { return El(LG(i)); };
   auto Q = [&](float e) -> unsigned long long { return (unsigned long long)((double)e * 4294967296.0); };   // 2^32 fixed point
   // total mass (fixed point, integer sum: order-independent)
   if (tid == 0) s_rem = 0;
   __syncthreads();
   {
     unsigned long long z = 0;
-    for (int i = tid; i < V; i += NT) z += Q(Ei(i));
+    each([&](int, float lg) { z += Q(El(lg)); });
     atomicAdd(&s_rem, z);
   }
   __syncthreads();
@@ -136,13 +168,13 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     for (int shift = 24; shift >= 0; shift -= 8) {
       if (tid < 256) hist[tid] = 0;
       __syncthreads();
-      for (int i = tid; i < V; i += NT) {
-        const float e = Ei(i);
+      each([&](int, float lg) {
+        const float e = El(lg);
         if (e > 0.f) {
           const unsigned k = __float_as_uint(e);
           if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255], Q(e));
         }
-      }
+      });
       __syncthreads();
       if (tid == 0) {
         unsigned long long r = R;
@@ -204,10 +236,9 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     __shared__ int fbi[NT / 64];
     float bv = -INFINITY;
     int bi = 0x7fffffff;
-    for (int i = tid; i < V; i += NT) {
-      const float x = a.logits[i];
+    each([&](int i, float x) {
       if (x > bv) { bv = x; bi = i; }     // NaN and -inf never pass
-    }
+    });
     for (int off = 32; off > 0; off >>= 1) {
       const float ov = __shfl_xor(bv, off, 64);
       const int oi = __shfl_xor(bi, off, 64);
@@ -224,10 +255,10 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
   }
   if (a.probs_out) {
     const double inv = Zk > 0 ? 1.0 / (double)Zk : 0.0;
-    for (int i = tid; i < V; i += NT) {
-      const float e = Ei(i);
+    each([&](int i, float lg) {
+      const float e = El(lg);
       a.probs_out[i] = (e > 0.f && __float_as_uint(e) >= pkey) ? (float)((double)Q(e) * inv) : 0.f;
-    }
+    });
   }
   if (tid == 0) {
     const int tok = s_tok + st.id_offset;
@@ -250,17 +281,41 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
 }
 }  // namespace
 
+namespace {
+int check_sample(const usdm_sample_args* pa, const usdm_decode_state* st, const void* embed_table, int32_t Hd, void* h_out,
+                 const char* who) {
+  USDM_CHECK_ARG(pa && pa->logits && pa->V > 0 && pa->V <= (1 << 20), "%s: logits / V", who);
+  USDM_CHECK_ARG(pa->dev_params || (pa->temperature > 0.f && pa->top_p > 0.f && pa->top_p <= 1.0f && pa->top_k >= 0),
+                 "%s: temperature > 0, 0 < top_p <= 1, top_k >= 0 (0 = off)", who);
+  USDM_CHECK_ARG(st && st->next_token && st->out_tokens && st->step && st->pos, "%s: decode state", who);
+  USDM_CHECK_ARG(!embed_table || (h_out && Hd > 0 && Hd % 8 == 0), "%s: embedding output missing", who);
+  return 0;
+}
+}  // namespace
+
 extern "C" int usdm_sample_final(const usdm_sample_args* pa, const usdm_decode_state* st, const void* embed_table, int32_t Hd,
                                  void* h_out, usdm_stream_t stream) {
-  USDM_CHECK_ARG(pa && pa->logits && pa->V > 0 && pa->V <= (1 << 20), "usdm_sample_final: logits / V");
-  USDM_CHECK_ARG(pa->dev_params || (pa->temperature > 0.f && pa->top_p > 0.f && pa->top_p <= 1.0f && pa->top_k >= 0),
-                 "usdm_sample_final: temperature > 0, 0 < top_p <= 1, top_k >= 0 (0 = off)");
-  USDM_CHECK_ARG(st && st->next_token && st->out_tokens && st->step && st->pos, "usdm_sample_final: decode state");
-  USDM_CHECK_ARG(!embed_table || (h_out && Hd > 0 && Hd % 8 == 0), "usdm_sample_final: embedding output missing");
+  if (int rc = check_sample(pa, st, embed_table, Hd, h_out, "usdm_sample_final")) return rc;
   const int nb = st->batch > 1 ? st->batch : 1;
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= pa->V && pa->dev_params), "usdm_sample_final: the batched form needs logits_bs >= V and dev_params[batch]");
-  hipLaunchKernelGGL(sample_final_kernel, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (const bf16_t*)embed_table, Hd,
-                     (bf16_t*)h_out);
+  hipLaunchKernelGGL(sample_final_kernel<false>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (const bf16_t*)embed_table, Hd,
+                     (bf16_t*)h_out, (int64_t)0, 0, 0u, pa->logits_bs);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int usdm_sample_final_seg(const usdm_sample_args* pa, int32_t nseg, int64_t seg_stride, int32_t seg_len,
+                                     const usdm_decode_state* st, const void* embed_table, int32_t Hd, void* h_out,
+                                     usdm_stream_t stream) {
+  if (int rc = check_sample(pa, st, embed_table, Hd, h_out, "usdm_sample_final_seg")) return rc;
+  const int nb = st->batch > 1 ? st->batch : 1;
+  USDM_CHECK_ARG(nseg >= 1 && seg_len >= 2 && seg_len <= (1 << 20) && (int64_t)nseg * seg_len >= pa->V,
+                 "usdm_sample_final_seg: nseg segments of seg_len ids must cover V");
+  USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= seg_len && pa->dev_params), "usdm_sample_final_seg: the batched form needs logits_bs >= seg_len and dev_params[batch]");
+  USDM_CHECK_ARG(nseg == 1 || seg_stride >= pa->logits_bs * (nb - 1) + seg_len, "usdm_sample_final_seg: segments overlap");
+  const unsigned magic = (unsigned)((((uint64_t)1 << 32) + (uint64_t)seg_len - 1) / (uint64_t)seg_len);
+  hipLaunchKernelGGL(sample_final_kernel<true>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (const bf16_t*)embed_table, Hd,
+                     (bf16_t*)h_out, seg_stride, (int)seg_len, magic, (int64_t)pa->V);
   USDM_LAUNCH_CHECK();
   return 0;
 }

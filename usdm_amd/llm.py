@@ -12,7 +12,8 @@ Host side: Python plans of C-ABI launches (libusdm_hip.so).
             partial sums is fused into those GEMVs' epilogues as a one-shot peer-to-peer exchange over xGMI
             (usdm_amd.p2p.P2PComm; the decode step stays ONE hipGraph with no collective launch), the vocab-parallel token
             pick likewise (usdm_argmax_p2p).  Prefill (4 MB messages) and the validation path use RCCL through
-            torch.distributed ('nccl'): f32 partial sums all-reduced, arg-max partials all-gathered.
+            torch.distributed ('nccl'): f32 partial sums all-reduced, arg-max partials all-gathered.  Sampling gathers the
+            full logits row on every rank (usdm_logits_p2p in the P2P step) and draws from it with rank 0's seed.
 Weights: HF state-dict key names (model.layers.N.self_attn.q_proj.weight, ...), bf16.
 """
 import math
@@ -48,6 +49,26 @@ def vocab_shard(V, rank, tp):
 
 
 NO_CANDIDATE_IDX = 0x7fffffff
+
+
+def agree_seed(seed, group, rank, device=None):
+    """Rank 0's value of `seed`, on every rank of a tensor-parallel group: one 8-byte all-gather that every rank must reach.
+    Ranks draw a seed from their own torch generator when the caller gives none; sampled tokens, and with them the device-side
+    EOS and the number of steps (hence the collectives), only agree across ranks if the Philox streams do.  Transport as the
+    model's other gathers: InProcessGroup (threaded: a lockstep group completes a gather only at its last rank), host-staged
+    on gloo, RCCL otherwise."""
+    import torch.distributed as dist
+    if hasattr(group, "usdm_all_gather"):
+        src = torch.tensor([int(seed)], dtype=torch.int64, device=device)
+        dst = torch.zeros(group.world, dtype=torch.int64, device=device)
+        group.usdm_all_gather(rank, [dst], [src])
+    elif dist.get_backend(group) == "gloo":
+        dst = torch.zeros(dist.get_world_size(group), dtype=torch.int64)
+        dist.all_gather_into_tensor(dst, torch.tensor([int(seed)], dtype=torch.int64), group=group)
+    else:
+        dst = torch.zeros(dist.get_world_size(group), dtype=torch.int64, device=device)
+        dist.all_gather_into_tensor(dst, torch.tensor([int(seed)], dtype=torch.int64, device=device), group=group)
+    return int(dst[0].item())
 
 
 def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16):
@@ -287,6 +308,12 @@ class USDMForCausalLM:
         self.part_val, self.part_idx = nv(self.nparts * self.tp_size), ni(self.nparts * self.tp_size)
         self.part_val_loc = nv(self.nparts) if self.tp_path else self.part_val
         self.part_idx_loc = ni(self.nparts) if self.tp_path else self.part_idx
+        # sampling under tensor parallelism: this rank's Vloc logits (the last rank's padding slots are never read) and the
+        # gathered [tp * Vloc] row in global-id order (v0 = rank * Vloc) that every rank samples with the same seed and step
+        if self.tp_path:
+            self.logits_loc = torch.zeros(self.Vloc, dtype=torch.float32, device=dev)
+            self.logits_row = torch.zeros(self.tp_size * self.Vloc, dtype=torch.float32, device=dev)
+            self._shard_logits = None
 
     # ------------------------------------------------------------------ collectives (TP only)
     def _host_staged(self):
@@ -323,6 +350,53 @@ class USDMForCausalLM:
         for dst, src in zip(dsts, srcs):
             dist.all_gather_into_tensor(dst, src, group=self.group)
 
+    def _agree_seed(self, seed):
+        """A seed drawn on this rank -> rank 0's (tensor-parallel path); unchanged on one GPU."""
+        return agree_seed(seed, self.group, self.tp_rank, self.device) if self.tp_path else seed
+
+    def _check_p2p_sampling(self):
+        from .p2p import P2PComm
+        need = P2PComm.sites_needed(self.cfg, self.tp_size, True, max_elems=self.p2p.max_elems)
+        if self.p2p.n_sites < need:
+            raise ValueError(f"sampling on a peer-to-peer model needs a P2PComm of {need} sites (2 * layers + 1 + ceil(Vloc / "
+                             f"max_elems) for the logits exchange); this one has {self.p2p.n_sites}")
+
+    def _tp_sample_and_pick(self, plan, x, advance_pos, segs, sampling, x_delta, sl, skip):
+        """Sampled token choice under tensor parallelism: every rank's Vloc ban-masked logits gathered into the full row (in the
+        kernels on a peer-to-peer model, else through the group), then the unchanged sampler over it on every rank with the same
+        seed and step: every rank draws the same token."""
+        c = self.cfg
+        single = sl is self
+        if sampling == "hook":
+            raise NotImplementedError("logits processors under tensor parallelism are not supported")
+        if self.p2p is not None and single:
+            self._check_p2p_sampling()
+        logits = self.logits_loc if single else sl.logits
+        ops.gemv(self.W["lm_head"], x, N=self.v1 - self.v0, K=c["hidden_size"], norm_w=self.W["norm"], eps=c["rms_norm_eps"],
+                 y32=logits, ban=self.ban, part_val=sl.part_val_loc, part_idx=sl.part_idx_loc, idx_offset=self.v0,
+                 x_delta=x_delta, skip=skip, plan=plan)
+        st = ops.decode_state(sl.st_next, sl.st_out, sl.st_step, sl.st_pos, advance_pos=advance_pos,
+                              done=self.st_done if single else None, eos=self.st_eos if single else None)
+        row = self.logits_row if single else sl.logits_row
+        if self.p2p is not None and single:
+            site0 = 2 * c["num_hidden_layers"] + 1
+            if self.p2p_fused:
+                ops.logits_p2p(logits, self.Vloc, st, self.p2p, site0, row, phase=0, plan=plan)
+            else:       # split form: put | get as two launches with a segment boundary between them
+                ops.logits_p2p(logits, self.Vloc, st, self.p2p, site0, row, phase=1, plan=plan)
+                plan.hold(st)
+                segs.append(plan)
+                plan = ops.Plan()
+                ops.logits_p2p(logits, self.Vloc, st, self.p2p, site0, row, phase=2, plan=plan)
+        else:
+            segs.append(plan)
+            segs.append(lambda: self._gather_partials([row], [logits]))
+            plan = ops.Plan()
+        ops.sample_final(row, st, V=c["vocab_size"], dev_params=self.sample_params if single else sl.sample_params,
+                         embed=self.W["embed"], h_out=sl.h_dec, Hd=c["hidden_size"], plan=plan)
+        plan.hold(st)
+        segs.append(plan)
+
     def _lm_head_and_pick(self, plan, x, advance_pos, segs, sampling=None, x_delta=None, slot=None, skip=None):
         """lm_head GEMV + token choice.  sampling=None: ban-masked arg-max (the reference's top_k=1 path);
         sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block self.sample_params
@@ -330,6 +404,8 @@ class USDMForCausalLM:
         c = self.cfg
         sl = slot or self   # where the picked token, the decode state and the next input row live (self = the single sequence)
         single = sl is self
+        if sampling and self.tp_path:
+            return self._tp_sample_and_pick(plan, x, advance_pos, segs, sampling, x_delta, sl, skip)
         want_logits = self.keep_logits or bool(sampling)
         if want_logits and self.last_logits is None:
             self.last_logits = torch.zeros(self.v1 - self.v0, dtype=torch.float32, device=self.device)
@@ -341,8 +417,6 @@ class USDMForCausalLM:
         st = ops.decode_state(sl.st_next, sl.st_out, sl.st_step, sl.st_pos, advance_pos=advance_pos,
                               done=self.st_done if single else None, eos=self.st_eos if single else None)
         if sampling:
-            if self.tp_path:
-                raise NotImplementedError("sampling needs the full logit row on one GPU (tensor-parallel decode is greedy only)")
             if sampling == "hook":      # Python logits processors (usdm_amd.serving): a host call between the two kernels
                 segs.append(plan)
                 segs.append(lambda: self.logits_hook())
@@ -431,7 +505,7 @@ class USDMForCausalLM:
         segs[0].hold(*[t for s in segs if isinstance(s, ops.Plan) for t in s.keep])
         return segs, io
 
-    def _build_decode_p2p(self):
+    def _build_decode_p2p(self, sampling=None):
         """Tensor-parallel decode step with the all-reduces done peer to peer: the launch sequence of the single-GPU step
         over this rank's shards; o_proj / down_proj carry the exchange in their epilogues (fused) or are followed by
         usdm_allreduce_p2p_reduce (split).  Returned as segments cut at every exchange so that a single-process harness can
@@ -464,15 +538,13 @@ class USDMForCausalLM:
             plan = row_parallel(plan, w["o"], ao, Hq * d, 2 * l, merge=mrg)
             ops.gemv(w["gu"], h, N=2 * I, K=H, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU, y16=act, skip=skp, plan=plan)
             plan = row_parallel(plan, w["down"], act, I, 2 * l + 1)
-        self._lm_head_and_pick(plan, h, True, segs, None, skip=skp)
+        self._lm_head_and_pick(plan, h, True, segs, sampling, skip=skp)
         segs[0].hold(*[t for s_ in segs for t in s_.keep])
         return segs
 
     def _build_decode(self, sampling=None):
         if self.p2p is not None:
-            if sampling:
-                raise NotImplementedError("sampling needs the full logit row on one GPU (tensor-parallel decode is greedy only)")
-            return self._build_decode_p2p()
+            return self._build_decode_p2p(sampling)
         c, dev, bf = self.cfg, self.device, torch.bfloat16
         H, d, L = c["hidden_size"], c["head_dim"], c["num_hidden_layers"]
         Hq, Hkv, I, tp = self.Hq, self.Hkv, self.I, (2 if self.tp_path else 1)
@@ -591,7 +663,7 @@ class USDMForCausalLM:
                   vc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=bf, device=dev),
                   nxt=i32(B), step=i32(B), pos=i32(B), out=i32(B, self.max_out), h=torch.zeros(B, H, dtype=bf, device=dev),
                   pv=torch.zeros(B, self.nparts, dtype=torch.float32, device=dev), pi=i32(B, self.nparts), prefill=LRU(16), decode=None,
-                  decode_sampled=None, logits=torch.zeros(B, self.v1 - self.v0, dtype=torch.float32, device=dev),
+                  decode_sampled=None, logits=torch.zeros(B, self.Vloc, dtype=torch.float32, device=dev),
                   sp=ops.sample_params_tensor(dev, B).view(B, -1))
         if self.tp_path:
             # tensor parallel: pv / pi hold THIS rank's partials; the decode step gathers them rank-major into pvg / pig
@@ -599,6 +671,10 @@ class USDMForCausalLM:
             tp = self.tp_size
             bb.update(pvg=torch.zeros(tp, B, self.nparts, dtype=torch.float32, device=dev), pig=i32(tp, B, self.nparts),
                       pvs=torch.zeros(B, tp * self.nparts, dtype=torch.float32, device=dev), pis=i32(B, tp * self.nparts))
+            # sampled: the ranks' [B][Vloc] logits gathered rank-major into lg [rank][sequence][Vloc] (usdm_sample_final_seg); a
+            # slot's sampled prefill gathers its row into lrow [tp * Vloc] (prefills run one at a time)
+            bb.update(lg=torch.zeros(tp, B, self.Vloc, dtype=torch.float32, device=dev),
+                      lrow=torch.zeros(tp * self.Vloc, dtype=torch.float32, device=dev))
         slots = []
         for b in range(B):
             sl = self._Slot()
@@ -610,6 +686,7 @@ class USDMForCausalLM:
             if self.tp_path:
                 sl.part_val, sl.part_idx = bb["pvs"][b], bb["pis"][b]
             sl.logits, sl.sample_params = bb["logits"][b], bb["sp"][b]
+            sl.logits_row = bb.get("lrow")
             slots.append(sl)
         bb["slots"] = slots
         self._batches[B] = bb
@@ -644,10 +721,9 @@ class USDMForCausalLM:
         # Tensor parallel (SURVEY.md 8e x 8f-2; round 4, the collective form): the row-parallel projections leave f32 partial sums
         # [B][H], all-reduced through the job's process group (RCCL: one collective of B x 16 KB per projection instead of B of them),
         # then usdm_residual_add applies HF's rounding points; the plan is cut into segments at the collectives, as the
-        # single-sequence RCCL path is.  Greedy only (the sampling kernel needs the full logit row on one GPU).
+        # single-sequence RCCL path is.  Sampled: the slots' logits rows are gathered and drawn from on every rank
+        # (usdm_sample_final_seg).
         tp = self.tp_path
-        if tp and sampling:
-            raise NotImplementedError("sampling needs the full logit row on one GPU (tensor-parallel decode is greedy only)")
         segs = []
         part, part2 = (Z(B, H, dt=torch.float32), Z(B, H, dt=torch.float32)) if tp else (None, None)
 
@@ -675,9 +751,14 @@ class USDMForCausalLM:
                 ops.gemv_batch(w["down"], act, nb=B, N=H, K=I, x_bs=I, y_bs=H, res_bs=H, residual=h, y16=h, ks=ks, plan=plan)
         ops.gemv_batch(self.W["lm_head"], h, nb=B, N=self.v1 - self.v0, K=H, x_bs=H, part_bs=self.nparts, norm_w=self.W["norm"],
                        eps=c["rms_norm_eps"], ban=self.ban, part_val=bb["pv"], part_idx=bb["pi"], idx_offset=self.v0,
-                       **(dict(y32=bb["logits"], y_bs=self.v1 - self.v0) if sampling else {}), plan=plan)
+                       **(dict(y32=bb["logits"], y_bs=self.Vloc) if sampling else {}), plan=plan)
         st = ops.decode_state(bb["nxt"], bb["out"], bb["step"], bb["pos"], advance_pos=True, batch=B)
-        if sampling:
+        if sampling and tp:   # [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
+            segs.extend([plan, (lambda: self._gather_partials([bb["lg"]], [bb["logits"]]))])
+            plan = ops.Plan()
+            ops.sample_final(bb["lg"], st, dev_params=bb["sp"], V=c["vocab_size"], nseg=self.tp_size, seg_stride=B * self.Vloc,
+                             seg_len=self.Vloc, embed=self.W["embed"], h_out=h, Hd=H, plan=plan)
+        elif sampling:
             ops.sample_final(bb["logits"], st, dev_params=bb["sp"], embed=self.W["embed"], h_out=h, Hd=H, plan=plan)
         elif tp:      # vocab-parallel pick: the ranks' [B][nparts] partials gathered rank-major, one pick per sequence over all of them
             segs.extend([plan, (lambda: self._gather_partials([bb["pvg"], bb["pig"]], [bb["pv"], bb["pi"]]))])
@@ -779,6 +860,11 @@ class USDMForCausalLM:
         """Per-call device state of generate(): prompt ids into the (cached) prefill plan, ban mask, position / step counters,
         device-side EOS list.  Returns (prefill segments, the EOS ids the device checks)."""
         L0 = input_ids.shape[1]
+        if self.tp_path:      # keep_logits: a sampled call exposes the gathered row, a greedy one this rank's shard
+            if sampling and self.last_logits is not self.logits_row:
+                self._shard_logits, self.last_logits = self.last_logits, self.logits_row
+            elif not sampling and self.last_logits is self.logits_row:
+                self.last_logits = self._shard_logits
         key = (L0 - past, past, sampling)
         segs, io = self._prefill_plans.get_or_build(key, lambda: self._build_prefill(L0 - past, sampling, past=past))
         io["ids"].copy_(input_ids[0, past:])
@@ -808,7 +894,7 @@ class USDMForCausalLM:
         sampling = False
         if _logits_hook is not None:      # arbitrary Python logits processors: eager steps, knobs still on the device
             if seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                seed = self._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
             sampling, self.logits_hook = "hook", _logits_hook
             ops.set_sample_params(self.sample_params, temperature if do_sample else 1.0, int(top_k or 0) if do_sample else 1,
                                   top_p if do_sample else 1.0, seed)
@@ -816,7 +902,7 @@ class USDMForCausalLM:
             if not (temperature > 0) or not (0 < top_p <= 1):
                 raise ValueError("temperature must be > 0 and top_p in (0, 1]")
             if seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                seed = self._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
             sampling = True
             ops.set_sample_params(self.sample_params, temperature, int(top_k or 0), top_p, seed)
         elif temperature != 1.0 or top_p != 1.0:

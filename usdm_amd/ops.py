@@ -344,16 +344,41 @@ def set_sample_params(t, temperature, top_k, top_p, seed):
 
 
 def sample_final(logits, st, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, probs_out=None, embed=None, h_out=None, Hd=0,
-                 dev_params=None, plan=None):
+                 dev_params=None, V=None, nseg=1, seg_stride=0, seg_len=0, plan=None):
     """usdm_sample_final: temperature / top-k / top-p sampling of one token from ban-masked f32 logits.
     dev_params (sample_params_tensor): the knobs are read from device memory instead (graph-replayable per request).
-    Batched state (decode_state(batch=B)): logits [B][V], dev_params [B][24], h_out [B][Hd]; one workgroup per sequence."""
+    Batched state (decode_state(batch=B)): logits [B][V], dev_params [B][24], h_out [B][Hd]; one workgroup per sequence.
+    V: ids drawn from (default logits.shape[-1]; a gathered tensor-parallel row is longer than the vocabulary by the last rank's
+    padding slots).  seg_len > 0 (usdm_sample_final_seg): logits is [nseg][B][seg_len], the ranks' shards gathered rank-major;
+    sequence b's id i is read at (i // seg_len) * seg_stride + b * seg_len + i % seg_len; probs_out is [B][V]."""
     _need_cuda(logits, probs_out, embed, h_out, dev_params)
     a = SampleArgs()
-    a.logits, a.V, a.temperature, a.top_k, a.top_p = _ptr(logits), logits.shape[-1], temperature, top_k, top_p
-    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
+    a.logits, a.V, a.temperature, a.top_k, a.top_p = _ptr(logits), logits.shape[-1] if V is None else V, temperature, top_k, top_p
     a.seed, a.probs_out, a.dev_params = seed, _ptr(probs_out), _ptr(dev_params)
+    if probs_out is not None and probs_out.numel() < max(1, st.batch) * a.V:
+        raise ValueError("sample_final: probs_out holds fewer than batch * V values")
+    if seg_len > 0:
+        if nseg < 1 or not logits.is_contiguous() or logits.shape[-1] != seg_len or logits.numel() < (nseg - 1) * seg_stride + max(1, st.batch) * seg_len:
+            raise ValueError("segmented sample_final: logits must be a contiguous [nseg][B][seg_len] tensor")
+        a.logits_bs = seg_len
+        _go(plan, "usdm_sample_final_seg", lib.usdm_sample_final_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride),
+            C_.c_int32(seg_len), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
+        return
+    if logits.dim() > 2 or a.V > logits.shape[-1]:
+        raise ValueError("sample_final: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
+    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
     _go(plan, "usdm_sample_final", lib.usdm_sample_final, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
+
+
+def logits_p2p(logits, Vloc, st, p2p, site0, row_out, phase=0, plan=None):
+    """usdm_logits_p2p: this rank's Vloc f32 logits to every rank, every rank's into row_out [world * Vloc] (global-id order),
+    epoch + 1.  The shard spans ceil(Vloc / max_elems) sites from site0.  phase 0: put + get; 1: put; 2: get."""
+    _need_cuda(logits, row_out)
+    if logits.numel() < Vloc or (phase != 1 and row_out.numel() < p2p.world * Vloc):
+        raise ValueError("logits_p2p: logits holds fewer than Vloc values or row_out fewer than world * Vloc")
+    p2p.check_site(site0 + (Vloc - 1) // p2p.max_elems, 1)
+    _go(plan, "usdm_logits_p2p", lib.usdm_logits_p2p, _ptr(logits), C_.c_int32(Vloc), C_.byref(st) if st is not None else None,
+        C_.c_void_p(p2p.dev_ptr), C_.c_int32(site0), C_.c_int32(phase), _ptr(row_out))
 
 
 def embed_rows(table, out, *, Hd, ids=None, next_token=None, n=1, plan=None):

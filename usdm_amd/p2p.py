@@ -108,6 +108,17 @@ class P2PComm:
             a.commit()
         return comms
 
+    @staticmethod
+    def sites_needed(cfg, tp, sampling, max_elems=None):
+        """Sites a decode step of the model `cfg` sharded `tp` ways uses: 2 per layer (o_proj, down_proj all-reduces) + 1 (the
+        greedy token pick); sampling adds the logits exchange (usdm_logits_p2p): this rank's Vloc = ceil(V / tp) logits over
+        ceil(Vloc / max_elems) consecutive sites.  max_elems defaults to hidden_size (what the decode step needs per site)."""
+        n = 2 * cfg["num_hidden_layers"] + 1
+        if sampling:
+            me = cfg["hidden_size"] if max_elems is None else max_elems
+            n += -(-(-(-cfg["vocab_size"] // tp)) // me)
+        return n
+
     # ---- use
     def check_site(self, site, n):
         if self.dev_ptr is None:

@@ -15,6 +15,9 @@ How requests are executed
     returns exactly the tokens it returns alone; a greedy request in a sampled batch carries top_k = 1;
   * a single request uses the single-sequence graph (usdm_sample_final: temperature / top-k / top-p on the device, `seed` per
     request);
+  * under tensor parallelism both forms sample as well: every rank gathers the full ban-masked logits row (the ranks' lm_head
+    shards) and draws from it with the same seed and step, so every rank picks the same token; a seed left to the server is
+    rank 0's draw on every rank.  Processors that depend on the history are not supported there (they would see one shard);
   * processors that really depend on the token history run as Python between the lm_head launch and the pick of every step
     (eager launches: correct, not fast).
 """
@@ -166,7 +169,8 @@ class LLM:
             room = self.llm.ctx_max - len(ids)
             seed = sp.seed
             if not sp.greedy and seed is None:      # as generate(): a fresh stream per call, reproducible under torch.manual_seed
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                # (tensor parallel: rank 0's draw on every rank, so that all ranks sample the same tokens)
+                seed = self.llm._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
             # n > 1 (vllm.SamplingParams.n): the request fans out into n sequences that share prompt, knobs and mask and draw from
             # the Philox streams seed, seed + 1, ...: completion j is exactly what a single request with seed + j returns, and the
             # copies ride the continuous batch like any other requests (the prompt is prefilled once per copy)
@@ -180,9 +184,9 @@ class LLM:
         # continuous batching: requests with the same static mask (greedy and sampled alike), at least two of them
         groups = {}
         for r in reqs:
-            # (tensor parallel: greedy requests only - the sampling kernel needs the full logit row on one GPU; every rank serves the
-            # same request list and sees the same tokens, so all ranks take the same scheduling decisions)
-            if r["mask"] is not None and r["max_new"] > 0 and (not self.llm.tp_path or r["sp"].greedy):
+            # (tensor parallel: every rank serves the same request list with the same seeds and sees the same tokens, so all ranks
+            # take the same scheduling decisions)
+            if r["mask"] is not None and r["max_new"] > 0:
                 groups.setdefault(bytes(r["mask"].cpu().numpy().tobytes()), []).append(r)
         for grp in groups.values():
             if len(grp) >= 2:
