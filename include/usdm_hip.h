@@ -325,6 +325,23 @@ typedef struct usdm_gemv_batch_args {
 int64_t usdm_gemv_batch_ks_floats(int32_t N, int32_t K);   /* 0: this shape is not split */
 int usdm_gemv_batch(const usdm_gemv_batch_args* args, usdm_stream_t stream);
 
+/* Weight-only FP8 decode GEMV (opt-in, usdm_amd/quant.py): b.g.W holds OCP e4m3fn bytes [N][ldw] (row-major, ldw in elements =
+ * bytes, a multiple of 8) and row r is scaled by 2^row_exp[r].  Every dequantized weight q * 2^e is a bf16 value, and the kernels
+ * convert it exactly in registers and then run the bf16 arithmetic unchanged: the result equals usdm_gemv (nb = 1) or the VALU
+ * form of usdm_gemv_batch (nb = 2..4) on the bf16 matrix W' = q * 2^e, bit for bit.  Supported: the plain single-GPU forms
+ * (RMSNorm, SwiGLU, residual, lm_head mode, skip).  Not supported (error, no fall-back): nb > 4 / the matrix-core forms, p2p,
+ * mrg_* / cmb_gran, x_delta / x_out. */
+typedef struct usdm_gemv_fp8_args {
+  usdm_gemv_batch_args b;    /* nb = 1: batch-1 kernel (strides unused); 2..4: the VALU batch kernel; form must be 0 or -1 */
+  const int8_t* row_exp;     /* [N] */
+} usdm_gemv_fp8_args;
+int usdm_gemv_fp8(const usdm_gemv_fp8_args* args, usdm_stream_t stream);
+/* out[r][k] = bf16(e4m3(q[r][k]) * 2^row_exp[r]) for r < N, k < K (prefill: the bf16 operand of usdm_gemm).  K, ldq and ldo
+ * multiples of 8; q 8-byte and out 16-byte aligned. */
+int usdm_dequant_fp8(const void* q, const int8_t* row_exp, int32_t N, int32_t K, int64_t ldq, void* out, int64_t ldo,
+                     usdm_stream_t stream);
+int usdm_sizeof_gemv_fp8_args(void);
+
 /* Device-resident greedy-decode state so that a decode step is replayable as one hipGraph. */
 typedef struct usdm_decode_state {
   int32_t* next_token;  /* [1] token fed to the next step                     */

@@ -149,6 +149,10 @@ class GemvBatchArgs(C.Structure):
     ]
 
 
+class GemvFp8Args(C.Structure):
+    _fields_ = [("b", GemvBatchArgs), ("row_exp", C.c_void_p)]
+
+
 class DecodeState(C.Structure):
     _fields_ = [
         ("next_token", C.c_void_p), ("out_tokens", C.c_void_p), ("step", C.c_void_p), ("pos", C.c_void_p),
@@ -207,7 +211,7 @@ def _selfcheck():
     for name, cls in (("norm", NormArgs), ("snake", SnakeArgs), ("attn", AttnArgs), ("vb_input", VbInputArgs),
                       ("vb_solver", VbSolverArgs), ("gemv", GemvArgs), ("decode_state", DecodeState),
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
-                      ("gemv_batch", GemvBatchArgs), ("p2p_dev", P2pDev)):
+                      ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("p2p_dev", P2pDev)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

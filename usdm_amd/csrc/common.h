@@ -142,3 +142,17 @@ __device__ __forceinline__ void st_wt(T* p, const T& v) {
   else if constexpr (sizeof(T) == 8) asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(__builtin_bit_cast(wt2, v)) : "memory");
   else *p = v;
 }
+
+// ---- weight-only FP8 (usdm_amd/quant.py): OCP e4m3fn bytes with a power-of-two scale 2^e per output row.  q * 2^e has at most
+// 4 significant bits and the quantizer keeps it a normal bf16, so the scaled conversion (v_cvt_scalef32_pk_bf16_fp8) is exact:
+// the kernels see the bf16 weights W' = q * 2^e bit for bit.
+__device__ __forceinline__ float fp8_row_scale(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }
+__device__ __forceinline__ u32x4 fp8x8_to_bf16x8(u32x2 w, float s) {   // 8 e4m3 bytes -> 8 bf16, element order kept
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_cvt;
+  u32x4 r;
+  r[0] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], s, false));
+  r[1] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], s, true));
+  r[2] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], s, false));
+  r[3] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], s, true));
+  return r;
+}

@@ -17,14 +17,25 @@ __device__ __forceinline__ float dot8b(u32x4 w, u32x4 x, float acc) {
   return acc;
 }
 
+// FP8: the weight-only FP8 format (usdm_gemv_fp8, as in gemv_kernel): 8-byte loads of e4m3 bytes, converted in registers with the
+// row's power-of-two scale (exact), then the bf16 arithmetic unchanged; a ring twice as deep.  The row exponents are one extra
+// kernel argument (FP8 only: the bf16 instantiations keep their exact signature and code).
+template <bool FP8> struct gemvb_fmt { typedef u32x4 wvec; };
+template <> struct gemvb_fmt<true> { typedef u32x2 wvec; };
+__device__ __forceinline__ const int8_t* gemvb_row_exp() { return nullptr; }
+__device__ __forceinline__ const int8_t* gemvb_row_exp(const int8_t* e) { return e; }
+
 // (NB = 4 needs 140 VGPRs in the gate/up variant = 3 workgroups per SIMD instead of 4, i.e. a third round of workgroups for
 // the 1792-workgroup launch: 57 us instead of 40.  Forcing 128 VGPRs spills and was measured slower: 898 vs 967 tok/s.)
-template <int RW, bool GLU, int NWV, int NB>
-__global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_batch_args ba) {
+template <int RW, bool GLU, int NWV, int NB, bool FP8 = false, class... FMT>
+__global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_batch_args ba, FMT... fmt) {
   const usdm_gemv_args& a = ba.g;
+  static_assert(FP8 == (sizeof...(FMT) == 1), "FP8 takes the row exponents");
+  typedef typename gemvb_fmt<FP8>::wvec wvec;
   constexpr int NTH = NWV * 64;
   constexpr int NR = GLU ? 2 * RW : RW;
-  constexpr int UNR = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : 8);
+  constexpr int UNR0 = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : 8);
+  constexpr int UNR = FP8 ? 2 * UNR0 : UNR0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = (bf16_t*)smem;  // [NB][Kpad] bf16, zero padded
   __shared__ float red[NB][NWV];
@@ -37,7 +48,8 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
 
   const int rows_per_block = NWV * RW;
   const int ob = blockIdx.x * rows_per_block + wave * RW;
-  const u32x4* wp[NR];
+  const wvec* wp[NR];
+  float wsc[NR];   // FP8: the rows' scales (unused in bf16)
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
     int r;
@@ -48,7 +60,12 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
       r = ob + j;
     }
     r = r < a.N ? r : a.N - 1;
-    wp[j] = (const u32x4*)((const bf16_t*)a.W + (int64_t)r * a.ldw) + lane;
+    if constexpr (FP8) {
+      wp[j] = (const wvec*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
+      wsc[j] = fp8_row_scale(gemvb_row_exp(fmt...)[r]);
+    } else {
+      wp[j] = (const u32x4*)((const bf16_t*)a.W + (int64_t)r * a.ldw) + lane;
+    }
   }
   const bool tail_ok = ((nit - 1) << 9) + lane * 8 < K;
   // lm_head mode: rows of banned ids are not streamed (see gemv_kernel)
@@ -72,12 +89,12 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
       if (ob + j < a.N) active |= (a.ban[ob + j] == 0);
     active = __builtin_amdgcn_readfirstlane(active);
   }
-  auto wload = [&](int j, int it) -> u32x4 {
-    if (!active) return u32x4{0u, 0u, 0u, 0u};
-    const u32x4* p = (it == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + it * 64;
+  auto wload = [&](int j, int it) -> wvec {
+    if (!active) return wvec{};
+    const wvec* p = (it == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + it * 64;
     return __builtin_nontemporal_load(p);
   };
-  u32x4 ring[NR][UNR];
+  wvec ring[NR][UNR];
 #pragma unroll
   for (int u = 0; u < UNR; ++u)
 #pragma unroll
@@ -153,8 +170,14 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
         for (int b = 0; b < NB; ++b) xv[b] = *(const u32x4*)(xs + (int64_t)b * Kpad + (it * 64 + lane) * 8);
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
+          if constexpr (FP8) {
+            const u32x4 wv = fp8x8_to_bf16x8(ring[j][u], wsc[j]);
 #pragma unroll
-          for (int b = 0; b < NB; ++b) acc[j][b] = dot8b(ring[j][u], xv[b], acc[j][b]);
+            for (int b = 0; b < NB; ++b) acc[j][b] = dot8b(wv, xv[b], acc[j][b]);
+          } else {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[j][b] = dot8b(ring[j][u], xv[b], acc[j][b]);
+          }
           if (it + UNR < nit) ring[j][u] = wload(j, it + UNR);
         }
       }
@@ -246,8 +269,8 @@ static int pick_rw(int nout, bool glu) {   // same balance rule as the batch-1 l
   return best;
 }
 
-template <int NB>
-int launch_nb(const usdm_gemv_batch_args& ba, hipStream_t st) {
+template <int NB, bool FP8 = false, class... FMT>
+int launch_nb(const usdm_gemv_batch_args& ba, hipStream_t st, FMT... fmt) {
   const usdm_gemv_args& a = ba.g;
   const bool glu = a.act == USDM_ACT_SWIGLU;
   const int nout = glu ? a.N / 2 : a.N;
@@ -255,9 +278,9 @@ int launch_nb(const usdm_gemv_batch_args& ba, hipStream_t st) {
   const size_t lds = (size_t)Kpad * 2 * NB;
 #define USDM_GB(RW, GLUV, NWV, GRID)                                                                              \
   do {                                                                                                             \
-    auto kfn = gemv_batch_kernel<RW, GLUV, NWV, NB>;                                                               \
+    auto kfn = gemv_batch_kernel<RW, GLUV, NWV, NB, FP8, FMT...>;                                                  \
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-    hipLaunchKernelGGL(kfn, dim3(GRID), dim3(NWV * 64), lds, st, ba);                                              \
+    hipLaunchKernelGGL(kfn, dim3(GRID), dim3(NWV * 64), lds, st, ba, fmt...);                                      \
   } while (0)
   if (!glu && !a.part_val && nout % 256 == 0 && (nout / 256 == 16 || nout / 256 == 24)) {
     if (nout / 256 == 16) USDM_GB(1, false, 16, 256);
@@ -305,6 +328,17 @@ extern "C" int usdm_gemv_batch(const usdm_gemv_batch_args* pa, usdm_stream_t str
     case 2: return launch_nb<2>(*pa, st);
     case 3: return launch_nb<3>(*pa, st);
     default: return launch_nb<4>(*pa, st);
+  }
+}
+// usdm_gemv_fp8 with 2..4 sequences (llm_k.hip checks the arguments it shares with the batch-1 form)
+int usdm_gemv_fp8_batch_launch(const usdm_gemv_fp8_args* pa, hipStream_t st) {
+  const usdm_gemv_args& a = pa->b.g;
+  USDM_CHECK_ARG(!a.part_val || pa->b.part_bs >= cdiv(a.N, 16), "usdm_gemv_fp8: lm_head partial buffers");
+  USDM_CHECK_ARG(pa->b.x_bs % 8 == 0, "usdm_gemv_fp8: x stride must keep 16-B alignment");
+  switch (pa->b.nb) {
+    case 2: return launch_nb<2, true>(pa->b, st, pa->row_exp);
+    case 3: return launch_nb<3, true>(pa->b, st, pa->row_exp);
+    default: return launch_nb<4, true>(pa->b, st, pa->row_exp);
   }
 }
 extern "C" int usdm_sizeof_gemv_batch_args(void) { return (int)sizeof(usdm_gemv_batch_args); }

@@ -55,11 +55,24 @@ __device__ unsigned long long g_gemv_trace[8192 * 8];
 // kernels carry none of it.
 // CMB: the hand-off form of the merged-attention input (usdm_gemv_args.cmb_gran): one combine per head by the launch's first
 // workgroups, granules to everyone, the wait under the first weight ring.  Its own instantiation for the same reason.
-template <int RW, bool GLU, int NWV, bool MRG = false, bool P2P = false, bool CMB = false>
-__global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a) {
+// FP8: the weight-only FP8 format (usdm_gemv_fp8): 8-byte loads of e4m3 bytes in the bf16 kernel's K-to-lane assignment, converted
+// in registers with the row's power-of-two scale (exact), then the bf16 arithmetic unchanged.  The ring is twice as deep, so the
+// same number of bytes is in flight per lane; only the weight load and unpack differ.  The row exponents come as one extra kernel
+// argument (FP8 only: the bf16 instantiations keep their exact signature and code).
+template <bool FP8> struct gemv_fmt { typedef u32x4 wvec; };
+template <> struct gemv_fmt<true> { typedef u32x2 wvec; };
+__device__ __forceinline__ const int8_t* gemv_row_exp() { return nullptr; }
+__device__ __forceinline__ const int8_t* gemv_row_exp(const int8_t* e) { return e; }
+
+template <int RW, bool GLU, int NWV, bool MRG = false, bool P2P = false, bool CMB = false, bool FP8 = false, class... FMT>
+__global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, FMT... fmt) {
+  typedef typename gemv_fmt<FP8>::wvec wvec;
+  static_assert(FP8 == (sizeof...(FMT) == 1), "FP8 takes the row exponents");
+  static_assert(!FP8 || (!MRG && !P2P && !CMB), "the FP8 weight format has the plain single-GPU forms only");
   constexpr int NTH = NWV * 64;
   constexpr int NR = GLU ? 2 * RW : RW;   // rows streamed together by one wave
-  constexpr int UNR = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : (NR == 2 ? 8 : USDM_UNR1));  // ring depth: NR*UNR = 15..16 loads in flight per lane
+  constexpr int UNR0 = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : (NR == 2 ? 8 : USDM_UNR1));  // ring depth: NR*UNR = 15..16 loads in flight per lane
+  constexpr int UNR = FP8 ? 2 * UNR0 : UNR0;   // (FP8: 8-byte loads, twice as many for the same bytes in flight)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = (bf16_t*)smem;  // [Kpad] bf16, zero padded
   __shared__ float red[NWV];
@@ -78,7 +91,8 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a) 
   // ---- rows of this wave
   const int rows_per_block = NWV * RW;                    // output features per workgroup
   const int ob = blockIdx.x * rows_per_block + wave * RW; // first output feature of this wave
-  const u32x4* wp[NR];
+  const wvec* wp[NR];
+  float wsc[NR];   // FP8: the rows' scales (requested here, before the hand-counted loads below; unused in bf16)
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
     int r;
@@ -89,7 +103,12 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a) 
       r = ob + j;
     }
     r = r < a.N ? r : a.N - 1;
-    wp[j] = (const u32x4*)((const bf16_t*)a.W + (int64_t)r * a.ldw) + lane;
+    if constexpr (FP8) {
+      wp[j] = (const wvec*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
+      wsc[j] = fp8_row_scale(gemv_row_exp(fmt...)[r]);
+    } else {
+      wp[j] = (const u32x4*)((const bf16_t*)a.W + (int64_t)r * a.ldw) + lane;
+    }
   }
   const bool tail_ok = ((nit - 1) << 9) + lane * 8 < K;  // is this lane inside K on the last iteration?
   // lm_head mode: a wave whose rows are ALL banned (the reference's bad_words_ids mask whole id ranges: 76 % of the vocabulary
@@ -111,10 +130,10 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a) 
       if (ob + j < a.N) active |= (a.ban[ob + j] == 0);
     active = __builtin_amdgcn_readfirstlane(active);
   }
-  auto wload = [&](int j, int it) -> u32x4 {
-    if (!active) return u32x4{0u, 0u, 0u, 0u};
+  auto wload = [&](int j, int it) -> wvec {
+    if (!active) return wvec{};
     // last iteration may run past K: redirect to the row start (x is zero there in LDS, contributes 0)
-    const u32x4* p = (it == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + it * 64;
+    const wvec* p = (it == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + it * 64;
     return __builtin_nontemporal_load(p);
   };
   // The residual values of this wave's rows are requested HERE, at the start, not in the epilogue (round 4): there the
@@ -149,13 +168,13 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a) 
   }
   // The first ring is ALWAYS NR x UNR loads (slots past the row's K, or of a wave whose rows are all banned, re-read the row start
   // and are never multiplied / their results never used): the wait for the early loads below can then name an exact count.
-  u32x4 ring[NR][UNR];
+  wvec ring[NR][UNR];
 #pragma unroll
   for (int u = 0; u < UNR; ++u)
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
       const bool real = active && u < nit;
-      const u32x4* p = real ? ((u == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + u * 64) : wp[j] - lane;
+      const wvec* p = real ? ((u == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + u * 64) : wp[j] - lane;
       ring[j][u] = __builtin_nontemporal_load(p);
     }
   GTR(1);
@@ -358,7 +377,8 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a) 
         const u32x4 xv = *(const u32x4*)(xs + (it * 64 + lane) * 8);
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
-          acc[j] = dot8(ring[j][u], xv, acc[j]);
+          if constexpr (FP8) acc[j] = dot8(fp8x8_to_bf16x8(ring[j][u], wsc[j]), xv, acc[j]);
+          else acc[j] = dot8(ring[j][u], xv, acc[j]);
           if (it + UNR < nit) ring[j][u] = wload(j, it + UNR);
         }
       }
@@ -1036,6 +1056,48 @@ __global__ void residual_add_kernel(bf16_t* h, const float* delta, int n) {
 }
 }  // namespace
 
+// the plain single-GPU forms (no merged input, no peer-to-peer epilogue): the variant per projection shape.  One selection for
+// both weight formats, so an FP8 launch partitions K and the RMSNorm sums exactly as the bf16 launch of the same shape.
+template <bool FP8, class... FMT>
+static int gemv_launch_plain(const usdm_gemv_args& a, size_t lds, hipStream_t st, FMT... fmt) {
+  const bool glu = a.act == USDM_ACT_SWIGLU;
+  const int nout = glu ? a.N / 2 : a.N;
+  if (!glu && !a.part_val && nout % 256 == 0) {
+    const int rows_per_cu = nout / 256;
+    if (rows_per_cu == 16) {
+      hipLaunchKernelGGL((gemv_kernel<1, false, 16, false, false, false, FP8, FMT...>), dim3(256), dim3(1024), lds, st, a, fmt...);
+      USDM_LAUNCH_CHECK();
+      return 0;
+    }
+    if (rows_per_cu == 24) {
+      hipLaunchKernelGGL((gemv_kernel<2, false, 12, false, false, false, FP8, FMT...>), dim3(256), dim3(768), lds, st, a, fmt...);
+      USDM_LAUNCH_CHECK();
+      return 0;
+    }
+  }
+  // (a 14-wave GLU variant with one workgroup per CU was measured 15 % slower than 7 four-wave workgroups per CU)
+  // gate/up of the 7B (14336 outputs): 7-wave workgroups of 14 outputs = 1024 workgroups = exactly two rounds of two
+  // workgroups per CU, instead of 1792 four-wave workgroups = 1.75 rounds of four
+  if (glu && nout % 14 == 0 && (nout / 14) % 512 == 0) {
+    hipLaunchKernelGGL((gemv_kernel<2, true, 7, false, false, false, FP8, FMT...>), dim3(nout / 14), dim3(448), lds, st, a, fmt...);
+    USDM_LAUNCH_CHECK();
+    return 0;
+  }
+  const int rw = a.part_val ? 4 : gemv_pick_rw(nout, glu);
+  dim3 grid(cdiv(nout, 4 * rw)), block(256);
+  if (glu) {
+    if (rw == 2) hipLaunchKernelGGL((gemv_kernel<2, true, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
+    else hipLaunchKernelGGL((gemv_kernel<1, true, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
+  } else {
+    if (rw == 4) hipLaunchKernelGGL((gemv_kernel<4, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
+    else if (rw == 3) hipLaunchKernelGGL((gemv_kernel<3, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
+    else if (rw == 2) hipLaunchKernelGGL((gemv_kernel<2, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
+    else hipLaunchKernelGGL((gemv_kernel<1, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
+  }
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int usdm_gemv(const usdm_gemv_args* pa, usdm_stream_t stream) {
   USDM_CHECK_ARG(pa && pa->W && (pa->x || pa->mrg_po), "usdm_gemv: null args");
   const usdm_gemv_args& a = *pa;
@@ -1085,41 +1147,57 @@ extern "C" int usdm_gemv(const usdm_gemv_args* pa, usdm_stream_t stream) {
     USDM_LAUNCH_CHECK();
     return 0;
   }
-  if (!glu && !a.part_val && nout % 256 == 0) {
-    const int rows_per_cu = nout / 256;
-    if (rows_per_cu == 16) {
-      hipLaunchKernelGGL((gemv_kernel<1, false, 16>), dim3(256), dim3(1024), lds, st, a);
-      USDM_LAUNCH_CHECK();
-      return 0;
-    }
-    if (rows_per_cu == 24) {
-      hipLaunchKernelGGL((gemv_kernel<2, false, 12>), dim3(256), dim3(768), lds, st, a);
-      USDM_LAUNCH_CHECK();
-      return 0;
-    }
+  return gemv_launch_plain<false>(a, lds, st);
+}
+
+
+int usdm_gemv_fp8_batch_launch(const usdm_gemv_fp8_args* pa, hipStream_t st);   // llm_batch_k.hip: nb = 2..4
+
+extern "C" int usdm_gemv_fp8(const usdm_gemv_fp8_args* pa, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->b.g.W && pa->b.g.x && pa->row_exp, "usdm_gemv_fp8: null args");
+  const usdm_gemv_args& a = pa->b.g;
+  USDM_CHECK_ARG(pa->b.nb >= 1 && pa->b.nb <= 4 && (pa->b.form == 0 || pa->b.form == -1),
+                 "usdm_gemv_fp8: 1..4 sequences on the VALU form (the matrix-core form has no FP8 weights)");
+  USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.cmb_gran && !a.x_delta && !a.x_out,
+                 "usdm_gemv_fp8: p2p / merged-attention input / cmb_gran / x_delta are not supported with FP8 weights");
+  USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.K % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && ((uintptr_t)a.W & 7) == 0, "usdm_gemv_fp8: bad N/K/ldw");
+  USDM_CHECK_ARG(a.K <= 16384, "usdm_gemv_fp8: K too large for the LDS-resident input vector");
+  const bool glu = a.act == USDM_ACT_SWIGLU;
+  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "usdm_gemv_fp8: swiglu needs N %% 32 == 0");
+  USDM_CHECK_ARG(a.y16 || a.y32 || a.part_val, "usdm_gemv_fp8: no output");
+  USDM_CHECK_ARG(!a.part_val || (a.part_idx && !glu), "usdm_gemv_fp8: part_idx missing / lm_head mode is not GLU");
+  hipStream_t st = (hipStream_t)stream;
+  if (pa->b.nb > 1) return usdm_gemv_fp8_batch_launch(pa, st);
+  const size_t lds = (size_t)((a.K + 511) & ~511) * 2;
+  return gemv_launch_plain<true>(a, lds, st, pa->row_exp);
+}
+
+namespace {
+// prefill operand of the FP8 model: one workgroup per row, 8 elements (8 bytes in, 16 bytes out) per thread and step
+__global__ __launch_bounds__(256) void dequant_fp8_kernel(const uint8_t* q, const int8_t* row_exp, int K, int64_t ldq, bf16_t* out,
+                                                          int64_t ldo) {
+  const int r = blockIdx.x;
+  const float s = fp8_row_scale(row_exp[r]);
+  const uint8_t* qr = q + (int64_t)r * ldq;
+  bf16_t* orow = out + (int64_t)r * ldo;
+  for (int i = threadIdx.x * 8; i < K; i += 256 * 8) {
+    const u32x2 w = __builtin_nontemporal_load((const u32x2*)(qr + i));
+    *(u32x4*)(orow + i) = fp8x8_to_bf16x8(w, s);
   }
-  // (a 14-wave GLU variant with one workgroup per CU was measured 15 % slower than 7 four-wave workgroups per CU)
-  // gate/up of the 7B (14336 outputs): 7-wave workgroups of 14 outputs = 1024 workgroups = exactly two rounds of two
-  // workgroups per CU, instead of 1792 four-wave workgroups = 1.75 rounds of four
-  if (glu && nout % 14 == 0 && (nout / 14) % 512 == 0) {
-    hipLaunchKernelGGL((gemv_kernel<2, true, 7>), dim3(nout / 14), dim3(448), lds, st, a);
-    USDM_LAUNCH_CHECK();
-    return 0;
-  }
-  const int rw = a.part_val ? 4 : gemv_pick_rw(nout, glu);
-  dim3 grid(cdiv(nout, 4 * rw)), block(256);
-  if (glu) {
-    if (rw == 2) hipLaunchKernelGGL((gemv_kernel<2, true, 4>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((gemv_kernel<1, true, 4>), grid, block, lds, st, a);
-  } else {
-    if (rw == 4) hipLaunchKernelGGL((gemv_kernel<4, false, 4>), grid, block, lds, st, a);
-    else if (rw == 3) hipLaunchKernelGGL((gemv_kernel<3, false, 4>), grid, block, lds, st, a);
-    else if (rw == 2) hipLaunchKernelGGL((gemv_kernel<2, false, 4>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((gemv_kernel<1, false, 4>), grid, block, lds, st, a);
-  }
+}
+}  // namespace
+
+extern "C" int usdm_dequant_fp8(const void* q, const int8_t* row_exp, int32_t N, int32_t K, int64_t ldq, void* out, int64_t ldo,
+                                usdm_stream_t stream) {
+  USDM_CHECK_ARG(q && row_exp && out, "usdm_dequant_fp8: null args");
+  USDM_CHECK_ARG(N > 0 && K > 0 && K % 8 == 0 && ldq >= K && ldq % 8 == 0 && ldo >= K && ldo % 8 == 0, "usdm_dequant_fp8: bad N/K/ldq/ldo");
+  USDM_CHECK_ARG(((uintptr_t)q & 7) == 0 && ((uintptr_t)out & 15) == 0, "usdm_dequant_fp8: q must be 8-byte, out 16-byte aligned");
+  hipLaunchKernelGGL(dequant_fp8_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)q, row_exp, K, ldq, (bf16_t*)out, ldo);
   USDM_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int usdm_sizeof_gemv_fp8_args(void) { return (int)sizeof(usdm_gemv_fp8_args); }
+
 #ifdef USDM_GEMV_TRACE
 extern "C" int usdm_dbg_gemv_trace(unsigned long long* host, int n) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemv_trace), sizeof(unsigned long long) * n);

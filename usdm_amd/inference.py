@@ -115,7 +115,7 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
     return audio
 
 
-def load_models(model_cache_dir, dev=None, ctx_max=None):
+def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None):
     """What the reference's __main__ does between argument parsing and sample() (src/inference.py:105-129), from LOCAL copies:
     hub names resolve inside model_cache_dir (huggingface_hub cache layout or plain <name>/ directories, checkpoints.py)."""
     import os
@@ -136,7 +136,8 @@ def load_models(model_cache_dir, dev=None, ctx_max=None):
     # the reference generates up to tokenizer.model_max_length (inference.py:64); beyond the 4096-token sliding window the attention
     # kernels bound their key range (llm.py), so the cache may be longer than the window.  8192 = the USDM tokenizer's limit.
     want = ctx_max or min(int(getattr(tokenizer, "model_max_length", 4096) or 4096), 8192)
-    model = USDMForCausalLM.from_pretrained(llm_dir, device=dev, torch_dtype=torch.bfloat16, ctx_max=want).to(dev).eval()
+    model = USDMForCausalLM.from_pretrained(llm_dir, device=dev, torch_dtype=torch.bfloat16, ctx_max=want,
+                                            quantization=quantization).to(dev).eval()
     return model, unit_extractor, voicebox, vocoder, tokenizer
 
 
@@ -151,10 +152,12 @@ def main(argv=None):
                         help="Directory holding the model checkpoints (the reference's download cache, or local <name>/ directories).")
     parser.add_argument('--output_path', type=str, required=True,
                         help="Path to save the spoken response.")
+    parser.add_argument('--quantization', type=str, default=None, choices=["fp8"],
+                        help="Weight-only FP8 for the LLM (e4m3, power-of-two row scales; opt-in, default bf16).")
     args = parser.parse_args(argv)
 
     device = torch.device("cuda")
-    model, unit_extractor, voicebox, vocoder, tokenizer = load_models(args.model_cache_dir, device)
+    model, unit_extractor, voicebox, vocoder, tokenizer = load_models(args.model_cache_dir, device, quantization=args.quantization)
     try:
         sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)

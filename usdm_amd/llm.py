@@ -14,7 +14,10 @@ Host side: Python plans of C-ABI launches (libusdm_hip.so).
             pick likewise (usdm_argmax_p2p).  Prefill (4 MB messages) and the validation path use RCCL through
             torch.distributed ('nccl'): f32 partial sums all-reduced, arg-max partials all-gathered.  Sampling gathers the
             full logits row on every rank (usdm_logits_p2p in the P2P step) and draws from it with rank 0's seed.
-Weights: HF state-dict key names (model.layers.N.self_attn.q_proj.weight, ...), bf16.
+Weights: HF state-dict key names (model.layers.N.self_attn.q_proj.weight, ...), bf16.  quantization="fp8" (opt-in): the streamed
+matrices (qkv, o, gate/up, down, lm_head) are held as e4m3 with a power-of-two scale per row (usdm_amd/quant.py), which makes the
+model exactly the bf16 model with the dequantized weights W'; decode streams half the bytes (usdm_gemv_fp8), prefill dequantizes
+each matrix into one bf16 scratch right before its usdm_gemm.  Single GPU only.
 """
 import math
 import os
@@ -25,6 +28,7 @@ from . import ops
 from ._lib import ACT_SWIGLU
 from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
+from .quant import Fp8Weight
 
 MISTRAL_7B_USDM = dict(vocab_size=42003, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
                        num_attention_heads=32, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-5,
@@ -71,9 +75,16 @@ def agree_seed(seed, group, rank, device=None):
     return int(dst[0].item())
 
 
-def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16):
+QUANT_KEYS = ("qkv", "o", "gu", "down")    # the streamed matrices of a layer (quantization="fp8"; with the lm_head shard)
+
+
+def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantization=None):
     """This rank's packed weights for tensor parallelism of degree `tp` (Megatron-style): q/k/v heads and MLP
-    columns split by rank, o_proj/down_proj split along K (their outputs are partial sums), vocab rows split."""
+    columns split by rank, o_proj/down_proj split along K (their outputs are partial sums), vocab rows split.
+    quantization="fp8": every streamed matrix becomes a quant.Fp8Weight as soon as its layer is packed (rows quantized after the
+    qkv concatenation and the gate/up packing; per-row scales do not depend on the row order), so at most one layer is ever held
+    in bf16 next to the FP8 copy.  The embedding stays bf16, the norms f32."""
+    qz = Fp8Weight.from_matrix if quantization == "fp8" else (lambda t: t)
     d = cfg["head_dim"]
     Hq, Hkv, I = cfg["num_attention_heads"] // tp, cfg["num_key_value_heads"] // tp, cfg["intermediate_size"] // tp
     V = cfg["vocab_size"]
@@ -81,7 +92,7 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16):
     g = lambda n: sd_get(n).to(device, dtype)
     f = lambda n: sd_get(n).to(device, torch.float32).contiguous()
     W = {"embed": g("model.embed_tokens.weight").contiguous(), "norm": f("model.norm.weight"),
-         "lm_head": g("lm_head.weight")[v0:v1].contiguous(), "layers": [], "v0": v0, "v1": v1}
+         "lm_head": qz(g("lm_head.weight")[v0:v1].contiguous()), "layers": [], "v0": v0, "v1": v1}
     for l in range(cfg["num_hidden_layers"]):
         p = f"model.layers.{l}."
         q = g(p + "self_attn.q_proj.weight")[rank * Hq * d:(rank + 1) * Hq * d]
@@ -91,15 +102,21 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16):
         ga = g(p + "mlp.gate_proj.weight")[rank * I:(rank + 1) * I]
         up = g(p + "mlp.up_proj.weight")[rank * I:(rank + 1) * I]
         dn = g(p + "mlp.down_proj.weight")[:, rank * I:(rank + 1) * I]
-        W["layers"].append(dict(qkv=torch.cat([q, k, v], 0).contiguous(), o=o.contiguous(), gu=_pack_gate_up(ga, up),
-                                down=dn.contiguous(), ln1=f(p + "input_layernorm.weight"),
+        W["layers"].append(dict(qkv=qz(torch.cat([q, k, v], 0).contiguous()), o=qz(o.contiguous()), gu=qz(_pack_gate_up(ga, up)),
+                                down=qz(dn.contiguous()), ln1=f(p + "input_layernorm.weight"),
                                 ln2=f(p + "post_attention_layernorm.weight")))
+        del q, k, v, o, ga, up, dn
     return W
 
 
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
-                 p2p_fused=None):
+                 p2p_fused=None, quantization=None):
+        if quantization not in (None, "fp8"):
+            raise ValueError(f"quantization={quantization!r}: supported are None (bf16) and 'fp8' (e4m3 weights, power-of-two row scales)")
+        if quantization == "fp8" and (tp_size > 1 or tp_segments or p2p is not None):
+            raise NotImplementedError("quantization='fp8' runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes bf16 weights")
+        self.quantization = quantization
         self.cfg = dict(cfg)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -169,6 +186,11 @@ class USDMForCausalLM:
         self.chain = int(mode.lstrip("e") or 0)
         if self.tp_path or c["hidden_size"] != 4096:
             self.chain = 0
+        if quantization == "fp8":
+            # the FP8 GEMVs have the plain forms only (usdm_gemv_fp8): the attention partials are combined by their own launch
+            # (bit-identical with the hand-off form) and every projection is its own launch
+            self.cmb = self.merge_in_oproj = False
+            self.chain = 0
         self.chain_sync = None
         self.W = None
         # bounded caches (plancache.LRU): prefill plans are keyed by exact prompt length (a plan is argument structs + ~60 KB of
@@ -186,7 +208,7 @@ class USDMForCausalLM:
     # ------------------------------------------------------------------ weights
     def _shard(self, sd_get):
         """Build this rank's packed weights from a getter name -> tensor (any device)."""
-        W = shard_weights(sd_get, self.cfg, self.tp_rank, self.tp_size, self.device)
+        W = shard_weights(sd_get, self.cfg, self.tp_rank, self.tp_size, self.device, quantization=self.quantization)
         assert (W["v0"], W["v1"]) == (self.v0, self.v1)
         return W
 
@@ -258,7 +280,9 @@ class USDMForCausalLM:
         return m
 
     def weight_bytes_per_token(self):
-        """bf16 bytes a decode step must stream on this rank (layers + lm_head shard)."""
+        """weight bytes a decode step must stream on this rank (layers + lm_head shard): bf16, or e4m3 + row exponents with fp8."""
+        if self.quantization == "fp8":
+            return sum(l[k].nbytes for l in self.W["layers"] for k in QUANT_KEYS) + self.W["lm_head"].nbytes
         n = sum(l[k].numel() for l in self.W["layers"] for k in ("qkv", "o", "gu", "down")) + self.W["lm_head"].numel()
         return 2 * n
 
@@ -314,6 +338,20 @@ class USDMForCausalLM:
             self.logits_loc = torch.zeros(self.Vloc, dtype=torch.float32, device=dev)
             self.logits_row = torch.zeros(self.tp_size * self.Vloc, dtype=torch.float32, device=dev)
             self._shard_logits = None
+        # fp8: ONE bf16 scratch for the prefill GEMM operand, sized for the largest streamed matrix (7B: gate/up, 235 MB); each
+        # matrix is dequantized into it right before its usdm_gemm (plans run their launches in order on one stream)
+        self.dq_scratch = None
+        if self.quantization == "fp8":
+            mats = [l[k] for l in self.W["layers"] for k in QUANT_KEYS]
+            self.dq_scratch = torch.empty(max(m.numel() for m in mats), dtype=bf, device=dev)
+
+    def _gemm_w(self, W, plan):
+        """The bf16 operand of a prefill usdm_gemm: the weight itself, or (fp8) its dequantization into the shared scratch."""
+        if not isinstance(W, Fp8Weight):
+            return W
+        out = self.dq_scratch[:W.N * W.K].view(W.N, W.K)
+        ops.dequant_fp8(W, out, plan=plan)
+        return out
 
     # ------------------------------------------------------------------ collectives (TP only)
     def _host_staged(self):
@@ -472,7 +510,7 @@ class USDMForCausalLM:
         for l in range(L):
             w = self.W["layers"][l]
             ops.norm(h, w["ln1"], None, rows=S, C=H, eps=c["rms_norm_eps"], rms=True, round_bf16=True, out16=xn, plan=plan)
-            ops.gemm(xn, w["qkv"], M=S, N=nq, Kc=H, out16=qkv, plan=plan)
+            ops.gemm(xn, self._gemm_w(w["qkv"], plan), M=S, N=nq, Kc=H, out16=qkv, plan=plan)
             if slot is not None:
                 ops.rope_cache(qkv, self.cos, self.sin, slot.kcache[l], slot.vcache[l], ld=nq, S=S, pos0=0, Hq=Hq, Hkv=Hkv,
                                ctx_max=self.ctx_max, max_pos=self.ctx_max, vt=vt, vt_ld=Spad, plan=plan)
@@ -486,16 +524,16 @@ class USDMForCausalLM:
                               Skv_alloc=self.ctx_max, q_pos0=past, q_strides=(0, d, nq), k_strides=(0, self.ctx_max * d, d),
                               v_strides=(0, d * self.ctx_max, self.ctx_max), o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=plan)
             if tp == 1:
-                ops.gemm(ao, w["o"], M=S, N=H, Kc=Hq * d, residual=h, ldr=H, round_bf16=True, out16=h, plan=plan)
+                ops.gemm(ao, self._gemm_w(w["o"], plan), M=S, N=H, Kc=Hq * d, residual=h, ldr=H, round_bf16=True, out16=h, plan=plan)
             else:
                 ops.gemm(ao, w["o"], M=S, N=H, Kc=Hq * d, out32=part, plan=plan)
                 segs += [plan, (lambda t=part: self._all_reduce(t))]
                 plan = ops.Plan()
                 ops.residual_add(h, part, S * H, plan=plan)
             ops.norm(h, w["ln2"], None, rows=S, C=H, eps=c["rms_norm_eps"], rms=True, round_bf16=True, out16=xn, plan=plan)
-            ops.gemm(xn, w["gu"], M=S, N=2 * I, Kc=H, act=ACT_SWIGLU, round_bf16=True, out16=act, ldc=I, plan=plan)
+            ops.gemm(xn, self._gemm_w(w["gu"], plan), M=S, N=2 * I, Kc=H, act=ACT_SWIGLU, round_bf16=True, out16=act, ldc=I, plan=plan)
             if tp == 1:
-                ops.gemm(act, w["down"], M=S, N=H, Kc=I, residual=h, ldr=H, round_bf16=True, out16=h, plan=plan)
+                ops.gemm(act, self._gemm_w(w["down"], plan), M=S, N=H, Kc=I, residual=h, ldr=H, round_bf16=True, out16=h, plan=plan)
             else:
                 ops.gemm(act, w["down"], M=S, N=H, Kc=I, out32=part, plan=plan)
                 segs += [plan, (lambda t=part: self._all_reduce(t))]
@@ -780,6 +818,8 @@ class USDMForCausalLM:
         """Sequences one decode step can take with THIS model's (per-rank) shapes: 16 on the matrix-core form, which splits K over
         8 waves in chunks of 32 (every projection's K must be a multiple of 256), else the 4 of the VALU form."""
         c = self.cfg
+        if self.quantization == "fp8":      # usdm_gemv_fp8 has the VALU form only
+            return 4
         ks = (c["hidden_size"], self.Hq * c["head_dim"], self.I)
         return self.MAX_BATCH if all(k % 256 == 0 for k in ks) else 4
 

@@ -9,8 +9,9 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
+from .quant import Fp8Weight
 
 
 def _stream():
@@ -239,7 +240,8 @@ def gemv(W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
          ban=None, part_val=None, part_idx=None, idx_offset=0, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0,
          p2p_mode=0, merge=None, cmb=None, plan=None, only_args=False):
     """usdm_gemv: batch-1 weight-streaming GEMV (see include/usdm_hip.h).  p2p: a usdm_amd.p2p.P2PComm (fused all-reduce).
-    only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain)."""
+    only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
+    W a quant.Fp8Weight: usdm_gemv_fp8 (the plain single-GPU forms only; the library refuses the others)."""
     _need_cuda(W, x, norm_w, residual, y16, y32, ban, part_val, part_idx, x_delta, x_out, skip)
     if x_out is not None and x_out.data_ptr() == x.data_ptr():
         raise ValueError("usdm_gemv: x_out must not alias x")
@@ -263,6 +265,13 @@ def gemv(W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
     if p2p is not None and p2p_mode:
         p2p.check_site(p2p_site, N)
         a.p2p, a.p2p_site, a.p2p_mode = p2p.dev_ptr, p2p_site, p2p_mode
+    if isinstance(W, Fp8Weight):
+        if only_args:
+            raise ValueError("usdm_gemv: FP8 weights have no chained form")
+        f = GemvFp8Args()
+        f.b.g, f.b.nb, f.row_exp = a, 1, _ptr(W.e)
+        _go(plan, "usdm_gemv_fp8", lib.usdm_gemv_fp8, C_.byref(f))
+        return
     if only_args:
         return a
     _go(plan, "usdm_gemv", lib.usdm_gemv, C_.byref(a))
@@ -414,7 +423,22 @@ def gemv_batch(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, n
         if part.dtype != torch.float32 or cnt.dtype != torch.int32 or cnt.numel() < -(-N // 16):
             raise ValueError("usdm_gemv_batch: ks = (float32 partials, int32 counters [ceil(N / 16)])")
         b.ks_part, b.ks_cnt, b.ks_part_floats = _ptr(part), _ptr(cnt), part.numel()
+    if isinstance(W, Fp8Weight):     # usdm_gemv_fp8: nb 1..4, VALU form (bit-identical with the bf16 launch on the dequantized matrix)
+        f = GemvFp8Args()
+        f.b, f.row_exp = b, _ptr(W.e)
+        _go(plan, "usdm_gemv_fp8", lib.usdm_gemv_fp8, C_.byref(f))
+        return
     _go(plan, "usdm_gemv_batch", lib.usdm_gemv_batch, C_.byref(b))
+
+
+def dequant_fp8(W, out, plan=None):
+    """usdm_dequant_fp8: a quant.Fp8Weight -> bf16 out [N][>= K] (the prefill operand of usdm_gemm)."""
+    _need_cuda(W, out)
+    if not isinstance(W, Fp8Weight) or out.dtype != torch.bfloat16 or out.dim() != 2 or out.shape[0] < W.N or out.shape[1] < W.K \
+            or out.stride(1) != 1:
+        raise ValueError("dequant_fp8: an Fp8Weight and a bf16 [N][>= K] output with unit column stride")
+    _go(plan, "usdm_dequant_fp8", lib.usdm_dequant_fp8, _ptr(W.q), _ptr(W.e), C_.c_int32(W.N), C_.c_int32(W.K), C_.c_int64(W.K),
+        _ptr(out), C_.c_int64(out.stride(0)))
 
 
 def gemv_batch_ks_floats(N, K):
