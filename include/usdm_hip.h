@@ -336,6 +336,14 @@ typedef struct usdm_gemv_fp8_args {
   const int8_t* row_exp;     /* [N] */
 } usdm_gemv_fp8_args;
 int usdm_gemv_fp8(const usdm_gemv_fp8_args* args, usdm_stream_t stream);
+/* The matrix-core form with FP8 weights (opt-in, 1..16 sequences): b.nb 1..16, b.form 0 (K split over workgroups where b.ks_*
+ * allow it, as in usdm_gemv_batch) or 5 (no K split).  The bytes are converted exactly to bf16 in registers and the bf16
+ * matrix-core arithmetic runs unchanged (same tiles, chunk order, wave merge, K split and epilogues): the result equals
+ * usdm_gemv_batch(form = 1, or 5) with the same ks_* arguments on W' = q * 2^e, bit for bit (like that form, NOT bit-identical
+ * with usdm_gemv / the VALU form).  W 16-byte aligned, ldw a multiple of 16, x 16-byte aligned.  Refused (error, no fall-back):
+ * nb > 16, any other form, p2p, mrg_* / cmb_gran, x_delta / x_out, and every shape the bf16 matrix-core form refuses (K %% 256,
+ * the fused RMSNorm with K > 4096, more than 64 tiles per workgroup). */
+int usdm_gemv_fp8_mfma(const usdm_gemv_fp8_args* args, usdm_stream_t stream);
 /* out[r][k] = bf16(e4m3(q[r][k]) * 2^row_exp[r]) for r < N, k < K (prefill: the bf16 operand of usdm_gemm).  K, ldq and ldo
  * multiples of 8; q 8-byte and out 16-byte aligned. */
 int usdm_dequant_fp8(const void* q, const int8_t* row_exp, int32_t N, int32_t K, int64_t ldq, void* out, int64_t ldo,

@@ -22,6 +22,10 @@
 // Per sequence the result is NOT bit-identical to usdm_gemv: the K partition and the MFMA's internal summation order differ (f32
 // rounding of the accumulation; the RMSNorm sum of squares is partitioned differently as well).  Parity is against the oracle
 // (tests/test_batch_gpu.py: near-tie rule), not against the batch-1 kernel.
+//
+// FP8 weights (usdm_gemv_fp8_mfma, opt-in): the same kernel with an FP8 template flag - e4m3 bytes with a power-of-two scale per row,
+// converted exactly to bf16 in registers right before each MFMA; everything else is the bf16 form, so the result equals it on the
+// dequantized weights W' bit for bit.
 #include "common.h"
 #include "../../include/usdm_hip.h"
 #include <type_traits>
@@ -66,11 +70,22 @@ __device__ __forceinline__ f32x4 mfma16(u32x4 w, u32x4 x, f32x4 acc) {
 // Hand-counted loads for the straight-line part of the HOLD stream (cdna_hip_programming.md 5.7, form (ii)): the compiler neither
 // sees these loads nor waits for them; every consumer below waits for exactly its own load (in-order completion: "all but the 23
 // youngest") inside the same asm statement that multiplies it.
-__device__ __forceinline__ void ld_nt_asm(u32x4& dst, const u32x4* p) {
+// (templates only so that the FP8 instantiations, whose generic-form ring holds u32x2, still parse the hand-counted bf16 branches they
+// never take; every use is u32x4)
+template <class V>
+__device__ __forceinline__ void ld_nt_asm(V& dst, const V* p) {
   asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(dst) : "v"(p) : "memory");
 }
-template <int WAIT, bool FIRST>
-__device__ __forceinline__ void wait_mfma_asm(f32x4& acc, const u32x4& w, const u32x4& x) {
+// FP8 (usdm_gemv_fp8_mfma): the row exponent of the lane's A-row, hand-counted like the weight loads of its unit
+__device__ __forceinline__ void ld_exp_asm(int& dst, const int8_t* p) {
+  asm volatile("global_load_sbyte %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
+}
+__device__ __forceinline__ const int8_t* mfma_row_exp() { return nullptr; }
+__device__ __forceinline__ const int8_t* mfma_row_exp(const int8_t* e) { return e; }
+template <int... I, class F>
+__device__ __forceinline__ void each_slot(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int WAIT, bool FIRST, class V>
+__device__ __forceinline__ void wait_mfma_asm(f32x4& acc, const V& w, const u32x4& x) {
   if constexpr (FIRST)
     asm volatile("s_waitcnt vmcnt(%3)\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(x), "n"(WAIT));
   else
@@ -82,8 +97,15 @@ __device__ __forceinline__ void wait_mfma_asm(f32x4& acc, const u32x4& w, const 
 // per wave (ds_write_b128 by rows, ds_read_b128 by fragments, XOR swizzle piece ^ row: conflict-free both ways).  The fragment-shaped
 // loads of the other variants (16 rows x 64 bytes per instruction) measured 4.4 TB/s at best: 64-byte requests and a DRAM page
 // visit per 64 - 128 bytes.  LDS traffic: 2 x 56 MB per CU and step against 56 MB of HBM traffic at a tenth of the LDS rate.
-template <bool HOLD, int CPWT, bool TRL>
-__global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
+//
+// FP8 (usdm_gemv_fp8_mfma): W holds e4m3 bytes [N][ldw] and row r is scaled by 2^row_exp[r] (usdm_amd/quant.py); the row exponents
+// are one extra kernel argument of the FP8 instantiations only, so the bf16 ones keep their signature and code.  Only the weight
+// load and its unpack differ: every tile, chunk order, wave merge, K split and epilogue is the bf16 one, and the exact conversion
+// (fp8x8_to_bf16x8) hands the MFMA the bf16 fragments of W' = q * 2^e, so the result equals the bf16 form on W' bit for bit.
+template <bool HOLD, int CPWT, bool TRL, bool FP8 = false, class... FMT>
+__global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT... fmt) {
+  static_assert(FP8 == (sizeof...(FMT) == 1), "FP8 takes the row exponents");
+  static_assert(!FP8 || TRL || CPWT == 0, "FP8: the row-contiguous forms and the generic ones (the fragment-shaped form 3 is bf16 only)");
   const usdm_gemv_args& a = d.ba.g;
   const int cpw = CPWT > 0 ? CPWT : d.cpw;
   constexpr int MTG = TRL ? MTG_TRL : MTG_DEF;             // tiles per reduction group
@@ -107,6 +129,8 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
   const bool glu = a.act == USDM_ACT_SWIGLU;
   const bool lmh = a.part_val != nullptr;
   const bf16_t* Wb = (const bf16_t*)a.W;
+  const int8_t* rexp = mfma_row_exp(fmt...);
+  typedef std::conditional_t<FP8, u32x2, u32x4> wvec;       // one lane's 8 weights of a chunk: 16 bf16 or 8 e4m3 bytes
 
   // ---- tiles of this workgroup: t = blockIdx.x + i * grid, i < ncand; lm_head: tiles whose 16 ids are all banned are not streamed
   // (K split over workgroups: workgroup = (slice ksi, member tile0 of the kwg workgroups that share the slice))
@@ -150,7 +174,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
   // CLAMPED to existing ones instead of masked: they only feed output rows / columns that the epilogue never stores, and every load
   // below stays unconditional (uniform control flow, one 64-bit base + immediates per tile).
   const int kc0 = wave * cpw;                             // first K chunk of this wave (host: K %% (MW * 32) == 0)
-  auto wbase = [&](int t) -> const u32x4* {
+  auto wbase = [&](int t) -> const wvec* {
     int row;
     if (glu) {
       const int f = t < 0 ? 0 : min(t * 8 + (r16 & 7), d.nout - 1);
@@ -163,12 +187,30 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
       // activation vector per instruction (one request instead of sixteen), a different line for every wave so that no L2 channel
       // becomes a hot spot (weight row 0 for everyone did).  Row 0 of x holds K * 2 bytes; chunk offsets reach 1 KiB further.
       const int line = (int)((blockIdx.x * MW + wave) % (unsigned)(K / 32 - 16));
-      return (const u32x4*)a.x + line * 4 + (lane & 3);
+      return (const wvec*)a.x + line * 4 + (lane & 3);
     }
-    return (const u32x4*)(Wb + (int64_t)row * a.ldw + (int64_t)kc0 * 32 + 8 * g);
+    if constexpr (FP8) return (const u32x2*)((const uint8_t*)a.W + (int64_t)row * a.ldw + (int64_t)kc0 * 32 + 8 * g);
+    else return (const u32x4*)(Wb + (int64_t)row * a.ldw + (int64_t)kc0 * 32 + 8 * g);
   };
-  auto wload = [&](const u32x4* base, int c) -> u32x4 {
+  auto wload = [&](const wvec* base, int c) -> wvec {
     return __builtin_nontemporal_load(base + c * 4);
+  };
+  // FP8: the A-row r of tile t (t < 0: row 0), its scale for this lane's row r16, and the bf16 fragment of 8 loaded bytes
+  auto row_of = [&](int t, int r) -> int {
+    if (t < 0) return 0;
+    if (glu) {
+      const int f = min(t * 8 + (r & 7), d.nout - 1);
+      return (f >> 4) * 32 + (f & 15) + (r >= 8 ? 16 : 0);
+    }
+    return min(t * d.rt + r, a.N - 1);
+  };
+  auto wscale = [&](int t) -> float {
+    if constexpr (FP8) return fp8_row_scale(rexp[row_of(t, r16)]);
+    else return 0.f;
+  };
+  auto wfrag = [&](const wvec& w, float s) -> u32x4 {
+    if constexpr (FP8) return fp8x8_to_bf16x8(w, s);
+    else return w;
   };
   const u32x4* xbase = (const u32x4*)((const bf16_t*)a.x + (int64_t)min(r16, nb - 1) * d.ba.x_bs + kofs + (int64_t)kc0 * 32 + 8 * g);
   auto xload = [&](int c) -> u32x4 { return xbase[c * 4]; };
@@ -191,7 +233,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
   // refilled with item j + 24 as soon as it has been multiplied; the stream loop below is unrolled over three tiles so that slot and
   // chunk indices are constants.  Otherwise (STREAM): CH (weight, activation) pairs.
   constexpr int RS = 24;
-  u32x4 ring[TRL ? 1 : (HOLD ? RS : CH)];
+  wvec ring[TRL ? 1 : (HOLD ? RS : CH)];
   u32x4 rx[HOLD ? 1 : CH];
   // ---- TRL: NR = 3 units of 8 row-contiguous loads (16 rows x 512 bytes = 8 chunks of this wave's K slice) = one and a half tiles in
   // flight (24 KiB per wave; four units next to the 16 held activation fragments spill)
@@ -213,9 +255,11 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
     return (const u32x4*)(Wb + (int64_t)row * a.ldw + kofs + (int64_t)wave * (cpw * 32) + sub * 256 + lp * 8);
   };
   int t0 = TRL ? -1 : next_tile(rem_ld), t1 = -1, t2 = -1;  // tile being multiplied, the next two (loads in flight / to be issued)
-  const u32x4* wp0 = wbase(t0);
-  const u32x4* wp1 = wp0;
-  const u32x4* wp2 = wp0;
+  const wvec* wp0 = wbase(t0);
+  const wvec* wp1 = wp0;
+  const wvec* wp2 = wp0;
+  float sc0 = 0.f, sc1 = 0.f, sc2 = 0.f;                    // FP8, generic forms: the scales of t0, t1, t2 for this lane's row
+  if constexpr (FP8 && !TRL) sc0 = wscale(t0);
   constexpr bool ASM_STREAM = HOLD && CPWT == CH && !USDM_MFMA_NO_ASM && !TRL;     // hand-counted loads (see the stream loop)
   int ua = -1, ub = -1, uc = -1;                            // TRL: the tile being multiplied and the next two
   // TRL with streamed activations (K = 14336): units are numbered through the tiles, 7 per tile; (lt, ls) = the next unit to load
@@ -229,13 +273,13 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
     for (int c = 0; c < 8; ++c) ld_nt_asm(X[q][c], xbase + (sub * 8 + c) * 4);
   };
   auto adv_unit = [&]() { if (++ls == UPT) { ls = 0; lt = next_tile(rem_ld); } };
-  if constexpr (TRL && !HOLD) {
+  if constexpr (!FP8 && TRL && !HOLD) {
     lt = next_tile(rem_ld);
     ld_unit_x(std::integral_constant<int, 0>{}, lt, ls); adv_unit();
     ld_unit_x(std::integral_constant<int, 1>{}, lt, ls); adv_unit();
   }
   int tq[4] = {-1, -1, -1, -1};                             // K-split form: the tiles whose single unit sits in slots 0 .. 3
-  if constexpr (TRL && HOLD && CPWT == 8) {
+  if constexpr (!FP8 && TRL && HOLD && CPWT == 8) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       tq[q] = next_tile(rem_ld);
@@ -243,7 +287,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
       for (int i = 0; i < 8; ++i) ld_nt_asm(U[q][i], unit_ptr(tq[q], 0, i));
     }
   }
-  if constexpr (TRL && HOLD && CPWT != 8) {
+  if constexpr (!FP8 && TRL && HOLD && CPWT != 8) {
     ua = next_tile(rem_ld); ub = next_tile(rem_ld); uc = next_tile(rem_ld);
 #pragma unroll
     for (int i = 0; i < 8; ++i) ld_nt_asm(U[0][i], unit_ptr(ua, 0, i));      // units 0, 1, 2 = (tile a, half 0), (a, 1), (b, 0)
@@ -272,6 +316,47 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
     }
     t2 = next_tile(rem_ld);
     wp2 = wbase(t2);
+    if constexpr (FP8) { sc1 = wscale(t1); sc2 = wscale(t2); }
+  }
+  // ---- FP8, row-contiguous forms: a unit = the 16 rows x ROW8 bytes of one tile's K slice of this wave (K = 4096: the whole 512-byte
+  // slice, two rows per load instruction as in bf16, 8 loads; K split / streamed: 256 bytes, four rows per instruction, 4 loads),
+  // then one byte load of the lane's row exponent (streamed: and the unit's 8 activation fragments), all hand-counted.  Twice the
+  // units of bf16 in flight, about the same bytes: K = 4096 three tiles (24 KiB per wave), K split eight, streamed three units.
+  constexpr int RPI8 = CPWT == 16 ? 2 : 4;                  // rows per load instruction
+  constexpr int ROW8 = 1024 / RPI8;                         // bytes of a row per unit
+  constexpr int NL8 = 16 / RPI8;                            // weight loads per unit
+  constexpr int NR8 = CPWT == 8 ? 8 : 3;                    // units in flight
+  constexpr int LPU8 = NL8 + 1 + (HOLD ? 0 : 8);            // loads per unit
+  using Slots8 = std::make_integer_sequence<int, NR8>;
+  u32x4 U8[FP8 && TRL ? NR8 : 1][NL8];
+  int E8[FP8 && TRL ? NR8 : 1];
+  u32x4 X8[FP8 && TRL && !HOLD ? NR8 : 1][8];
+  int tq8[FP8 && TRL ? NR8 : 1];                            // held forms: the tile whose unit sits in slot q (tile n in slot n % NR8)
+  const int lrow8 = lane / (64 / RPI8), lp8 = lane % (64 / RPI8);
+  auto unit8_ptr = [&](int t, int sub, int i) -> const u32x4* {
+    if (t < 0) return (const u32x4*)a.x + ((blockIdx.x * MW + wave) & 7) * 4 + (lane & 3) + i * 32;      // placeholder (see unit_ptr)
+    return (const u32x4*)((const uint8_t*)a.W + (int64_t)row_of(t, RPI8 * i + lrow8) * a.ldw + kofs + (int64_t)wave * (cpw * 32) +
+                          sub * ROW8 + lp8 * 16);
+  };
+  auto ld_unit8 = [&](auto SLOT, int t, int sub) __attribute__((always_inline)) {
+    constexpr int q = decltype(SLOT)::value;
+#pragma unroll
+    for (int i = 0; i < NL8; ++i) ld_nt_asm(U8[q][i], unit8_ptr(t, sub, i));
+    ld_exp_asm(E8[q], rexp + row_of(t, r16));
+    if constexpr (!HOLD) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) ld_nt_asm(X8[q][c], xbase + (sub * 8 + c) * 4);
+    }
+  };
+  if constexpr (FP8 && TRL && !HOLD) {
+    lt = next_tile(rem_ld);
+    each_slot(Slots8{}, [&](auto Q) __attribute__((always_inline)) { ld_unit8(Q, lt, ls); adv_unit(); });
+  }
+  if constexpr (FP8 && TRL && HOLD) {
+    each_slot(Slots8{}, [&](auto Q) __attribute__((always_inline)) {
+      tq8[decltype(Q)::value] = next_tile(rem_ld);
+      ld_unit8(Q, tq8[decltype(Q)::value], 0);
+    });
   }
 
   TRM(1);
@@ -451,7 +536,99 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
   };
 
   // ---- stream
-  if constexpr (TRL && !HOLD) {
+  if constexpr (FP8 && TRL) {
+    char* tb = smem + TB_OFF + wave * 8192;                 // this wave's transposition buffer: [16 rows][ROW8 bytes], piece ^ row
+    // wait for unit q (the younger units stay in flight), its rows -> LDS; returns the scale of this lane's row
+    auto take8 = [&](auto SLOT) __attribute__((always_inline)) -> float {
+      constexpr int q = decltype(SLOT)::value;
+      asm volatile("s_waitcnt vmcnt(%5)" : "+v"(U8[q][0]), "+v"(U8[q][1]), "+v"(U8[q][2]), "+v"(U8[q][3]), "+v"(E8[q])
+                   : "n"((NR8 - 1) * LPU8) : "memory");
+      if constexpr (NL8 == 8) asm volatile("" : "+v"(U8[q][4]), "+v"(U8[q][5]), "+v"(U8[q][6]), "+v"(U8[q][7]));
+      if constexpr (!HOLD)
+        asm volatile("" : "+v"(X8[q][0]), "+v"(X8[q][1]), "+v"(X8[q][2]), "+v"(X8[q][3]), "+v"(X8[q][4]), "+v"(X8[q][5]), "+v"(X8[q][6]), "+v"(X8[q][7]));
+#pragma unroll
+      for (int i = 0; i < NL8; ++i) {
+        const int r = RPI8 * i + lrow8;
+        *(u32x4*)(tb + r * ROW8 + ((lp8 ^ r) << 4)) = U8[q][i];
+      }
+      return fp8_row_scale(E8[q]);
+    };
+    // chunk c of this lane's row as bf16: 8 bytes of piece 2 c + g / 2, converted just before the MFMA
+    auto frag8 = [&](int c, float s) __attribute__((always_inline)) -> u32x4 {
+      const int p = 2 * c + (g >> 1);
+      return fp8x8_to_bf16x8(*(const u32x2*)(tb + r16 * ROW8 + ((p ^ r16) << 4) + (g & 1) * 8), s);
+    };
+    using Q0 = std::integral_constant<int, 0>; using Q1 = std::integral_constant<int, 1>; using Q2 = std::integral_constant<int, 2>;
+    if constexpr (!HOLD) {
+      // streamed activations (K = 14336): units numbered through the tiles, 7 per tile, in slot n % 3; the tile's chain runs over
+      // its units in order, as in bf16
+      int ct = next_tile(rem_cp), cs = 0;
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      auto unit = [&](auto SLOT) __attribute__((always_inline)) -> bool {
+        constexpr int q = decltype(SLOT)::value;
+        if (ct < 0) return false;
+        const float s = take8(SLOT);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc = mfma16(frag8(c, s), X8[q][c], acc);
+        ld_unit8(SLOT, lt, ls); adv_unit();
+        if (++cs == UPT) {
+          cs = 0;
+          const int t = ct;
+          ct = next_tile(rem_cp);
+          finish_tile(t, acc);
+          acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        return true;
+      };
+      while (unit(Q0{}) && unit(Q1{}) && unit(Q2{})) {}
+    } else if constexpr (CPWT == 8) {
+      // K split over workgroups: one unit per tile and wave, all (<= MTG) tiles of the workgroup in flight at once; reduced and merged
+      // after the stream, as in bf16
+      auto unit = [&](auto SLOT) __attribute__((always_inline)) {
+        constexpr int q = decltype(SLOT)::value;
+        const int t = tq8[q];
+        const float s = take8(SLOT);
+        tq8[q] = next_tile(rem_ld);
+        ld_unit8(SLOT, tq8[q], 0);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc = mfma16(frag8(c, s), xf[c], acc);
+        if (t >= 0) {
+          red[(done * MW + wave) * 64 + lane] = acc;
+          if (tid == 0) tl[done] = t;
+          ++done;
+        }
+      };
+      while (tq8[0] >= 0) each_slot(Slots8{}, unit);
+    } else {
+      // K = 4096: one unit = one tile; refilled with the tile three further on
+      auto tile8 = [&](auto SLOT) __attribute__((always_inline)) -> bool {
+        constexpr int q = decltype(SLOT)::value;
+        const int t = tq8[q];
+        if (t < 0) return false;
+        (void)next_tile(rem_cp);
+        const float s = take8(SLOT);
+        tq8[q] = next_tile(rem_ld);
+        ld_unit8(SLOT, tq8[q], 0);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 16; ++c) acc = mfma16(frag8(c, s), xf[c], acc);
+        finish_tile(t, acc);
+        return true;
+      };
+      while (tile8(Q0{}) && tile8(Q1{}) && tile8(Q2{})) {}
+    }
+    // drain: loads for tiles that do not exist may still be in flight; naming every load register after the wait keeps the compiler
+    // from reusing any of them before it
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int q = 0; q < NR8; ++q) {
+      asm volatile("" ::"v"(U8[q][0]), "v"(U8[q][1]), "v"(U8[q][2]), "v"(U8[q][3]), "v"(E8[q]) : "memory");
+      if constexpr (NL8 == 8) asm volatile("" ::"v"(U8[q][4]), "v"(U8[q][5]), "v"(U8[q][6]), "v"(U8[q][7]) : "memory");
+      if constexpr (!HOLD)
+        asm volatile("" ::"v"(X8[q][0]), "v"(X8[q][1]), "v"(X8[q][2]), "v"(X8[q][3]), "v"(X8[q][4]), "v"(X8[q][5]), "v"(X8[q][6]), "v"(X8[q][7]) : "memory");
+    }
+  } else if constexpr (TRL && !HOLD) {
     char* tb = smem + TB_OFF + wave * 8192;
     int ct = next_tile(rem_cp), cs = 0;                     // the unit being multiplied
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -585,13 +762,13 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
         const int sl = (CH * ph + c) % RS;
         if (c < cpw) {
           // item + 24 = (next tile, chunk c + 8) for c < 8, (tile after next, chunk c - 8) otherwise
-          const u32x4* np = c < RS - CH ? wp1 + (c + (RS - CH)) * 4 : wp2 + (c - (RS - CH)) * 4;
+          const wvec* np = c < RS - CH ? wp1 + (c + (RS - CH)) * 4 : wp2 + (c - (RS - CH)) * 4;
           if constexpr (stat) {
             if (c == 0) wait_mfma_asm<RS - 1, true>(acc, ring[sl], xf[c]);
             else wait_mfma_asm<RS - 1, false>(acc, ring[sl], xf[c]);
             ld_nt_asm(ring[sl], np);
           } else {
-            acc = mfma16(ring[sl], xf[c], acc);
+            acc = mfma16(wfrag(ring[sl], sc0), xf[c], acc);
             if ((c < RS - CH ? c + (RS - CH) : c - (RS - CH)) < cpw) ring[sl] = __builtin_nontemporal_load(np);
             __builtin_amdgcn_sched_barrier(0);               // keep (multiply, refill) pairs in program order
           }
@@ -608,6 +785,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
       t0 = t1; t1 = t2; wp1 = wp2;
       t2 = next_tile(rem_ld);
       wp2 = wbase(t2);
+      if constexpr (FP8) { sc0 = sc1; sc1 = sc2; sc2 = wscale(t2); }
       return true;
     };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
@@ -638,14 +816,14 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
     // activations streamed beside the weights (K slices longer than CH chunks: down_proj): a ring of CH (weight, activation) pairs,
     // each refilled CH chunks ahead as soon as it has been multiplied
     int t = next_tile(rem_cp);
-    const u32x4* wp = wp0;
+    const wvec* wp = wp0;
     while (t >= 0) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       for (int c0 = 0; c0 < cpw; c0 += CH) {
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
           if (c0 + u < cpw) {
-            acc = mfma16(ring[u], rx[u], acc);
+            acc = mfma16(wfrag(ring[u], sc0), rx[u], acc);
             const int cn = c0 + u + CH;
             if (cn < cpw) { ring[u] = wload(wp, cn); rx[u] = xload(cn); }
             __builtin_amdgcn_sched_barrier(0);
@@ -655,6 +833,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d) {
       finish_tile(t, acc);
       t = next_tile(rem_cp);
       wp = wbase(t);
+      if constexpr (FP8) sc0 = wscale(t);
 #pragma unroll
       for (int c = 0; c < CH; ++c)
         if (c < cpw) { ring[c] = wload(wp, c); rx[c] = xload(c); }
@@ -702,26 +881,29 @@ extern "C" int64_t usdm_gemv_batch_ks_floats(int32_t N, int32_t K) {
   return (int64_t)cdiv(N, 16) * (K / KS_K) * 256;
 }
 
-// called by usdm_gemv_batch (llm_batch_k.hip) for 5..16 sequences, or when the caller forces the matrix-core form
-int usdm_gemv_mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st) {
+namespace {
+// the matrix-core launch of usdm_gemv_batch (bf16) and usdm_gemv_fp8_mfma (FP8: fmt = the row exponents); both take the same
+// decisions (tiles, rows per tile, K split, variant) for the same shape
+template <bool FP8, class... FMT>
+int mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st, const char* who, FMT... fmt) {
   const usdm_gemv_args& a = pa->g;
-  USDM_CHECK_ARG(pa->nb >= 1 && pa->nb <= 16, "usdm_gemv_batch (matrix-core form): 1..16 sequences per step");
+  USDM_CHECK_ARG(pa->nb >= 1 && pa->nb <= 16, "%s (matrix-core form): 1..16 sequences per step", who);
   USDM_CHECK_ARG(a.K % (MW * 32) == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && pa->x_bs % 8 == 0,
-                 "usdm_gemv_batch (matrix-core form): K %% %d, ldw %% 8, x stride %% 8", MW * 32);
+                 "%s (matrix-core form): K %% %d, ldw %% 8, x stride %% 8", who, MW * 32);
   const bool glu = a.act == USDM_ACT_SWIGLU, lmh = a.part_val != nullptr;
   MfmaDev d;
   d.ba = *pa;
   d.nchunks = a.K / 32;
   d.cpw = cdiv(d.nchunks, MW);
   const bool hold = d.cpw <= CH;
-  USDM_CHECK_ARG(!a.norm_w || (hold && a.K <= GAM_FLOATS && a.K % 4 == 0), "usdm_gemv_batch (matrix-core form): the fused RMSNorm needs K <= 4096");
-  USDM_CHECK_ARG(!lmh || (a.part_idx && !glu), "usdm_gemv_batch: lm_head partial buffers");
+  USDM_CHECK_ARG(!a.norm_w || (hold && a.K <= GAM_FLOATS && a.K % 4 == 0), "%s (matrix-core form): the fused RMSNorm needs K <= 4096", who);
+  USDM_CHECK_ARG(!lmh || (a.part_idx && !glu), "%s: lm_head partial buffers", who);
   d.nout = glu ? a.N / 2 : a.N;
   d.rt = 16;
   d.ksplit = 1;
   const int64_t ksf = usdm_gemv_batch_ks_floats(a.N, a.K);
   if (ksf && pa->ks_part && pa->ks_cnt && !glu && !lmh && !a.norm_w && pa->form != 3 && pa->form != 5) {
-    USDM_CHECK_ARG(pa->ks_part_floats >= ksf && (((uintptr_t)pa->ks_part) & 15) == 0, "usdm_gemv_batch: ks_part must hold %lld floats (16-byte aligned)", (long long)ksf);
+    USDM_CHECK_ARG(pa->ks_part_floats >= ksf && (((uintptr_t)pa->ks_part) & 15) == 0, "%s: ks_part must hold %lld floats (16-byte aligned)", who, (long long)ksf);
     d.ksplit = a.K / KS_K;
     if (cdiv(cdiv(a.N, 16), min(256 / d.ksplit, cdiv(a.N, 16))) > MTG_TRL) d.ksplit = 1;      // one reduction group per workgroup
   }
@@ -748,32 +930,64 @@ int usdm_gemv_mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st) {
     d.grid = d.kwg * d.ksplit;
     d.cpw = KS_K / 32 / MW;
   }
-  USDM_CHECK_ARG(cdiv(d.ntiles, d.kwg) <= 64, "usdm_gemv_batch (matrix-core form): N too large (more than 64 tiles per workgroup)");
-  USDM_CHECK_ARG(!lmh || pa->part_bs >= d.grid, "usdm_gemv_batch: part_bs must hold one partial per workgroup (%d)", d.grid);
+  USDM_CHECK_ARG(cdiv(d.ntiles, d.kwg) <= 64, "%s (matrix-core form): N too large (more than 64 tiles per workgroup)", who);
+  USDM_CHECK_ARG(!lmh || pa->part_bs >= d.grid, "%s: part_bs must hold one partial per workgroup (%d)", who, d.grid);
   // K = 4096 (every RMSNorm-fed projection and o_proj of the 7B): row-contiguous loads re-cut through LDS; form 3 forces the
   // fragment-shaped loads there (A/B: tools/gemv_mfma_bench.py)
   const bool trl = (hold ? d.cpw == 16 : d.cpw == 56) && pa->form != 3;
   if (d.ksplit > 1) {
     static bool ks_attr = false;
-    if (!ks_attr) { (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL); ks_attr = true; }
-    hipLaunchKernelGGL((gemv_mfma_kernel<true, 8, true>), dim3(d.grid), dim3(MW * 64), LDS_BYTES_TRL, st, d);
+    if (!ks_attr) { (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 8, true, FP8, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL); ks_attr = true; }
+    hipLaunchKernelGGL((gemv_mfma_kernel<true, 8, true, FP8, FMT...>), dim3(d.grid), dim3(MW * 64), LDS_BYTES_TRL, st, d, fmt...);
     USDM_LAUNCH_CHECK();
     return 0;
   }
-  void (*kfn)(const MfmaDev) = trl ? (hold ? gemv_mfma_kernel<true, 16, true> : gemv_mfma_kernel<false, 56, true>)
-                             : hold ? (d.cpw == 16 ? gemv_mfma_kernel<true, 16, false> : gemv_mfma_kernel<true, 0, false>)
-                                    : (d.cpw == 56 ? gemv_mfma_kernel<false, 56, false> : gemv_mfma_kernel<false, 0, false>);
+  void (*kfn)(const MfmaDev, FMT...);
   static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
-    (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
-    (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_done = true;
+  if constexpr (FP8) {      // (the fragment-shaped variants of K = 4096 / 14336 are form 3 only: bf16)
+    kfn = trl ? (hold ? gemv_mfma_kernel<true, 16, true, true, FMT...> : gemv_mfma_kernel<false, 56, true, true, FMT...>)
+              : (hold ? gemv_mfma_kernel<true, 0, false, true, FMT...> : gemv_mfma_kernel<false, 0, false, true, FMT...>);
+    if (!attr_done) {
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, true, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, true, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 0, false, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 0, false, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      attr_done = true;
+    }
+  } else {
+    kfn = trl ? (hold ? gemv_mfma_kernel<true, 16, true> : gemv_mfma_kernel<false, 56, true>)
+              : hold ? (d.cpw == 16 ? gemv_mfma_kernel<true, 16, false> : gemv_mfma_kernel<true, 0, false>)
+                     : (d.cpw == 56 ? gemv_mfma_kernel<false, 56, false> : gemv_mfma_kernel<false, 0, false>);
+    if (!attr_done) {
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      attr_done = true;
+    }
   }
-  hipLaunchKernelGGL(kfn, dim3(d.grid), dim3(MW * 64), trl ? LDS_BYTES_TRL : LDS_BYTES, st, d);
+  hipLaunchKernelGGL(kfn, dim3(d.grid), dim3(MW * 64), trl ? LDS_BYTES_TRL : LDS_BYTES, st, d, fmt...);
   USDM_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace
+
+// called by usdm_gemv_batch (llm_batch_k.hip) for 5..16 sequences, or when the caller forces the matrix-core form
+int usdm_gemv_mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st) { return mfma_launch<false>(pa, st, "usdm_gemv_batch"); }
+
+extern "C" int usdm_gemv_fp8_mfma(const usdm_gemv_fp8_args* pa, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->b.g.W && pa->b.g.x && pa->row_exp, "usdm_gemv_fp8_mfma: null args");
+  const usdm_gemv_batch_args& b = pa->b;
+  const usdm_gemv_args& a = b.g;
+  USDM_CHECK_ARG(b.nb >= 1 && b.nb <= 16, "usdm_gemv_fp8_mfma: 1..16 sequences per step");
+  USDM_CHECK_ARG(b.form == 0 || b.form == 5, "usdm_gemv_fp8_mfma: form 0 (K split where ks_* allow it) or 5 (no K split)");
+  USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.mrg_pm && !a.mrg_pl && !a.cmb_gran && !a.x_delta && !a.x_out,
+                 "usdm_gemv_fp8_mfma: p2p / merged-attention input / cmb_gran / x_delta are not supported");
+  USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.ldw % 16 == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.x & 15) == 0,
+                 "usdm_gemv_fp8_mfma: bad N/K, or W / ldw / x not 16-byte aligned");
+  USDM_CHECK_ARG(a.y16 || a.y32 || a.part_val, "usdm_gemv_fp8_mfma: no output");
+  USDM_CHECK_ARG(a.act != USDM_ACT_SWIGLU || a.N % 32 == 0, "usdm_gemv_fp8_mfma: swiglu needs N %% 32 == 0 (packed gate/up rows)");
+  return mfma_launch<true>(&b, (hipStream_t)stream, "usdm_gemv_fp8_mfma", pa->row_exp);
 }

@@ -111,12 +111,17 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
 
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
-                 p2p_fused=None, quantization=None):
+                 p2p_fused=None, quantization=None, fp8_matrix_cores=False):
         if quantization not in (None, "fp8"):
             raise ValueError(f"quantization={quantization!r}: supported are None (bf16) and 'fp8' (e4m3 weights, power-of-two row scales)")
         if quantization == "fp8" and (tp_size > 1 or tp_segments or p2p is not None):
             raise NotImplementedError("quantization='fp8' runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes bf16 weights")
+        if fp8_matrix_cores and quantization != "fp8":
+            raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
         self.quantization = quantization
+        # fp8_matrix_cores (opt-in): decode steps of 5..16 sequences on the matrix cores (usdm_gemv_fp8_mfma) instead of groups of 4;
+        # like bf16's matrix-core form they equal the oracle up to near-ties, not generate() bit for bit
+        self.fp8_matrix_cores = bool(fp8_matrix_cores)
         self.cfg = dict(cfg)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -765,6 +770,10 @@ class USDMForCausalLM:
         segs = []
         part, part2 = (Z(B, H, dt=torch.float32), Z(B, H, dt=torch.float32)) if tp else (None, None)
 
+        # fp8_matrix_cores: the FP8 projections of 5..16 sequences on the matrix cores (usdm_gemv_fp8_mfma: the bf16 form's tiles, K
+        # split and epilogues, so the same ks scratch); <= 4 keep the VALU FP8 form of gemv_batch
+        gemv_b = ops.gemv_fp8_mfma if (self.fp8_matrix_cores and B > 4) else ops.gemv_batch
+
         def row_parallel(W, x, K, buf, plan):
             ops.gemv_batch(W, x, nb=B, N=H, K=K, x_bs=K, y_bs=H, round_bf16=False, y32=buf, plan=plan)
             segs.extend([plan, (lambda t=buf: self._all_reduce(t))])
@@ -773,23 +782,23 @@ class USDMForCausalLM:
             return plan
         for l in range(L):
             w = self.W["layers"][l]
-            ops.gemv_batch(w["qkv"], h, nb=B, N=nq, K=H, x_bs=H, y_bs=nq, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, plan=plan)
+            gemv_b(w["qkv"], h, nb=B, N=nq, K=H, x_bs=H, y_bs=nq, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, plan=plan)
             ops.attn_decode(qkv, bb["pos"], self.cos, self.sin, bb["kc"][0, l], bb["vc"][0, l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
                             ctx_max=self.ctx_max, NS=NS, scale=d ** -0.5, batch=B, qkv_bs=nq, out_bs=Hq * d, cache_bs=cache_bs, window=self.window,
                             counters=cnt, plan=plan)
             if tp:
                 plan = row_parallel(w["o"], ao, Hq * d, part, plan)
             else:
-                ops.gemv_batch(w["o"], ao, nb=B, N=H, K=Hq * d, x_bs=Hq * d, y_bs=H, res_bs=H, residual=h, y16=h, plan=plan)
-            ops.gemv_batch(w["gu"], h, nb=B, N=2 * I, K=H, x_bs=H, y_bs=I, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU,
-                           y16=act, plan=plan)
+                gemv_b(w["o"], ao, nb=B, N=H, K=Hq * d, x_bs=Hq * d, y_bs=H, res_bs=H, residual=h, y16=h, plan=plan)
+            gemv_b(w["gu"], h, nb=B, N=2 * I, K=H, x_bs=H, y_bs=I, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU,
+                   y16=act, plan=plan)
             if tp:
                 plan = row_parallel(w["down"], act, I, part2, plan)
             else:
-                ops.gemv_batch(w["down"], act, nb=B, N=H, K=I, x_bs=I, y_bs=H, res_bs=H, residual=h, y16=h, ks=ks, plan=plan)
-        ops.gemv_batch(self.W["lm_head"], h, nb=B, N=self.v1 - self.v0, K=H, x_bs=H, part_bs=self.nparts, norm_w=self.W["norm"],
-                       eps=c["rms_norm_eps"], ban=self.ban, part_val=bb["pv"], part_idx=bb["pi"], idx_offset=self.v0,
-                       **(dict(y32=bb["logits"], y_bs=self.Vloc) if sampling else {}), plan=plan)
+                gemv_b(w["down"], act, nb=B, N=H, K=I, x_bs=I, y_bs=H, res_bs=H, residual=h, y16=h, ks=ks, plan=plan)
+        gemv_b(self.W["lm_head"], h, nb=B, N=self.v1 - self.v0, K=H, x_bs=H, part_bs=self.nparts, norm_w=self.W["norm"],
+               eps=c["rms_norm_eps"], ban=self.ban, part_val=bb["pv"], part_idx=bb["pi"], idx_offset=self.v0,
+               **(dict(y32=bb["logits"], y_bs=self.Vloc) if sampling else {}), plan=plan)
         st = ops.decode_state(bb["nxt"], bb["out"], bb["step"], bb["pos"], advance_pos=True, batch=B)
         if sampling and tp:   # [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
             segs.extend([plan, (lambda: self._gather_partials([bb["lg"]], [bb["logits"]]))])
@@ -818,9 +827,14 @@ class USDMForCausalLM:
         """Sequences one decode step can take with THIS model's (per-rank) shapes: 16 on the matrix-core form, which splits K over
         8 waves in chunks of 32 (every projection's K must be a multiple of 256), else the 4 of the VALU form."""
         c = self.cfg
-        if self.quantization == "fp8":      # usdm_gemv_fp8 has the VALU form only
-            return 4
         ks = (c["hidden_size"], self.Hq * c["head_dim"], self.I)
+        if self.quantization == "fp8":
+            if not self.fp8_matrix_cores:       # usdm_gemv_fp8: the VALU form only
+                return 4
+            # usdm_gemv_fp8_mfma refuses what the launcher cannot run: K % 256, the fused RMSNorm with K > 4096, more than 64
+            # lm_head tiles of 16 rows per workgroup
+            fits = all(k % 256 == 0 for k in ks) and c["hidden_size"] <= 4096 and -(-(self.v1 - self.v0) // 16) <= 64 * 256
+            return self.MAX_BATCH if fits else 4
         return self.MAX_BATCH if all(k % 256 == 0 for k in ks) else 4
 
     @torch.no_grad()

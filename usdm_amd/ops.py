@@ -404,7 +404,8 @@ def rope_cache(qkv, cos, sin, kcache, vcache, *, ld, S, pos0, Hq, Hkv, ctx_max, 
 
 
 def gemv_batch(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
-               residual=None, y16=None, y32=None, ban=None, part_val=None, part_idx=None, idx_offset=0, form=0, ks=None, plan=None):
+               residual=None, y16=None, y32=None, ban=None, part_val=None, part_idx=None, idx_offset=0, form=0, ks=None, plan=None,
+               only_args=False):
     """usdm_gemv_batch: the decode projection over nb <= 16 input vectors (x is [nb][x_bs], outputs [nb][y_bs]).
     form 0: VALU kernel for nb <= 4, matrix-core kernel above; 1: matrix cores; -1: VALU; 3 / 5: A/B forms of the matrix-core kernel.
     ks = (part f32 [gemv_batch_ks_floats(N, K)], counters int32 [ceil(N / 16)], zero): K split over workgroups (K > 4096)."""
@@ -423,12 +424,29 @@ def gemv_batch(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, n
         if part.dtype != torch.float32 or cnt.dtype != torch.int32 or cnt.numel() < -(-N // 16):
             raise ValueError("usdm_gemv_batch: ks = (float32 partials, int32 counters [ceil(N / 16)])")
         b.ks_part, b.ks_cnt, b.ks_part_floats = _ptr(part), _ptr(cnt), part.numel()
+    if only_args:         # (gemv_fp8_mfma: the filled usdm_gemv_batch_args)
+        return b
     if isinstance(W, Fp8Weight):     # usdm_gemv_fp8: nb 1..4, VALU form (bit-identical with the bf16 launch on the dequantized matrix)
         f = GemvFp8Args()
         f.b, f.row_exp = b, _ptr(W.e)
         _go(plan, "usdm_gemv_fp8", lib.usdm_gemv_fp8, C_.byref(f))
         return
     _go(plan, "usdm_gemv_batch", lib.usdm_gemv_batch, C_.byref(b))
+
+
+def gemv_fp8_mfma(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
+                  residual=None, y16=None, y32=None, ban=None, part_val=None, part_idx=None, idx_offset=0, form=0, ks=None, plan=None):
+    """usdm_gemv_fp8_mfma: the matrix-core form (nb <= 16) on a quant.Fp8Weight, opt-in.  Keywords as gemv_batch; form 0 (K split
+    where ks is given) or 5 (no split).  Equals gemv_batch(W.dequantize(), ..., form=1 or 5) bit for bit; NOT bit-identical with the
+    VALU form that gemv_batch runs on an Fp8Weight (nb <= 4)."""
+    if not isinstance(W, Fp8Weight):
+        raise TypeError("gemv_fp8_mfma takes a quant.Fp8Weight (bf16 weights: gemv_batch)")
+    b = gemv_batch(W.q, x, nb=nb, N=N, K=K, x_bs=x_bs, y_bs=y_bs, res_bs=res_bs, part_bs=part_bs, ldw=ldw, norm_w=norm_w, eps=eps,
+                   act=act, round_bf16=round_bf16, residual=residual, y16=y16, y32=y32, ban=ban, part_val=part_val, part_idx=part_idx,
+                   idx_offset=idx_offset, form=form, ks=ks, only_args=True)
+    f = GemvFp8Args()
+    f.b, f.row_exp = b, _ptr(W.e)
+    _go(plan, "usdm_gemv_fp8_mfma", lib.usdm_gemv_fp8_mfma, C_.byref(f))
 
 
 def dequant_fp8(W, out, plan=None):

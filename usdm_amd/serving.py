@@ -104,19 +104,24 @@ class LLM:
     download_dir), or `LLM(model=<USDMForCausalLM>, tokenizer=<tokenizer>)` around objects that are already loaded."""
 
     def __init__(self, model, tokenizer=None, download_dir=None, gpu_memory_utilization=0.9, max_model_len=None, device="cuda",
-                 dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, **unused):
+                 dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, **unused):
         # max_num_seqs (vllm's name): sequences decoded per step, 1..16.  <= 4: the VALU batch kernel (per slot bit-identical with the
         # single-request path); above: the matrix-core form (usdm_gemv_batch form 1)
         self.max_slots = max(1, min(int(max_num_seqs), MAX_SLOTS))
         # quantization (vllm's name): None = bf16, "fp8" = e4m3 weights with power-of-two row scales (usdm_amd/quant.py); the
-        # FP8 model decodes at most 4 sequences per step (its max_batch())
+        # FP8 model decodes at most 4 sequences per step (its max_batch()) unless fp8_matrix_cores (opt-in) runs steps of 5..16
+        # sequences on the matrix cores (usdm_gemv_fp8_mfma)
         if quantization not in (None, "fp8"):
             raise ValueError(f"quantization={quantization!r} is not supported (None or 'fp8')")
+        if fp8_matrix_cores and quantization != "fp8":
+            raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
         from .llm import USDMForCausalLM
         if isinstance(model, USDMForCausalLM):
             if quantization is not None and getattr(model, "quantization", None) != quantization:
                 raise ValueError(f"quantization={quantization!r}, but the model object was loaded with "
                                  f"quantization={getattr(model, 'quantization', None)!r}")
+            if fp8_matrix_cores and not getattr(model, "fp8_matrix_cores", False):
+                raise ValueError("fp8_matrix_cores=True, but the model object was loaded with fp8_matrix_cores=False")
             self.llm = model
         else:
             from .checkpoints import resolve_local
@@ -125,7 +130,8 @@ class LLM:
                 from transformers import AutoTokenizer
                 tokenizer = AutoTokenizer.from_pretrained(path, local_files_only=True)
             ctx = min(int(max_model_len or getattr(tokenizer, "model_max_length", 4096) or 4096), 8192)
-            self.llm = USDMForCausalLM.from_pretrained(path, device=device, ctx_max=ctx, quantization=quantization)
+            self.llm = USDMForCausalLM.from_pretrained(path, device=device, ctx_max=ctx, quantization=quantization,
+                                                       fp8_matrix_cores=fp8_matrix_cores)
         if isinstance(tokenizer, str):
             from transformers import AutoTokenizer
             tokenizer = AutoTokenizer.from_pretrained(tokenizer, local_files_only=True)
