@@ -451,6 +451,34 @@ typedef struct usdm_attn_decode_args {
 } usdm_attn_decode_args;
 int usdm_attn_decode(const usdm_attn_decode_args* args, usdm_stream_t stream);
 
+/* FP8 KV cache (opt-in, usdm_amd/quant.py quantize_kv_rows): a cache row = the 128 values of one (token, kv head) as OCP e4m3fn
+ * bytes plus ONE int8 power-of-two exponent, exactly quantize_rows of the bf16 row the bf16 cache would hold.  Caches: uint8
+ * [Hkv][ctx_max][128] (16-byte aligned), exponents int8 [Hkv][ctx_max] (4-byte aligned); zero-initialised = rows of 0.0.
+ *
+ * usdm_attn_decode_fp8: a.kcache / a.vcache are the byte caches, a.cache_bs is in bytes, everything else as usdm_attn_decode's
+ * split form (batch, window, skip, counters, defer_merge, cmb_gran).  The cached rows are converted exactly to the bf16 values
+ * K' / V' in registers and the bf16 arithmetic runs unchanged: out (or the partials) equal usdm_attn_decode on the dequantized
+ * caches bit for bit.  The new token's own K / V are used unquantized (as the bf16 kernel takes them from LDS, not from the cache);
+ * the appended row is quantize_rows of the bf16 row usdm_attn_decode appends.  Refused (error, no fall-back): NS == 1 (the
+ * one-workgroup form is not built for fp8 caches), unaligned caches / exponents, and everything usdm_attn_decode refuses. */
+typedef struct usdm_attn_decode_fp8_args {
+  usdm_attn_decode_args a;
+  int8_t* kexp; int8_t* vexp;   /* [Hkv][ctx_max] */
+  int64_t exp_bs;               /* batched: item b's exponents at kexp + b * exp_bs (a multiple of 4) */
+} usdm_attn_decode_fp8_args;
+int usdm_attn_decode_fp8(const usdm_attn_decode_fp8_args* args, usdm_stream_t stream);
+/* Prefill twin of usdm_rope_cache: q and k roped as there (q in place); the S new K / V rows are QUANTIZED into r.kcache /
+ * r.vcache (+ kexp / vexp) at positions pos0 .. pos0+S-1; the bf16 roped K rows go to kscr [Hkv][kscr_ld][128] (row s = token s of
+ * this call) and V^T to r.vt [Hkv][128][vt_ld] - the unquantized operands of the prompt's own usdm_attention (either may be NULL). */
+typedef struct usdm_rope_fp8_args {
+  usdm_rope_args r;
+  int8_t* kexp; int8_t* vexp;   /* [Hkv][ctx_max] */
+  void* kscr; int64_t kscr_ld;
+} usdm_rope_fp8_args;
+int usdm_rope_cache_fp8(const usdm_rope_fp8_args* args, usdm_stream_t stream);
+int usdm_sizeof_attn_decode_fp8_args(void);
+int usdm_sizeof_rope_fp8_args(void);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot peer-to-peer all-reduce for the tensor-parallel decode step (replaces the single-GPU
  * model.generate of src/inference.py:116-123 when the 7B is sharded over the 8 GPUs of a node).  Messages are 4096 f32

@@ -22,6 +22,8 @@ lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)      # (global: the experimental libr
 lib.usdm_last_error.restype = C.c_char_p
 lib.usdm_gemv_batch_ks_floats.restype = C.c_int64
 lib.usdm_gemv_fp8_mfma.restype = C.c_int     # (the FP8 matrix-core form; resolving it here makes a stale library fail at import)
+lib.usdm_attn_decode_fp8.restype = C.c_int   # (the FP8 KV cache entry points: likewise)
+lib.usdm_rope_cache_fp8.restype = C.c_int
 _exp = None
 
 
@@ -199,6 +201,14 @@ class AttnDecodeArgs(C.Structure):
     ]
 
 
+class AttnDecodeFp8Args(C.Structure):
+    _fields_ = [("a", AttnDecodeArgs), ("kexp", C.c_void_p), ("vexp", C.c_void_p), ("exp_bs", C.c_int64)]
+
+
+class RopeFp8Args(C.Structure):
+    _fields_ = [("r", RopeArgs), ("kexp", C.c_void_p), ("vexp", C.c_void_p), ("kscr", C.c_void_p), ("kscr_ld", C.c_int64)]
+
+
 def check(rc, what=""):
     if rc != 0:
         raise UsdmError(f"{what} failed (rc={rc}): {lib.usdm_last_error().decode()}")
@@ -212,7 +222,8 @@ def _selfcheck():
     for name, cls in (("norm", NormArgs), ("snake", SnakeArgs), ("attn", AttnArgs), ("vb_input", VbInputArgs),
                       ("vb_solver", VbSolverArgs), ("gemv", GemvArgs), ("decode_state", DecodeState),
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
-                      ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("p2p_dev", P2pDev)):
+                      ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("p2p_dev", P2pDev),
+                      ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

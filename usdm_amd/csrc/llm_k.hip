@@ -603,6 +603,78 @@ __global__ void rope_cache_kernel(const usdm_rope_args a) {
   }
 }
 
+// ---- FP8 KV cache (opt-in; usdm_amd/quant.py quantize_kv_rows): the device side of quantize_rows for ONE row of 128 bf16 values.
+// e = the smallest integer with amax / 2^e <= 448 = 1.75 * 2^8, clamped to [-117, 119], 0 for a zero row (quant._row_exponents):
+// from amax's exponent field and a mantissa test.  (An f32 subnormal amax has field 0 and lands on the lower clamp, where it belongs.)
+__device__ __forceinline__ int kv8_row_exp(float amax) {
+  const unsigned b = __builtin_bit_cast(unsigned, amax);
+  if ((b & 0x7fffffffu) == 0u) return 0;
+  const int e = (int)((b >> 23) & 0xffu) - 127 - 8 + ((b & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return min(119, max(-117, e));
+}
+// f32 (finite) -> OCP e4m3fn byte, round to nearest even, saturating at +-448: integer arithmetic, so that the bytes do not depend
+// on a conversion instruction's corner cases (torch's float8_e4m3fn cast gives the same byte for every |x| <= 448).
+__device__ __forceinline__ unsigned kv8_byte(float x) {
+  const unsigned sgn = (__builtin_bit_cast(unsigned, x) >> 24) & 0x80u;
+  const float ax = fminf(fabsf(x), 448.0f);
+  if (ax >= 0x1p-6f) {                       // e4m3 normal: keep 3 mantissa bits (ties to even), rebias 127 -> 7
+    unsigned u = __builtin_bit_cast(unsigned, ax);
+    u += 0x7ffffu + ((u >> 20) & 1u);
+    return sgn | ((u >> 20) - (120u << 3));
+  }
+  return sgn | (unsigned)rintf(ax * 512.0f);  // subnormal: multiples of 2^-9 (8 = the smallest normal, the same encoding)
+}
+// the calling wave's 64 lanes hold the row, x0 / x1 = elements 2 * lane, 2 * lane + 1 (bf16 values): bytes to row8, exponent to *ep
+__device__ __forceinline__ void kv8_store_row(float x0, float x1, int lane, uint8_t* row8, int8_t* ep) {
+  // row maximum on the magnitude BITS (monotonic for finite values): independent of how v_max treats f32 subnormals
+  unsigned m = max(__builtin_bit_cast(unsigned, x0) & 0x7fffffffu, __builtin_bit_cast(unsigned, x1) & 0x7fffffffu);
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+  const int e = kv8_row_exp(__builtin_bit_cast(float, m));
+  const float inv = fp8_row_scale(-e);       // exact power-of-two scaling
+  *(unsigned short*)(row8 + 2 * lane) = (unsigned short)(kv8_byte(x0 * inv) | (kv8_byte(x1 * inv) << 8));
+  if (lane == 0) *ep = (int8_t)e;
+}
+
+// prefill with an FP8 KV cache: RoPE of q,k in place as rope_cache_kernel; the quantized K / V rows + exponents go to the caches,
+// the bf16 K rows and V^T that the prefill attention consumes to per-plan scratch (the prompt attends to its unquantized K / V).
+// One wave per (token, head); a lane owns elements 2 * lane, 2 * lane + 1 and the rotation partner comes from lane ^ 32.
+__global__ __launch_bounds__(64) void rope_cache_fp8_kernel(const usdm_rope_args a, int8_t* kexp, int8_t* vexp, bf16_t* kscr, int64_t kscr_ld) {
+  const int s = blockIdx.x, hh = blockIdx.y;
+  const int lane = threadIdx.x;
+  const int pos = a.pos0 + s;
+  bf16_t* row = (bf16_t*)a.qkv + (int64_t)s * a.ld + hh * 128;
+  const int d0 = 2 * lane, dd = d0 & 63;     // rope pairs (d, d + 64): this lane holds d0, d0 + 1 of one half, lane ^ 32 the other
+  const unsigned raw = *(const unsigned*)(row + d0);
+  const float x0 = bf2f(raw & 0xffff), x1 = bf2f(raw >> 16);
+  float y0 = x0, y1 = x1;
+  if (hh < a.Hq + a.Hkv) {
+    const float p0 = __shfl_xor(x0, 32, 64), p1 = __shfl_xor(x1, 32, 64);
+    const float c0 = bf2f(a.cos[(int64_t)pos * 64 + dd]), s0 = bf2f(a.sin[(int64_t)pos * 64 + dd]);
+    const float c1 = bf2f(a.cos[(int64_t)pos * 64 + dd + 1]), s1 = bf2f(a.sin[(int64_t)pos * 64 + dd + 1]);
+    float o1, o2;
+    if (lane < 32) { rope_pair(x0, p0, c0, s0, o1, o2); y0 = o1; rope_pair(x1, p1, c1, s1, o1, o2); y1 = o1; }
+    else { rope_pair(p0, x0, c0, s0, o1, o2); y0 = o2; rope_pair(p1, x1, c1, s1, o1, o2); y1 = o2; }
+  }
+  const unsigned packed = pack_bf2(y0, y1);  // exact: y0 / y1 are bf16 values
+  if (hh < a.Hq) {
+    *(unsigned*)(row + d0) = packed;
+  } else if (hh < a.Hq + a.Hkv) {
+    const int kh = hh - a.Hq;
+    // (as in rope_cache_kernel, the k section of qkv itself stays unroped)
+    if (kscr) *(unsigned*)(kscr + ((int64_t)kh * kscr_ld + s) * 128 + d0) = packed;
+    kv8_store_row(y0, y1, lane, (uint8_t*)a.kcache + ((int64_t)kh * a.ctx_max + pos) * 128, kexp + (int64_t)kh * a.ctx_max + pos);
+  } else {
+    const int vh = hh - a.Hq - a.Hkv;
+    kv8_store_row(x0, x1, lane, (uint8_t*)a.vcache + ((int64_t)vh * a.ctx_max + pos) * 128, vexp + (int64_t)vh * a.ctx_max + pos);
+    if (a.vt) {
+      bf16_t* vt = (bf16_t*)a.vt + (int64_t)vh * 128 * a.vt_ld;
+      vt[(int64_t)d0 * a.vt_ld + s] = (bf16_t)(raw & 0xffff);
+      vt[(int64_t)(d0 + 1) * a.vt_ld + s] = (bf16_t)(raw >> 16);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Decode attention, split over the context: grid (Hkv, NS).  Each block ropes the new q (G heads of
 // its kv head) and the new k itself, so no block depends on another block's cache write.
@@ -611,8 +683,26 @@ constexpr int DA_KMAX = 512;  // max keys per split
 // PIPE (round 4, the many-sequence step: few splits of up to 512 keys each): the K / V rows of the NEXT batch of keys are requested
 // before the current batch is consumed (second register set).  The batch-1 step (NS = 32: ~20 keys per split, one batch) keeps
 // the plain form.  Same keys per thread in the same order: bit-identical results (profiles/r04_decode_ablation.txt 11).
-template <int G, bool PIPE = false>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode_args a) {
+// FP8 (opt-in, usdm_attn_decode_fp8): the caches hold e4m3 rows with one power-of-two exponent per (key, kv head)
+// (usdm_amd/quant.py).  A lane's 16 d of a K row are 16 bytes, a thread's 4 d of a V row 4 bytes; they are converted exactly to the
+// bf16 values K' / V' in registers and the bf16 arithmetic runs unchanged on the same keys per lane in the same order, so the
+// result equals the bf16 kernel's on the dequantized caches bit for bit.  Sweep depth: USDM_KV8_SWEEPS below.
+// The exponents are requested with the rows.  The cache pointers of usdm_attn_decode_args are the byte caches; the exponent
+// pointers come as one extra kernel argument (FP8 only: the bf16 instantiations keep their signature and code).
+#ifndef USDM_KV8_SWEEPS
+#define USDM_KV8_SWEEPS 4   // sweeps in flight of the FP8 instantiations.  4 = the bf16 depth, i.e. half the bytes in flight; 8 (the same
+                            // bytes in flight, 200 instead of ~170 VGPRs at G = 4) measured 2-3 % SLOWER per launch (profiles/kv8_batch_rate.txt)
+#endif
+struct kv8_exps { int8_t* k; int8_t* v; int64_t bs; };
+__device__ __forceinline__ kv8_exps kv8_get() { return kv8_exps{nullptr, nullptr, 0}; }
+__device__ __forceinline__ kv8_exps kv8_get(kv8_exps e) { return e; }
+template <bool FP8> struct kv_fmt { typedef u32x2 vvec; };
+template <> struct kv_fmt<true> { typedef unsigned vvec; };
+
+template <int G, bool PIPE = false, bool FP8 = false, class... FMT>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode_args a, FMT... fmt) {
+  static_assert(FP8 == (sizeof...(FMT) == 1), "FP8 takes the row exponents");
+  typedef typename kv_fmt<FP8>::vvec vvec;
   __shared__ float qs[G][128];
   __shared__ float knew[128], vnew[128];
   __shared__ float sc[G][DA_KMAX];
@@ -639,6 +729,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
   bf16_t* vcache_b = (bf16_t*)a.vcache + (int64_t)bi * a.cache_bs;
   const bf16_t* Kc = kcache_b + (int64_t)kh * a.ctx_max * 128;
   const bf16_t* Vc = vcache_b + (int64_t)kh * a.ctx_max * 128;
+  // FP8: the same rows as bytes, and the exponents of this kv head's keys
+  const kv8_exps ex = kv8_get(fmt...);
+  uint8_t* k8_b = (uint8_t*)a.kcache + (int64_t)bi * a.cache_bs;
+  uint8_t* v8_b = (uint8_t*)a.vcache + (int64_t)bi * a.cache_bs;
+  const uint8_t* Kc8 = k8_b + (int64_t)kh * a.ctx_max * 128;
+  const uint8_t* Vc8 = v8_b + (int64_t)kh * a.ctx_max * 128;
+  int8_t* Ke = ex.k + (int64_t)bi * ex.bs + (int64_t)kh * a.ctx_max;
+  int8_t* Ve = ex.v + (int64_t)bi * ex.bs + (int64_t)kh * a.ctx_max;
   float* pm_b = a.pm + (int64_t)bi * a.Hq * NS;
   float* pl_b = a.pl + (int64_t)bi * a.Hq * NS;
   float* po_b = a.po + (int64_t)bi * a.Hq * NS * 128;
@@ -646,24 +744,37 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
   // ---- everything that depends only on pos is requested NOW: the first batch of K rows (scores layout) and of V rows
   // (PV layout) is in flight while q/k are roped; at ~25 keys per split that is the whole split, so the kernel pays one
   // memory latency instead of three (rope inputs -> K -> V).
-  constexpr int SW = 4, PW = 4;
+  constexpr int SW = FP8 ? USDM_KV8_SWEEPS : 4, PW = FP8 ? USDM_KV8_SWEEPS : 4;
   const int j = lane & 7, gk = (wave << 3) + (lane >> 3);  // scores: 8 lanes per key, key slot within a 32-key sweep
   const int d4 = (tid & 31) * 4, kl = tid >> 5;            // PV: thread = (4 d's, key lane)
-  u32x4 r0[SW], r1[SW];
-  u32x2 rv[PW];
+  u32x4 r0[SW], r1[FP8 ? 1 : SW];
+  vvec rv[PW];
+  int ek[FP8 ? SW : 1], ev[FP8 ? PW : 1];                  // FP8: the keys' exponents
+  // key kk of this split -> registers: the lane's 16 d of the K row (bf16: two 16-byte loads; FP8: one + the exponent byte) ...
+  auto ldk = [&](int kk, u32x4& x0, u32x4& x1, int& e) {
+    if constexpr (FP8) {
+      x0 = *(const u32x4*)(Kc8 + (int64_t)(k0 + kk) * 128 + j * 16);
+      e = Ke[k0 + kk];
+    } else {
+      const bf16_t* kp = Kc + (int64_t)(k0 + kk) * 128 + j * 16;
+      x0 = *(const u32x4*)kp;
+      x1 = *(const u32x4*)(kp + 8);
+    }
+  };
+  // ... and the thread's 4 d of the V row (bf16: 8 bytes; FP8: 4 + the exponent byte)
+  auto ldv = [&](int kk, vvec& x, int& e) {
+    if constexpr (FP8) {
+      x = *(const unsigned*)(Vc8 + (int64_t)(k0 + kk) * 128 + d4);
+      e = Ve[k0 + kk];
+    } else {
+      x = *(const u32x2*)(Vc + (int64_t)(k0 + kk) * 128 + d4);
+    }
+  };
   if (nk > 0) {
 #pragma unroll
-    for (int w = 0; w < SW; ++w) {
-      const int kk = min(32 * w + gk, nk - 1);
-      const bf16_t* kp = Kc + (int64_t)(k0 + kk) * 128 + j * 16;
-      r0[w] = *(const u32x4*)kp;
-      r1[w] = *(const u32x4*)(kp + 8);
-    }
+    for (int w = 0; w < SW; ++w) ldk(min(32 * w + gk, nk - 1), r0[w], r1[FP8 ? 0 : w], ek[FP8 ? w : 0]);
 #pragma unroll
-    for (int w = 0; w < PW; ++w) {
-      const int kk = min(8 * w + kl, nk - 1);
-      rv[w] = *(const u32x2*)(Vc + (int64_t)(k0 + kk) * 128 + d4);
-    }
+    for (int w = 0; w < PW; ++w) ldv(min(8 * w + kl, nk - 1), rv[w], ev[FP8 ? w : 0]);
   }
   if (skipv) return;   // sequence already ended (usdm_decode_state.done): nothing may be appended to the cache
   // ---- rope q (G heads) and the new k; stash v
@@ -678,9 +789,18 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
   }
   if (tid < 128) vnew[tid] = bf2f(qkv[(a.Hq + a.Hkv + kh) * 128 + tid]);
   __syncthreads();
+  if constexpr (FP8) {
+    // designated writer: wave 0 quantizes the K row, wave 1 the V row (knew / vnew hold bf16 values: the row the bf16 kernel stores)
+    if (sp == 0 && tid < 128) {
+      const float* src = wave == 0 ? knew : vnew;
+      const int64_t r = (int64_t)kh * a.ctx_max + pos;
+      kv8_store_row(src[2 * lane], src[2 * lane + 1], lane, (wave == 0 ? k8_b : v8_b) + r * 128, (wave == 0 ? Ke : Ve) + pos);
+    }
+  } else {
   if (sp == 0 && tid < 128) {  // designated writer of the new cache row
     kcache_b[((int64_t)kh * a.ctx_max + pos) * 128 + tid] = f2bf(knew[tid]);
     vcache_b[((int64_t)kh * a.ctx_max + pos) * 128 + tid] = f2bf(vnew[tid]);
+  }
   }
   // ---- scores: 8 lanes per key, 16 d each; the K rows of SW sweeps are requested before any of them is used
   {
@@ -689,25 +809,16 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
     for (int h = 0; h < G; ++h)
 #pragma unroll
       for (int e = 0; e < 16; ++e) qr[h][e] = qs[h][j * 16 + e];
-    u32x4 n0[PIPE ? SW : 1], n1[PIPE ? SW : 1];      // PIPE: the next batch's rows
+    u32x4 n0[PIPE ? SW : 1], n1[PIPE && !FP8 ? SW : 1];      // PIPE: the next batch's rows
+    int nek[PIPE && FP8 ? SW : 1];
     for (int base = 0; base < nk; base += 32 * SW) {
       if constexpr (PIPE) {
         // unconditional (clamped) requests: a branch here would make the wait-count pass drain everything at the join
 #pragma unroll
-        for (int w = 0; w < SW; ++w) {
-          const int kk = min(base + 32 * SW + 32 * w + gk, nk - 1);
-          const bf16_t* kp = Kc + (int64_t)(k0 + kk) * 128 + j * 16;
-          n0[w] = *(const u32x4*)kp;
-          n1[w] = *(const u32x4*)(kp + 8);
-        }
+        for (int w = 0; w < SW; ++w) ldk(min(base + 32 * SW + 32 * w + gk, nk - 1), n0[w], n1[FP8 ? 0 : w], nek[FP8 ? w : 0]);
       } else if (base > 0) {
 #pragma unroll
-        for (int w = 0; w < SW; ++w) {
-          const int kk = min(base + 32 * w + gk, nk - 1);
-          const bf16_t* kp = Kc + (int64_t)(k0 + kk) * 128 + j * 16;
-          r0[w] = *(const u32x4*)kp;
-          r1[w] = *(const u32x4*)(kp + 8);
-        }
+        for (int w = 0; w < SW; ++w) ldk(min(base + 32 * w + gk, nk - 1), r0[w], r1[FP8 ? 0 : w], ek[FP8 ? w : 0]);
       }
 #pragma unroll
       for (int w = 0; w < SW; ++w) {
@@ -715,10 +826,18 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
         if (kk >= nk) continue;
         const bool is_new = (k0 + kk) == pos;     // the new token's K is not in the cache yet: take it from LDS
         float kv[16];
+        u32x4 b0, b1;                              // the 16 d as bf16 pairs
+        if constexpr (FP8) {
+          const float s = fp8_row_scale(ek[w]);
+          b0 = fp8x8_to_bf16x8(u32x2{r0[w][0], r0[w][1]}, s);
+          b1 = fp8x8_to_bf16x8(u32x2{r0[w][2], r0[w][3]}, s);
+        } else {
+          b0 = r0[w]; b1 = r1[w];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          kv[2 * e] = bf2f(r0[w][e] & 0xffff); kv[2 * e + 1] = bf2f(r0[w][e] >> 16);
-          kv[8 + 2 * e] = bf2f(r1[w][e] & 0xffff); kv[8 + 2 * e + 1] = bf2f(r1[w][e] >> 16);
+          kv[2 * e] = bf2f(b0[e] & 0xffff); kv[2 * e + 1] = bf2f(b0[e] >> 16);
+          kv[8 + 2 * e] = bf2f(b1[e] & 0xffff); kv[8 + 2 * e + 1] = bf2f(b1[e] >> 16);
         }
         if (is_new) {
 #pragma unroll
@@ -735,7 +854,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
       }
       if constexpr (PIPE) {
 #pragma unroll
-        for (int w = 0; w < SW; ++w) { r0[w] = n0[w]; r1[w] = n1[w]; }
+        for (int w = 0; w < SW; ++w) {
+          r0[w] = n0[w];
+          if constexpr (FP8) ek[w] = nek[w];
+          else r1[w] = n1[w];
+        }
       }
     }
   }
@@ -762,26 +885,30 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
     for (int h = 0; h < G; ++h)
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[h][e] = 0.f;
-    u32x2 nv[PIPE ? PW : 1];
+    vvec nv[PIPE ? PW : 1];
+    int nev[PIPE && FP8 ? PW : 1];
     for (int base = 0; base < nk; base += 8 * PW) {
       if constexpr (PIPE) {
 #pragma unroll
-        for (int w = 0; w < PW; ++w) {
-          const int kk = min(base + 8 * PW + 8 * w + kl, nk - 1);
-          nv[w] = *(const u32x2*)(Vc + (int64_t)(k0 + kk) * 128 + d4);
-        }
+        for (int w = 0; w < PW; ++w) ldv(min(base + 8 * PW + 8 * w + kl, nk - 1), nv[w], nev[FP8 ? w : 0]);
       } else if (base > 0) {
 #pragma unroll
-        for (int w = 0; w < PW; ++w) {
-          const int kk = min(base + 8 * w + kl, nk - 1);
-          rv[w] = *(const u32x2*)(Vc + (int64_t)(k0 + kk) * 128 + d4);
-        }
+        for (int w = 0; w < PW; ++w) ldv(min(base + 8 * w + kl, nk - 1), rv[w], ev[FP8 ? w : 0]);
       }
 #pragma unroll
       for (int w = 0; w < PW; ++w) {
         const int kk = base + 8 * w + kl;
         if (kk >= nk) continue;
-        float v[4] = {bf2f(rv[w][0] & 0xffff), bf2f(rv[w][0] >> 16), bf2f(rv[w][1] & 0xffff), bf2f(rv[w][1] >> 16)};
+        u32x2 bv;                                  // the 4 d as bf16 pairs
+        if constexpr (FP8) {
+          typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_cvt;
+          const float s = fp8_row_scale(ev[w]);
+          bv[0] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(rv[w], s, false));
+          bv[1] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(rv[w], s, true));
+        } else {
+          bv = rv[w];
+        }
+        float v[4] = {bf2f(bv[0] & 0xffff), bf2f(bv[0] >> 16), bf2f(bv[1] & 0xffff), bf2f(bv[1] >> 16)};
         if (k0 + kk == pos) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = vnew[d4 + e];
@@ -795,7 +922,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const usdm_attn_decode
       }
       if constexpr (PIPE) {
 #pragma unroll
-        for (int w = 0; w < PW; ++w) rv[w] = nv[w];
+        for (int w = 0; w < PW; ++w) {
+          rv[w] = nv[w];
+          if constexpr (FP8) ev[w] = nev[w];
+        }
       }
     }
 #pragma unroll
@@ -1259,6 +1389,64 @@ extern "C" int usdm_rope_cache(const usdm_rope_args* pa, usdm_stream_t stream) {
   return 0;
 }
 
+extern "C" int usdm_rope_cache_fp8(const usdm_rope_fp8_args* pa, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->r.qkv && pa->r.cos && pa->r.sin && pa->r.kcache && pa->r.vcache && pa->kexp && pa->vexp, "usdm_rope_cache_fp8: null args");
+  const usdm_rope_args& a = pa->r;
+  USDM_CHECK_ARG(a.S > 0 && a.pos0 >= 0 && a.pos0 + a.S <= a.ctx_max && a.pos0 + a.S <= a.max_pos, "usdm_rope_cache_fp8: positions exceed the cache / rope table");
+  USDM_CHECK_ARG(a.Hq >= 0 && a.Hkv > 0 && a.ld >= (int64_t)(a.Hq + 2 * a.Hkv) * 128 && a.ld % 2 == 0 && ((uintptr_t)a.qkv & 3) == 0, "usdm_rope_cache_fp8: qkv 4-byte aligned, ld even and >= (Hq + 2 Hkv) * 128");
+  USDM_CHECK_ARG(!a.vt || a.vt_ld >= a.S, "usdm_rope_cache_fp8: vt_ld");
+  USDM_CHECK_ARG(!pa->kscr || (pa->kscr_ld >= a.S && ((uintptr_t)pa->kscr & 3) == 0), "usdm_rope_cache_fp8: kscr_ld >= S, kscr 4-byte aligned");
+  USDM_CHECK_ARG(((uintptr_t)a.kcache & 15) == 0 && ((uintptr_t)a.vcache & 15) == 0, "usdm_rope_cache_fp8: the fp8 caches must be 16-byte aligned");
+  USDM_CHECK_ARG(((uintptr_t)pa->kexp & 3) == 0 && ((uintptr_t)pa->vexp & 3) == 0, "usdm_rope_cache_fp8: the exponent arrays must be 4-byte aligned");
+  hipLaunchKernelGGL(rope_cache_fp8_kernel, dim3(a.S, a.Hq + 2 * a.Hkv), dim3(64), 0, (hipStream_t)stream, a, pa->kexp, pa->vexp, (bf16_t*)pa->kscr, pa->kscr_ld);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int usdm_sizeof_rope_fp8_args(void) { return (int)sizeof(usdm_rope_fp8_args); }
+extern "C" int usdm_sizeof_attn_decode_fp8_args(void) { return (int)sizeof(usdm_attn_decode_fp8_args); }
+
+// the split form (NS > 1), one selection for both cache formats: an FP8 launch partitions the keys exactly as the bf16 launch
+template <bool FP8, class... FMT>
+static int attn_decode_launch_split(const char* who, const usdm_attn_decode_args& a, int span, hipStream_t st, FMT... fmt) {
+  const int G = a.Hq / a.Hkv;
+  const int nbatch = a.batch > 1 ? a.batch : 1;
+  dim3 grid(a.Hkv, a.NS, nbatch);
+  const bool pipe = nbatch > 1 && cdiv(span, a.NS) > 64;      // long splits (the many-sequence step): next batch of keys prefetched
+  if (pipe && G == 4) hipLaunchKernelGGL((attn_decode_kernel<4, true, FP8, FMT...>), grid, dim3(256), 0, st, a, fmt...);
+  else if (pipe && G == 2) hipLaunchKernelGGL((attn_decode_kernel<2, true, FP8, FMT...>), grid, dim3(256), 0, st, a, fmt...);
+  else if (pipe && G == 1) hipLaunchKernelGGL((attn_decode_kernel<1, true, FP8, FMT...>), grid, dim3(256), 0, st, a, fmt...);
+  else if (G == 4) hipLaunchKernelGGL((attn_decode_kernel<4, false, FP8, FMT...>), grid, dim3(256), 0, st, a, fmt...);
+  else if (G == 2) hipLaunchKernelGGL((attn_decode_kernel<2, false, FP8, FMT...>), grid, dim3(256), 0, st, a, fmt...);
+  else if (G == 1) hipLaunchKernelGGL((attn_decode_kernel<1, false, FP8, FMT...>), grid, dim3(256), 0, st, a, fmt...);
+  else { usdm_set_error("%s: group size %d unsupported (1,2,4)", who, G); return 2; }
+  USDM_LAUNCH_CHECK();
+  if (!a.counters && !a.defer_merge) {
+    hipLaunchKernelGGL(attn_combine_kernel, dim3(a.Hq, nbatch), dim3(128), 0, st, a.pm, a.pl, a.po, a.NS, (bf16_t*)a.out, a.out_bs, a.skip);
+    USDM_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int usdm_attn_decode_fp8(const usdm_attn_decode_fp8_args* pf, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pf && pf->a.qkv && pf->a.pos && pf->a.kcache && pf->a.vcache && pf->kexp && pf->vexp && (pf->a.out || pf->a.defer_merge),
+                 "usdm_attn_decode_fp8: null args");
+  const usdm_attn_decode_args& a = pf->a;
+  USDM_CHECK_ARG(a.NS != 1, "usdm_attn_decode_fp8: the one-workgroup form (NS == 1) is not built for an fp8 cache (use NS > 1)");
+  USDM_CHECK_ARG(!a.defer_merge || (a.NS > 1 && !a.counters && a.batch <= 1), "usdm_attn_decode_fp8: defer_merge needs NS > 1, no counters, one sequence");
+  USDM_CHECK_ARG(a.pm && a.pl && a.po, "usdm_attn_decode_fp8: partial buffers missing");
+  USDM_CHECK_ARG(a.Hkv > 0 && a.Hq % a.Hkv == 0 && a.NS > 1 && a.NS <= 64, "usdm_attn_decode_fp8: heads / NS (2..64)");
+  USDM_CHECK_ARG(a.batch <= 1 || (a.batch <= 64 && a.qkv_bs > 0 && a.out_bs > 0 && a.cache_bs > 0 && pf->exp_bs > 0),
+                 "usdm_attn_decode_fp8: batched form needs the four strides");
+  USDM_CHECK_ARG(a.window >= 0, "usdm_attn_decode_fp8: window >= 0");
+  USDM_CHECK_ARG(a.ctx_max > 0 && ((uintptr_t)a.kcache & 15) == 0 && ((uintptr_t)a.vcache & 15) == 0 && (a.batch <= 1 || a.cache_bs % 16 == 0),
+                 "usdm_attn_decode_fp8: the fp8 caches (and cache_bs) must be 16-byte aligned");
+  USDM_CHECK_ARG(((uintptr_t)pf->kexp & 3) == 0 && ((uintptr_t)pf->vexp & 3) == 0 && (a.batch <= 1 || pf->exp_bs % 4 == 0),
+                 "usdm_attn_decode_fp8: the exponent arrays (and exp_bs) must be 4-byte aligned");
+  const int span = (a.window > 0 && a.window < a.ctx_max) ? a.window : a.ctx_max;      // most keys a step can see
+  USDM_CHECK_ARG(cdiv(span, a.NS) <= DA_KMAX, "usdm_attn_decode_fp8: visible keys / NS exceeds %d keys per split", DA_KMAX);
+  return attn_decode_launch_split<true>("usdm_attn_decode_fp8", a, span, (hipStream_t)stream, kv8_exps{pf->kexp, pf->vexp, a.batch > 1 ? pf->exp_bs : 0});
+}
+
 extern "C" int usdm_attn_decode(const usdm_attn_decode_args* pa, usdm_stream_t stream) {
   USDM_CHECK_ARG(pa && pa->qkv && pa->pos && pa->kcache && pa->vcache && (pa->out || pa->defer_merge), "usdm_attn_decode: null args");
   USDM_CHECK_ARG(!pa->defer_merge || (pa->NS > 1 && !pa->counters && pa->batch <= 1), "usdm_attn_decode: defer_merge needs NS > 1, no counters, one sequence");
@@ -1290,22 +1478,7 @@ extern "C" int usdm_attn_decode(const usdm_attn_decode_args* pa, usdm_stream_t s
     USDM_LAUNCH_CHECK();
     return 0;
   }
-  const int nbatch = a.batch > 1 ? a.batch : 1;
-  dim3 grid(a.Hkv, a.NS, nbatch);
-  const bool pipe = nbatch > 1 && cdiv(span, a.NS) > 64;      // long splits (the many-sequence step): next batch of keys prefetched
-  if (pipe && G == 4) hipLaunchKernelGGL((attn_decode_kernel<4, true>), grid, dim3(256), 0, st, a);
-  else if (pipe && G == 2) hipLaunchKernelGGL((attn_decode_kernel<2, true>), grid, dim3(256), 0, st, a);
-  else if (pipe && G == 1) hipLaunchKernelGGL((attn_decode_kernel<1, true>), grid, dim3(256), 0, st, a);
-  else if (G == 4) hipLaunchKernelGGL(attn_decode_kernel<4>, grid, dim3(256), 0, st, a);
-  else if (G == 2) hipLaunchKernelGGL(attn_decode_kernel<2>, grid, dim3(256), 0, st, a);
-  else if (G == 1) hipLaunchKernelGGL(attn_decode_kernel<1>, grid, dim3(256), 0, st, a);
-  else { usdm_set_error("usdm_attn_decode: group size %d unsupported (1,2,4)", G); return 2; }
-  USDM_LAUNCH_CHECK();
-  if (!a.counters && !a.defer_merge) {
-    hipLaunchKernelGGL(attn_combine_kernel, dim3(a.Hq, nbatch), dim3(128), 0, st, a.pm, a.pl, a.po, a.NS, (bf16_t*)a.out, a.out_bs, a.skip);
-    USDM_LAUNCH_CHECK();
-  }
-  return 0;
+  return attn_decode_launch_split<false>("usdm_attn_decode", a, span, st);
 }
 
 extern "C" int usdm_residual_add(void* h, const float* delta, int32_t n, usdm_stream_t stream) {

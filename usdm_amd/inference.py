@@ -115,7 +115,7 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
     return audio
 
 
-def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None):
+def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None, kv_cache_dtype=None):
     """What the reference's __main__ does between argument parsing and sample() (src/inference.py:105-129), from LOCAL copies:
     hub names resolve inside model_cache_dir (huggingface_hub cache layout or plain <name>/ directories, checkpoints.py)."""
     import os
@@ -137,7 +137,7 @@ def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None):
     # kernels bound their key range (llm.py), so the cache may be longer than the window.  8192 = the USDM tokenizer's limit.
     want = ctx_max or min(int(getattr(tokenizer, "model_max_length", 4096) or 4096), 8192)
     model = USDMForCausalLM.from_pretrained(llm_dir, device=dev, torch_dtype=torch.bfloat16, ctx_max=want,
-                                            quantization=quantization).to(dev).eval()
+                                            quantization=quantization, kv_cache_dtype=kv_cache_dtype).to(dev).eval()
     return model, unit_extractor, voicebox, vocoder, tokenizer
 
 
@@ -154,10 +154,14 @@ def main(argv=None):
                         help="Path to save the spoken response.")
     parser.add_argument('--quantization', type=str, default=None, choices=["fp8"],
                         help="Weight-only FP8 for the LLM (e4m3, power-of-two row scales; opt-in, default bf16).")
+    parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["bf16", "fp8"],
+                        help="KV cache of the LLM: bf16 (default) or fp8 (e4m3 rows, one power-of-two scale per token and kv head; opt-in, "
+                             "switches prefix reuse between the three rounds off).")
     args = parser.parse_args(argv)
 
     device = torch.device("cuda")
-    model, unit_extractor, voicebox, vocoder, tokenizer = load_models(args.model_cache_dir, device, quantization=args.quantization)
+    model, unit_extractor, voicebox, vocoder, tokenizer = load_models(args.model_cache_dir, device, quantization=args.quantization,
+                                                                         kv_cache_dtype=args.kv_cache_dtype)
     try:
         sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)

@@ -18,6 +18,10 @@ Weights: HF state-dict key names (model.layers.N.self_attn.q_proj.weight, ...), 
 matrices (qkv, o, gate/up, down, lm_head) are held as e4m3 with a power-of-two scale per row (usdm_amd/quant.py), which makes the
 model exactly the bf16 model with the dequantized weights W'; decode streams half the bytes (usdm_gemv_fp8), prefill dequantizes
 each matrix into one bf16 scratch right before its usdm_gemm.  Single GPU only.
+KV cache: bf16 rows.  kv_cache_dtype="fp8" (opt-in, independent of `quantization`): every cached row (one token, one kv head) is
+held as e4m3 bytes + one power-of-two exponent (quant.quantize_kv_rows), written by usdm_rope_cache_fp8 / usdm_attn_decode_fp8.
+The model is then exactly the bf16-cache model whose decode steps read the round-tripped rows K', V'; a prompt's own prefill
+attention reads its unquantized K / V from per-plan scratch.  Half the cache bytes per step and per slot; no prefix reuse; single GPU.
 """
 import math
 import os
@@ -28,7 +32,7 @@ from . import ops
 from ._lib import ACT_SWIGLU
 from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
-from .quant import Fp8Weight
+from .quant import Fp8Weight, check_kv_cache_dtype
 
 MISTRAL_7B_USDM = dict(vocab_size=42003, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
                        num_attention_heads=32, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-5,
@@ -111,13 +115,19 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
 
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
-                 p2p_fused=None, quantization=None, fp8_matrix_cores=False):
+                 p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None):
         if quantization not in (None, "fp8"):
             raise ValueError(f"quantization={quantization!r}: supported are None (bf16) and 'fp8' (e4m3 weights, power-of-two row scales)")
         if quantization == "fp8" and (tp_size > 1 or tp_segments or p2p is not None):
             raise NotImplementedError("quantization='fp8' runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes bf16 weights")
         if fp8_matrix_cores and quantization != "fp8":
             raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
+        self.kv_cache_dtype = check_kv_cache_dtype(kv_cache_dtype)
+        self.kv8 = self.kv_cache_dtype == "fp8"
+        if self.kv8 and (tp_size > 1 or tp_segments or p2p is not None):
+            raise NotImplementedError("kv_cache_dtype='fp8' runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes a bf16 cache")
+        if self.kv8 and os.environ.get("USDM_GEMV_CHAIN", "0") not in ("", "0"):
+            raise NotImplementedError("kv_cache_dtype='fp8': the chained decode GEMVs (USDM_GEMV_CHAIN) take a bf16 cache")
         self.quantization = quantization
         # fp8_matrix_cores (opt-in): decode steps of 5..16 sequences on the matrix cores (usdm_gemv_fp8_mfma) instead of groups of 4;
         # like bf16's matrix-core form they equal the oracle up to near-ties, not generate() bit for bit
@@ -177,6 +187,9 @@ class USDMForCausalLM:
                     and c["hidden_size"] == 4096 and self.Hq * c["head_dim"] == 4096)
         dflt = max(8, -(-self.ctx_max // 512)) if self.merge_in_oproj else 32
         self.NS = int(os.environ.get("USDM_DECODE_SPLITS", str(dflt))) if decode_splits is None else decode_splits
+        if self.kv8 and self.NS == 1:
+            # usdm_attn_decode_fp8 has the split form only: the fewest splits the 512-keys-per-split bound allows
+            self.NS = max(2, -(-(self.window or self.ctx_max) // 512))
         if self.NS == 1:
             self.merge_in_oproj = False          # one workgroup per kv head: nothing to merge
         # Chained decode GEMVs (usdm_gemv_chain): consecutive projections of a layer in ONE persistent launch whose weight stream
@@ -291,13 +304,25 @@ class USDMForCausalLM:
         n = sum(l[k].numel() for l in self.W["layers"] for k in ("qkv", "o", "gu", "down")) + self.W["lm_head"].numel()
         return 2 * n
 
+    def kv_bytes_per_token_row(self):
+        """K + V bytes a decode step reads per cached token of ONE sequence on this rank (all layers): bf16 rows, or e4m3 rows +
+        one exponent byte each with kv_cache_dtype="fp8".  A step of B sequences streams the sum over them of this x context."""
+        d = self.cfg["head_dim"]
+        return 2 * self.cfg["num_hidden_layers"] * self.Hkv * ((d + 1) if self.kv8 else 2 * d)
+
     # ------------------------------------------------------------------ buffers
     def _alloc(self):
         c, dev = self.cfg, self.device
         L, d = c["num_hidden_layers"], c["head_dim"]
         bf = torch.bfloat16
-        self.kcache = torch.zeros(L, self.Hkv, self.ctx_max, d, dtype=bf, device=dev)
-        self.vcache = torch.zeros(L, self.Hkv, self.ctx_max, d, dtype=bf, device=dev)
+        if self.kv8:   # e4m3 rows + one exponent per (token, kv head); all-zero = rows of 0.0 (pad keys stay finite)
+            self.kcache = torch.zeros(L, self.Hkv, self.ctx_max, d, dtype=torch.uint8, device=dev)
+            self.vcache = torch.zeros(L, self.Hkv, self.ctx_max, d, dtype=torch.uint8, device=dev)
+            self.kexp = torch.zeros(L, self.Hkv, self.ctx_max, dtype=torch.int8, device=dev)
+            self.vexp = torch.zeros(L, self.Hkv, self.ctx_max, dtype=torch.int8, device=dev)
+        else:
+            self.kcache = torch.zeros(L, self.Hkv, self.ctx_max, d, dtype=bf, device=dev)
+            self.vcache = torch.zeros(L, self.Hkv, self.ctx_max, d, dtype=bf, device=dev)
         # V^T of the prompt tokens (what the prefill attention consumes), kept across generate() calls so that a prompt which
         # extends the cached sequence only prefills its new tokens (the reference's three rounds: src/inference.py:61-83)
         # reuse_prefix = "exact" (default; USDM_PREFIX_REUSE=exact): only cache rows that a PREFILL launch wrote are reused.  A row of
@@ -308,7 +333,12 @@ class USDMForCausalLM:
         # differ from a from-scratch prefill by a bf16 ulp (close to, not identical with, the reference).  False / 0: off.
         mode = os.environ.get("USDM_PREFIX_REUSE", "exact")
         self.reuse_prefix = {"0": False, "off": False, "1": True, "all": True}.get(mode, "exact")
-        self.vtc = torch.zeros(L, self.Hkv, d, self.ctx_max, dtype=bf, device=dev)
+        if self.kv8:
+            # fp8 cache: no reuse and no persistent V^T.  A reused prefix would have to be dequantized for the prefill attention and
+            # would no longer equal a recomputed prompt (which attends to its unquantized K / V); every call prefills its whole prompt.
+            self.reuse_prefix, self.vtc = False, None
+        else:
+            self.vtc = torch.zeros(L, self.Hkv, d, self.ctx_max, dtype=bf, device=dev)
         self._kv_ids, self._vt_upto = None, 0
         # rope tables exactly as HF MistralRotaryEmbedding computes them (fp32 on the host, cast to bf16)
         inv_freq = 1.0 / (c["rope_theta"] ** (torch.arange(0, d, 2, dtype=torch.int64).float() / d))
@@ -508,15 +538,24 @@ class USDMForCausalLM:
         Z = lambda *s, dt=bf: plan.hold(torch.zeros(*s, device=dev, dtype=dt))
         io = dict(ids=Z(S, dt=torch.int64))
         h, xn, qkv, ao, act = Z(S, H), Z(S, H), Z(S, nq), Z(S, Hq * d), Z(S, I)
-        vt = Z(Hkv, d, Spad) if slot is not None else None     # batch slots: scratch V^T of this prompt only
-        assert past == 0 or slot is None
+        vt = Z(Hkv, d, Spad) if (slot is not None or self.kv8) else None     # batch slots / fp8 cache: scratch V^T of this prompt only
+        kscr = Z(Hkv, Spad, d) if self.kv8 else None           # fp8 cache: the prompt's bf16 K rows (one scratch, reused by every layer)
+        assert past == 0 or (slot is None and not self.kv8)
         part = Z(S, H, dt=torch.float32) if tp > 1 else None
         ops.embed_rows(self.W["embed"], h, Hd=H, ids=io["ids"], n=S, plan=plan)
         for l in range(L):
             w = self.W["layers"][l]
             ops.norm(h, w["ln1"], None, rows=S, C=H, eps=c["rms_norm_eps"], rms=True, round_bf16=True, out16=xn, plan=plan)
             ops.gemm(xn, self._gemm_w(w["qkv"], plan), M=S, N=nq, Kc=H, out16=qkv, plan=plan)
-            if slot is not None:
+            if self.kv8:
+                # quantized rows into the cache; the prompt's own attention reads the unquantized K rows / V^T from scratch
+                cs = slot if slot is not None else self
+                ops.rope_cache(qkv, self.cos, self.sin, cs.kcache[l], cs.vcache[l], ld=nq, S=S, pos0=0, Hq=Hq, Hkv=Hkv, ctx_max=self.ctx_max,
+                               max_pos=self.ctx_max, vt=vt, vt_ld=Spad, kv8=(cs.kexp[l], cs.vexp[l]), kscr=kscr, kscr_ld=Spad, plan=plan)
+                ops.attention(qkv, kscr, vt, ao, mode=1, dh=d, B=1, Hq=Hq, Hkv=Hkv, Sq=S, Skv=S, Skv_alloc=Spad,
+                              q_strides=(0, d, nq), k_strides=(0, Spad * d, d), v_strides=(0, d * Spad, Spad),
+                              o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=plan)
+            elif slot is not None:
                 ops.rope_cache(qkv, self.cos, self.sin, slot.kcache[l], slot.vcache[l], ld=nq, S=S, pos0=0, Hq=Hq, Hkv=Hkv,
                                ctx_max=self.ctx_max, max_pos=self.ctx_max, vt=vt, vt_ld=Spad, plan=plan)
                 ops.attention(qkv, slot.kcache[l], vt, ao, mode=1, dh=d, B=1, Hq=Hq, Hkv=Hkv, Sq=S, Skv=S, Skv_alloc=Spad,
@@ -650,7 +689,7 @@ class USDMForCausalLM:
             gran = cmb_gran[l] if use_cmb else None
             ops.attn_decode(qkv, self.st_pos, self.cos, self.sin, self.kcache[l], self.vcache[l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
                             ctx_max=self.ctx_max, NS=self.NS, scale=d ** -0.5, counters=cnt, skip=skp, defer_merge=mrg is not None, window=self.window,
-                            cmb_gran=gran, plan=plan)
+                            cmb_gran=gran, kv8=(self.kexp[l], self.vexp[l]) if self.kv8 else None, plan=plan)
             if tp == 1:
                 ops.gemv(w["o"], ao, N=H, K=Hq * d, residual=h, y16=h, skip=skp, merge=mrg, cmb=(gran, self.cmb_err) if use_cmb else None, plan=plan)
             else:
@@ -702,8 +741,9 @@ class USDMForCausalLM:
         c, dev, bf = self.cfg, self.device, torch.bfloat16
         L, d, H = c["num_hidden_layers"], c["head_dim"], c["hidden_size"]
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
-        bb = dict(kc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=bf, device=dev),
-                  vc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=bf, device=dev),
+        cdt = torch.uint8 if self.kv8 else bf
+        bb = dict(kc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=cdt, device=dev),
+                  vc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=cdt, device=dev),
                   nxt=i32(B), step=i32(B), pos=i32(B), out=i32(B, self.max_out), h=torch.zeros(B, H, dtype=bf, device=dev),
                   pv=torch.zeros(B, self.nparts, dtype=torch.float32, device=dev), pi=i32(B, self.nparts), prefill=LRU(16), decode=None,
                   decode_sampled=None, logits=torch.zeros(B, self.Vloc, dtype=torch.float32, device=dev),
@@ -718,10 +758,15 @@ class USDMForCausalLM:
             # slot's sampled prefill gathers its row into lrow [tp * Vloc] (prefills run one at a time)
             bb.update(lg=torch.zeros(tp, B, self.Vloc, dtype=torch.float32, device=dev),
                       lrow=torch.zeros(tp * self.Vloc, dtype=torch.float32, device=dev))
+        if self.kv8:
+            bb.update(ke=torch.zeros(B, L, self.Hkv, self.ctx_max, dtype=torch.int8, device=dev),
+                      ve=torch.zeros(B, L, self.Hkv, self.ctx_max, dtype=torch.int8, device=dev))
         slots = []
         for b in range(B):
             sl = self._Slot()
             sl.kcache, sl.vcache = bb["kc"][b], bb["vc"][b]
+            if self.kv8:
+                sl.kexp, sl.vexp = bb["ke"][b], bb["ve"][b]
             sl.st_next, sl.st_step, sl.st_pos, sl.st_out = bb["nxt"][b:b + 1], bb["step"][b:b + 1], bb["pos"][b:b + 1], bb["out"][b]
             sl.h_dec = bb["h"][b]
             sl.part_val = sl.part_val_loc = bb["pv"][b]
@@ -785,7 +830,7 @@ class USDMForCausalLM:
             gemv_b(w["qkv"], h, nb=B, N=nq, K=H, x_bs=H, y_bs=nq, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, plan=plan)
             ops.attn_decode(qkv, bb["pos"], self.cos, self.sin, bb["kc"][0, l], bb["vc"][0, l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
                             ctx_max=self.ctx_max, NS=NS, scale=d ** -0.5, batch=B, qkv_bs=nq, out_bs=Hq * d, cache_bs=cache_bs, window=self.window,
-                            counters=cnt, plan=plan)
+                            counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=plan)
             if tp:
                 plan = row_parallel(w["o"], ao, Hq * d, part, plan)
             else:

@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight
 
@@ -395,12 +395,36 @@ def embed_rows(table, out, *, Hd, ids=None, next_token=None, n=1, plan=None):
     _go(plan, "usdm_embed_rows", lib.usdm_embed_rows, _ptr(table), _ptr(ids), _ptr(next_token), C_.c_int32(n), C_.c_int32(Hd), _ptr(out))
 
 
-def rope_cache(qkv, cos, sin, kcache, vcache, *, ld, S, pos0, Hq, Hkv, ctx_max, max_pos, vt=None, vt_ld=0, plan=None):
-    _need_cuda(qkv, cos, sin, kcache, vcache, vt)
-    a = RopeArgs()
-    a.qkv, a.ld, a.S, a.pos0, a.Hq, a.Hkv, a.ctx_max, a.max_pos = _ptr(qkv), ld, S, pos0, Hq, Hkv, ctx_max, max_pos
-    a.cos, a.sin, a.kcache, a.vcache, a.vt, a.vt_ld = _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), _ptr(vt), vt_ld
-    _go(plan, "usdm_rope_cache", lib.usdm_rope_cache, C_.byref(a))
+def _kv8(kv8, kcache, vcache):
+    """kv8 = (kexp, vexp) int8 exponent arrays of uint8 e4m3 caches (usdm_amd/quant.py quantize_kv_rows)."""
+    kexp, vexp = kv8
+    _need_cuda(kexp, vexp)
+    if kcache.dtype != torch.uint8 or vcache.dtype != torch.uint8 or kexp.dtype != torch.int8 or vexp.dtype != torch.int8:
+        raise TypeError("kv8: uint8 caches [Hkv][ctx_max][128] with int8 exponents [Hkv][ctx_max]")
+    return kexp, vexp
+
+
+def rope_cache(qkv, cos, sin, kcache, vcache, *, ld, S, pos0, Hq, Hkv, ctx_max, max_pos, vt=None, vt_ld=0, kv8=None, kscr=None,
+               kscr_ld=0, plan=None):
+    """usdm_rope_cache; kv8=(kexp, vexp): usdm_rope_cache_fp8 - kcache / vcache are the uint8 caches, the bf16 roped K rows go to
+    kscr [Hkv][kscr_ld][128] and V^T to vt (the prompt's own attention reads those)."""
+    _need_cuda(qkv, cos, sin, kcache, vcache, vt, kscr)
+
+    def fill(a):
+        a.qkv, a.ld, a.S, a.pos0, a.Hq, a.Hkv, a.ctx_max, a.max_pos = _ptr(qkv), ld, S, pos0, Hq, Hkv, ctx_max, max_pos
+        a.cos, a.sin, a.kcache, a.vcache, a.vt, a.vt_ld = _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), _ptr(vt), vt_ld
+    if kv8 is None:
+        if kscr is not None:
+            raise ValueError("rope_cache: kscr belongs to the fp8 cache form (kv8=)")
+        a = RopeArgs()
+        fill(a)
+        _go(plan, "usdm_rope_cache", lib.usdm_rope_cache, C_.byref(a))
+        return
+    kexp, vexp = _kv8(kv8, kcache, vcache)
+    f = RopeFp8Args()
+    fill(f.r)
+    f.kexp, f.vexp, f.kscr, f.kscr_ld = _ptr(kexp), _ptr(vexp), _ptr(kscr), kscr_ld
+    _go(plan, "usdm_rope_cache_fp8", lib.usdm_rope_cache_fp8, C_.byref(f))
 
 
 def gemv_batch(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
@@ -465,9 +489,15 @@ def gemv_batch_ks_floats(N, K):
 
 
 def attn_decode(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, Hq, Hkv, ctx_max, NS, scale, counters=None, batch=0,
-                qkv_bs=0, out_bs=0, cache_bs=0, skip=None, defer_merge=False, window=0, cmb_gran=None, plan=None):
+                qkv_bs=0, out_bs=0, cache_bs=0, skip=None, defer_merge=False, window=0, cmb_gran=None, kv8=None, exp_bs=0, plan=None):
+    """usdm_attn_decode; kv8=(kexp, vexp): usdm_attn_decode_fp8 on uint8 e4m3 caches (cache_bs in bytes, exp_bs between the
+    sequences' exponent arrays)."""
     _need_cuda(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, counters)
-    a = AttnDecodeArgs()
+    if kv8 is not None:
+        f = AttnDecodeFp8Args()
+        a = f.a       # (a view of f's leading usdm_attn_decode_args)
+    else:
+        a = AttnDecodeArgs()
     a.qkv, a.pos, a.Hq, a.Hkv, a.ctx_max, a.NS, a.scale = _ptr(qkv), _ptr(pos), Hq, Hkv, ctx_max, NS, scale
     a.cos, a.sin, a.kcache, a.vcache = _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache)
     a.pm, a.pl, a.po, a.out, a.counters = _ptr(pm), _ptr(pl), _ptr(po), _ptr(out), _ptr(counters)
@@ -479,6 +509,11 @@ def attn_decode(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, Hq, Hkv,
         if cmb_gran.numel() * cmb_gran.element_size() < Hq * 64 * 8:
             raise ValueError("usdm_attn_decode: cmb_gran holds Hq*64 8-byte granules")
         a.cmb_gran = _ptr(cmb_gran)
+    if kv8 is not None:
+        kexp, vexp = _kv8(kv8, kcache, vcache)
+        f.kexp, f.vexp, f.exp_bs = _ptr(kexp), _ptr(vexp), exp_bs
+        _go(plan, "usdm_attn_decode_fp8", lib.usdm_attn_decode_fp8, C_.byref(f))
+        return
     _go(plan, "usdm_attn_decode", lib.usdm_attn_decode, C_.byref(a))
 
 

@@ -53,6 +53,38 @@ def dequantize_rows(q, e):
     return torch.ldexp(v, e.float()[:, None]).to(torch.bfloat16)
 
 
+# ---- FP8 KV cache (opt-in, kv_cache_dtype="fp8"): the SAME format, one row = the 128 values of one (token, kv head) --------------
+# k8 / v8 uint8 [..., ctx_max, 128] with ke / ve int8 [..., ctx_max]: exactly quantize_rows of the bf16 row the bf16 cache would
+# hold (K after RoPE, V as it leaves the qkv projection).  Byte 0 with exponent 0 is 0.0, so a zero-initialised cache is a cache
+# of zero rows.  The decode kernels (usdm_attn_decode_fp8) and the prefill append (usdm_rope_cache_fp8) write this format on the
+# device; these helpers are the one host-side definition that tests and tools share.
+def quantize_kv_rows(x):
+    """x: [..., D] (bf16 or f32, finite) -> (q uint8 [..., D], e int8 [...]): quantize_rows over the last dimension."""
+    q, e = quantize_rows(x.reshape(-1, x.shape[-1]))
+    return q.view(x.shape), e.view(x.shape[:-1])
+
+
+def dequantize_kv_rows(q, e):
+    """(q uint8 [..., D], e int8 [...]) -> bf16 [..., D] (exact)."""
+    return dequantize_rows(q.reshape(-1, q.shape[-1]), e.reshape(-1)).view(q.shape)
+
+
+def roundtrip_kv_rows(x):
+    """The bf16 rows an FP8 cache returns for the bf16 rows x: dequantize(quantize(x)).  Idempotent in values."""
+    return dequantize_kv_rows(*quantize_kv_rows(x)).to(x.dtype)
+
+
+KV_CACHE_DTYPES = (None, "bf16", "fp8")
+
+
+def check_kv_cache_dtype(v):
+    """Validated kv_cache_dtype -> "bf16" | "fp8" (None = bf16)."""
+    if v not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype={v!r}: supported are None / 'bf16' and 'fp8' (e4m3 rows, one power-of-two scale per "
+                         "(token, kv head))")
+    return v or "bf16"
+
+
 class Fp8Weight:
     """A quantized matrix as the kernels take it: q uint8 [N][K], e int8 [N].  ops.gemv / ops.gemv_batch dispatch on this type."""
     __slots__ = ("q", "e", "N", "K")

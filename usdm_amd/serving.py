@@ -104,7 +104,7 @@ class LLM:
     download_dir), or `LLM(model=<USDMForCausalLM>, tokenizer=<tokenizer>)` around objects that are already loaded."""
 
     def __init__(self, model, tokenizer=None, download_dir=None, gpu_memory_utilization=0.9, max_model_len=None, device="cuda",
-                 dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, **unused):
+                 dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None, **unused):
         # max_num_seqs (vllm's name): sequences decoded per step, 1..16.  <= 4: the VALU batch kernel (per slot bit-identical with the
         # single-request path); above: the matrix-core form (usdm_gemv_batch form 1)
         self.max_slots = max(1, min(int(max_num_seqs), MAX_SLOTS))
@@ -115,8 +115,14 @@ class LLM:
             raise ValueError(f"quantization={quantization!r} is not supported (None or 'fp8')")
         if fp8_matrix_cores and quantization != "fp8":
             raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
+        # kv_cache_dtype (vllm's name): None / "bf16", or "fp8" = e4m3 cache rows with one power-of-two scale per (token, kv head)
+        from .quant import check_kv_cache_dtype
+        kvd = check_kv_cache_dtype(kv_cache_dtype)
         from .llm import USDMForCausalLM
         if isinstance(model, USDMForCausalLM):
+            if kv_cache_dtype is not None and getattr(model, "kv_cache_dtype", "bf16") != kvd:
+                raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}, but the model object was loaded with "
+                                 f"kv_cache_dtype={getattr(model, 'kv_cache_dtype', 'bf16')!r}")
             if quantization is not None and getattr(model, "quantization", None) != quantization:
                 raise ValueError(f"quantization={quantization!r}, but the model object was loaded with "
                                  f"quantization={getattr(model, 'quantization', None)!r}")
@@ -131,7 +137,7 @@ class LLM:
                 tokenizer = AutoTokenizer.from_pretrained(path, local_files_only=True)
             ctx = min(int(max_model_len or getattr(tokenizer, "model_max_length", 4096) or 4096), 8192)
             self.llm = USDMForCausalLM.from_pretrained(path, device=device, ctx_max=ctx, quantization=quantization,
-                                                       fp8_matrix_cores=fp8_matrix_cores)
+                                                       fp8_matrix_cores=fp8_matrix_cores, kv_cache_dtype=kv_cache_dtype)
         if isinstance(tokenizer, str):
             from transformers import AutoTokenizer
             tokenizer = AutoTokenizer.from_pretrained(tokenizer, local_files_only=True)
