@@ -119,24 +119,32 @@ def test_attention_voicebox_form_both_kernels(dev, monkeypatch, v16, B, H, Sq):
     _attention_case(dev, 0, 64, B, H, H, Sq)
 
 
-def _attention_case(dev, mode, dh, B, H, Hkv, Sq):
+@pytest.mark.parametrize("dh,H,Hkv,q_pos0,Sq", [(128, 8, 2, 377, 200), (64, 2, 2, 64, 65)])
+def test_attention_causal_after_a_cached_prefix(dev, dh, H, Hkv, q_pos0, Sq):
+    """causal mode with Skv = q_pos0 + Sq > Sq: the queries of a prefill that follows q_pos0 cached tokens (exact weights:
+    tests/test_attn_exact_gpu.py)"""
+    _attention_case(dev, 1, dh, 1, H, Hkv, Sq, q_pos0=q_pos0)
+
+
+def _attention_case(dev, mode, dh, B, H, Hkv, Sq, q_pos0=0):
     from usdm_amd import ops
-    Spad = (Sq + 63) // 64 * 64
+    Skv = q_pos0 + Sq
+    Spad = (Skv + 63) // 64 * 64
     bf = torch.bfloat16
     q = _r((B, H, Sq, dh), 1, 0.5).to(bf)
-    k = _r((B, Hkv, Sq, dh), 2, 0.5).to(bf)
-    v = _r((B, Hkv, Sq, dh), 3, 1.0).to(bf)
+    k = _r((B, Hkv, Skv, dh), 2, 0.5).to(bf)
+    v = _r((B, Hkv, Skv, dh), 3, 1.0).to(bf)
     slopes = torch.tensor([2.0 ** (-(i + 1) / 2) for i in range(H)])
     kv_len = torch.tensor([Sq, max(1, Sq - 37), 1][:B], dtype=torch.int32)
     scale = 1.0 if mode == 0 else dh ** -0.5
     qd = torch.zeros(B, H, Spad, dh, dtype=bf, device=dev); qd[:, :, :Sq] = q.to(dev)
-    kd = torch.zeros(B, Hkv, Spad, dh, dtype=bf, device=dev); kd[:, :, :Sq] = k.to(dev)
-    vt = torch.zeros(B, Hkv, dh, Spad, dtype=bf, device=dev); vt[:, :, :, :Sq] = v.transpose(-1, -2).to(dev)
+    kd = torch.zeros(B, Hkv, Spad, dh, dtype=bf, device=dev); kd[:, :, :Skv] = k.to(dev)
+    vt = torch.zeros(B, Hkv, dh, Spad, dtype=bf, device=dev); vt[:, :, :, :Skv] = v.transpose(-1, -2).to(dev)
     o = torch.zeros(B, Sq, H * dh, dtype=bf, device=dev)
-    ops.attention(qd, kd, vt, o, mode=mode, dh=dh, B=B, Hq=H, Hkv=Hkv, Sq=Sq, Skv=Sq, Skv_alloc=Spad,
+    ops.attention(qd, kd, vt, o, mode=mode, dh=dh, B=B, Hq=H, Hkv=Hkv, Sq=Sq, Skv=Skv, Skv_alloc=Spad, q_pos0=q_pos0,
                   q_strides=(H * Spad * dh, Spad * dh, dh), k_strides=(Hkv * Spad * dh, Spad * dh, dh),
                   v_strides=(Hkv * dh * Spad, dh * Spad, Spad), o_strides=(Sq * H * dh, H * dh),
                   scale=scale, kv_len=kv_len.to(dev) if mode == 0 else None, slopes=slopes.to(dev) if mode == 0 else None)
-    ref = _attn_ref(q.float(), k.float(), v.float(), mode, slopes, kv_len, scale)
+    ref = _attn_ref(q.float(), k.float(), v.float(), mode, slopes, kv_len, scale, q_pos0)
     ref = ref.permute(0, 2, 1, 3).reshape(B, Sq, H * dh)
     _close(o.float(), ref, 2e-2, f"attention mode{mode} dh{dh}")
