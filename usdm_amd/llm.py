@@ -82,6 +82,47 @@ def agree_seed(seed, group, rank, device=None):
 QUANT_KEYS = ("qkv", "o", "gu", "down")    # the streamed matrices of a layer (quantization="fp8"; with the lm_head shard)
 
 
+def check_quantization(quantization, fp8_matrix_cores):
+    """The values of the two weight-format arguments (USDMForCausalLM and serving.LLM take them)."""
+    if quantization not in (None, "fp8"):
+        raise ValueError(f"quantization={quantization!r}: supported are None (bf16) and 'fp8' (e4m3 weights, power-of-two row scales)")
+    if fp8_matrix_cores and quantization != "fp8":
+        raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
+
+
+def stop_ids(eos_token_id):
+    """generate()'s eos_token_id (None, an id or a list of ids) as a set."""
+    if eos_token_id is None:
+        return set()
+    return set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])
+
+
+def stop_index(toks, stops, min_new):
+    """How many of `toks` a sequence keeps when it ends at its first stop id that is at least its min_new-th token; None: no stop."""
+    return next((i + 1 for i, t in enumerate(toks) if t in stops and i + 1 >= min_new), None)
+
+
+class _Segments:
+    """A plan under construction as the list of its segments: launches are added to .plan; cut() ends that plan, with a host call
+    to run after it (a collective, the logits hook) or without (the boundary between a peer-to-peer put and its get), and starts
+    the next one."""
+
+    def __init__(self):
+        self.segs, self.plan = [], ops.Plan()
+
+    def cut(self, host_call=None):
+        self.segs.append(self.plan)
+        if host_call is not None:
+            self.segs.append(host_call)
+        self.plan = ops.Plan()
+
+    def finish(self):
+        """The segments; the first one holds every tensor any of them keeps."""
+        self.segs.append(self.plan)
+        self.segs[0].hold(*[t for s in self.segs if isinstance(s, ops.Plan) for t in s.keep])
+        return self.segs
+
+
 def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantization=None):
     """This rank's packed weights for tensor parallelism of degree `tp` (Megatron-style): q/k/v heads and MLP
     columns split by rank, o_proj/down_proj split along K (their outputs are partial sums), vocab rows split.
@@ -116,12 +157,9 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
                  p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None):
-        if quantization not in (None, "fp8"):
-            raise ValueError(f"quantization={quantization!r}: supported are None (bf16) and 'fp8' (e4m3 weights, power-of-two row scales)")
+        check_quantization(quantization, fp8_matrix_cores)
         if quantization == "fp8" and (tp_size > 1 or tp_segments or p2p is not None):
             raise NotImplementedError("quantization='fp8' runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes bf16 weights")
-        if fp8_matrix_cores and quantization != "fp8":
-            raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
         self.kv_cache_dtype = check_kv_cache_dtype(kv_cache_dtype)
         self.kv8 = self.kv_cache_dtype == "fp8"
         if self.kv8 and (tp_size > 1 or tp_segments or p2p is not None):
@@ -146,8 +184,7 @@ class USDMForCausalLM:
         # p2p: a committed usdm_amd.p2p.P2PComm -> the decode step exchanges its partial sums peer to peer inside the GEMV
         # epilogues (p2p_fused, default) or through put + usdm_allreduce_p2p_reduce launches (split form, USDM_P2P_FUSED=0)
         self.p2p = p2p
-        _os = os
-        self.p2p_fused = (_os.environ.get("USDM_P2P_FUSED", "1") == "1") if p2p_fused is None else bool(p2p_fused)
+        self.p2p_fused = (os.environ.get("USDM_P2P_FUSED", "1") == "1") if p2p_fused is None else bool(p2p_fused)
         if p2p is not None:
             if not self.tp_path:
                 raise ValueError("p2p needs the tensor-parallel path (tp_size > 1 or tp_segments=True)")
@@ -210,6 +247,9 @@ class USDMForCausalLM:
             self.cmb = self.merge_in_oproj = False
             self.chain = 0
         self.chain_sync = None
+        # decode attention of a step of more than 4 sequences (tools/batch_rate.py A/B): workgroup target of the context split, and
+        # the merge by the last-arriving workgroup of a kv head instead of the combine launch
+        self.batch_attn_wgs, self.batch_fused_merge = 512, False
         self.W = None
         # bounded caches (plancache.LRU): prefill plans are keyed by exact prompt length (a plan is argument structs + ~60 KB of
         # workspace per token; no hipGraph), decode plans / graphs by {greedy, sampling} only
@@ -360,6 +400,7 @@ class USDMForCausalLM:
         # monotonic in lockstep with its generation, so launches with different phase counts must not share a block
         self.chain_sync = torch.zeros(2, 8, dtype=torch.int32, device=dev)
         self.chain_gran = torch.zeros(3 * 8192, dtype=torch.int64, device=dev)     # usdm_gemv_engine hand-off granules
+        self.cmb_err = torch.zeros(1, dtype=torch.int32, device=dev) if self.cmb else None      # error word of the o_proj hand-off (usdm_gemv cmb_gran)
         # arg-max partials: nparts slots per rank, the same on every rank (vocab_shard); slots the lm_head launch does not
         # write (last rank's shorter shard) stay "no candidate"
         nv = lambda n: torch.full((n,), float("-inf"), dtype=torch.float32, device=dev)
@@ -434,294 +475,252 @@ class USDMForCausalLM:
             raise ValueError(f"sampling on a peer-to-peer model needs a P2PComm of {need} sites (2 * layers + 1 + ceil(Vloc / "
                              f"max_elems) for the logits exchange); this one has {self.p2p.n_sites}")
 
-    def _tp_sample_and_pick(self, plan, x, advance_pos, segs, sampling, x_delta, sl, skip):
-        """Sampled token choice under tensor parallelism: every rank's Vloc ban-masked logits gathered into the full row (in the
-        kernels on a peer-to-peer model, else through the group), then the unchanged sampler over it on every rank with the same
-        seed and step: every rank draws the same token."""
-        c = self.cfg
-        single = sl is self
-        if sampling == "hook":
-            raise NotImplementedError("logits processors under tensor parallelism are not supported")
-        if self.p2p is not None and single:
-            self._check_p2p_sampling()
-        logits = self.logits_loc if single else sl.logits
-        ops.gemv(self.W["lm_head"], x, N=self.v1 - self.v0, K=c["hidden_size"], norm_w=self.W["norm"], eps=c["rms_norm_eps"],
-                 y32=logits, ban=self.ban, part_val=sl.part_val_loc, part_idx=sl.part_idx_loc, idx_offset=self.v0,
-                 x_delta=x_delta, skip=skip, plan=plan)
-        st = ops.decode_state(sl.st_next, sl.st_out, sl.st_step, sl.st_pos, advance_pos=advance_pos,
-                              done=self.st_done if single else None, eos=self.st_eos if single else None)
-        row = self.logits_row if single else sl.logits_row
-        if self.p2p is not None and single:
-            site0 = 2 * c["num_hidden_layers"] + 1
-            if self.p2p_fused:
-                ops.logits_p2p(logits, self.Vloc, st, self.p2p, site0, row, phase=0, plan=plan)
-            else:       # split form: put | get as two launches with a segment boundary between them
-                ops.logits_p2p(logits, self.Vloc, st, self.p2p, site0, row, phase=1, plan=plan)
-                plan.hold(st)
-                segs.append(plan)
-                plan = ops.Plan()
-                ops.logits_p2p(logits, self.Vloc, st, self.p2p, site0, row, phase=2, plan=plan)
-        else:
-            segs.append(plan)
-            segs.append(lambda: self._gather_partials([row], [logits]))
-            plan = ops.Plan()
-        ops.sample_final(row, st, V=c["vocab_size"], dev_params=self.sample_params if single else sl.sample_params,
-                         embed=self.W["embed"], h_out=sl.h_dec, Hd=c["hidden_size"], plan=plan)
-        plan.hold(st)
-        segs.append(plan)
+    def _p2p_exchange(self, rec, st, launch):
+        """A peer-to-peer exchange launch: put + get in ONE launch (phase 0, p2p_fused), or the split form: put | get as two
+        launches with a segment boundary between them."""
+        if self.p2p_fused:
+            return launch(0)
+        launch(1)
+        rec.plan.hold(st)
+        rec.cut()
+        launch(2)
 
-    def _lm_head_and_pick(self, plan, x, advance_pos, segs, sampling=None, x_delta=None, slot=None, skip=None):
-        """lm_head GEMV + token choice.  sampling=None: ban-masked arg-max (the reference's top_k=1 path);
-        sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block self.sample_params
-        (written per request by generate(): plans and graphs do not depend on temperature / top-k / top-p / seed)."""
-        c = self.cfg
+    def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None):
+        """lm_head GEMV + token choice, for the single sequence (slot=None), a batch slot's prefill, and the batched step
+        (slot = the batch's "all" view, batch_gemv = its projection launcher).  sampling=None: ban-masked arg-max (the reference's
+        top_k=1 path); sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block sample_params
+        (written per request by generate(): plans and graphs do not depend on temperature / top-k / top-p / seed).
+        Under tensor parallelism the ranks' arg-max partials, or (sampled) their Vloc ban-masked logits, are gathered first - in the
+        kernels on a peer-to-peer model, else through the group; the sampler then runs unchanged over the full row on every rank with
+        the same seed and step: every rank draws the same token."""
+        c, H = self.cfg, self.cfg["hidden_size"]
         sl = slot or self   # where the picked token, the decode state and the next input row live (self = the single sequence)
         single = sl is self
-        if sampling and self.tp_path:
-            return self._tp_sample_and_pick(plan, x, advance_pos, segs, sampling, x_delta, sl, skip)
-        want_logits = self.keep_logits or bool(sampling)
-        if want_logits and self.last_logits is None:
-            self.last_logits = torch.zeros(self.v1 - self.v0, dtype=torch.float32, device=self.device)
-        # a batch slot samples from ITS logits row with ITS knobs (per-slot sampling inside a continuous batch)
-        logits = (self.last_logits if single else sl.logits) if want_logits else None
-        ops.gemv(self.W["lm_head"], x, N=self.v1 - self.v0, K=c["hidden_size"], norm_w=self.W["norm"], eps=c["rms_norm_eps"],
-                 y32=logits, ban=self.ban, part_val=sl.part_val_loc, part_idx=sl.part_idx_loc, idx_offset=self.v0,
-                 x_delta=x_delta, skip=skip, plan=plan)
-        st = ops.decode_state(sl.st_next, sl.st_out, sl.st_step, sl.st_pos, advance_pos=advance_pos,
-                              done=self.st_done if single else None, eos=self.st_eos if single else None)
-        if sampling:
-            if sampling == "hook":      # Python logits processors (usdm_amd.serving): a host call between the two kernels
-                segs.append(plan)
-                segs.append(lambda: self.logits_hook())
-                plan = ops.Plan()
-            ops.sample_final(logits, st, dev_params=self.sample_params if single else sl.sample_params,
-                             embed=self.W["embed"], h_out=sl.h_dec, Hd=c["hidden_size"], plan=plan)
-            plan.hold(st)
-            segs.append(plan)
-            return
-        if self.p2p is not None and single:
-            # vocab-parallel pick across ranks in ONE launch (pairs exchanged peer to peer; advances the exchange epoch)
-            kw = dict(embed=self.W["embed"], h_out=sl.h_dec, Hd=c["hidden_size"])
-            site = 2 * c["num_hidden_layers"]
-            if self.p2p_fused:
-                ops.argmax_p2p(sl.part_val_loc, sl.part_idx_loc, self.nparts, st, self.p2p, site, phase=0, plan=plan, **kw)
-            else:       # split form: put | get as two launches with a segment boundary between them
-                ops.argmax_p2p(sl.part_val_loc, sl.part_idx_loc, self.nparts, st, self.p2p, site, phase=1, plan=plan, **kw)
-                plan.hold(st)
-                segs.append(plan)
-                plan = ops.Plan()
-                ops.argmax_p2p(sl.part_val_loc, sl.part_idx_loc, self.nparts, st, self.p2p, site, phase=2, plan=plan, **kw)
-            plan.hold(st)
-            segs.append(plan)
-            return
-        if self.tp_path:
-            segs.append(plan)
-            segs.append(self._gather_partials if single else
-                        (lambda: self._gather_partials([sl.part_val, sl.part_idx], [sl.part_val_loc, sl.part_idx_loc])))
-            plan = ops.Plan()
+        B = 0 if single else sl.batch
+        tp_sampled = bool(sampling) and self.tp_path
+        p2p = self.p2p if single else None      # a batch exchanges through the group, on a peer-to-peer model too
+        if tp_sampled:
+            if sampling == "hook":
+                raise NotImplementedError("logits processors under tensor parallelism are not supported")
+            if p2p is not None:
+                self._check_p2p_sampling()
+            logits = self.logits_loc if single else sl.logits
+        else:
+            want_logits = bool(sampling) or (self.keep_logits and not B)
+            if want_logits and not B and self.last_logits is None:
+                self.last_logits = torch.zeros(self.v1 - self.v0, dtype=torch.float32, device=self.device)
+            # a batch slot samples from ITS logits row with ITS knobs (per-slot sampling inside a continuous batch)
+            logits = (self.last_logits if single else sl.logits) if want_logits else None
+        head = dict(N=self.v1 - self.v0, K=H, norm_w=self.W["norm"], eps=c["rms_norm_eps"], y32=logits, ban=self.ban,
+                    part_val=sl.part_val_loc, part_idx=sl.part_idx_loc, idx_offset=self.v0)
+        if B:
+            batch_gemv(self.W["lm_head"], x, part_bs=self.nparts, y_bs=self.Vloc if sampling else 0, **head)
+        else:
+            ops.gemv(self.W["lm_head"], x, x_delta=x_delta, skip=skip, plan=rec.plan, **head)
+        st = ops.decode_state(sl.st_next, sl.st_out, sl.st_step, sl.st_pos, advance_pos=advance_pos, batch=B, done=sl.st_done, eos=sl.st_eos)
         # the picked token's embedding row is written straight into the decode step's input vector
-        ops.argmax_final(sl.part_val, sl.part_idx, self.nparts * self.tp_size, st, embed=self.W["embed"], h_out=sl.h_dec,
-                         Hd=c["hidden_size"], plan=plan)
-        plan.hold(st)
-        segs.append(plan)
+        out = dict(embed=self.W["embed"], h_out=sl.h_dec, Hd=H)
+        if tp_sampled:
+            row = sl.logits_row     # a batch: [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
+            if p2p is not None:
+                site0 = 2 * c["num_hidden_layers"] + 1
+                self._p2p_exchange(rec, st, lambda ph: ops.logits_p2p(logits, self.Vloc, st, p2p, site0, row, phase=ph, plan=rec.plan))
+            else:
+                rec.cut(lambda: self._gather_partials([row], [logits]))
+            seg = dict(nseg=self.tp_size, seg_stride=B * self.Vloc, seg_len=self.Vloc) if B else {}
+            ops.sample_final(row, st, V=c["vocab_size"], dev_params=sl.sample_params, plan=rec.plan, **seg, **out)
+        elif sampling:
+            if sampling == "hook":      # Python logits processors (usdm_amd.serving): a host call between the two kernels
+                rec.cut(lambda: self.logits_hook())
+            ops.sample_final(logits, st, dev_params=sl.sample_params, plan=rec.plan, **out)
+        elif p2p is not None:
+            # vocab-parallel pick across ranks in ONE launch (pairs exchanged peer to peer; advances the exchange epoch)
+            site = 2 * c["num_hidden_layers"]
+            self._p2p_exchange(rec, st, lambda ph: ops.argmax_p2p(sl.part_val_loc, sl.part_idx_loc, self.nparts, st, p2p, site, phase=ph,
+                                                                  plan=rec.plan, **out))
+        else:
+            if self.tp_path:      # (the single sequence: the bound method itself, which tools/tp8_proxy.py replaces)
+                rec.cut(self._gather_partials if single else
+                        (lambda: self._gather_partials([sl.part_val, sl.part_idx], [sl.part_val_loc, sl.part_idx_loc])))
+            # a batch's gathered partials are [rank][sequence][nparts], one pick per sequence over the nseg = tp segments; a single
+            # sequence's are one row of tp * nparts
+            seg = dict(nseg=self.tp_size, seg_stride=B * self.nparts) if (B and self.tp_path) else {}
+            ops.argmax_final(sl.part_val, sl.part_idx, self.nparts * (1 if B else self.tp_size), st, plan=rec.plan, **seg, **out)
+        rec.plan.hold(st)
 
     # ------------------------------------------------------------------ plans
+    def _dims(self):
+        c = self.cfg
+        H, d = c["hidden_size"], c["head_dim"]
+        return H, d, c["num_hidden_layers"], self.Hq, self.Hkv, self.I, (self.Hq + 2 * self.Hkv) * d
+
+    def _layers(self, rec, gemv, attn, h, qkv, ao, act, way, n=0, parts=None, h_alt=None, down_kw={}):
+        """The Mistral layers of every plan: this loop is the one statement of a layer's launch order.
+        gemv(W, x, N=, K=, ...): the plan's projection launcher, in usdm_gemv's keywords (norm_w / eps: RMSNorm of x fused in front).
+        attn(l): rope, cache and attention of layer l from qkv into ao; returns the keywords its hand-off adds to the o_proj launch.
+        way: how a row-parallel projection (o_proj, down_proj; partial sums under tensor parallelism) lands in the residual stream h:
+          "fused"    one GPU: residual add in the launch's epilogue;
+          "reduce"   f32 partial sums (parts[0] o_proj, parts[1] down_proj) + all-reduce through the group + usdm_residual_add over n
+                     values; the plan is cut at the collective;
+          "deferred" the same, but the add is folded into the NEXT GEMV's prologue (usdm_gemv x_delta / x_out) instead of a
+                     usdm_residual_add launch; the residual stream ping-pongs between h and h_alt because workgroup 0 publishes the
+                     updated stream while the others still read the old one;
+          "p2p"      the exchange in the launch's epilogue (p2p_fused) or put there and followed by usdm_allreduce_p2p_reduce
+                     (split); cut at every exchange so that a single-process harness can interleave logical ranks.
+        Returns (h, pend): the residual stream after the last layer and the all-reduced sum not yet added to it (or None)."""
+        H, d, _, Hq, Hkv, I, nq = self._dims()
+        eps, h0, pend = self.cfg["rms_norm_eps"], h, None
+
+        def proj(W, ln, N, out, a=0):
+            nonlocal h, pend
+            if pend is None:
+                return gemv(W, h, N=N, K=H, norm_w=ln, eps=eps, act=a, y16=out)
+            nxt = h_alt if h is h0 else h0
+            gemv(W, h, N=N, K=H, norm_w=ln, eps=eps, act=a, y16=out, x_delta=pend, x_out=nxt)
+            h, pend = nxt, None
+
+        def land(W, x, K, site, **kw):
+            nonlocal pend
+            if way == "fused":
+                return gemv(W, x, N=H, K=K, residual=h, y16=h, **kw)
+            if way == "p2p":
+                mode = 1 if self.p2p_fused else 2
+                gemv(W, x, N=H, K=K, residual=h, y16=h, p2p=self.p2p, p2p_site=site, p2p_mode=mode, **kw)
+                rec.cut()
+                if mode == 2:
+                    ops.p2p_reduce(self.p2p, site, H, h, skip=self.st_done, plan=rec.plan)
+                return
+            part = parts[site & 1]
+            gemv(W, x, N=H, K=K, round_bf16=False, y32=part, **kw)
+            rec.cut(lambda: self._all_reduce(part))
+            if way == "deferred":
+                pend = part
+            else:
+                ops.residual_add(h, part, n, plan=rec.plan)
+
+        for l, w in enumerate(self.W["layers"]):
+            proj(w["qkv"], w["ln1"], nq, qkv)
+            o_kw = attn(l) or {}
+            land(w["o"], ao, Hq * d, 2 * l, **o_kw)
+            proj(w["gu"], w["ln2"], 2 * I, act, ACT_SWIGLU)
+            land(w["down"], act, I, 2 * l + 1, **down_kw)
+        return h, pend
+
     def _build_prefill(self, S, sampling=None, slot=None, past=0):
         """Prefill of S new tokens at positions past .. past+S-1 (past > 0: the KV cache already holds the first `past`
         tokens of the same sequence; only the single-sequence cache keeps the V^T that makes this possible)."""
-        c, dev, bf = self.cfg, self.device, torch.bfloat16
-        H, d, L = c["hidden_size"], c["head_dim"], c["num_hidden_layers"]
-        Hq, Hkv, I, tp = self.Hq, self.Hkv, self.I, (2 if self.tp_path else 1)
-        nq = (Hq + 2 * Hkv) * d
+        dev, bf = self.device, torch.bfloat16
+        H, d, L, Hq, Hkv, I, nq = self._dims()
         Spad = (S + 63) // 64 * 64
-        segs, plan = [], ops.Plan()
-        Z = lambda *s, dt=bf: plan.hold(torch.zeros(*s, device=dev, dtype=dt))
+        rec = _Segments()
+        Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
         io = dict(ids=Z(S, dt=torch.int64))
         h, xn, qkv, ao, act = Z(S, H), Z(S, H), Z(S, nq), Z(S, Hq * d), Z(S, I)
         vt = Z(Hkv, d, Spad) if (slot is not None or self.kv8) else None     # batch slots / fp8 cache: scratch V^T of this prompt only
         kscr = Z(Hkv, Spad, d) if self.kv8 else None           # fp8 cache: the prompt's bf16 K rows (one scratch, reused by every layer)
         assert past == 0 or (slot is None and not self.kv8)
-        part = Z(S, H, dt=torch.float32) if tp > 1 else None
-        ops.embed_rows(self.W["embed"], h, Hd=H, ids=io["ids"], n=S, plan=plan)
-        for l in range(L):
-            w = self.W["layers"][l]
-            ops.norm(h, w["ln1"], None, rows=S, C=H, eps=c["rms_norm_eps"], rms=True, round_bf16=True, out16=xn, plan=plan)
-            ops.gemm(xn, self._gemm_w(w["qkv"], plan), M=S, N=nq, Kc=H, out16=qkv, plan=plan)
-            if self.kv8:
-                # quantized rows into the cache; the prompt's own attention reads the unquantized K rows / V^T from scratch
-                cs = slot if slot is not None else self
-                ops.rope_cache(qkv, self.cos, self.sin, cs.kcache[l], cs.vcache[l], ld=nq, S=S, pos0=0, Hq=Hq, Hkv=Hkv, ctx_max=self.ctx_max,
-                               max_pos=self.ctx_max, vt=vt, vt_ld=Spad, kv8=(cs.kexp[l], cs.vexp[l]), kscr=kscr, kscr_ld=Spad, plan=plan)
-                ops.attention(qkv, kscr, vt, ao, mode=1, dh=d, B=1, Hq=Hq, Hkv=Hkv, Sq=S, Skv=S, Skv_alloc=Spad,
-                              q_strides=(0, d, nq), k_strides=(0, Spad * d, d), v_strides=(0, d * Spad, Spad),
-                              o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=plan)
-            elif slot is not None:
-                ops.rope_cache(qkv, self.cos, self.sin, slot.kcache[l], slot.vcache[l], ld=nq, S=S, pos0=0, Hq=Hq, Hkv=Hkv,
-                               ctx_max=self.ctx_max, max_pos=self.ctx_max, vt=vt, vt_ld=Spad, plan=plan)
-                ops.attention(qkv, slot.kcache[l], vt, ao, mode=1, dh=d, B=1, Hq=Hq, Hkv=Hkv, Sq=S, Skv=S, Skv_alloc=Spad,
-                              q_strides=(0, d, nq), k_strides=(0, self.ctx_max * d, d), v_strides=(0, d * Spad, Spad),
-                              o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=plan)
-            else:
-                ops.rope_cache(qkv, self.cos, self.sin, self.kcache[l], self.vcache[l], ld=nq, S=S, pos0=past, Hq=Hq, Hkv=Hkv,
-                               ctx_max=self.ctx_max, max_pos=self.ctx_max, vt=self.vtc[l][:, :, past:], vt_ld=self.ctx_max, plan=plan)
-                ops.attention(qkv, self.kcache[l], self.vtc[l], ao, mode=1, dh=d, B=1, Hq=Hq, Hkv=Hkv, Sq=S, Skv=past + S,
-                              Skv_alloc=self.ctx_max, q_pos0=past, q_strides=(0, d, nq), k_strides=(0, self.ctx_max * d, d),
-                              v_strides=(0, d * self.ctx_max, self.ctx_max), o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=plan)
-            if tp == 1:
-                ops.gemm(ao, self._gemm_w(w["o"], plan), M=S, N=H, Kc=Hq * d, residual=h, ldr=H, round_bf16=True, out16=h, plan=plan)
-            else:
-                ops.gemm(ao, w["o"], M=S, N=H, Kc=Hq * d, out32=part, plan=plan)
-                segs += [plan, (lambda t=part: self._all_reduce(t))]
-                plan = ops.Plan()
-                ops.residual_add(h, part, S * H, plan=plan)
-            ops.norm(h, w["ln2"], None, rows=S, C=H, eps=c["rms_norm_eps"], rms=True, round_bf16=True, out16=xn, plan=plan)
-            ops.gemm(xn, self._gemm_w(w["gu"], plan), M=S, N=2 * I, Kc=H, act=ACT_SWIGLU, round_bf16=True, out16=act, ldc=I, plan=plan)
-            if tp == 1:
-                ops.gemm(act, self._gemm_w(w["down"], plan), M=S, N=H, Kc=I, residual=h, ldr=H, round_bf16=True, out16=h, plan=plan)
-            else:
-                ops.gemm(act, w["down"], M=S, N=H, Kc=I, out32=part, plan=plan)
-                segs += [plan, (lambda t=part: self._all_reduce(t))]
-                plan = ops.Plan()
-                ops.residual_add(h, part, S * H, plan=plan)
-        self._lm_head_and_pick(plan, h[S - 1], False, segs, sampling, slot=slot)
-        segs[0].hold(*[t for s in segs if isinstance(s, ops.Plan) for t in s.keep])
-        return segs, io
+        part = Z(S, H, dt=torch.float32) if self.tp_path else None
+        ops.embed_rows(self.W["embed"], h, Hd=H, ids=io["ids"], n=S, plan=rec.plan)
+
+        def gemm(W, x, *, N, K, norm_w=None, eps=None, act=0, residual=None, y16=None, y32=None, round_bf16=True):
+            """usdm_gemv's keywords on the prefill launches: usdm_norm (when asked for) + usdm_gemm (fp8: the matrix dequantized
+            first), which rounds to bf16 only in front of an epilogue"""
+            if norm_w is not None:
+                ops.norm(x, norm_w, None, rows=S, C=H, eps=eps, rms=True, round_bf16=True, out16=xn, plan=rec.plan)
+                x = xn
+            ops.gemm(x, self._gemm_w(W, rec.plan), M=S, N=N, Kc=K, act=act, round_bf16=round_bf16 and (bool(act) or residual is not None),
+                     residual=residual, ldr=H if residual is not None else 0, out32=y32, out16=y16, ldc=N // 2 if act else N, plan=rec.plan)
+
+        # Rows go to the cache of the slot or of the single sequence (fp8 cache: quantized).  The prompt's own attention reads K from
+        # that cache, or (fp8 cache) the unquantized K rows from scratch, and V^T from this plan's scratch or the persistent V^T of the
+        # single sequence (the only one that can hold a prefix: past > 0)
+        cs = slot if slot is not None else self
+        k_ld = Spad if self.kv8 else self.ctx_max
+        vt_ld = Spad if vt is not None else self.ctx_max
+
+        def attn(l):
+            vtl = vt if vt is not None else self.vtc[l]
+            ops.rope_cache(qkv, self.cos, self.sin, cs.kcache[l], cs.vcache[l], ld=nq, S=S, pos0=past, Hq=Hq, Hkv=Hkv, ctx_max=self.ctx_max,
+                           max_pos=self.ctx_max, vt=vtl[:, :, past:], vt_ld=vt_ld, kv8=(cs.kexp[l], cs.vexp[l]) if self.kv8 else None,
+                           kscr=kscr, kscr_ld=Spad if self.kv8 else 0, plan=rec.plan)
+            ops.attention(qkv, kscr if self.kv8 else cs.kcache[l], vtl, ao, mode=1, dh=d, B=1, Hq=Hq, Hkv=Hkv, Sq=S, Skv=past + S,
+                          Skv_alloc=vt_ld, q_pos0=past, q_strides=(0, d, nq), k_strides=(0, k_ld * d, d), v_strides=(0, d * vt_ld, vt_ld),
+                          o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=rec.plan)
+
+        self._layers(rec, gemm, attn, h, qkv, ao, act, "reduce" if self.tp_path else "fused", n=S * H, parts=(part, part))
+        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot)
+        return rec.finish(), io
 
     def _build_decode_p2p(self, sampling=None):
-        """Tensor-parallel decode step with the all-reduces done peer to peer: the launch sequence of the single-GPU step
-        over this rank's shards; o_proj / down_proj carry the exchange in their epilogues (fused) or are followed by
-        usdm_allreduce_p2p_reduce (split).  Returned as segments cut at every exchange so that a single-process harness can
-        interleave logical ranks; a real rank runs them back to back inside one hipGraph."""
-        c, dev, bf = self.cfg, self.device, torch.bfloat16
-        H, d, L = c["hidden_size"], c["head_dim"], c["num_hidden_layers"]
-        Hq, Hkv, I = self.Hq, self.Hkv, self.I
-        nq = (Hq + 2 * Hkv) * d
-        segs, plan = [], ops.Plan()
-        Z = lambda *s, dt=bf: plan.hold(torch.zeros(*s, device=dev, dtype=dt))
-        h, qkv, ao, act = self.h_dec, Z(nq), Z(Hq * d), Z(I)
-        pm, pl, po = Z(Hq * self.NS, dt=torch.float32), Z(Hq * self.NS, dt=torch.float32), Z(Hq * self.NS * d, dt=torch.float32)
-        skp, mode = self.st_done, (1 if self.p2p_fused else 2)
-
-        mrg = (pm, pl, po, self.NS) if self.merge_in_oproj else None
-
-        def row_parallel(plan, W, x, K, site, merge=None):
-            ops.gemv(W, x, N=H, K=K, residual=h, y16=h, skip=skp, p2p=self.p2p, p2p_site=site, p2p_mode=mode, merge=merge, plan=plan)
-            segs.append(plan)
-            plan = ops.Plan()
-            if mode == 2:
-                ops.p2p_reduce(self.p2p, site, H, h, skip=skp, plan=plan)
-            return plan
-
-        for l in range(L):
-            w = self.W["layers"][l]
-            ops.gemv(w["qkv"], h, N=nq, K=H, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, skip=skp, plan=plan)
-            ops.attn_decode(qkv, self.st_pos, self.cos, self.sin, self.kcache[l], self.vcache[l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
-                            ctx_max=self.ctx_max, NS=self.NS, scale=d ** -0.5, skip=skp, defer_merge=mrg is not None, window=self.window, plan=plan)
-            plan = row_parallel(plan, w["o"], ao, Hq * d, 2 * l, merge=mrg)
-            ops.gemv(w["gu"], h, N=2 * I, K=H, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU, y16=act, skip=skp, plan=plan)
-            plan = row_parallel(plan, w["down"], act, I, 2 * l + 1)
-        self._lm_head_and_pick(plan, h, True, segs, sampling, skip=skp)
-        segs[0].hold(*[t for s_ in segs for t in s_.keep])
-        return segs
+        """The decode step of a peer-to-peer model (_build_decode builds it: way "p2p")."""
+        if self.p2p is None:
+            raise ValueError("_build_decode_p2p needs a model with a P2PComm")
+        return self._build_decode(sampling)
 
     def _build_decode(self, sampling=None):
+        """One decode step of the single sequence.  Tensor parallel with a P2PComm: the launch sequence of the single-GPU step over
+        this rank's shards, o_proj / down_proj carry the exchange (_layers, way "p2p"); returned as segments cut at every exchange,
+        which a real rank runs back to back inside one hipGraph."""
+        dev, bf = self.device, torch.bfloat16
+        H, d, L, Hq, Hkv, I, nq = self._dims()
         if self.p2p is not None:
-            return self._build_decode_p2p(sampling)
-        c, dev, bf = self.cfg, self.device, torch.bfloat16
-        H, d, L = c["hidden_size"], c["head_dim"], c["num_hidden_layers"]
-        Hq, Hkv, I, tp = self.Hq, self.Hkv, self.I, (2 if self.tp_path else 1)
-        nq = (Hq + 2 * Hkv) * d
-        segs, plan = [], ops.Plan()
-        Z = lambda *s, dt=bf: plan.hold(torch.zeros(*s, device=dev, dtype=dt))
+            way = "p2p"
+        elif not self.tp_path:
+            way = "fused"
+        else:
+            way = "deferred" if os.environ.get("USDM_TP_FUSED_RESIDUAL", "1") == "1" else "reduce"
+        collective = way in ("deferred", "reduce")
+        rec = _Segments()
+        Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
         h, qkv, ao, act = self.h_dec, Z(nq), Z(Hq * d), Z(I)
         pm, pl, po = Z(Hq * self.NS, dt=torch.float32), Z(Hq * self.NS, dt=torch.float32), Z(Hq * self.NS * d, dt=torch.float32)
-        part = Z(H, dt=torch.float32) if tp > 1 else None
+        parts = (Z(H, dt=torch.float32), Z(H, dt=torch.float32)) if collective else None
+        h_alt = Z(H) if collective else None
         # last-arriver counters of the fused partial merge (self-resetting).  Off by default: measured 11.3-11.6 us per layer
         # against 5.9 + 4.6 us for the split kernel + merge kernel (profiles/r01_decode_ablation.txt)
-        cnt = Z(Hkv, dt=torch.int32) if os.environ.get("USDM_ATTN_FUSED_MERGE", "0") == "1" else None
-        # Tensor-parallel path: the residual add that follows each all-reduce is folded into the NEXT GEMV's prologue
-        # (usdm_gemv x_delta / x_out) instead of a usdm_residual_add launch; the residual stream ping-pongs between two
-        # buffers because workgroup 0 publishes the updated stream while the others still read the old one.
-        h_alt = Z(H) if tp > 1 else None
-        fuse_res = tp > 1 and os.environ.get("USDM_TP_FUSED_RESIDUAL", "1") == "1"
-        pend = None   # f32 partial (already all-reduced) not yet added to the residual stream
-        part2 = Z(H, dt=torch.float32) if tp > 1 else None
-
-        def flip(cur):
-            return h_alt if cur is self.h_dec else self.h_dec
-
+        cnt = Z(Hkv, dt=torch.int32) if (os.environ.get("USDM_ATTN_FUSED_MERGE", "0") == "1" and way != "p2p") else None
         skp = self.st_done   # decode kernels return at once after a device-side EOS (see _alloc)
         cmb_gran = Z(L, Hq * 64, dt=torch.int64) if self.cmb else None      # one granule block per layer (tags cleared by the layer's attention launch)
-        if self.cmb and not hasattr(self, "cmb_err"):
-            self.cmb_err = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the chained forms (USDM_GEMV_CHAIN): o_proj -> gate/up -> down_proj [-> the next layer's qkv] become the phases of ONE
+        # launch; `chain` holds the phases of the open chain (None: every projection is its own launch)
+        chained = way == "fused" and self.chain in (3, 4) and cnt is None and not self.merge_in_oproj
+        use_cmb = self.cmb and way == "fused" and not chained and cnt is None and self.NS > 1
+        mrg = (pm, pl, po, self.NS) if ((self.merge_in_oproj or use_cmb) and cnt is None) else None
+        chain = None
 
-        if tp == 1 and self.chain in (3, 4) and cnt is None and not self.merge_in_oproj:
-            G = lambda *a_, **k_: ops.gemv(*a_, skip=skp, only_args=True, **k_)
-            for l in range(L):
-                w = self.W["layers"][l]
-                if l == 0 or self.chain == 3:
-                    ops.gemv(w["qkv"], h, N=nq, K=H, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, skip=skp, plan=plan)
-                ops.attn_decode(qkv, self.st_pos, self.cos, self.sin, self.kcache[l], self.vcache[l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
-                                ctx_max=self.ctx_max, NS=self.NS, scale=d ** -0.5, skip=skp, window=self.window, plan=plan)
-                ph = [G(w["o"], ao, N=H, K=Hq * d, residual=h, y16=h),
-                      G(w["gu"], h, N=2 * I, K=H, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU, y16=act),
-                      G(w["down"], act, N=H, K=I, residual=h, y16=h)]
-                if self.chain == 4 and l + 1 < L:
-                    w2 = self.W["layers"][l + 1]
-                    ph.append(G(w2["qkv"], h, N=nq, K=H, norm_w=w2["ln1"], eps=c["rms_norm_eps"], y16=qkv))
-                sync = self.chain_sync[0 if len(ph) == self.chain else 1]
-                if self.chain_engine:
-                    ops.gemv_engine(ph, sync, self.chain_gran, plan=plan)
-                else:
-                    ops.gemv_chain(ph, sync, plan=plan)
-            self._lm_head_and_pick(plan, h, True, segs, sampling, skip=skp)
-            segs[0].hold(*[t for s in segs if isinstance(s, ops.Plan) for t in s.keep])
-            return segs
-        for l in range(L):   # h already holds the embedding of the current token (written by usdm_argmax_final)
-            w = self.W["layers"][l]
-            if pend is not None:
-                ops.gemv(w["qkv"], h, N=nq, K=H, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, x_delta=pend, x_out=flip(h), skip=skp, plan=plan)
-                h, pend = flip(h), None
+        def flush():
+            nonlocal chain
+            sync = self.chain_sync[0 if len(chain) == self.chain else 1]
+            if self.chain_engine:
+                ops.gemv_engine(chain, sync, self.chain_gran, plan=rec.plan)
             else:
-                ops.gemv(w["qkv"], h, N=nq, K=H, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, skip=skp, plan=plan)
-            use_cmb = self.cmb and tp == 1 and cnt is None and self.NS > 1 and cmb_gran is not None
-            mrg = (pm, pl, po, self.NS) if ((self.merge_in_oproj or use_cmb) and cnt is None) else None
+                ops.gemv_chain(chain, sync, plan=rec.plan)
+            chain = None
+
+        def gemv(W, x, **kw):
+            if chain is None:
+                return ops.gemv(W, x, skip=skp, plan=rec.plan, **kw)
+            chain.append(ops.gemv(W, x, skip=skp, only_args=True, **kw))
+            if len(chain) == self.chain:
+                flush()
+
+        def attn(l):   # h already holds the embedding of the current token (written by usdm_argmax_final)
+            nonlocal chain
             gran = cmb_gran[l] if use_cmb else None
             ops.attn_decode(qkv, self.st_pos, self.cos, self.sin, self.kcache[l], self.vcache[l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
                             ctx_max=self.ctx_max, NS=self.NS, scale=d ** -0.5, counters=cnt, skip=skp, defer_merge=mrg is not None, window=self.window,
-                            cmb_gran=gran, kv8=(self.kexp[l], self.vexp[l]) if self.kv8 else None, plan=plan)
-            if tp == 1:
-                ops.gemv(w["o"], ao, N=H, K=Hq * d, residual=h, y16=h, skip=skp, merge=mrg, cmb=(gran, self.cmb_err) if use_cmb else None, plan=plan)
-            else:
-                ops.gemv(w["o"], ao, N=H, K=Hq * d, round_bf16=False, y32=part, skip=skp, merge=mrg, plan=plan)
-                segs += [plan, (lambda t=part: self._all_reduce(t))]
-                plan = ops.Plan()
-                if fuse_res:
-                    pend = part
-                else:
-                    ops.residual_add(h, part, H, plan=plan)
-            if pend is not None:
-                ops.gemv(w["gu"], h, N=2 * I, K=H, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU, y16=act, x_delta=pend,
-                         x_out=flip(h), skip=skp, plan=plan)
-                h, pend = flip(h), None
-            else:
-                ops.gemv(w["gu"], h, N=2 * I, K=H, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU, y16=act, skip=skp, plan=plan)
-            if tp == 1:
-                ops.gemv(w["down"], act, N=H, K=I, residual=h, y16=h, skip=skp, plan=plan)
-            else:
-                ops.gemv(w["down"], act, N=H, K=I, round_bf16=False, y32=part2, skip=skp, plan=plan)
-                segs += [plan, (lambda t=part2: self._all_reduce(t))]
-                plan = ops.Plan()
-                if fuse_res:
-                    pend = part2
-                else:
-                    ops.residual_add(h, part2, H, plan=plan)
-        if pend is not None:   # the last down-projection's sum goes into the final norm + lm_head
-            self._lm_head_and_pick(plan, h, True, segs, sampling, x_delta=pend, skip=skp)
-        else:
-            self._lm_head_and_pick(plan, h, True, segs, sampling, skip=skp)
-        segs[0].hold(*[t for s in segs if isinstance(s, ops.Plan) for t in s.keep])
-        return segs
+                            cmb_gran=gran, kv8=(self.kexp[l], self.vexp[l]) if self.kv8 else None, plan=rec.plan)
+            if chained:
+                chain = []
+                return None
+            return dict(merge=mrg, cmb=(gran, self.cmb_err) if use_cmb else None)
+
+        h, pend = self._layers(rec, gemv, attn, h, qkv, ao, act, way, n=H, parts=parts, h_alt=h_alt)
+        if chain:     # the last layer's chain has no next qkv to wait for
+            flush()
+        # (pend: the last down-projection's sum goes into the final norm + lm_head)
+        self._lm_head_and_pick(rec, h, True, sampling, x_delta=pend, skip=skp)
+        return rec.finish()
 
     @staticmethod
     def _run_segs(segs):
@@ -731,9 +730,26 @@ class USDMForCausalLM:
             else:
                 s()
 
+    def _graphed(self, built, enabled=None):
+        """What a builder returned -> the step that replays it: a GraphedPlan when no host call sits between the launches (segments
+        that were cut for the lockstep harness only, the peer-to-peer step, are joined: kernels only, one plan, one hipGraph), else
+        GraphedSegments."""
+        segs = built if isinstance(built, list) else [built]
+        if any(not isinstance(s, ops.Plan) for s in segs):
+            return GraphedSegments(segs, self._run_segs, enabled=enabled)
+        plan = segs[0]
+        if len(segs) > 1:
+            plan = ops.Plan()
+            for s in segs:
+                plan.calls += s.calls
+                plan.hold(*s.keep)
+        return GraphedPlan(plan)
+
     # ------------------------------------------------------------------ batched decode (SURVEY.md §8f-2)
     class _Slot:
-        """Views of the batch buffers that stand in for the single-sequence attributes during a per-item prefill."""
+        """Views of the batch buffers that stand in for the single-sequence attributes during a per-item prefill (batch = 0), or, as
+        the batch's "all" view, during the lm_head + pick of the batched step (batch = B).  No device-side end of sequence."""
+        batch, st_done, st_eos = 0, None, None
 
     def _batch_buffers(self, B):
         if B in self._batches:
@@ -777,6 +793,11 @@ class USDMForCausalLM:
             sl.logits_row = bb.get("lrow")
             slots.append(sl)
         bb["slots"] = slots
+        al = bb["all"] = self._Slot()      # the whole batch, for the batched step's lm_head + pick
+        al.batch, al.st_next, al.st_step, al.st_pos, al.st_out, al.h_dec = B, bb["nxt"], bb["step"], bb["pos"], bb["out"], bb["h"]
+        al.part_val_loc, al.part_idx_loc = bb["pv"], bb["pi"]
+        al.part_val, al.part_idx = (bb["pvg"], bb["pig"]) if self.tp_path else (bb["pv"], bb["pi"])
+        al.logits, al.sample_params, al.logits_row = bb["logits"], bb["sp"], bb.get("lg")
         self._batches[B] = bb
         return bb
 
@@ -784,23 +805,20 @@ class USDMForCausalLM:
         """One decode step of B sequences: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
         sampling: the pick is usdm_sample_final's batched form - every slot draws with its OWN knobs (bb["sp"][b]: temperature,
         top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1."""
-        c, dev, bf = self.cfg, self.device, torch.bfloat16
-        H, d, L = c["hidden_size"], c["head_dim"], c["num_hidden_layers"]
-        Hq, Hkv, I = self.Hq, self.Hkv, self.I
-        nq = (Hq + 2 * Hkv) * d
+        dev, bf = self.device, torch.bfloat16
+        H, d, L, Hq, Hkv, I, nq = self._dims()
         bb = self._batch_buffers(B)
-        plan = ops.Plan()
-        Z = lambda *s, dt=bf: plan.hold(torch.zeros(*s, device=dev, dtype=dt))
+        rec = _Segments()
+        Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
         h, qkv, ao, act = bb["h"], Z(B, nq), Z(B, Hq * d), Z(B, I)
         NS = max(2, self.NS)
         if B > 4:
             # many sequences: B x Hkv x NS workgroups of ctx / NS keys each.  The batch-1 choice (32 splits of ~20 keys: latency-bound,
             # one per CU) would be 4096 tiny workgroups at B = 16 (measured 35.6 us per layer); ~512 workgroups with up to 512 keys
             # (the split kernel's LDS bound) keep the KV stream at full width.  (B <= 4 keeps the batch-1 splits: bit-identical.)
-            NS = max(-(-self.ctx_max // 512), min(self.NS, max(2, getattr(self, "batch_attn_wgs", 512) // (B * Hkv))))
+            NS = max(-(-self.ctx_max // 512), min(self.NS, max(2, self.batch_attn_wgs // (B * Hkv))))
         pm, pl, po = Z(B * Hq * NS, dt=torch.float32), Z(B * Hq * NS, dt=torch.float32), Z(B * Hq * NS * d, dt=torch.float32)
-        # (tools/batch_rate.py A/B: the merge by the last-arriving workgroup of a kv head instead of the combine launch)
-        cnt = Z(B * Hkv, dt=torch.int32) if B > 4 and getattr(self, "batch_fused_merge", False) else None
+        cnt = Z(B * Hkv, dt=torch.int32) if B > 4 and self.batch_fused_merge else None
         cache_bs = L * Hkv * self.ctx_max * d
         # down_proj on the matrix cores (K = 14336): K split over workgroups, each holding its activation slice (usdm_gemv_batch ks_*);
         # one scratch for all layers - the launches of a step are serial and each leaves the counters zero
@@ -809,62 +827,28 @@ class USDMForCausalLM:
         # Tensor parallel (SURVEY.md 8e x 8f-2; round 4, the collective form): the row-parallel projections leave f32 partial sums
         # [B][H], all-reduced through the job's process group (RCCL: one collective of B x 16 KB per projection instead of B of them),
         # then usdm_residual_add applies HF's rounding points; the plan is cut into segments at the collectives, as the
-        # single-sequence RCCL path is.  Sampled: the slots' logits rows are gathered and drawn from on every rank
-        # (usdm_sample_final_seg).
+        # single-sequence RCCL path is (_layers, way "reduce").  Sampled: the slots' logits rows are gathered and drawn from on every
+        # rank (usdm_sample_final_seg).
         tp = self.tp_path
-        segs = []
-        part, part2 = (Z(B, H, dt=torch.float32), Z(B, H, dt=torch.float32)) if tp else (None, None)
-
+        parts = (Z(B, H, dt=torch.float32), Z(B, H, dt=torch.float32)) if tp else None
         # fp8_matrix_cores: the FP8 projections of 5..16 sequences on the matrix cores (usdm_gemv_fp8_mfma: the bf16 form's tiles, K
         # split and epilogues, so the same ks scratch); <= 4 keep the VALU FP8 form of gemv_batch
         gemv_b = ops.gemv_fp8_mfma if (self.fp8_matrix_cores and B > 4) else ops.gemv_batch
 
-        def row_parallel(W, x, K, buf, plan):
-            ops.gemv_batch(W, x, nb=B, N=H, K=K, x_bs=K, y_bs=H, round_bf16=False, y32=buf, plan=plan)
-            segs.extend([plan, (lambda t=buf: self._all_reduce(t))])
-            plan = ops.Plan()
-            ops.residual_add(h, buf, B * H, plan=plan)
-            return plan
-        for l in range(L):
-            w = self.W["layers"][l]
-            gemv_b(w["qkv"], h, nb=B, N=nq, K=H, x_bs=H, y_bs=nq, norm_w=w["ln1"], eps=c["rms_norm_eps"], y16=qkv, plan=plan)
+        def gemv(W, x, *, N, K, act=0, residual=None, y_bs=None, **kw):
+            """usdm_gemv's keywords over the B rows: x [B][K], outputs [B][N] (SwiGLU: half of that), residual [B][N]"""
+            gemv_b(W, x, nb=B, N=N, K=K, x_bs=K, y_bs=(N // 2 if act else N) if y_bs is None else y_bs, res_bs=N if residual is not None else 0,
+                   act=act, residual=residual, plan=rec.plan, **kw)
+
+        def attn(l):
             ops.attn_decode(qkv, bb["pos"], self.cos, self.sin, bb["kc"][0, l], bb["vc"][0, l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
                             ctx_max=self.ctx_max, NS=NS, scale=d ** -0.5, batch=B, qkv_bs=nq, out_bs=Hq * d, cache_bs=cache_bs, window=self.window,
-                            counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=plan)
-            if tp:
-                plan = row_parallel(w["o"], ao, Hq * d, part, plan)
-            else:
-                gemv_b(w["o"], ao, nb=B, N=H, K=Hq * d, x_bs=Hq * d, y_bs=H, res_bs=H, residual=h, y16=h, plan=plan)
-            gemv_b(w["gu"], h, nb=B, N=2 * I, K=H, x_bs=H, y_bs=I, norm_w=w["ln2"], eps=c["rms_norm_eps"], act=ACT_SWIGLU,
-                   y16=act, plan=plan)
-            if tp:
-                plan = row_parallel(w["down"], act, I, part2, plan)
-            else:
-                gemv_b(w["down"], act, nb=B, N=H, K=I, x_bs=I, y_bs=H, res_bs=H, residual=h, y16=h, ks=ks, plan=plan)
-        gemv_b(self.W["lm_head"], h, nb=B, N=self.v1 - self.v0, K=H, x_bs=H, part_bs=self.nparts, norm_w=self.W["norm"],
-               eps=c["rms_norm_eps"], ban=self.ban, part_val=bb["pv"], part_idx=bb["pi"], idx_offset=self.v0,
-               **(dict(y32=bb["logits"], y_bs=self.Vloc) if sampling else {}), plan=plan)
-        st = ops.decode_state(bb["nxt"], bb["out"], bb["step"], bb["pos"], advance_pos=True, batch=B)
-        if sampling and tp:   # [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
-            segs.extend([plan, (lambda: self._gather_partials([bb["lg"]], [bb["logits"]]))])
-            plan = ops.Plan()
-            ops.sample_final(bb["lg"], st, dev_params=bb["sp"], V=c["vocab_size"], nseg=self.tp_size, seg_stride=B * self.Vloc,
-                             seg_len=self.Vloc, embed=self.W["embed"], h_out=h, Hd=H, plan=plan)
-        elif sampling:
-            ops.sample_final(bb["logits"], st, dev_params=bb["sp"], embed=self.W["embed"], h_out=h, Hd=H, plan=plan)
-        elif tp:      # vocab-parallel pick: the ranks' [B][nparts] partials gathered rank-major, one pick per sequence over all of them
-            segs.extend([plan, (lambda: self._gather_partials([bb["pvg"], bb["pig"]], [bb["pv"], bb["pi"]]))])
-            plan = ops.Plan()
-            ops.argmax_final(bb["pvg"], bb["pig"], self.nparts, st, embed=self.W["embed"], h_out=h, Hd=H, nseg=self.tp_size,
-                             seg_stride=B * self.nparts, plan=plan)
-        else:
-            ops.argmax_final(bb["pv"], bb["pi"], self.nparts, st, embed=self.W["embed"], h_out=h, Hd=H, plan=plan)
-        plan.hold(st)
-        if tp:
-            segs.append(plan)
-            segs[0].hold(*[t for sg in segs if isinstance(sg, ops.Plan) for t in sg.keep])
-            return segs
-        return plan
+                            counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=rec.plan)
+
+        self._layers(rec, gemv, attn, h, qkv, ao, act, "reduce" if tp else "fused", n=B * H, parts=parts, down_kw={} if tp else dict(ks=ks))
+        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv)
+        segs = rec.finish()
+        return segs if tp else segs[0]
 
     MAX_BATCH = 16      # sequences per decode step (usdm_gemv_batch: VALU form up to 4, matrix-core form up to 16)
 
@@ -895,6 +879,24 @@ class USDMForCausalLM:
             outs += self._generate_group(input_ids_list[g0:g0 + group], max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens)
         return outs
 
+    def _batch_step(self, B, sampling=False):
+        """The replayable decode step of the B slots, greedy or sampled (built at first use)."""
+        bb = self._batch_buffers(B)
+        key = "decode_sampled" if sampling else "decode"
+        if bb[key] is None:
+            bb[key] = self._graphed(self._build_decode_batch(B, sampling=sampling))
+        return bb[key]
+
+    def _admit(self, B, b, ids, sampling=False):
+        """Admit a prompt (ids [L]) into slot b of the B slots: its step / position counters, then the per-item prefill into the
+        slot's cache, which also picks the first token (sampled too when the batch runs on the sampling step)."""
+        bb, L = self._batch_buffers(B), int(ids.shape[0])
+        bb["step"][b] = 0
+        bb["pos"][b] = L
+        segs, io = bb["prefill"].get_or_build((L, b, sampling), lambda: self._build_prefill(L, True if sampling else None, slot=bb["slots"][b]))
+        io["ids"].copy_(ids)
+        self._run_segs(segs)
+
     def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens):
         B = len(ids_list)
         for ids in ids_list:
@@ -906,31 +908,22 @@ class USDMForCausalLM:
         max_new = min(max_new_tokens, self.ctx_max - max(L0), self.max_out)
         if max_new <= 0:
             return [ids.clone() for ids in ids_list]
-        bb["step"].zero_()
-        bb["pos"].copy_(torch.tensor(L0, dtype=torch.int32))
-        for b, ids in enumerate(ids_list):            # per-item prefill into that item's cache / state slot (+ first token)
-            key = (L0[b], b)
-            segs, io = bb["prefill"].get_or_build(key, lambda: self._build_prefill(L0[b], None, slot=bb["slots"][b]))
-            io["ids"].copy_(ids[0])
-            self._run_segs(segs)
-        if bb["decode"] is None:
-            built = self._build_decode_batch(B)
-            bb["decode"] = GraphedSegments(built, self._run_segs) if isinstance(built, list) else GraphedPlan(built)
-        eos = set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]) if eos_token_id is not None else set()
+        for b, ids in enumerate(ids_list):
+            self._admit(B, b, ids[0])
+        decode = self._batch_step(B)
+        eos = stop_ids(eos_token_id)
         produced, chunk = 1, 8
         ends = [None] * B
         while True:
             toks = bb["out"][:, :produced].tolist()     # host sync point (EOS check)
             for b in range(B):
                 if ends[b] is None:
-                    hit = [i for i, t in enumerate(toks[b]) if t in eos and i + 1 >= min_new_tokens]
-                    if hit:
-                        ends[b] = hit[0] + 1
+                    ends[b] = stop_index(toks[b], eos, min_new_tokens)
             if all(e is not None for e in ends) or produced >= max_new:
                 break
             n = min(chunk, max_new - produced)
             for _ in range(n):
-                bb["decode"].run()
+                decode.run()
             produced += n
         res = []
         for b, ids in enumerate(ids_list):
@@ -974,7 +967,7 @@ class USDMForCausalLM:
             self.ban.copy_(self._ban_mask(bad_words_ids))
         self.st_pos.fill_(L0)
         self.st_step.zero_()
-        eos_list = sorted(set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])) if eos_token_id is not None else []
+        eos_list = sorted(stop_ids(eos_token_id))
         dev_eos = eos_list if len(eos_list) <= 6 else []      # more ids than the device list holds: host-side check only
         self.st_eos.copy_(torch.tensor(([len(dev_eos), int(min_new_tokens)] + dev_eos + [0] * 6)[:8], dtype=torch.int32))
         self.st_done.zero_()
@@ -1032,20 +1025,10 @@ class USDMForCausalLM:
                 self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
         segs, dev_eos = self._setup_call(input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask)
         self._run_segs(segs)  # prefill + first token
-        if sampling not in self._decodes:
-            dsegs = self._build_decode(sampling)
-            if self.p2p is not None:      # kernels only (the exchange lives inside them): one plan, one hipGraph
-                merged = ops.Plan()
-                for s_ in dsegs:
-                    merged.calls += s_.calls
-                    merged.hold(*s_.keep)
-                dsegs = [merged]
-            if sampling == "hook":
-                self._decodes[sampling] = GraphedSegments(dsegs, self._run_segs, enabled=False)      # host code inside: never captured
-            else:
-                self._decodes[sampling] = GraphedPlan(dsegs[0]) if (len(dsegs) == 1) else GraphedSegments(dsegs, self._run_segs)
+        if sampling not in self._decodes:      # (the hooked step has host code inside: never captured)
+            self._decodes[sampling] = self._graphed(self._build_decode(sampling), enabled=False if sampling == "hook" else None)
         self._decode = self._decodes[sampling]
-        eos = set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]) if eos_token_id is not None else set()
+        eos = stop_ids(eos_token_id)
         produced, done, chunk = 1, False, 8
         toks = []
         while True:
@@ -1057,12 +1040,12 @@ class USDMForCausalLM:
             if self.chain and int(self.chain_sync[:, 1].sum().item()):
                 raise RuntimeError("usdm_gemv_chain: a grid barrier timed out (the persistent decode kernel was not fully resident); "
                                    "results are invalid - rerun with USDM_GEMV_CHAIN=0")
-            if getattr(self, "cmb_err", None) is not None and int(self.cmb_err.item()):
+            if self.cmb_err is not None and int(self.cmb_err.item()):
                 raise RuntimeError("usdm_gemv (cmb_gran): the in-launch attention hand-off timed out (the o_proj launch was not fully "
                                    "resident); results are invalid - rerun with USDM_ATTN_CMB=0")
-            hit = [i for i, t in enumerate(toks) if t in eos and i + 1 >= min_new_tokens]
-            if hit:
-                toks = toks[:hit[0] + 1]
+            end = stop_index(toks, eos, min_new_tokens)
+            if end is not None:
+                toks = toks[:end]
                 break
             if produced >= max_new_tokens:
                 toks = toks[:max_new_tokens]

@@ -2,8 +2,7 @@
 
 These exist for the parity tests and for the Python drop-ins; they add no arithmetic.
 """
-import ctypes as C
-import ctypes as C_
+import ctypes as C_      # (C is the channel count in several wrappers' keywords)
 import os
 
 import torch
@@ -15,7 +14,7 @@ from .quant import Fp8Weight
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return C_.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class Plan:
@@ -54,7 +53,7 @@ def _go(plan, what, fn, *args):
 
 
 def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    return C_.c_void_p(t.data_ptr()) if t is not None else C_.c_void_p(0)
 
 
 def _dt(t):
@@ -112,8 +111,8 @@ def gemm(A, W, *, M, N, Kc, taps=1, lda=None, rowsA=None, a_row_mul=1, a_row_off
         a.qkv_S, a.qkv_Spad, a.qkv_H, a.qkv_D = qkv["S"], qkv["Spad"], qkv["H"], qkv["D"]
         a.qkv_q, a.qkv_k, a.qkv_v = _ptr(qkv["q"]), _ptr(qkv["k"]), _ptr(qkv["v"])
     if tile_query:
-        return lib.usdm_gemm_tile_for(C.byref(a))
-    _go(plan, "usdm_gemm", lib.usdm_gemm, C.byref(a))
+        return lib.usdm_gemm_tile_for(C_.byref(a))
+    _go(plan, "usdm_gemm", lib.usdm_gemm, C_.byref(a))
 
 
 def norm(x, gamma, beta=None, *, rows, C, eps=1e-5, res=None, rms=False, act=0, round_bf16=False, premask=False,
@@ -172,7 +171,7 @@ def attention(q, k, vt, o, *, mode, dh, B, Hq, Hkv, Sq, Skv, Skv_alloc, q_stride
 def sum3_scale(a, b, c, scale, *, out32=None, out16=None, plan=None):
     _need_cuda(a, b, c, out32, out16)
     n = a.numel()
-    _go(plan, "usdm_sum3_scale", lib.usdm_sum3_scale, _ptr(a), _ptr(b), _ptr(c), C.c_float(scale), C.c_int64(n),
+    _go(plan, "usdm_sum3_scale", lib.usdm_sum3_scale, _ptr(a), _ptr(b), _ptr(c), C_.c_float(scale), C_.c_int64(n),
         _ptr(out32), _ptr(out16))
 
 
@@ -236,21 +235,28 @@ def process_unit(units, rep, hop):
     return out
 
 
-def gemv(W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True, residual=None, y16=None, y32=None,
-         ban=None, part_val=None, part_idx=None, idx_offset=0, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0,
-         p2p_mode=0, merge=None, cmb=None, plan=None, only_args=False):
-    """usdm_gemv: batch-1 weight-streaming GEMV (see include/usdm_hip.h).  p2p: a usdm_amd.p2p.P2PComm (fused all-reduce).
-    only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
-    W a quant.Fp8Weight: usdm_gemv_fp8 (the plain single-GPU forms only; the library refuses the others)."""
-    _need_cuda(W, x, norm_w, residual, y16, y32, ban, part_val, part_idx, x_delta, x_out, skip)
-    if x_out is not None and x_out.data_ptr() == x.data_ptr():
-        raise ValueError("usdm_gemv: x_out must not alias x")
-    a = GemvArgs()
+def _fill_gemv(a, W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True, residual=None, y16=None, y32=None,
+               ban=None, part_val=None, part_idx=None, idx_offset=0):
+    """The usdm_gemv_args fields that gemv, gemv_batch and gemv_fp8_mfma share (see include/usdm_hip.h)."""
+    _need_cuda(W, x, norm_w, residual, y16, y32, ban, part_val, part_idx)
     a.W, a.ldw, a.N, a.K = _ptr(W), (ldw if ldw is not None else K), N, K
     a.x, a.norm_w, a.eps = _ptr(x), _ptr(norm_w), eps
     a.act, a.round_bf16 = act, int(round_bf16)
     a.residual, a.y16, a.y32 = _ptr(residual), _ptr(y16), _ptr(y32)
     a.ban, a.part_val, a.part_idx, a.idx_offset = _ptr(ban), _ptr(part_val), _ptr(part_idx), idx_offset
+
+
+def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p_mode=0, merge=None, cmb=None, plan=None,
+         only_args=False, **common):
+    """usdm_gemv: batch-1 weight-streaming GEMV (see include/usdm_hip.h; **common: the keywords of _fill_gemv).
+    p2p: a usdm_amd.p2p.P2PComm (fused all-reduce).
+    only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
+    W a quant.Fp8Weight: usdm_gemv_fp8 (the plain single-GPU forms only; the library refuses the others)."""
+    _need_cuda(x_delta, x_out, skip)
+    if x_out is not None and x_out.data_ptr() == x.data_ptr():
+        raise ValueError("usdm_gemv: x_out must not alias x")
+    a = GemvArgs()
+    _fill_gemv(a, W, x, **common)
     a.x_delta, a.x_out, a.skip = _ptr(x_delta), _ptr(x_out), _ptr(skip)
     if merge is not None:       # (pm, pl, po, NS): x is merged from the decode-attention partials in the prologue
         pm, pl, po, ns = merge
@@ -259,11 +265,11 @@ def gemv(W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
     if cmb is not None:         # (granules int64 [K/2], err int32 [1]): the hand-off form of `merge` (one combine per head, see usdm_hip.h)
         gran, err = cmb
         _need_cuda(gran, err)
-        if merge is None or gran.numel() * gran.element_size() < (K // 2) * 8:
+        if merge is None or gran.numel() * gran.element_size() < (a.K // 2) * 8:
             raise ValueError("usdm_gemv: cmb needs merge=(pm, pl, po, NS) and K/2 8-byte granules")
         a.cmb_gran, a.cmb_err, a.cmb_timeout_ms = _ptr(gran), _ptr(err), 200
     if p2p is not None and p2p_mode:
-        p2p.check_site(p2p_site, N)
+        p2p.check_site(p2p_site, a.N)
         a.p2p, a.p2p_site, a.p2p_mode = p2p.dev_ptr, p2p_site, p2p_mode
     if isinstance(W, Fp8Weight):
         if only_args:
@@ -342,7 +348,7 @@ def argmax_final(part_val, part_idx, nparts, st, embed=None, h_out=None, Hd=0, n
 
 def sample_params_tensor(device, n=1):
     """Device block holding n usdm_sample_params (24 bytes each: temperature, top_k, top_p, reserved, seed)."""
-    sz = C.sizeof(_lib.SampleParams)
+    sz = C_.sizeof(_lib.SampleParams)
     return torch.zeros(sz if n == 1 else (n, sz), dtype=torch.uint8, device=device)
 
 
@@ -427,25 +433,18 @@ def rope_cache(qkv, cos, sin, kcache, vcache, *, ld, S, pos0, Hq, Hkv, ctx_max, 
     _go(plan, "usdm_rope_cache_fp8", lib.usdm_rope_cache_fp8, C_.byref(f))
 
 
-def gemv_batch(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
-               residual=None, y16=None, y32=None, ban=None, part_val=None, part_idx=None, idx_offset=0, form=0, ks=None, plan=None,
-               only_args=False):
-    """usdm_gemv_batch: the decode projection over nb <= 16 input vectors (x is [nb][x_bs], outputs [nb][y_bs]).
+def gemv_batch(W, x, *, nb, x_bs, y_bs=0, res_bs=0, part_bs=0, form=0, ks=None, plan=None, only_args=False, **common):
+    """usdm_gemv_batch: the decode projection over nb <= 16 input vectors (x is [nb][x_bs], outputs [nb][y_bs]; **common: the
+    keywords of _fill_gemv).
     form 0: VALU kernel for nb <= 4, matrix-core kernel above; 1: matrix cores; -1: VALU; 3 / 5: A/B forms of the matrix-core kernel.
     ks = (part f32 [gemv_batch_ks_floats(N, K)], counters int32 [ceil(N / 16)], zero): K split over workgroups (K > 4096)."""
-    _need_cuda(W, x, norm_w, residual, y16, y32, ban, part_val, part_idx)
     b = GemvBatchArgs()
-    a = b.g
-    a.W, a.ldw, a.N, a.K = _ptr(W), (ldw if ldw is not None else K), N, K
-    a.x, a.norm_w, a.eps = _ptr(x), _ptr(norm_w), eps
-    a.act, a.round_bf16 = act, int(round_bf16)
-    a.residual, a.y16, a.y32 = _ptr(residual), _ptr(y16), _ptr(y32)
-    a.ban, a.part_val, a.part_idx, a.idx_offset = _ptr(ban), _ptr(part_val), _ptr(part_idx), idx_offset
+    _fill_gemv(b.g, W, x, **common)
     b.nb, b.x_bs, b.y_bs, b.res_bs, b.part_bs, b.form = nb, x_bs, y_bs, res_bs, part_bs, form
     if ks is not None:
         part, cnt = ks
         _need_cuda(part, cnt)
-        if part.dtype != torch.float32 or cnt.dtype != torch.int32 or cnt.numel() < -(-N // 16):
+        if part.dtype != torch.float32 or cnt.dtype != torch.int32 or cnt.numel() < -(-b.g.N // 16):
             raise ValueError("usdm_gemv_batch: ks = (float32 partials, int32 counters [ceil(N / 16)])")
         b.ks_part, b.ks_cnt, b.ks_part_floats = _ptr(part), _ptr(cnt), part.numel()
     if only_args:         # (gemv_fp8_mfma: the filled usdm_gemv_batch_args)
@@ -458,18 +457,14 @@ def gemv_batch(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, n
     _go(plan, "usdm_gemv_batch", lib.usdm_gemv_batch, C_.byref(b))
 
 
-def gemv_fp8_mfma(W, x, *, nb, N, K, x_bs, y_bs=0, res_bs=0, part_bs=0, ldw=None, norm_w=None, eps=1e-5, act=0, round_bf16=True,
-                  residual=None, y16=None, y32=None, ban=None, part_val=None, part_idx=None, idx_offset=0, form=0, ks=None, plan=None):
+def gemv_fp8_mfma(W, x, *, plan=None, **kw):
     """usdm_gemv_fp8_mfma: the matrix-core form (nb <= 16) on a quant.Fp8Weight, opt-in.  Keywords as gemv_batch; form 0 (K split
     where ks is given) or 5 (no split).  Equals gemv_batch(W.dequantize(), ..., form=1 or 5) bit for bit; NOT bit-identical with the
     VALU form that gemv_batch runs on an Fp8Weight (nb <= 4)."""
     if not isinstance(W, Fp8Weight):
         raise TypeError("gemv_fp8_mfma takes a quant.Fp8Weight (bf16 weights: gemv_batch)")
-    b = gemv_batch(W.q, x, nb=nb, N=N, K=K, x_bs=x_bs, y_bs=y_bs, res_bs=res_bs, part_bs=part_bs, ldw=ldw, norm_w=norm_w, eps=eps,
-                   act=act, round_bf16=round_bf16, residual=residual, y16=y16, y32=y32, ban=ban, part_val=part_val, part_idx=part_idx,
-                   idx_offset=idx_offset, form=form, ks=ks, only_args=True)
     f = GemvFp8Args()
-    f.b, f.row_exp = b, _ptr(W.e)
+    f.b, f.row_exp = gemv_batch(W.q, x, **dict(kw, only_args=True)), _ptr(W.e)
     _go(plan, "usdm_gemv_fp8_mfma", lib.usdm_gemv_fp8_mfma, C_.byref(f))
 
 

@@ -26,7 +26,9 @@ from collections import deque
 
 import torch
 
-from .graph import GraphedPlan, GraphedSegments
+from . import ops
+from .llm import USDMForCausalLM, check_quantization, stop_index
+from .quant import check_kv_cache_dtype
 
 MAX_SLOTS = 16      # usdm_gemv_batch streams the weights once per step for up to 16 sequences (matrix-core form above 4)
 SMALL_SLOTS = 4     # groups of <= 4 requests use the 4-slot plan (VALU form: per slot bit-identical with the single-request path)
@@ -111,22 +113,17 @@ class LLM:
         # quantization (vllm's name): None = bf16, "fp8" = e4m3 weights with power-of-two row scales (usdm_amd/quant.py); the
         # FP8 model decodes at most 4 sequences per step (its max_batch()) unless fp8_matrix_cores (opt-in) runs steps of 5..16
         # sequences on the matrix cores (usdm_gemv_fp8_mfma)
-        if quantization not in (None, "fp8"):
-            raise ValueError(f"quantization={quantization!r} is not supported (None or 'fp8')")
-        if fp8_matrix_cores and quantization != "fp8":
-            raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
+        check_quantization(quantization, fp8_matrix_cores)
         # kv_cache_dtype (vllm's name): None / "bf16", or "fp8" = e4m3 cache rows with one power-of-two scale per (token, kv head)
-        from .quant import check_kv_cache_dtype
         kvd = check_kv_cache_dtype(kv_cache_dtype)
-        from .llm import USDMForCausalLM
         if isinstance(model, USDMForCausalLM):
-            if kv_cache_dtype is not None and getattr(model, "kv_cache_dtype", "bf16") != kvd:
+            if kv_cache_dtype is not None and model.kv_cache_dtype != kvd:
                 raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}, but the model object was loaded with "
-                                 f"kv_cache_dtype={getattr(model, 'kv_cache_dtype', 'bf16')!r}")
-            if quantization is not None and getattr(model, "quantization", None) != quantization:
+                                 f"kv_cache_dtype={model.kv_cache_dtype!r}")
+            if quantization is not None and model.quantization != quantization:
                 raise ValueError(f"quantization={quantization!r}, but the model object was loaded with "
-                                 f"quantization={getattr(model, 'quantization', None)!r}")
-            if fp8_matrix_cores and not getattr(model, "fp8_matrix_cores", False):
+                                 f"quantization={model.quantization!r}")
+            if fp8_matrix_cores and not model.fp8_matrix_cores:
                 raise ValueError("fp8_matrix_cores=True, but the model object was loaded with fp8_matrix_cores=False")
             self.llm = model
         else:
@@ -255,15 +252,10 @@ class LLM:
     # ------------------------------------------------------------------ continuous batching over the decode slots
     def _run_batched(self, grp):
         llm = self.llm
-        from . import ops
         nslots = min(self.max_slots, llm.max_batch(), SMALL_SLOTS if len(grp) <= SMALL_SLOTS else MAX_SLOTS)
         bb = llm._batch_buffers(nslots)
         sampled = any(not r["sp"].greedy for r in grp)       # one sampled request -> the whole group runs on the sampling graph
-        key = "decode_sampled" if sampled else "decode"
-        if bb[key] is None:
-            built = llm._build_decode_batch(nslots, sampling=sampled)
-            bb[key] = GraphedSegments(built, llm._run_segs) if isinstance(built, list) else GraphedPlan(built)
-        decode = bb[key]
+        decode = llm._batch_step(nslots, sampling=sampled)
         self.stats["sampled_in_batch"] = self.stats.get("sampled_in_batch", 0) + sum(not r["sp"].greedy for r in grp)
         for b in range(nslots):                               # idle slots: harmless greedy knobs
             ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
@@ -274,18 +266,12 @@ class LLM:
             for b in range(nslots):                               # admit: prefill the prompt into the free slot's cache
                 if slots[b] is None and queue:
                     r = queue.popleft()
-                    L = len(r["ids"])
-                    bb["step"][b] = 0
-                    bb["pos"][b] = L
                     sp = r["sp"]
                     if sp.greedy:
                         ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
                     else:
                         ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"])
-                    # the first token is picked by the prefill: sampled too when the group runs on the sampling graph
-                    segs, io = bb["prefill"].get_or_build((L, b, sampled), lambda: llm._build_prefill(L, True if sampled else None, slot=bb["slots"][b]))
-                    io["ids"].copy_(torch.tensor(r["ids"], dtype=torch.long))
-                    llm._run_segs(segs)                               # (+ first token)
+                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), sampling=sampled)      # (+ first token)
                     slots[b] = dict(r=r, produced=1)
                     self.stats["admissions"] += 1
             active = [b for b in range(nslots) if slots[b] is not None]
@@ -300,7 +286,7 @@ class LLM:
             for b in active:
                 s, r = slots[b], slots[b]["r"]
                 seq = toks[b][:s["produced"]]
-                end = next((i + 1 for i, t in enumerate(seq) if t in r["stops"] and i + 1 >= r["sp"].min_tokens), None)
+                end = stop_index(seq, r["stops"], r["sp"].min_tokens)
                 if end is not None or s["produced"] >= r["max_new"]:
                     n = end if end is not None else r["max_new"]
                     results.append((r, seq[:n], "stop" if end is not None and end <= n else "length"))
