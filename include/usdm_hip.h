@@ -350,6 +350,30 @@ int usdm_dequant_fp8(const void* q, const int8_t* row_exp, int32_t N, int32_t K,
                      usdm_stream_t stream);
 int usdm_sizeof_gemv_fp8_args(void);
 
+/* Weight-only MXFP4 (opt-in; usdm_amd/quant.py): OCP e2m1 codes (magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; bit 3 the sign) with one
+ * e8m0 scale byte (2^(byte - 127)) per block of 32 consecutive K elements of a row.  Every W'[r][k] = e2m1(code) * 2^s is exactly
+ * a bf16 value.  Memory layout (private to quant.Mxfp4Weight, which is the one packer): a row is cut into groups of 2048 elements,
+ * the last one padded with zero codes and scale bytes 127.  A group is 1024 code bytes = 64 pieces of 16 bytes; dword i (0..3) of
+ * piece L holds elements 2048g + 512i + 8L .. +7 of the row, element 2m of a byte pair in bits 3:0 and 2m+1 in bits 7:4.  The
+ * group's 64 scale bytes are 16 dwords; byte i of dword q is the scale of block 64g + 16i + q.  b.g.W points to the codes with
+ * row stride b.g.ldw BYTES (a multiple of 1024, 2 * ldw >= K), scales to the scale bytes with row stride lds bytes (a multiple of
+ * 64, 32 * lds >= K); W 16-byte and scales 4-byte aligned, K a multiple of 32.
+ * usdm_gemv_mxfp4 converts the codes to bf16 in registers (exact) and runs the bf16 arithmetic unchanged: the result equals usdm_gemv
+ * (nb = 1) / the VALU form of usdm_gemv_batch (nb = 2..4) on the bf16 matrix W', bit for bit.  Supported: RMSNorm, SwiGLU on packed
+ * gate/up rows, residual, plain, skip.  Refused (error, no fall-back): nb > 4 / the matrix-core forms, the lm_head mode
+ * (part_val / ban; y32 is refused too), p2p, mrg_* / cmb_gran, x_delta / x_out, misaligned pointers or strides. */
+typedef struct usdm_gemv_mxfp4_args {
+  usdm_gemv_batch_args b;    /* nb = 1: batch-1 kernel (strides unused); 2..4: the VALU batch kernel; form must be 0 or -1 */
+  const uint8_t* scales;     /* [N][lds] */
+  int64_t lds;
+} usdm_gemv_mxfp4_args;
+int usdm_gemv_mxfp4(const usdm_gemv_mxfp4_args* args, usdm_stream_t stream);
+/* out[r][k] = W'[r][k] as bf16 for r < N, k < K (prefill: the bf16 operand of usdm_gemm).  codes / ldw / scales / lds as above;
+ * K a multiple of 32, ldo a multiple of 8, out 16-byte aligned. */
+int usdm_dequant_mxfp4(const void* codes, int64_t ldw, const uint8_t* scales, int64_t lds, int32_t N, int32_t K, void* out,
+                       int64_t ldo, usdm_stream_t stream);
+int usdm_sizeof_gemv_mxfp4_args(void);
+
 /* Device-resident greedy-decode state so that a decode step is replayable as one hipGraph. */
 typedef struct usdm_decode_state {
   int32_t* next_token;  /* [1] token fed to the next step                     */

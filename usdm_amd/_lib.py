@@ -24,6 +24,8 @@ lib.usdm_gemv_batch_ks_floats.restype = C.c_int64
 lib.usdm_gemv_fp8_mfma.restype = C.c_int     # (the FP8 matrix-core form; resolving it here makes a stale library fail at import)
 lib.usdm_attn_decode_fp8.restype = C.c_int   # (the FP8 KV cache entry points: likewise)
 lib.usdm_rope_cache_fp8.restype = C.c_int
+lib.usdm_gemv_mxfp4.restype = C.c_int        # (the MXFP4 entry points: likewise)
+lib.usdm_dequant_mxfp4.restype = C.c_int
 _exp = None
 
 
@@ -156,6 +158,10 @@ class GemvFp8Args(C.Structure):
     _fields_ = [("b", GemvBatchArgs), ("row_exp", C.c_void_p)]
 
 
+class GemvMxfp4Args(C.Structure):
+    _fields_ = [("b", GemvBatchArgs), ("scales", C.c_void_p), ("lds", C.c_int64)]
+
+
 class DecodeState(C.Structure):
     _fields_ = [
         ("next_token", C.c_void_p), ("out_tokens", C.c_void_p), ("step", C.c_void_p), ("pos", C.c_void_p),
@@ -222,7 +228,7 @@ def _selfcheck():
     for name, cls in (("norm", NormArgs), ("snake", SnakeArgs), ("attn", AttnArgs), ("vb_input", VbInputArgs),
                       ("vb_solver", VbSolverArgs), ("gemv", GemvArgs), ("decode_state", DecodeState),
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
-                      ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("p2p_dev", P2pDev),
+                      ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):

@@ -156,3 +156,19 @@ __device__ __forceinline__ u32x4 fp8x8_to_bf16x8(u32x2 w, float s) {   // 8 e4m3
   r[3] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], s, true));
   return r;
 }
+
+// ---- weight-only MXFP4 (usdm_amd/quant.py): OCP e2m1 codes, two per byte (element 2m in bits 3:0, element 2m+1 in bits 7:4), with
+// one e8m0 scale byte per 32 elements.  code * 2^s has at most 2 significant bits and the quantizer keeps it a normal bf16, so the
+// scaled conversion (v_cvt_scalef32_pk_bf16_fp4) is exact: the kernels see the bf16 weights W' bit for bit.
+// `sc` holds four scale bytes (one dword of the scale array); byte I is the scale of the 8 codes in `codes`.
+template <int I>
+__device__ __forceinline__ u32x4 mx4x8_to_bf16x8(unsigned codes, unsigned sc) {   // 8 e2m1 codes -> 8 bf16, element order kept
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_cvt;
+  const float s = __builtin_bit_cast(float, (I == 3 ? sc >> 1 : sc << (23 - 8 * I)) & 0x7f800000u);
+  u32x4 r;
+  r[0] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 0));
+  r[1] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 1));
+  r[2] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 2));
+  r[3] = __builtin_bit_cast(unsigned, (bf16x2_cvt)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 3));
+  return r;
+}

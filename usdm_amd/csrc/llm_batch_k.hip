@@ -22,6 +22,16 @@ __device__ __forceinline__ float dot8b(u32x4 w, u32x4 x, float acc) {
 // kernel argument (FP8 only: the bf16 instantiations keep their exact signature and code).
 template <bool FP8> struct gemvb_fmt { typedef u32x4 wvec; };
 template <> struct gemvb_fmt<true> { typedef u32x2 wvec; };
+// MX4: the weight-only MXFP4 format (usdm_gemv_mxfp4, as in gemv_kernel: the layout is described there): one 16-byte load carries
+// a lane's codes of four K iterations, one dword the four block scales; a ring slot is one such group.  Selected by the type of the
+// extra argument, so the existing instantiations keep their names.
+struct gemvb_mx4 { const uint8_t* scales; int64_t lds; };
+template <class... FMT> struct gemvb_is_mx4 { static constexpr bool value = false; };
+template <> struct gemvb_is_mx4<gemvb_mx4> { static constexpr bool value = true; };
+template <int I> struct gemvb_ic { static constexpr int value = I; };
+__device__ __forceinline__ gemvb_mx4 gemvb_mx4_fmt() { return gemvb_mx4{nullptr, 0}; }
+__device__ __forceinline__ gemvb_mx4 gemvb_mx4_fmt(const int8_t*) { return gemvb_mx4{nullptr, 0}; }
+__device__ __forceinline__ gemvb_mx4 gemvb_mx4_fmt(gemvb_mx4 m) { return m; }
 __device__ __forceinline__ const int8_t* gemvb_row_exp() { return nullptr; }
 __device__ __forceinline__ const int8_t* gemvb_row_exp(const int8_t* e) { return e; }
 
@@ -30,12 +40,13 @@ __device__ __forceinline__ const int8_t* gemvb_row_exp(const int8_t* e) { return
 template <int RW, bool GLU, int NWV, int NB, bool FP8 = false, class... FMT>
 __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_batch_args ba, FMT... fmt) {
   const usdm_gemv_args& a = ba.g;
-  static_assert(FP8 == (sizeof...(FMT) == 1), "FP8 takes the row exponents");
+  constexpr bool MX4 = gemvb_is_mx4<FMT...>::value;
+  static_assert((FP8 || MX4) == (sizeof...(FMT) == 1) && !(FP8 && MX4), "FP8 takes the row exponents, MXFP4 the block scales");
   typedef typename gemvb_fmt<FP8>::wvec wvec;
   constexpr int NTH = NWV * 64;
   constexpr int NR = GLU ? 2 * RW : RW;
   constexpr int UNR0 = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : 8);
-  constexpr int UNR = FP8 ? 2 * UNR0 : UNR0;
+  constexpr int UNR = MX4 ? (NR >= 3 ? 2 : 4) : FP8 ? 2 * UNR0 : UNR0;   // (MX4: slots of one group = 4 K iterations, as gemv_kernel)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = (bf16_t*)smem;  // [NB][Kpad] bf16, zero padded
   __shared__ float red[NB][NWV];
@@ -50,6 +61,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
   const int ob = blockIdx.x * rows_per_block + wave * RW;
   const wvec* wp[NR];
   float wsc[NR];   // FP8: the rows' scales (unused in bf16)
+  const unsigned* wsp[MX4 ? NR : 1];   // MX4: the rows' scale dwords of this lane's quad
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
     int r;
@@ -63,10 +75,15 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
     if constexpr (FP8) {
       wp[j] = (const wvec*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
       wsc[j] = fp8_row_scale(gemvb_row_exp(fmt...)[r]);
+    } else if constexpr (MX4) {
+      const gemvb_mx4 m = gemvb_mx4_fmt(fmt...);
+      wp[j] = (const u32x4*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
+      wsp[j] = (const unsigned*)(m.scales + (int64_t)r * m.lds) + (lane >> 2);
     } else {
       wp[j] = (const u32x4*)((const bf16_t*)a.W + (int64_t)r * a.ldw) + lane;
     }
   }
+  const int ngr = (nit + 3) >> 2;   // MX4: groups of four K iterations
   const bool tail_ok = ((nit - 1) << 9) + lane * 8 < K;
   // lm_head mode: rows of banned ids are not streamed (see gemv_kernel)
   bool active = true;
@@ -95,11 +112,20 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
     return __builtin_nontemporal_load(p);
   };
   wvec ring[NR][UNR];
+  unsigned rsc[MX4 ? NR : 1][MX4 ? UNR : 1];   // MX4: the slots' scale dwords
 #pragma unroll
   for (int u = 0; u < UNR; ++u)
 #pragma unroll
-    for (int j = 0; j < NR; ++j)
-      if (u < nit) ring[j][u] = wload(j, u);
+    for (int j = 0; j < NR; ++j) {
+      if constexpr (MX4) {   // (the padded storage holds whole groups: no tail redirect)
+        if (u < ngr) {
+          ring[j][u] = __builtin_nontemporal_load(wp[j] + u * 64);
+          rsc[j][u] = __builtin_nontemporal_load(wsp[j] + u * 16);
+        }
+      } else {
+        if (u < nit) ring[j][u] = wload(j, u);
+      }
+    }
 
   // ---- stage the NB input vectors (optionally RMS-normalised, HF rounding) while the first ring is in flight
   if (a.norm_w) {
@@ -160,6 +186,40 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
   for (int j = 0; j < NR; ++j)
 #pragma unroll
     for (int b = 0; b < NB; ++b) acc[j][b] = 0.f;
+  if constexpr (MX4) {
+    // slot u = group g: its four K iterations in order (the bf16 kernel's accumulation order per lane), then the refill
+    auto step = [&](auto I, int g, int u) {
+      constexpr int i = decltype(I)::value;
+      const int it = 4 * g + i;
+      if (it < nit) {
+        u32x4 xv[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) xv[b] = *(const u32x4*)(xs + (int64_t)b * Kpad + (it * 64 + lane) * 8);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+          const u32x4 wv = mx4x8_to_bf16x8<i>(ring[j][u][i], rsc[j][u]);
+#pragma unroll
+          for (int b = 0; b < NB; ++b) acc[j][b] = dot8b(wv, xv[b], acc[j][b]);
+        }
+      }
+    };
+    for (int g0 = 0; g0 < ngr; g0 += UNR) {
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const int g = g0 + u;
+        if (g < ngr) {
+          step(gemvb_ic<0>{}, g, u); step(gemvb_ic<1>{}, g, u); step(gemvb_ic<2>{}, g, u); step(gemvb_ic<3>{}, g, u);
+          if (g + UNR < ngr) {
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+              ring[j][u] = __builtin_nontemporal_load(wp[j] + (g + UNR) * 64);
+              rsc[j][u] = __builtin_nontemporal_load(wsp[j] + (g + UNR) * 16);
+            }
+          }
+        }
+      }
+    }
+  } else
   for (int it0 = 0; it0 < nit; it0 += UNR) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
@@ -339,6 +399,16 @@ int usdm_gemv_fp8_batch_launch(const usdm_gemv_fp8_args* pa, hipStream_t st) {
     case 2: return launch_nb<2, true>(pa->b, st, pa->row_exp);
     case 3: return launch_nb<3, true>(pa->b, st, pa->row_exp);
     default: return launch_nb<4, true>(pa->b, st, pa->row_exp);
+  }
+}
+// usdm_gemv_mxfp4 with 2..4 sequences (llm_k.hip checks the arguments it shares with the batch-1 form)
+int usdm_gemv_mxfp4_batch_launch(const usdm_gemv_mxfp4_args* pa, hipStream_t st) {
+  USDM_CHECK_ARG(pa->b.x_bs % 8 == 0, "usdm_gemv_mxfp4: x stride must keep 16-B alignment");
+  const gemvb_mx4 m{pa->scales, pa->lds};
+  switch (pa->b.nb) {
+    case 2: return launch_nb<2, false>(pa->b, st, m);
+    case 3: return launch_nb<3, false>(pa->b, st, m);
+    default: return launch_nb<4, false>(pa->b, st, m);
   }
 }
 extern "C" int usdm_sizeof_gemv_batch_args(void) { return (int)sizeof(usdm_gemv_batch_args); }

@@ -59,20 +59,36 @@ __device__ unsigned long long g_gemv_trace[8192 * 8];
 // in registers with the row's power-of-two scale (exact), then the bf16 arithmetic unchanged.  The ring is twice as deep, so the
 // same number of bytes is in flight per lane; only the weight load and unpack differ.  The row exponents come as one extra kernel
 // argument (FP8 only: the bf16 instantiations keep their exact signature and code).
+// MX4: the weight-only MXFP4 format (usdm_gemv_mxfp4; selected by the type of the extra argument, so FP8 stays a bool and the
+// existing instantiations keep their names).  A row is stored in groups of 2048 elements = 1024 bytes, interleaved so that the 16
+// bytes of lane L in group g are its codes of the four K iterations 4g .. 4g+3 (dword i: elements 2048g + 512i + 8L ..+7, the
+// elements that lane accumulates in iteration 4g+i of the bf16 kernel); the scale bytes are interleaved the same way, so the four
+// lanes that share a block read ONE dword holding their scales of the four iterations.  Rows are padded with zero codes to whole
+// groups (x in LDS is zero only up to Kpad: iterations past nit are skipped, not multiplied).  A ring slot is one group.
 template <bool FP8> struct gemv_fmt { typedef u32x4 wvec; };
 template <> struct gemv_fmt<true> { typedef u32x2 wvec; };
+struct gemv_mx4 { const uint8_t* scales; int64_t lds; };   // scale bytes [N][lds], lds = (row stride of the codes in bytes) / 16
+template <class... FMT> struct gemv_is_mx4 { static constexpr bool value = false; };
+template <> struct gemv_is_mx4<gemv_mx4> { static constexpr bool value = true; };
 __device__ __forceinline__ const int8_t* gemv_row_exp() { return nullptr; }
 __device__ __forceinline__ const int8_t* gemv_row_exp(const int8_t* e) { return e; }
+template <int I> struct gemv_ic { static constexpr int value = I; };
+__device__ __forceinline__ gemv_mx4 gemv_mx4_fmt() { return gemv_mx4{nullptr, 0}; }
+__device__ __forceinline__ gemv_mx4 gemv_mx4_fmt(const int8_t*) { return gemv_mx4{nullptr, 0}; }
+__device__ __forceinline__ gemv_mx4 gemv_mx4_fmt(gemv_mx4 m) { return m; }
 
 template <int RW, bool GLU, int NWV, bool MRG = false, bool P2P = false, bool CMB = false, bool FP8 = false, class... FMT>
 __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, FMT... fmt) {
   typedef typename gemv_fmt<FP8>::wvec wvec;
-  static_assert(FP8 == (sizeof...(FMT) == 1), "FP8 takes the row exponents");
-  static_assert(!FP8 || (!MRG && !P2P && !CMB), "the FP8 weight format has the plain single-GPU forms only");
+  constexpr bool MX4 = gemv_is_mx4<FMT...>::value;
+  static_assert((FP8 || MX4) == (sizeof...(FMT) == 1) && !(FP8 && MX4), "FP8 takes the row exponents, MXFP4 the block scales");
+  static_assert(!(FP8 || MX4) || (!MRG && !P2P && !CMB), "the FP8 / MXFP4 weight formats have the plain single-GPU forms only");
   constexpr int NTH = NWV * 64;
   constexpr int NR = GLU ? 2 * RW : RW;   // rows streamed together by one wave
   constexpr int UNR0 = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : (NR == 2 ? 8 : USDM_UNR1));  // ring depth: NR*UNR = 15..16 loads in flight per lane
-  constexpr int UNR = FP8 ? 2 * UNR0 : UNR0;   // (FP8: 8-byte loads, twice as many for the same bytes in flight)
+  // (FP8: 8-byte loads, twice as many for the same bytes in flight; MX4: slots of one group = 4 K iterations, 6..8 in flight with
+  // their scale dwords - K = 4096 is two groups, so more slots would only add re-reads of the row start)
+  constexpr int UNR = MX4 ? (NR >= 3 ? 2 : 4) : FP8 ? 2 * UNR0 : UNR0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = (bf16_t*)smem;  // [Kpad] bf16, zero padded
   __shared__ float red[NWV];
@@ -93,6 +109,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   const int ob = blockIdx.x * rows_per_block + wave * RW; // first output feature of this wave
   const wvec* wp[NR];
   float wsc[NR];   // FP8: the rows' scales (requested here, before the hand-counted loads below; unused in bf16)
+  const unsigned* wsp[MX4 ? NR : 1];   // MX4: the rows' scale dwords of this lane's quad
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
     int r;
@@ -106,10 +123,15 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
     if constexpr (FP8) {
       wp[j] = (const wvec*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
       wsc[j] = fp8_row_scale(gemv_row_exp(fmt...)[r]);
+    } else if constexpr (MX4) {
+      const gemv_mx4 m = gemv_mx4_fmt(fmt...);
+      wp[j] = (const u32x4*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
+      wsp[j] = (const unsigned*)(m.scales + (int64_t)r * m.lds) + (lane >> 2);
     } else {
       wp[j] = (const u32x4*)((const bf16_t*)a.W + (int64_t)r * a.ldw) + lane;
     }
   }
+  const int ngr = (nit + 3) >> 2;   // MX4: groups of four K iterations
   const bool tail_ok = ((nit - 1) << 9) + lane * 8 < K;  // is this lane inside K on the last iteration?
   // lm_head mode: a wave whose rows are ALL banned (the reference's bad_words_ids mask whole id ranges: 76 % of the vocabulary
   // in the text->unit round, inference.py:51-53) streams nothing; its logits are -inf either way
@@ -169,19 +191,26 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   // The first ring is ALWAYS NR x UNR loads (slots past the row's K, or of a wave whose rows are all banned, re-read the row start
   // and are never multiplied / their results never used): the wait for the early loads below can then name an exact count.
   wvec ring[NR][UNR];
+  unsigned rsc[MX4 ? NR : 1][MX4 ? UNR : 1];   // MX4: the slots' scale dwords
 #pragma unroll
   for (int u = 0; u < UNR; ++u)
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-      const bool real = active && u < nit;
-      const wvec* p = real ? ((u == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + u * 64) : wp[j] - lane;
-      ring[j][u] = __builtin_nontemporal_load(p);
+      if constexpr (MX4) {   // (the padded storage holds whole groups: no tail redirect; slots past the row re-read group 0)
+        const int g = u < ngr ? u : 0;
+        ring[j][u] = __builtin_nontemporal_load(wp[j] + g * 64);
+        rsc[j][u] = __builtin_nontemporal_load(wsp[j] + g * 16);
+      } else {
+        const bool real = active && u < nit;
+        const wvec* p = real ? ((u == nit - 1 && !tail_ok) ? wp[j] - lane : wp[j] + u * 64) : wp[j] - lane;
+        ring[j][u] = __builtin_nontemporal_load(p);
+      }
     }
   GTR(1);
   if constexpr (EARLY) {
     // in-order completion: "all but the NY youngest" = the three early loads have landed, the ring stays in flight.  ONE wait site on
     // every path (two sites in two branches made the compiler copy the registers of the loads at the branch - before the wait)
-    constexpr int NY = UNR * NR;      // (the residual loads above are older: nothing else is issued between the early loads and here)
+    constexpr int NY = (MX4 ? 2 : 1) * UNR * NR;      // (the residual loads above are older: nothing else is issued between the early loads and here)
     asm volatile("s_waitcnt vmcnt(%3)" : "+v"(x0), "+v"(ge0v), "+v"(ge1v) : "n"(NY));
   }
   if (skipv) return;   // the sequence ended in an earlier step of this host chunk (usdm_decode_state.done)
@@ -369,6 +398,34 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   float acc[NR];
 #pragma unroll
   for (int j = 0; j < NR; ++j) acc[j] = 0.f;
+  if constexpr (MX4) {
+    // slot u = group g: its four K iterations in order (the bf16 kernel's accumulation order per lane), then the refill
+    auto step = [&](auto I, int g, int u) {
+      constexpr int i = decltype(I)::value;
+      const int it = 4 * g + i;
+      if (it < nit) {
+        const u32x4 xv = *(const u32x4*)(xs + (it * 64 + lane) * 8);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) acc[j] = dot8(mx4x8_to_bf16x8<i>(ring[j][u][i], rsc[j][u]), xv, acc[j]);
+      }
+    };
+    for (int g0 = 0; g0 < ngr; g0 += UNR) {
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const int g = g0 + u;
+        if (g < ngr) {
+          step(gemv_ic<0>{}, g, u); step(gemv_ic<1>{}, g, u); step(gemv_ic<2>{}, g, u); step(gemv_ic<3>{}, g, u);
+          if (g + UNR < ngr) {
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+              ring[j][u] = __builtin_nontemporal_load(wp[j] + (g + UNR) * 64);
+              rsc[j][u] = __builtin_nontemporal_load(wsp[j] + (g + UNR) * 16);
+            }
+          }
+        }
+      }
+    }
+  } else
   for (int it0 = 0; it0 < nit; it0 += UNR) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
@@ -1327,6 +1384,68 @@ extern "C" int usdm_dequant_fp8(const void* q, const int8_t* row_exp, int32_t N,
   return 0;
 }
 extern "C" int usdm_sizeof_gemv_fp8_args(void) { return (int)sizeof(usdm_gemv_fp8_args); }
+
+int usdm_gemv_mxfp4_batch_launch(const usdm_gemv_mxfp4_args* pa, hipStream_t st);   // llm_batch_k.hip: nb = 2..4
+
+extern "C" int usdm_gemv_mxfp4(const usdm_gemv_mxfp4_args* pa, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->b.g.W && pa->b.g.x && pa->scales, "usdm_gemv_mxfp4: null args");
+  const usdm_gemv_args& a = pa->b.g;
+  USDM_CHECK_ARG(pa->b.nb >= 1 && pa->b.nb <= 4 && (pa->b.form == 0 || pa->b.form == -1),
+                 "usdm_gemv_mxfp4: 1..4 sequences on the VALU form (the matrix-core form has no MXFP4 weights)");
+  USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.mrg_pm && !a.mrg_pl && !a.cmb_gran && !a.x_delta && !a.x_out,
+                 "usdm_gemv_mxfp4: p2p / merged-attention input / cmb_gran / x_delta are not supported with MXFP4 weights");
+  USDM_CHECK_ARG(!a.part_val && !a.part_idx && !a.ban && !a.y32, "usdm_gemv_mxfp4: the lm_head mode (part_val / ban / y32) is not supported with MXFP4 weights");
+  USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.K % 32 == 0 && a.K <= 16384, "usdm_gemv_mxfp4: K must be a multiple of 32, at most 16384");
+  USDM_CHECK_ARG(a.ldw % 1024 == 0 && 2 * a.ldw >= a.K && pa->lds % 64 == 0 && 32 * pa->lds >= a.K,
+                 "usdm_gemv_mxfp4: ldw (bytes) must hold whole groups of 1024 bytes and lds whole groups of 64 bytes covering K");
+  USDM_CHECK_ARG(((uintptr_t)a.W & 15) == 0 && ((uintptr_t)pa->scales & 3) == 0 && ((uintptr_t)a.x & 15) == 0,
+                 "usdm_gemv_mxfp4: codes and x must be 16-byte, scales 4-byte aligned");
+  const bool glu = a.act == USDM_ACT_SWIGLU;
+  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "usdm_gemv_mxfp4: swiglu needs N %% 32 == 0");
+  USDM_CHECK_ARG(a.y16, "usdm_gemv_mxfp4: no output");
+  hipStream_t st = (hipStream_t)stream;
+  if (pa->b.nb > 1) return usdm_gemv_mxfp4_batch_launch(pa, st);
+  const size_t lds = (size_t)((a.K + 511) & ~511) * 2;
+  return gemv_launch_plain<false>(a, lds, st, gemv_mx4{pa->scales, pa->lds});
+}
+
+namespace {
+// prefill operand of the MXFP4 model: one workgroup per row; a thread takes one 16-byte piece of a group (its codes of four K
+// iterations) and writes four 16-byte pieces of bf16 (the threads of a wave write 1 KB contiguous per store)
+__global__ __launch_bounds__(256) void dequant_mxfp4_kernel(const uint8_t* codes, int64_t ldw, const uint8_t* scales, int64_t lds, int K,
+                                                            bf16_t* out, int64_t ldo) {
+  const int r = blockIdx.x;
+  const u32x4* cr = (const u32x4*)(codes + (int64_t)r * ldw);
+  const unsigned* sr = (const unsigned*)(scales + (int64_t)r * lds);
+  bf16_t* orow = out + (int64_t)r * ldo;
+  const int npiece = ((K + 2047) >> 11) * 64;
+  for (int p = threadIdx.x; p < npiece; p += 256) {
+    const int g = p >> 6, L = p & 63;
+    const u32x4 w = __builtin_nontemporal_load(cr + p);
+    const unsigned sc = sr[g * 16 + (L >> 2)];
+    const int e = g * 2048 + L * 8;
+    if (e < K) *(u32x4*)(orow + e) = mx4x8_to_bf16x8<0>(w[0], sc);
+    if (e + 512 < K) *(u32x4*)(orow + e + 512) = mx4x8_to_bf16x8<1>(w[1], sc);
+    if (e + 1024 < K) *(u32x4*)(orow + e + 1024) = mx4x8_to_bf16x8<2>(w[2], sc);
+    if (e + 1536 < K) *(u32x4*)(orow + e + 1536) = mx4x8_to_bf16x8<3>(w[3], sc);
+  }
+}
+}  // namespace
+
+extern "C" int usdm_dequant_mxfp4(const void* codes, int64_t ldw, const uint8_t* scales, int64_t lds, int32_t N, int32_t K, void* out,
+                                  int64_t ldo, usdm_stream_t stream) {
+  USDM_CHECK_ARG(codes && scales && out, "usdm_dequant_mxfp4: null args");
+  USDM_CHECK_ARG(N > 0 && K > 0 && K % 32 == 0 && ldo >= K && ldo % 8 == 0, "usdm_dequant_mxfp4: bad N/K/ldo");
+  USDM_CHECK_ARG(ldw % 1024 == 0 && 2 * ldw >= K && lds % 64 == 0 && 32 * lds >= K,
+                 "usdm_dequant_mxfp4: ldw (bytes) must hold whole groups of 1024 bytes and lds whole groups of 64 bytes covering K");
+  USDM_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)scales & 3) == 0 && ((uintptr_t)out & 15) == 0,
+                 "usdm_dequant_mxfp4: codes and out must be 16-byte, scales 4-byte aligned");
+  hipLaunchKernelGGL(dequant_mxfp4_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)codes, ldw, scales, lds, K,
+                     (bf16_t*)out, ldo);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int usdm_sizeof_gemv_mxfp4_args(void) { return (int)sizeof(usdm_gemv_mxfp4_args); }
 
 #ifdef USDM_GEMV_TRACE
 extern "C" int usdm_dbg_gemv_trace(unsigned long long* host, int n) {

@@ -152,8 +152,9 @@ def main(argv=None):
                         help="Directory holding the model checkpoints (the reference's download cache, or local <name>/ directories).")
     parser.add_argument('--output_path', type=str, required=True,
                         help="Path to save the spoken response.")
-    parser.add_argument('--quantization', type=str, default=None, choices=["fp8"],
-                        help="Weight-only FP8 for the LLM (e4m3, power-of-two row scales; opt-in, default bf16).")
+    parser.add_argument('--quantization', type=str, default=None, choices=["fp8", "mxfp4"],
+                        help="Weight-only quantization of the LLM (opt-in, default bf16): fp8 (e4m3, power-of-two row scales) or mxfp4 "
+                             "(e2m1 with a power-of-two scale per 32 elements, fp8 lm_head; about 11.5 %% weight error).")
     parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["bf16", "fp8"],
                         help="KV cache of the LLM: bf16 (default) or fp8 (e4m3 rows, one power-of-two scale per token and kv head; opt-in, "
                              "switches prefix reuse between the three rounds off).")

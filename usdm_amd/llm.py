@@ -17,7 +17,9 @@ Host side: Python plans of C-ABI launches (libusdm_hip.so).
 Weights: HF state-dict key names (model.layers.N.self_attn.q_proj.weight, ...), bf16.  quantization="fp8" (opt-in): the streamed
 matrices (qkv, o, gate/up, down, lm_head) are held as e4m3 with a power-of-two scale per row (usdm_amd/quant.py), which makes the
 model exactly the bf16 model with the dequantized weights W'; decode streams half the bytes (usdm_gemv_fp8), prefill dequantizes
-each matrix into one bf16 scratch right before its usdm_gemm.  Single GPU only.
+each matrix into one bf16 scratch right before its usdm_gemm.  Single GPU only.  quantization="mxfp4" (opt-in): the layers' matrices
+as OCP MXFP4 (e2m1, one power-of-two scale per 32 elements; 4.25 bits per weight, about 11.5 % relative weight error), the lm_head
+fp8; the same contract and the same structure (usdm_gemv_mxfp4, usdm_dequant_mxfp4), at most 4 sequences per decode step.
 KV cache: bf16 rows.  kv_cache_dtype="fp8" (opt-in, independent of `quantization`): every cached row (one token, one kv head) is
 held as e4m3 bytes + one power-of-two exponent (quant.quantize_kv_rows), written by usdm_rope_cache_fp8 / usdm_attn_decode_fp8.
 The model is then exactly the bf16-cache model whose decode steps read the round-tripped rows K', V'; a prompt's own prefill
@@ -32,7 +34,7 @@ from . import ops
 from ._lib import ACT_SWIGLU
 from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
-from .quant import Fp8Weight, check_kv_cache_dtype
+from .quant import Fp8Weight, Mxfp4Weight, check_kv_cache_dtype
 
 MISTRAL_7B_USDM = dict(vocab_size=42003, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
                        num_attention_heads=32, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-5,
@@ -82,10 +84,14 @@ def agree_seed(seed, group, rank, device=None):
 QUANT_KEYS = ("qkv", "o", "gu", "down")    # the streamed matrices of a layer (quantization="fp8"; with the lm_head shard)
 
 
+QUANTIZATIONS = (None, "fp8", "mxfp4")
+
+
 def check_quantization(quantization, fp8_matrix_cores):
     """The values of the two weight-format arguments (USDMForCausalLM and serving.LLM take them)."""
-    if quantization not in (None, "fp8"):
-        raise ValueError(f"quantization={quantization!r}: supported are None (bf16) and 'fp8' (e4m3 weights, power-of-two row scales)")
+    if quantization not in QUANTIZATIONS:
+        raise ValueError(f"quantization={quantization!r}: supported are None (bf16), 'fp8' (e4m3 weights, power-of-two row scales) "
+                         "and 'mxfp4' (e2m1 weights, one power-of-two scale per 32 elements; the lm_head stays fp8)")
     if fp8_matrix_cores and quantization != "fp8":
         raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
 
@@ -128,8 +134,11 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
     columns split by rank, o_proj/down_proj split along K (their outputs are partial sums), vocab rows split.
     quantization="fp8": every streamed matrix becomes a quant.Fp8Weight as soon as its layer is packed (rows quantized after the
     qkv concatenation and the gate/up packing; per-row scales do not depend on the row order), so at most one layer is ever held
-    in bf16 next to the FP8 copy.  The embedding stays bf16, the norms f32."""
-    qz = Fp8Weight.from_matrix if quantization == "fp8" else (lambda t: t)
+    in bf16 next to the FP8 copy.  The embedding stays bf16, the norms f32.
+    quantization="mxfp4": likewise with quant.Mxfp4Weight for qkv, o, gate/up and down (blocks of 32 run along K, so the row packing
+    only permutes rows of blocks); the lm_head shard is an Fp8Weight."""
+    qz = {"fp8": Fp8Weight.from_matrix, "mxfp4": Mxfp4Weight.from_matrix}.get(quantization, lambda t: t)
+    qz_head = Fp8Weight.from_matrix if quantization in ("fp8", "mxfp4") else (lambda t: t)
     d = cfg["head_dim"]
     Hq, Hkv, I = cfg["num_attention_heads"] // tp, cfg["num_key_value_heads"] // tp, cfg["intermediate_size"] // tp
     V = cfg["vocab_size"]
@@ -137,7 +146,7 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
     g = lambda n: sd_get(n).to(device, dtype)
     f = lambda n: sd_get(n).to(device, torch.float32).contiguous()
     W = {"embed": g("model.embed_tokens.weight").contiguous(), "norm": f("model.norm.weight"),
-         "lm_head": qz(g("lm_head.weight")[v0:v1].contiguous()), "layers": [], "v0": v0, "v1": v1}
+         "lm_head": qz_head(g("lm_head.weight")[v0:v1].contiguous()), "layers": [], "v0": v0, "v1": v1}
     for l in range(cfg["num_hidden_layers"]):
         p = f"model.layers.{l}."
         q = g(p + "self_attn.q_proj.weight")[rank * Hq * d:(rank + 1) * Hq * d]
@@ -158,8 +167,8 @@ class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
                  p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None):
         check_quantization(quantization, fp8_matrix_cores)
-        if quantization == "fp8" and (tp_size > 1 or tp_segments or p2p is not None):
-            raise NotImplementedError("quantization='fp8' runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes bf16 weights")
+        if quantization is not None and (tp_size > 1 or tp_segments or p2p is not None):
+            raise NotImplementedError(f"quantization={quantization!r} runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes bf16 weights")
         self.kv_cache_dtype = check_kv_cache_dtype(kv_cache_dtype)
         self.kv8 = self.kv_cache_dtype == "fp8"
         if self.kv8 and (tp_size > 1 or tp_segments or p2p is not None):
@@ -241,8 +250,8 @@ class USDMForCausalLM:
         self.chain = int(mode.lstrip("e") or 0)
         if self.tp_path or c["hidden_size"] != 4096:
             self.chain = 0
-        if quantization == "fp8":
-            # the FP8 GEMVs have the plain forms only (usdm_gemv_fp8): the attention partials are combined by their own launch
+        if quantization is not None:
+            # the FP8 / MXFP4 GEMVs have the plain forms only (usdm_gemv_fp8, usdm_gemv_mxfp4): the attention partials are combined by their own launch
             # (bit-identical with the hand-off form) and every projection is its own launch
             self.cmb = self.merge_in_oproj = False
             self.chain = 0
@@ -338,8 +347,9 @@ class USDMForCausalLM:
         return m
 
     def weight_bytes_per_token(self):
-        """weight bytes a decode step must stream on this rank (layers + lm_head shard): bf16, or e4m3 + row exponents with fp8."""
-        if self.quantization == "fp8":
+        """weight bytes a decode step must stream on this rank (layers + lm_head shard): bf16, e4m3 + row exponents with fp8, or packed e2m1
+        codes + block scale bytes (and the fp8 lm_head) with mxfp4."""
+        if self.quantization is not None:
             return sum(l[k].nbytes for l in self.W["layers"] for k in QUANT_KEYS) + self.W["lm_head"].nbytes
         n = sum(l[k].numel() for l in self.W["layers"] for k in ("qkv", "o", "gu", "down")) + self.W["lm_head"].numel()
         return 2 * n
@@ -414,19 +424,19 @@ class USDMForCausalLM:
             self.logits_loc = torch.zeros(self.Vloc, dtype=torch.float32, device=dev)
             self.logits_row = torch.zeros(self.tp_size * self.Vloc, dtype=torch.float32, device=dev)
             self._shard_logits = None
-        # fp8: ONE bf16 scratch for the prefill GEMM operand, sized for the largest streamed matrix (7B: gate/up, 235 MB); each
+        # fp8 / mxfp4: ONE bf16 scratch for the prefill GEMM operand, sized for the largest streamed matrix (7B: gate/up, 235 MB); each
         # matrix is dequantized into it right before its usdm_gemm (plans run their launches in order on one stream)
         self.dq_scratch = None
-        if self.quantization == "fp8":
+        if self.quantization is not None:
             mats = [l[k] for l in self.W["layers"] for k in QUANT_KEYS]
             self.dq_scratch = torch.empty(max(m.numel() for m in mats), dtype=bf, device=dev)
 
     def _gemm_w(self, W, plan):
-        """The bf16 operand of a prefill usdm_gemm: the weight itself, or (fp8) its dequantization into the shared scratch."""
-        if not isinstance(W, Fp8Weight):
+        """The bf16 operand of a prefill usdm_gemm: the weight itself, or (fp8 / mxfp4) its dequantization into the shared scratch."""
+        if not isinstance(W, (Fp8Weight, Mxfp4Weight)):
             return W
         out = self.dq_scratch[:W.N * W.K].view(W.N, W.K)
-        ops.dequant_fp8(W, out, plan=plan)
+        (ops.dequant_mxfp4 if isinstance(W, Mxfp4Weight) else ops.dequant_fp8)(W, out, plan=plan)
         return out
 
     # ------------------------------------------------------------------ collectives (TP only)
@@ -857,6 +867,8 @@ class USDMForCausalLM:
         8 waves in chunks of 32 (every projection's K must be a multiple of 256), else the 4 of the VALU form."""
         c = self.cfg
         ks = (c["hidden_size"], self.Hq * c["head_dim"], self.I)
+        if self.quantization == "mxfp4":        # usdm_gemv_mxfp4: the VALU form only
+            return 4
         if self.quantization == "fp8":
             if not self.fp8_matrix_cores:       # usdm_gemv_fp8: the VALU form only
                 return 4

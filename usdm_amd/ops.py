@@ -8,9 +8,9 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
-from .quant import Fp8Weight
+from .quant import Fp8Weight, Mxfp4Weight
 
 
 def _stream():
@@ -240,6 +240,8 @@ def _fill_gemv(a, W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_b
     """The usdm_gemv_args fields that gemv, gemv_batch and gemv_fp8_mfma share (see include/usdm_hip.h)."""
     _need_cuda(W, x, norm_w, residual, y16, y32, ban, part_val, part_idx)
     a.W, a.ldw, a.N, a.K = _ptr(W), (ldw if ldw is not None else K), N, K
+    if isinstance(W, Mxfp4Weight):      # (its packed rows: the stride is in bytes and belongs to the weight, not to the caller)
+        a.ldw = W.q.shape[1]
     a.x, a.norm_w, a.eps = _ptr(x), _ptr(norm_w), eps
     a.act, a.round_bf16 = act, int(round_bf16)
     a.residual, a.y16, a.y32 = _ptr(residual), _ptr(y16), _ptr(y32)
@@ -251,7 +253,8 @@ def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p
     """usdm_gemv: batch-1 weight-streaming GEMV (see include/usdm_hip.h; **common: the keywords of _fill_gemv).
     p2p: a usdm_amd.p2p.P2PComm (fused all-reduce).
     only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
-    W a quant.Fp8Weight: usdm_gemv_fp8 (the plain single-GPU forms only; the library refuses the others)."""
+    W a quant.Fp8Weight / quant.Mxfp4Weight: usdm_gemv_fp8 / usdm_gemv_mxfp4 (the plain single-GPU forms only; the library refuses
+    the others)."""
     _need_cuda(x_delta, x_out, skip)
     if x_out is not None and x_out.data_ptr() == x.data_ptr():
         raise ValueError("usdm_gemv: x_out must not alias x")
@@ -277,6 +280,13 @@ def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p
         f = GemvFp8Args()
         f.b.g, f.b.nb, f.row_exp = a, 1, _ptr(W.e)
         _go(plan, "usdm_gemv_fp8", lib.usdm_gemv_fp8, C_.byref(f))
+        return
+    if isinstance(W, Mxfp4Weight):
+        if only_args:
+            raise ValueError("usdm_gemv: MXFP4 weights have no chained form")
+        f = GemvMxfp4Args()
+        f.b.g, f.b.nb, f.scales, f.lds = a, 1, _ptr(W.s), W.s.shape[1]
+        _go(plan, "usdm_gemv_mxfp4", lib.usdm_gemv_mxfp4, C_.byref(f))
         return
     if only_args:
         return a
@@ -454,6 +464,11 @@ def gemv_batch(W, x, *, nb, x_bs, y_bs=0, res_bs=0, part_bs=0, form=0, ks=None, 
         f.b, f.row_exp = b, _ptr(W.e)
         _go(plan, "usdm_gemv_fp8", lib.usdm_gemv_fp8, C_.byref(f))
         return
+    if isinstance(W, Mxfp4Weight):   # usdm_gemv_mxfp4: likewise
+        f = GemvMxfp4Args()
+        f.b, f.scales, f.lds = b, _ptr(W.s), W.s.shape[1]
+        _go(plan, "usdm_gemv_mxfp4", lib.usdm_gemv_mxfp4, C_.byref(f))
+        return
     _go(plan, "usdm_gemv_batch", lib.usdm_gemv_batch, C_.byref(b))
 
 
@@ -476,6 +491,16 @@ def dequant_fp8(W, out, plan=None):
         raise ValueError("dequant_fp8: an Fp8Weight and a bf16 [N][>= K] output with unit column stride")
     _go(plan, "usdm_dequant_fp8", lib.usdm_dequant_fp8, _ptr(W.q), _ptr(W.e), C_.c_int32(W.N), C_.c_int32(W.K), C_.c_int64(W.K),
         _ptr(out), C_.c_int64(out.stride(0)))
+
+
+def dequant_mxfp4(W, out, plan=None):
+    """usdm_dequant_mxfp4: a quant.Mxfp4Weight -> bf16 out [N][>= K] (the prefill operand of usdm_gemm)."""
+    _need_cuda(W, out)
+    if not isinstance(W, Mxfp4Weight) or out.dtype != torch.bfloat16 or out.dim() != 2 or out.shape[0] < W.N or out.shape[1] < W.K \
+            or out.stride(1) != 1:
+        raise ValueError("dequant_mxfp4: an Mxfp4Weight and a bf16 [N][>= K] output with unit column stride")
+    _go(plan, "usdm_dequant_mxfp4", lib.usdm_dequant_mxfp4, _ptr(W.q), C_.c_int64(W.q.shape[1]), _ptr(W.s), C_.c_int64(W.s.shape[1]),
+        C_.c_int32(W.N), C_.c_int32(W.K), _ptr(out), C_.c_int64(out.stride(0)))
 
 
 def gemv_batch_ks_floats(N, K):

@@ -12,6 +12,10 @@ arithmetic unchanged, and prefill dequantizes into a bf16 scratch for usdm_gemm.
 Byte layout (only this module, usdm_dequant_fp8 and the FP8 GEMV kernels know it): q is row-major [N][K] bytes with row stride K
 (K a multiple of 8: lane L of the GEMV reads the 8 bytes of the 8 bf16 elements it reads in the bf16 kernel); e is [N].
 Quantization runs once, at load time, with torch ops on whatever device the matrix is on; it is deterministic.
+
+Weight-only MXFP4 (opt-in, `quantization="mxfp4"`): OCP MX e2m1 elements with one power-of-two scale per block of 32 consecutive K
+elements of a row (quantize_mxfp4 / dequantize_mxfp4 / Mxfp4Weight below).  4.25 bits per weight, and a much coarser grid than fp8:
+round-to-nearest MXFP4 has a relative L2 weight error of about 11.5 % on Gaussian rows (fp8 with row scales: 2.7 %).
 """
 import torch
 
@@ -120,3 +124,116 @@ class Fp8Weight:
 
     def numel(self):
         return self.q.numel()
+
+
+# ---- Weight-only MXFP4 (opt-in, quantization="mxfp4") ---------------------------------------------------------------------------
+# Logical format (public; tests and kernels share it).  A [N][K] matrix, K % 32 == 0, is cut into blocks of 32 consecutive K
+# elements of one row.
+#   scale of a block: s = floor(log2(amax)) - 2 (the OCP MX rule; amax the block's largest magnitude), clamped to
+#       [MX_EXP_MIN, MX_EXP_MAX]; an all-zero block gets 0.  Stored as the e8m0 byte s + 127.
+#   element: the e2m1 code (bit 3 sign, bits 2:0 index into E2M1_VALUES) of w / 2^s, rounded to nearest, ties to the even code,
+#       magnitudes above 6 saturate to 6.  A value that rounds to zero gets code 0 whatever its sign.
+#   W'[r][k] = e2m1(code) * 2^s: at most 2 significant bits times a power of two inside the clamp, so exactly a normal bf16 or 0.
+# An MXFP4 model is therefore exactly the bf16 model with the weights W'.
+# Memory layout (private to Mxfp4Weight, usdm_dequant_mxfp4 and the MXFP4 GEMV kernels; include/usdm_hip.h describes it): nibbles
+# and scale bytes are interleaved so that a GEMV lane fetches its codes of four K iterations with one 16-byte load.
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MX_BLOCK = 32
+MX_EXP_MIN = -125     # 0.5 * 2^-125 = 2^-126: the smallest nonzero dequantized value is a normal bf16
+MX_EXP_MAX = 125      # 6 * 2^125 < the largest finite bf16
+MX_GROUP = 2048       # elements of a row that the packed layout interleaves (four K iterations of 512 of the GEMV)
+
+
+def quantize_mxfp4(w):
+    """w: [N][K] (bf16 or f32, finite), K % 32 == 0 -> (codes uint8 [N][K], one e2m1 code per element; scales uint8 [N][K/32],
+    e8m0 bytes) on w's device.  Deterministic: comparisons and integer ops only."""
+    if w.dim() != 2 or w.shape[1] % MX_BLOCK:
+        raise ValueError("quantize_mxfp4 takes a [N][K] matrix with K a multiple of 32")
+    w32 = w.float()
+    if not bool(torch.isfinite(w32).all()):
+        raise ValueError("quantize_mxfp4: the matrix holds a non-finite value")
+    N, K = w32.shape
+    blk = w32.view(N, K // MX_BLOCK, MX_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    nz = amax > 0
+    _, x = torch.frexp(torch.where(nz, amax, torch.ones_like(amax)))     # amax = m * 2^x, m in [0.5, 1): floor(log2) = x - 1
+    e = (x.to(torch.int32) - 3).clamp(MX_EXP_MIN, MX_EXP_MAX)
+    e = torch.where(nz, e, torch.zeros_like(e))
+    v = torch.ldexp(blk.abs(), (-e).float()[:, :, None])                  # exact: a power-of-two scaling
+    code = torch.zeros(blk.shape, dtype=torch.uint8, device=w.device)
+    for t, closed in ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False), (3.5, True), (5.0, False)):
+        code += (v >= t if closed else v > t).to(torch.uint8)             # ties go to the even code
+    code |= ((blk < 0) & (code != 0)).to(torch.uint8) << 3                # no negative zero
+    return code.view(N, K).contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes, scales):
+    """(codes uint8 [N][K], scales uint8 [N][K/32]) -> bf16 [N][K] = e2m1(code) * 2^(scale - 127) (exact)."""
+    N, K = codes.shape
+    lut = torch.tensor(E2M1_VALUES + tuple(-x for x in E2M1_VALUES), dtype=torch.float32, device=codes.device)
+    v = lut[codes.long()].view(N, K // MX_BLOCK, MX_BLOCK)
+    return torch.ldexp(v, (scales.float() - 127.0)[:, :, None]).view(N, K).to(torch.bfloat16)
+
+
+class Mxfp4Weight:
+    """A quantized matrix as the kernels take it: q uint8 [N][Kp / 2] packed codes and s uint8 [N][Kp / 32] scale bytes, Kp = K
+    rounded up to whole groups of 2048 (zero codes, scale bytes 127).  ops.gemv / ops.gemv_batch dispatch on this type."""
+    __slots__ = ("q", "s", "N", "K")
+
+    def __init__(self, q, s, K):
+        Kp = -(-K // MX_GROUP) * MX_GROUP
+        if q.dtype != torch.uint8 or s.dtype != torch.uint8 or q.dim() != 2 or K % MX_BLOCK or q.shape[1] != Kp // 2 \
+                or s.shape != (q.shape[0], Kp // MX_BLOCK):
+            raise ValueError("Mxfp4Weight: q uint8 [N][Kp / 2] and s uint8 [N][Kp / 32], Kp = K (a multiple of 32) rounded up to 2048")
+        self.q, self.s = q.contiguous(), s.contiguous()
+        self.N, self.K = q.shape[0], K
+
+    @classmethod
+    def from_codes(cls, codes, scales):
+        """Pack the logical (codes [N][K], scales [N][K/32]) of quantize_mxfp4 into the kernels' layout."""
+        N, K = codes.shape
+        G = -(-K // MX_GROUP)
+        c = torch.zeros(N, G * MX_GROUP, dtype=torch.uint8, device=codes.device)
+        c[:, :K] = codes
+        byts = c[:, 0::2] | (c[:, 1::2] << 4)                             # element 2m in bits 3:0, element 2m+1 in bits 7:4
+        # linear dword 256 g + 64 i + L (elements 2048 g + 512 i + 8 L ..+7) -> dword 256 g + 4 L + i
+        q = byts.view(N, G, 4, 64, 4).permute(0, 1, 3, 2, 4).reshape(N, G * MX_GROUP // 2)
+        sc = torch.full((N, G * MX_GROUP // MX_BLOCK), 127, dtype=torch.uint8, device=codes.device)
+        sc[:, :K // MX_BLOCK] = scales
+        # block 64 g + 16 i + b -> byte 64 g + 4 b + i
+        s = sc.view(N, G, 4, 16).permute(0, 1, 3, 2).reshape(N, G * MX_GROUP // MX_BLOCK)
+        return cls(q, s, K)
+
+    @classmethod
+    def from_matrix(cls, w):
+        return cls.from_codes(*quantize_mxfp4(w))
+
+    def unpack(self):
+        """-> the logical (codes uint8 [N][K], scales uint8 [N][K/32])."""
+        N, G = self.N, self.q.shape[1] * 2 // MX_GROUP
+        byts = self.q.view(N, G, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(N, G * MX_GROUP // 2)
+        c = torch.stack((byts & 15, byts >> 4), dim=2).view(N, G * MX_GROUP)
+        sc = self.s.view(N, G, 16, 4).permute(0, 1, 3, 2).reshape(N, G * MX_GROUP // MX_BLOCK)
+        return c[:, :self.K].contiguous(), sc[:, :self.K // MX_BLOCK].contiguous()
+
+    def dequantize(self):
+        return dequantize_mxfp4(*self.unpack())
+
+    @property
+    def is_cuda(self):
+        return self.q.is_cuda
+
+    @property
+    def shape(self):
+        return torch.Size((self.N, self.K))
+
+    @property
+    def nbytes(self):
+        """bytes one pass over the matrix streams (packed codes + scale bytes, padding included)"""
+        return self.q.numel() + self.s.numel()
+
+    def data_ptr(self):
+        return self.q.data_ptr()
+
+    def numel(self):
+        return self.N * self.K

@@ -113,6 +113,7 @@ class LLM:
         # quantization (vllm's name): None = bf16, "fp8" = e4m3 weights with power-of-two row scales (usdm_amd/quant.py); the
         # FP8 model decodes at most 4 sequences per step (its max_batch()) unless fp8_matrix_cores (opt-in) runs steps of 5..16
         # sequences on the matrix cores (usdm_gemv_fp8_mfma)
+        # "mxfp4" = e2m1 weights with one power-of-two scale per 32 elements (fp8 lm_head): at most 4 sequences per step
         check_quantization(quantization, fp8_matrix_cores)
         # kv_cache_dtype (vllm's name): None / "bf16", or "fp8" = e4m3 cache rows with one power-of-two scale per (token, kv head)
         kvd = check_kv_cache_dtype(kv_cache_dtype)
