@@ -77,3 +77,22 @@ def test_p2p_buffer_layout_arithmetic():
     h = ctypes.c_void_p()
     rc = p2p.lib.usdm_allreduce_p2p_create(ctypes.c_int32(0), ctypes.c_int32(9), ctypes.c_int32(1), ctypes.c_int32(2), ctypes.c_int32(10), ctypes.byref(h))
     assert rc == 2 and b"world" in p2p.lib.usdm_last_error()
+
+
+def test_gemv_threads_table():
+    """usdm_gemv_threads = 64 x the waves of the one launch selection (csrc/gemv_launch.h gemv_select): the table for the shapes
+    the project runs.  usdm_gemv_engine reproduces the RMSNorm partition from it."""
+    from usdm_amd import _lib
+    f = _lib.lib.usdm_gemv_threads
+
+    def threads(N, K=4096, **kw):
+        a = _lib.GemvArgs(N=N, K=K, ldw=K, **kw)
+        return f(ctypes.byref(a))
+
+    assert threads(6144) == 768                                        # 24 rows per CU: 2 x 12 waves
+    assert threads(4096) == 1024 and threads(4096, K=14336) == 1024    # 16 rows per CU: 1 x 16 waves
+    assert threads(28672, act=3) == 448                                # gate/up of the 7B: 14 outputs per 7-wave workgroup
+    assert threads(42003, part_val=8, part_idx=8) == 256               # lm_head: 4 rows x 4 waves
+    for kw in (dict(mrg_po=8), dict(p2p_mode=1), dict(mrg_po=8, p2p_mode=1)):
+        assert threads(4096, **kw) == 1024 and threads(1024, **kw) == 256
+    assert threads(1000) == 256                                        # no special row: the balance rule's pick, 4 waves

@@ -224,7 +224,7 @@ def asm(tmp_path_factory):
 def _mx4_kernels(t, asm):
     """(file, name, first line, end line, holds an asm load) of every MXFP4 instantiation of the two GEMV kernels"""
     out = []
-    for f, kern, tag in (("llm_k", "gemv_kernel", "gemv_mx4"), ("llm_batch_k", "gemv_batch_kernel", "gemvb_mx4")):
+    for f, kern, tag in (("llm_k", "gemv_kernel", "gemv_mx4"), ("llm_batch_k", "gemv_batch_kernel", "gemv_mx4")):
         lines = asm[f]
         for name, i0, i1 in t.kernels(lines, kern):
             if tag in name:

@@ -4,49 +4,23 @@
 // identical to the batch-1 kernel, so a batched step reproduces NB independent steps bit for bit.
 #include "common.h"
 #include "../../include/usdm_hip.h"
+#include "gemv_launch.h"
 
 namespace {
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-__device__ __forceinline__ float dot8b(u32x4 w, u32x4 x, float acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned a = w[i], b = x[i];
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), acc, false);
-  }
-  return acc;
-}
-
-// FP8: the weight-only FP8 format (usdm_gemv_fp8, as in gemv_kernel): 8-byte loads of e4m3 bytes, converted in registers with the
-// row's power-of-two scale (exact), then the bf16 arithmetic unchanged; a ring twice as deep.  The row exponents are one extra
-// kernel argument (FP8 only: the bf16 instantiations keep their exact signature and code).
-template <bool FP8> struct gemvb_fmt { typedef u32x4 wvec; };
-template <> struct gemvb_fmt<true> { typedef u32x2 wvec; };
-// MX4: the weight-only MXFP4 format (usdm_gemv_mxfp4, as in gemv_kernel: the layout is described there): one 16-byte load carries
-// a lane's codes of four K iterations, one dword the four block scales; a ring slot is one such group.  Selected by the type of the
-// extra argument, so the existing instantiations keep their names.
-struct gemvb_mx4 { const uint8_t* scales; int64_t lds; };
-template <class... FMT> struct gemvb_is_mx4 { static constexpr bool value = false; };
-template <> struct gemvb_is_mx4<gemvb_mx4> { static constexpr bool value = true; };
-template <int I> struct gemvb_ic { static constexpr int value = I; };
-__device__ __forceinline__ gemvb_mx4 gemvb_mx4_fmt() { return gemvb_mx4{nullptr, 0}; }
-__device__ __forceinline__ gemvb_mx4 gemvb_mx4_fmt(const int8_t*) { return gemvb_mx4{nullptr, 0}; }
-__device__ __forceinline__ gemvb_mx4 gemvb_mx4_fmt(gemvb_mx4 m) { return m; }
-__device__ __forceinline__ const int8_t* gemvb_row_exp() { return nullptr; }
-__device__ __forceinline__ const int8_t* gemvb_row_exp(const int8_t* e) { return e; }
-
+// The weight formats (FP8: the row exponents as one extra kernel argument; MXFP4: selected by the type of that argument) are those
+// of gemv_kernel, where the layouts are described; the format trait (load width, MXFP4 argument, ring depth, dot8) is
+// gemv_common.h's, one text for both kernels.
 // (NB = 4 needs 140 VGPRs in the gate/up variant = 3 workgroups per SIMD instead of 4, i.e. a third round of workgroups for
 // the 1792-workgroup launch: 57 us instead of 40.  Forcing 128 VGPRs spills and was measured slower: 898 vs 967 tok/s.)
 template <int RW, bool GLU, int NWV, int NB, bool FP8 = false, class... FMT>
 __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_batch_args ba, FMT... fmt) {
   const usdm_gemv_args& a = ba.g;
-  constexpr bool MX4 = gemvb_is_mx4<FMT...>::value;
+  constexpr bool MX4 = gemv_is_mx4<FMT...>::value;
   static_assert((FP8 || MX4) == (sizeof...(FMT) == 1) && !(FP8 && MX4), "FP8 takes the row exponents, MXFP4 the block scales");
-  typedef typename gemvb_fmt<FP8>::wvec wvec;
+  typedef typename gemv_fmt<FP8>::wvec wvec;
   constexpr int NTH = NWV * 64;
   constexpr int NR = GLU ? 2 * RW : RW;
-  constexpr int UNR0 = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : 8);
-  constexpr int UNR = MX4 ? (NR >= 3 ? 2 : 4) : FP8 ? 2 * UNR0 : UNR0;   // (MX4: slots of one group = 4 K iterations, as gemv_kernel)
+  constexpr int UNR = gemv_ring_depth(NR, FP8, MX4);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = (bf16_t*)smem;  // [NB][Kpad] bf16, zero padded
   __shared__ float red[NB][NWV];
@@ -74,9 +48,9 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
     r = r < a.N ? r : a.N - 1;
     if constexpr (FP8) {
       wp[j] = (const wvec*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
-      wsc[j] = fp8_row_scale(gemvb_row_exp(fmt...)[r]);
+      wsc[j] = fp8_row_scale(gemv_row_exp(fmt...)[r]);
     } else if constexpr (MX4) {
-      const gemvb_mx4 m = gemvb_mx4_fmt(fmt...);
+      const gemv_mx4 m = gemv_mx4_fmt(fmt...);
       wp[j] = (const u32x4*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
       wsp[j] = (const unsigned*)(m.scales + (int64_t)r * m.lds) + (lane >> 2);
     } else {
@@ -199,7 +173,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
         for (int j = 0; j < NR; ++j) {
           const u32x4 wv = mx4x8_to_bf16x8<i>(ring[j][u][i], rsc[j][u]);
 #pragma unroll
-          for (int b = 0; b < NB; ++b) acc[j][b] = dot8b(wv, xv[b], acc[j][b]);
+          for (int b = 0; b < NB; ++b) acc[j][b] = dot8(wv, xv[b], acc[j][b]);
         }
       }
     };
@@ -208,7 +182,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
       for (int u = 0; u < UNR; ++u) {
         const int g = g0 + u;
         if (g < ngr) {
-          step(gemvb_ic<0>{}, g, u); step(gemvb_ic<1>{}, g, u); step(gemvb_ic<2>{}, g, u); step(gemvb_ic<3>{}, g, u);
+          step(gemv_ic<0>{}, g, u); step(gemv_ic<1>{}, g, u); step(gemv_ic<2>{}, g, u); step(gemv_ic<3>{}, g, u);
           if (g + UNR < ngr) {
 #pragma unroll
             for (int j = 0; j < NR; ++j) {
@@ -233,10 +207,10 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
           if constexpr (FP8) {
             const u32x4 wv = fp8x8_to_bf16x8(ring[j][u], wsc[j]);
 #pragma unroll
-            for (int b = 0; b < NB; ++b) acc[j][b] = dot8b(wv, xv[b], acc[j][b]);
+            for (int b = 0; b < NB; ++b) acc[j][b] = dot8(wv, xv[b], acc[j][b]);
           } else {
 #pragma unroll
-            for (int b = 0; b < NB; ++b) acc[j][b] = dot8b(ring[j][u], xv[b], acc[j][b]);
+            for (int b = 0; b < NB; ++b) acc[j][b] = dot8(ring[j][u], xv[b], acc[j][b]);
           }
           if (it + UNR < nit) ring[j][u] = wload(j, it + UNR);
         }
@@ -284,14 +258,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
       for (int j = 0; j < RW; ++j) {
         const int o = ob + j;
         if (2 * o >= a.N) continue;
-        const float g = acc[j][b], u = acc[j + RW][b];
-        float r;
-        if (a.round_bf16) {
-          const float gt = round_bf(g), up = round_bf(u);
-          r = round_bf(round_bf(gt / (1.0f + __expf(-gt))) * up);
-        } else {
-          r = (g / (1.0f + __expf(-g))) * u;
-        }
+        const float r = gemv_swiglu_value(acc[j][b], acc[j + RW][b], a.round_bf16);
         if (a.y16) ((bf16_t*)a.y16)[(int64_t)b * ba.y_bs + o] = f2bf(r);
         if (a.y32) a.y32[(int64_t)b * ba.y_bs + o] = r;
       }
@@ -313,52 +280,17 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
   }
 }
 
-static int pick_rw(int nout, bool glu) {   // same balance rule as the batch-1 launcher
-  const int ncand = glu ? 2 : 4;
-  const int cands[4] = {glu ? 2 : 4, glu ? 1 : 3, 2, 1};
-  int best = cands[ncand - 1];
-  double best_score = -1.0;
-  for (int c = 0; c < ncand; ++c) {
-    const int rw = cands[c];
-    const int blocks = cdiv(nout, 4 * rw);
-    const double eff = (blocks / 256.0) / (double)((blocks + 255) / 256);
-    if (blocks >= 1024 && eff >= 0.9) return rw;
-    const double score = eff * (blocks >= 512 ? 1.0 : 0.5 + blocks / 1024.0);
-    if (score > best_score) { best_score = score; best = rw; }
-  }
-  return best;
-}
-
 template <int NB, bool FP8 = false, class... FMT>
 int launch_nb(const usdm_gemv_batch_args& ba, hipStream_t st, FMT... fmt) {
-  const usdm_gemv_args& a = ba.g;
-  const bool glu = a.act == USDM_ACT_SWIGLU;
-  const int nout = glu ? a.N / 2 : a.N;
-  const int Kpad = (a.K + 511) & ~511;
-  const size_t lds = (size_t)Kpad * 2 * NB;
-#define USDM_GB(RW, GLUV, NWV, GRID)                                                                              \
-  do {                                                                                                             \
-    auto kfn = gemv_batch_kernel<RW, GLUV, NWV, NB, FP8, FMT...>;                                                  \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-    hipLaunchKernelGGL(kfn, dim3(GRID), dim3(NWV * 64), lds, st, ba, fmt...);                                      \
-  } while (0)
-  if (!glu && !a.part_val && nout % 256 == 0 && (nout / 256 == 16 || nout / 256 == 24)) {
-    if (nout / 256 == 16) USDM_GB(1, false, 16, 256);
-    else USDM_GB(2, false, 12, 256);
-  } else {
-    const int rw = a.part_val ? 4 : pick_rw(nout, glu);
-    const int grid = cdiv(nout, 4 * rw);
-    if (glu) {
-      if (rw == 2) USDM_GB(2, true, 4, grid);
-      else USDM_GB(1, true, 4, grid);
-    } else {
-      if (rw == 4) USDM_GB(4, false, 4, grid);
-      else if (rw == 3) USDM_GB(3, false, 4, grid);
-      else if (rw == 2) USDM_GB(2, false, 4, grid);
-      else USDM_GB(1, false, 4, grid);
-    }
-  }
-#undef USDM_GB
+  const size_t lds = (size_t)((ba.g.K + 511) & ~511) * 2 * NB;
+  const gemv_sel s = gemv_select(ba.g, true);   // the batch-1 launcher's table, without the forms that are batch-1 only
+  const bool found = gemv_dispatch<GEMV_BATCH>(s, [&](auto RW, auto GLU, auto NWV) {
+    constexpr int nwv = decltype(NWV)::value;
+    auto kfn = gemv_batch_kernel<decltype(RW)::value, decltype(GLU)::value != 0, nwv, NB, FP8, FMT...>;
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    hipLaunchKernelGGL(kfn, dim3(s.grid), dim3(nwv * 64), lds, st, ba, fmt...);
+  });
+  if (!found) return gemv_no_instantiation(s);
   USDM_LAUNCH_CHECK();
   return 0;
 }
@@ -374,13 +306,8 @@ extern "C" int usdm_gemv_batch(const usdm_gemv_batch_args* pa, usdm_stream_t str
   USDM_CHECK_ARG(!a.x_delta && !a.x_out, "usdm_gemv_batch: x_delta / x_out are batch-1 (tensor-parallel) only");
   if (pa->form == 1 || pa->form == 3 || pa->form == 5 || (pa->form == 0 && pa->nb > 4)) return usdm_gemv_mfma_launch(pa, (hipStream_t)stream);
   USDM_CHECK_ARG(pa->nb >= 1 && pa->nb <= 4, "usdm_gemv_batch: the VALU form takes 1..4 sequences per step (form = 1 or nb > 4: matrix cores, <= 16)");
-  USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.K % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K, "usdm_gemv_batch: bad N/K/ldw");
-  USDM_CHECK_ARG(a.K <= 16384, "usdm_gemv_batch: K too large for the LDS-resident input vectors");
-  const bool glu = a.act == USDM_ACT_SWIGLU;
-  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "usdm_gemv_batch: swiglu needs N %% 32 == 0");
-  USDM_CHECK_ARG(a.y16 || a.y32 || a.part_val, "usdm_gemv_batch: no output");
-  USDM_CHECK_ARG(!a.part_val || (a.part_idx && !glu && pa->part_bs >= cdiv(a.N, 16)), "usdm_gemv_batch: lm_head partial buffers");
-  USDM_CHECK_ARG(!a.x_delta && !a.x_out, "usdm_gemv_batch: x_delta / x_out are batch-1 (tensor-parallel) only");
+  if (int rc = gemv_check_shape("usdm_gemv_batch", a, "input vectors")) return rc;   // (outputs: checked above, for both forms)
+  USDM_CHECK_ARG(!a.part_val || (a.part_idx && a.act != USDM_ACT_SWIGLU && pa->part_bs >= cdiv(a.N, 16)), "usdm_gemv_batch: lm_head partial buffers");
   USDM_CHECK_ARG(pa->x_bs % 8 == 0, "usdm_gemv_batch: x stride must keep 16-B alignment");
   hipStream_t st = (hipStream_t)stream;
   switch (pa->nb) {
@@ -404,7 +331,7 @@ int usdm_gemv_fp8_batch_launch(const usdm_gemv_fp8_args* pa, hipStream_t st) {
 // usdm_gemv_mxfp4 with 2..4 sequences (llm_k.hip checks the arguments it shares with the batch-1 form)
 int usdm_gemv_mxfp4_batch_launch(const usdm_gemv_mxfp4_args* pa, hipStream_t st) {
   USDM_CHECK_ARG(pa->b.x_bs % 8 == 0, "usdm_gemv_mxfp4: x stride must keep 16-B alignment");
-  const gemvb_mx4 m{pa->scales, pa->lds};
+  const gemv_mx4 m{pa->scales, pa->lds};
   switch (pa->b.nb) {
     case 2: return launch_nb<2, false>(pa->b, st, m);
     case 3: return launch_nb<3, false>(pa->b, st, m);

@@ -12,10 +12,10 @@
 // (sc1) stores, every storing wave drains them, ONE lane adds to the arrival counter; consumers poll the counter (bounded) and read
 // the handed-off vectors only with agent-scope loads.
 #include "common.h"
+#include "gemv_common.h"
 #include "../../include/usdm_hip_experimental.h"
 
 namespace {
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 constexpr int CW = 7;             // waves per workgroup
 constexpr int CTH = CW * 64;      // 448 threads
 constexpr int CGRID = 512;        // resident workgroups (2 per CU)
@@ -24,15 +24,6 @@ constexpr int TILE = 2 * CW;      // outputs per workgroup tile
 __device__ __forceinline__ int ntiles_of(const usdm_gemv_args& a) {
   const int nout = a.act == USDM_ACT_SWIGLU ? a.N / 2 : a.N;
   return (nout + TILE - 1) / TILE;
-}
-
-__device__ __forceinline__ float cdot8(u32x4 w, u32x4 x, float acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned a = w[i], b = x[i];
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), acc, false);
-  }
-  return acc;
 }
 
 // 8 consecutive bf16 of a vector that another workgroup may have written in this launch: agent-scope (sc1) loads only
@@ -94,7 +85,7 @@ __device__ __forceinline__ void run_tile(const usdm_gemv_args& a, int tile, cons
         const u32x4 xv = *(const u32x4*)(xs + (it * 64 + lane) * 8);
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
-          acc[j] = cdot8(ring[j * UNR + u], xv, acc[j]);
+          acc[j] = dot8(ring[j * UNR + u], xv, acc[j]);
           if (it + UNR < nit) ring[j * UNR + u] = __builtin_nontemporal_load((const u32x4*)(W + wp[j] + (it + UNR) * 1024));
         }
       }

@@ -19,10 +19,10 @@
 // Per output row the arithmetic is usdm_gemv's, bit for bit (lane l owns 16-byte pieces l, l + 64, ... of K and accumulates them
 // in order; the RMSNorm partial sums follow the thread partition of the usdm_gemv variant that would run the projection).
 #include "common.h"
+#include "gemv_common.h"
 #include "../../include/usdm_hip_experimental.h"
 
 namespace {
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 constexpr int NSLOT = 7, SLOTB = 16384;
 constexpr int XR0 = NSLOT * SLOTB, XR1 = XR0 + 8192, XR2 = XR1 + 8192;   // input-vector regions: 8 KB, 8 KB, 28 KB
 constexpr int CTL = XR2 + 28672;                                         // control words + CU-local residual values
@@ -60,15 +60,6 @@ __device__ __forceinline__ Ph make_ph(const usdm_gemv_args& a, int xreg) {
   p.nslots = p.njobs * p.spj;
   p.xreg = xreg;
   return p;
-}
-
-__device__ __forceinline__ float edot8(u32x4 w, u32x4 x, float acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned a = w[i], b = x[i];
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), acc, false);
-  }
-  return acc;
 }
 
 // control words live in LDS and are touched only through address-space-3 volatile accesses (ds_read / ds_write: a generic
@@ -316,8 +307,8 @@ __device__ __forceinline__ void consumer(const usdm_gemv_chain_args& c, char* sm
             const u32x4 xv = *(const u32x4*)(xs + (it * 64 + lane) * 8);
             const u32x4 w0 = *(const u32x4*)(slot + it * 1024 + lane * 16);
             const u32x4 w1 = *(const u32x4*)(slot + (8 + it) * 1024 + lane * 16);
-            a0 = edot8(w0, xv, a0);
-            a1 = edot8(w1, xv, a1);
+            a0 = dot8(w0, xv, a0);
+            a1 = dot8(w1, xv, a1);
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           if (lane == 0) ctl[W_FREE + i] = (unsigned)(s + 1);      // the slot's bytes are in registers: hand it back
@@ -349,7 +340,7 @@ __device__ __forceinline__ void consumer(const usdm_gemv_chain_args& c, char* sm
               const int it = hf * ph.pps + k;
               const u32x4 xv = *(const u32x4*)(xs + (it * 64 + lane) * 8);
               const u32x4 w = *(const u32x4*)(slot + k * 1024 + lane * 16);
-              acc = edot8(w, xv, acc);
+              acc = dot8(w, xv, acc);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (lane == 0) ctl[W_FREE + i] = (unsigned)(s + 1);

@@ -9,11 +9,9 @@
 #include "common.h"
 #include <stdlib.h>
 #include "../../include/usdm_hip.h"
+#include "gemv_launch.h"
 #include "p2p.h"
 
-#ifndef USDM_UNR1
-#define USDM_UNR1 8   // ring depth of the one-row-per-wave variants (o_proj / down_proj)
-#endif
 #ifndef USDM_GEMV_X_FIRST
 #define USDM_GEMV_X_FIRST 1   // 0: the input vector is requested behind the first weight ring and read twice by the RMSNorm prologue (A/B builds)
 #endif
@@ -21,17 +19,6 @@
 #define USDM_GEMV_RES_PREFETCH 1   // 0: the residual is read in the epilogue (A/B builds)
 #endif
 namespace {
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-__device__ __forceinline__ float dot8(u32x4 w, u32x4 x, float acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned a = w[i], b = x[i];
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), acc, false);
-  }
-  return acc;
-}
-
 // ---------------------------------------------------------------------------------------------
 // GEMV: y = W x, W bf16 [N][ldw] row-major (the nn.Linear layout).
 //   * workgroup = 4 waves; a wave owns RW output rows (GLU: RW gate + RW up rows) and streams them
@@ -65,17 +52,7 @@ __device__ unsigned long long g_gemv_trace[8192 * 8];
 // elements that lane accumulates in iteration 4g+i of the bf16 kernel); the scale bytes are interleaved the same way, so the four
 // lanes that share a block read ONE dword holding their scales of the four iterations.  Rows are padded with zero codes to whole
 // groups (x in LDS is zero only up to Kpad: iterations past nit are skipped, not multiplied).  A ring slot is one group.
-template <bool FP8> struct gemv_fmt { typedef u32x4 wvec; };
-template <> struct gemv_fmt<true> { typedef u32x2 wvec; };
-struct gemv_mx4 { const uint8_t* scales; int64_t lds; };   // scale bytes [N][lds], lds = (row stride of the codes in bytes) / 16
-template <class... FMT> struct gemv_is_mx4 { static constexpr bool value = false; };
-template <> struct gemv_is_mx4<gemv_mx4> { static constexpr bool value = true; };
-__device__ __forceinline__ const int8_t* gemv_row_exp() { return nullptr; }
-__device__ __forceinline__ const int8_t* gemv_row_exp(const int8_t* e) { return e; }
-template <int I> struct gemv_ic { static constexpr int value = I; };
-__device__ __forceinline__ gemv_mx4 gemv_mx4_fmt() { return gemv_mx4{nullptr, 0}; }
-__device__ __forceinline__ gemv_mx4 gemv_mx4_fmt(const int8_t*) { return gemv_mx4{nullptr, 0}; }
-__device__ __forceinline__ gemv_mx4 gemv_mx4_fmt(gemv_mx4 m) { return m; }
+// The format trait (load width, MXFP4 argument, ring depth, dot8) is gemv_common.h's, shared with gemv_batch_kernel.
 
 template <int RW, bool GLU, int NWV, bool MRG = false, bool P2P = false, bool CMB = false, bool FP8 = false, class... FMT>
 __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, FMT... fmt) {
@@ -85,10 +62,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   static_assert(!(FP8 || MX4) || (!MRG && !P2P && !CMB), "the FP8 / MXFP4 weight formats have the plain single-GPU forms only");
   constexpr int NTH = NWV * 64;
   constexpr int NR = GLU ? 2 * RW : RW;   // rows streamed together by one wave
-  constexpr int UNR0 = (NR >= 8) ? 2 : (NR >= 4) ? 4 : (NR == 3 ? 5 : (NR == 2 ? 8 : USDM_UNR1));  // ring depth: NR*UNR = 15..16 loads in flight per lane
-  // (FP8: 8-byte loads, twice as many for the same bytes in flight; MX4: slots of one group = 4 K iterations, 6..8 in flight with
-  // their scale dwords - K = 4096 is two groups, so more slots would only add re-reads of the row start)
-  constexpr int UNR = MX4 ? (NR >= 3 ? 2 : 4) : FP8 ? 2 * UNR0 : UNR0;
+  constexpr int UNR = gemv_ring_depth(NR, FP8, MX4);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = (bf16_t*)smem;  // [Kpad] bf16, zero padded
   __shared__ float red[NWV];
@@ -515,14 +489,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
     for (int j = 0; j < RW; ++j) {
       const int o = ob + j;
       if (2 * o >= a.N) continue;
-      const float g = acc[j], u = acc[j + RW];
-      float r;
-      if (a.round_bf16) {
-        const float gt = round_bf(g), up = round_bf(u);
-        r = round_bf(round_bf(gt / (1.0f + __expf(-gt))) * up);
-      } else {
-        r = (g / (1.0f + __expf(-g))) * u;
-      }
+      const float r = gemv_swiglu_value(acc[j], acc[j + RW], a.round_bf16);
       if (a.y16) ((bf16_t*)a.y16)[o] = f2bf(r);
       if (a.y32) a.y32[o] = r;
     }
@@ -541,24 +508,6 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
       if (a.y32) a.y32[n] = v;
     }
   }
-}
-
-// Rows per wave: HBM streaming wants >= ~4 workgroups (16 waves) per CU in flight AND a grid that is a whole
-// number of workgroups per CU (256 CUs); take the largest RW that gives both, else the best balanced one.
-static int gemv_pick_rw(int nout, bool glu) {
-  const int ncand = glu ? 2 : 4;
-  const int cands[4] = {glu ? 2 : 4, glu ? 1 : 3, 2, 1};
-  int best = cands[ncand - 1];
-  double best_score = -1.0;
-  for (int c = 0; c < ncand; ++c) {
-    const int rw = cands[c];
-    const int blocks = cdiv(nout, 4 * rw);
-    const double eff = (blocks / 256.0) / (double)((blocks + 255) / 256);  // 1.0 = perfectly balanced
-    if (blocks >= 1024 && eff >= 0.9) return rw;
-    const double score = eff * (blocks >= 512 ? 1.0 : 0.5 + blocks / 1024.0);
-    if (score > best_score) { best_score = score; best = rw; }
-  }
-  return best;
 }
 
 // final arg-max over the per-block partials; advances the device-side decode state
@@ -1243,44 +1192,19 @@ __global__ void residual_add_kernel(bf16_t* h, const float* delta, int n) {
 }
 }  // namespace
 
-// the plain single-GPU forms (no merged input, no peer-to-peer epilogue): the variant per projection shape.  One selection for
-// both weight formats, so an FP8 launch partitions K and the RMSNorm sums exactly as the bf16 launch of the same shape.
-template <bool FP8, class... FMT>
-static int gemv_launch_plain(const usdm_gemv_args& a, size_t lds, hipStream_t st, FMT... fmt) {
-  const bool glu = a.act == USDM_ACT_SWIGLU;
-  const int nout = glu ? a.N / 2 : a.N;
-  if (!glu && !a.part_val && nout % 256 == 0) {
-    const int rows_per_cu = nout / 256;
-    if (rows_per_cu == 16) {
-      hipLaunchKernelGGL((gemv_kernel<1, false, 16, false, false, false, FP8, FMT...>), dim3(256), dim3(1024), lds, st, a, fmt...);
-      USDM_LAUNCH_CHECK();
-      return 0;
-    }
-    if (rows_per_cu == 24) {
-      hipLaunchKernelGGL((gemv_kernel<2, false, 12, false, false, false, FP8, FMT...>), dim3(256), dim3(768), lds, st, a, fmt...);
-      USDM_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  // (a 14-wave GLU variant with one workgroup per CU was measured 15 % slower than 7 four-wave workgroups per CU)
-  // gate/up of the 7B (14336 outputs): 7-wave workgroups of 14 outputs = 1024 workgroups = exactly two rounds of two
-  // workgroups per CU, instead of 1792 four-wave workgroups = 1.75 rounds of four
-  if (glu && nout % 14 == 0 && (nout / 14) % 512 == 0) {
-    hipLaunchKernelGGL((gemv_kernel<2, true, 7, false, false, false, FP8, FMT...>), dim3(nout / 14), dim3(448), lds, st, a, fmt...);
-    USDM_LAUNCH_CHECK();
-    return 0;
-  }
-  const int rw = a.part_val ? 4 : gemv_pick_rw(nout, glu);
-  dim3 grid(cdiv(nout, 4 * rw)), block(256);
-  if (glu) {
-    if (rw == 2) hipLaunchKernelGGL((gemv_kernel<2, true, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
-    else hipLaunchKernelGGL((gemv_kernel<1, true, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
-  } else {
-    if (rw == 4) hipLaunchKernelGGL((gemv_kernel<4, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
-    else if (rw == 3) hipLaunchKernelGGL((gemv_kernel<3, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
-    else if (rw == 2) hipLaunchKernelGGL((gemv_kernel<2, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
-    else hipLaunchKernelGGL((gemv_kernel<1, false, 4, false, false, false, FP8, FMT...>), grid, block, lds, st, a, fmt...);
-  }
+// Launches the instantiation gemv_select names.  One selection for every weight format, so an FP8 or MXFP4 launch partitions K and
+// the RMSNorm sums exactly as the bf16 launch of the same shape.  FORM: GEMV_PLAIN (no merged input, no peer-to-peer epilogue:
+// the only form of the FP8 / MXFP4 weights), GEMV_MRG or GEMV_CMB, with the kernel's MRG / P2P / CMB flags.
+template <int FORM, bool MRG, bool P2P, bool CMB, bool FP8, class... FMT>
+static int gemv_launch(const usdm_gemv_args& a, hipStream_t st, FMT... fmt) {
+  const size_t lds = (size_t)((a.K + 511) & ~511) * 2;
+  const gemv_sel s = gemv_select(a, false);
+  const bool found = gemv_dispatch<FORM>(s, [&](auto RW, auto GLU, auto NWV) {
+    constexpr int nwv = decltype(NWV)::value;
+    hipLaunchKernelGGL((gemv_kernel<decltype(RW)::value, decltype(GLU)::value != 0, nwv, MRG, P2P, CMB, FP8, FMT...>), dim3(s.grid),
+                       dim3(nwv * 64), lds, st, a, fmt...);
+  });
+  if (!found) return gemv_no_instantiation(s);
   USDM_LAUNCH_CHECK();
   return 0;
 }
@@ -1288,12 +1212,9 @@ static int gemv_launch_plain(const usdm_gemv_args& a, size_t lds, hipStream_t st
 extern "C" int usdm_gemv(const usdm_gemv_args* pa, usdm_stream_t stream) {
   USDM_CHECK_ARG(pa && pa->W && (pa->x || pa->mrg_po), "usdm_gemv: null args");
   const usdm_gemv_args& a = *pa;
-  USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.K % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K, "usdm_gemv: bad N/K/ldw");
-  USDM_CHECK_ARG(a.K <= 16384, "usdm_gemv: K too large for the LDS-resident input vector");
+  if (int rc = gemv_check_shape("usdm_gemv", a, "input vector")) return rc;
+  if (int rc = gemv_check_outputs("usdm_gemv", a)) return rc;
   const bool glu = a.act == USDM_ACT_SWIGLU;
-  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "usdm_gemv: swiglu needs N %% 32 == 0");
-  USDM_CHECK_ARG(a.y16 || a.y32 || a.part_val, "usdm_gemv: no output");
-  USDM_CHECK_ARG(!a.part_val || (a.part_idx && !glu), "usdm_gemv: part_idx missing / lm_head mode is not GLU");
   USDM_CHECK_ARG(!a.norm_w || a.K % 8 == 0, "usdm_gemv: K");
   USDM_CHECK_ARG(!a.x_out || (a.x_delta && a.x_out != a.x), "usdm_gemv: x_out needs x_delta and must not alias x");
   USDM_CHECK_ARG(!a.mrg_po || (a.mrg_pm && a.mrg_pl && a.mrg_ns >= 1 && a.mrg_ns <= 64 && a.K % 128 == 0 && !a.norm_w && !a.x_delta),
@@ -1303,40 +1224,22 @@ extern "C" int usdm_gemv(const usdm_gemv_args* pa, usdm_stream_t stream) {
                  "usdm_gemv: the fused all-reduce needs a plain row-parallel projection with residual + y16");
   // (its LDS scratch, 9 x rows-per-workgroup floats <= 864 B, reuses the x staging area: Kpad * 2 >= 1024 B always)
   const int nout = glu ? a.N / 2 : a.N;
-  const int Kpad = (a.K + 511) & ~511;
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)Kpad * 2;
-  // Wide workgroups for the mid-size projections: one workgroup per CU with 12-16 waves stages x (and the fused
-  // RMSNorm) once per 16-24 rows instead of once per 4, at the same number of loads in flight.
   if (a.cmb_gran) {   // hand-off form of the merged-attention input
     USDM_CHECK_ARG(a.mrg_po && a.mrg_pm && a.mrg_pl && a.mrg_ns >= 1 && a.mrg_ns <= 64 && !a.p2p_mode && !glu && !a.part_val && !a.norm_w && !a.x_delta &&
                        nout % 256 == 0 && nout / 256 == 16 && a.K % 128 == 0 && a.K / 128 <= 256,
                    "usdm_gemv: cmb_gran needs the mrg_* partials, a plain 4096-output projection and K / 128 <= 256 heads");
-    hipLaunchKernelGGL((gemv_kernel<1, false, 16, false, false, true>), dim3(256), dim3(1024), lds, st, a);
-    USDM_LAUNCH_CHECK();
-    return 0;
+    return gemv_launch<GEMV_CMB, false, false, true, false>(a, st);
   }
   if (a.mrg_po || a.p2p_mode) {   // o_proj with the attention merge in its prologue and / or a row-parallel projection with the
-    // peer-to-peer all-reduce in its epilogue: the 4096-output shape of the 7B (one 16-wave workgroup per CU) or the general form
+    // peer-to-peer all-reduce in its epilogue
     USDM_CHECK_ARG(!glu && !a.part_val, "usdm_gemv: merged-attention input / fused all-reduce are for plain projections");
-    const bool big = nout % 256 == 0 && nout / 256 == 16;
-    const dim3 gb(256), bb(1024), gs(cdiv(nout, 4)), bs(256);
-    if (a.mrg_po && a.p2p_mode) {
-      if (big) hipLaunchKernelGGL((gemv_kernel<1, false, 16, true, true>), gb, bb, lds, st, a);
-      else hipLaunchKernelGGL((gemv_kernel<1, false, 4, true, true>), gs, bs, lds, st, a);
-    } else if (a.mrg_po) {
-      if (big) hipLaunchKernelGGL((gemv_kernel<1, false, 16, true, false>), gb, bb, lds, st, a);
-      else hipLaunchKernelGGL((gemv_kernel<1, false, 4, true, false>), gs, bs, lds, st, a);
-    } else {
-      if (big) hipLaunchKernelGGL((gemv_kernel<1, false, 16, false, true>), gb, bb, lds, st, a);
-      else hipLaunchKernelGGL((gemv_kernel<1, false, 4, false, true>), gs, bs, lds, st, a);
-    }
-    USDM_LAUNCH_CHECK();
-    return 0;
+    if (a.mrg_po && a.p2p_mode) return gemv_launch<GEMV_MRG, true, true, false, false>(a, st);
+    if (a.mrg_po) return gemv_launch<GEMV_MRG, true, false, false, false>(a, st);
+    return gemv_launch<GEMV_MRG, false, true, false, false>(a, st);
   }
-  return gemv_launch_plain<false>(a, lds, st);
+  return gemv_launch<GEMV_PLAIN, false, false, false, false>(a, st);
 }
-
 
 int usdm_gemv_fp8_batch_launch(const usdm_gemv_fp8_args* pa, hipStream_t st);   // llm_batch_k.hip: nb = 2..4
 
@@ -1347,16 +1250,12 @@ extern "C" int usdm_gemv_fp8(const usdm_gemv_fp8_args* pa, usdm_stream_t stream)
                  "usdm_gemv_fp8: 1..4 sequences on the VALU form (the matrix-core form has no FP8 weights)");
   USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.cmb_gran && !a.x_delta && !a.x_out,
                  "usdm_gemv_fp8: p2p / merged-attention input / cmb_gran / x_delta are not supported with FP8 weights");
-  USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.K % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && ((uintptr_t)a.W & 7) == 0, "usdm_gemv_fp8: bad N/K/ldw");
-  USDM_CHECK_ARG(a.K <= 16384, "usdm_gemv_fp8: K too large for the LDS-resident input vector");
-  const bool glu = a.act == USDM_ACT_SWIGLU;
-  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "usdm_gemv_fp8: swiglu needs N %% 32 == 0");
-  USDM_CHECK_ARG(a.y16 || a.y32 || a.part_val, "usdm_gemv_fp8: no output");
-  USDM_CHECK_ARG(!a.part_val || (a.part_idx && !glu), "usdm_gemv_fp8: part_idx missing / lm_head mode is not GLU");
+  USDM_CHECK_ARG(((uintptr_t)a.W & 7) == 0, "usdm_gemv_fp8: bad N/K/ldw");
+  if (int rc = gemv_check_shape("usdm_gemv_fp8", a, "input vector")) return rc;
+  if (int rc = gemv_check_outputs("usdm_gemv_fp8", a)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (pa->b.nb > 1) return usdm_gemv_fp8_batch_launch(pa, st);
-  const size_t lds = (size_t)((a.K + 511) & ~511) * 2;
-  return gemv_launch_plain<true>(a, lds, st, pa->row_exp);
+  return gemv_launch<GEMV_PLAIN, false, false, false, true>(a, st, pa->row_exp);
 }
 
 namespace {
@@ -1400,13 +1299,11 @@ extern "C" int usdm_gemv_mxfp4(const usdm_gemv_mxfp4_args* pa, usdm_stream_t str
                  "usdm_gemv_mxfp4: ldw (bytes) must hold whole groups of 1024 bytes and lds whole groups of 64 bytes covering K");
   USDM_CHECK_ARG(((uintptr_t)a.W & 15) == 0 && ((uintptr_t)pa->scales & 3) == 0 && ((uintptr_t)a.x & 15) == 0,
                  "usdm_gemv_mxfp4: codes and x must be 16-byte, scales 4-byte aligned");
-  const bool glu = a.act == USDM_ACT_SWIGLU;
-  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "usdm_gemv_mxfp4: swiglu needs N %% 32 == 0");
-  USDM_CHECK_ARG(a.y16, "usdm_gemv_mxfp4: no output");
+  USDM_CHECK_ARG(a.act != USDM_ACT_SWIGLU || a.N % 32 == 0, "usdm_gemv_mxfp4: swiglu needs N %% 32 == 0");
+  if (int rc = gemv_check_outputs("usdm_gemv_mxfp4", a)) return rc;   // (y32 and part_val are refused above: "no output" means no y16)
   hipStream_t st = (hipStream_t)stream;
   if (pa->b.nb > 1) return usdm_gemv_mxfp4_batch_launch(pa, st);
-  const size_t lds = (size_t)((a.K + 511) & ~511) * 2;
-  return gemv_launch_plain<false>(a, lds, st, gemv_mx4{pa->scales, pa->lds});
+  return gemv_launch<GEMV_PLAIN, false, false, false, false>(a, st, gemv_mx4{pa->scales, pa->lds});
 }
 
 namespace {
@@ -1455,20 +1352,9 @@ extern "C" int usdm_dbg_gemv_trace(unsigned long long* host, int n) {
 
 extern "C" int usdm_gemv_nblocks(int32_t N, int32_t act) { return cdiv(N, 16); }
 
-// threads per workgroup of the variant usdm_gemv picks for this projection (the fused RMSNorm's partial sums follow that
-// partition; usdm_gemv_engine reproduces it to stay bit-identical).  Keep in step with usdm_gemv below.
-extern "C" int usdm_gemv_threads(const usdm_gemv_args* pa) {
-  const usdm_gemv_args& a = *pa;
-  const bool glu = a.act == USDM_ACT_SWIGLU;
-  const int nout = glu ? a.N / 2 : a.N;
-  if (a.mrg_po || a.p2p_mode) return (nout % 256 == 0 && nout / 256 == 16) ? 1024 : 256;
-  if (!glu && !a.part_val && nout % 256 == 0) {
-    if (nout / 256 == 16) return 1024;
-    if (nout / 256 == 24) return 768;
-  }
-  if (glu && nout % 14 == 0 && (nout / 14) % 512 == 0) return 448;
-  return 256;
-}
+// threads per workgroup of the variant usdm_gemv launches for this projection: gemv_select's, the launcher's own choice (the
+// fused RMSNorm's partial sums follow that partition; usdm_gemv_engine reproduces it to stay bit-identical)
+extern "C" int usdm_gemv_threads(const usdm_gemv_args* pa) { return 64 * gemv_select(*pa, false).nwv; }
 
 extern "C" int usdm_argmax_final_seg(const float* part_val, const int32_t* part_idx, int32_t nparts, int32_t nseg, int64_t seg_stride,
                                      const usdm_decode_state* st, const void* embed_table, int32_t Hd, void* h_out,

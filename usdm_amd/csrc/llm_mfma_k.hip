@@ -28,6 +28,7 @@
 // dequantized weights W' bit for bit.
 #include "common.h"
 #include "../../include/usdm_hip.h"
+#include "gemv_common.h"
 #include <type_traits>
 
 namespace {
@@ -80,8 +81,6 @@ __device__ __forceinline__ void ld_nt_asm(V& dst, const V* p) {
 __device__ __forceinline__ void ld_exp_asm(int& dst, const int8_t* p) {
   asm volatile("global_load_sbyte %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
 }
-__device__ __forceinline__ const int8_t* mfma_row_exp() { return nullptr; }
-__device__ __forceinline__ const int8_t* mfma_row_exp(const int8_t* e) { return e; }
 template <int... I, class F>
 __device__ __forceinline__ void each_slot(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int WAIT, bool FIRST, class V>
@@ -129,7 +128,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   const bool glu = a.act == USDM_ACT_SWIGLU;
   const bool lmh = a.part_val != nullptr;
   const bf16_t* Wb = (const bf16_t*)a.W;
-  const int8_t* rexp = mfma_row_exp(fmt...);
+  const int8_t* rexp = gemv_row_exp(fmt...);
   typedef std::conditional_t<FP8, u32x2, u32x4> wvec;       // one lane's 8 weights of a chunk: 16 bf16 or 8 e4m3 bytes
 
   // ---- tiles of this workgroup: t = blockIdx.x + i * grid, i < ncand; lm_head: tiles whose 16 ids are all banned are not streamed
