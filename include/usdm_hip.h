@@ -437,6 +437,34 @@ int usdm_sample_final(const usdm_sample_args* args, const usdm_decode_state* st,
 int usdm_sample_final_seg(const usdm_sample_args* args, int32_t nseg, int64_t seg_stride, int32_t seg_len, const usdm_decode_state* st,
                           const void* embed_table_bf16, int32_t Hd, void* h_out_bf16, usdm_stream_t stream);
 
+/* Per-token log-probabilities of the step whose token usdm_sample_final has JUST picked, from the same ban-masked f32 row (after a
+ * host logits hook: the row as the hook left it).  lp(i) = x_i - logsumexp(x) over ids 0 .. V-1: the model's distribution over the
+ * allowed ids BEFORE temperature, top-k and top-p, independent of the sampling knobs (vLLM's "raw" log-probabilities; its versions
+ * differ on the default).  The pick has already advanced *st->step, so the row index is t = *st->step - 1, and the picked id is
+ * *st->next_token - st->id_offset.  Written for that t:
+ *   tok_lp[t]            lp of the picked token
+ *   tok_rank[t]          1 + number of ids whose logit is strictly greater than the picked one (vLLM's rank)
+ *   top_id / top_lp      [t][K]: the K most likely ids in descending log-probability, exact ties by lowest id first; 0 <= K <= 20
+ *                        (K = 0: not written, may be NULL); with V < K the tail is id -1, lp -inf
+ * A row with no finite logit gives -inf everywhere (never NaN); NaN appears only if the row holds one.  t >= st->max_out or t < 0
+ * writes nothing.  Exact and deterministic: radix select on unique (value, id) keys, the sum behind the logsumexp is an integer
+ * fixed-point sum, so the same logical row gives bit-identical output single or batched, contiguous or segmented.
+ * count [batch] (device, rows written so far; the caller zeroes it with st->step): a row is written only while count[b] < *st->step,
+ * and count[b] = *st->step afterwards.  REQUIRED with a device-side st->done: the pick of the final token sets `done` and still gets
+ * its row, replays after it (step no longer moves) write nothing.  NULL: every launch writes row t. */
+typedef struct usdm_logprob_args {
+  const float* logits; int32_t V; int32_t K;
+  int64_t logits_bs;        /* batched (st->batch > 1): sequence b reads logits + b * logits_bs */
+  float* tok_lp; int32_t* tok_rank; int32_t* top_id; float* top_lp;
+  int64_t tok_bs, top_bs;   /* batched: per-sequence strides (elements) of tok_lp / tok_rank (>= max_out) and top_id / top_lp (>= max_out * K) */
+  int32_t* count;
+} usdm_logprob_args;
+int usdm_logprobs(const usdm_logprob_args* args, const usdm_decode_state* st, usdm_stream_t stream);
+/* The same over a row of nseg segments, addressed as usdm_sample_final_seg addresses it (ids >= V never read). */
+int usdm_logprobs_seg(const usdm_logprob_args* args, int32_t nseg, int64_t seg_stride, int32_t seg_len, const usdm_decode_state* st,
+                      usdm_stream_t stream);
+int usdm_sizeof_logprob_args(void);
+
 /* out[r][:] = table[ids[r]][:] (bf16 rows; ids == NULL -> single row from *next_token) */
 int usdm_embed_rows(const void* table, const int64_t* ids, const int32_t* next_token, int32_t n, int32_t Hd,
                     void* out, usdm_stream_t stream);

@@ -26,6 +26,8 @@ lib.usdm_attn_decode_fp8.restype = C.c_int   # (the FP8 KV cache entry points: l
 lib.usdm_rope_cache_fp8.restype = C.c_int
 lib.usdm_gemv_mxfp4.restype = C.c_int        # (the MXFP4 entry points: likewise)
 lib.usdm_dequant_mxfp4.restype = C.c_int
+lib.usdm_logprobs.restype = C.c_int          # (the log-probability entry points: likewise)
+lib.usdm_logprobs_seg.restype = C.c_int
 _exp = None
 
 
@@ -186,6 +188,14 @@ class SampleArgs(C.Structure):
     ]
 
 
+class LogprobArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("V", C.c_int32), ("K", C.c_int32), ("logits_bs", C.c_int64),
+        ("tok_lp", C.c_void_p), ("tok_rank", C.c_void_p), ("top_id", C.c_void_p), ("top_lp", C.c_void_p),
+        ("tok_bs", C.c_int64), ("top_bs", C.c_int64), ("count", C.c_void_p),
+    ]
+
+
 class RopeArgs(C.Structure):
     _fields_ = [
         ("qkv", C.c_void_p), ("ld", C.c_int64), ("S", C.c_int32), ("pos0", C.c_int32), ("Hq", C.c_int32),
@@ -229,7 +239,7 @@ def _selfcheck():
                       ("vb_solver", VbSolverArgs), ("gemv", GemvArgs), ("decode_state", DecodeState),
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
-                      ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args)):
+                      ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

@@ -6,6 +6,7 @@ librosa is absent, so audio loading uses scipy (polyphase resampling to 16 kHz; 
 """
 import argparse
 import re
+import sys
 
 import numpy as np
 import torch
@@ -77,8 +78,9 @@ def _bad(name, *a, **k):
 
 @torch.inference_mode()
 def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, output_path,
-           reference_mel=None, n_timesteps=50):
-    """src/inference.py:48-89."""
+           reference_mel=None, n_timesteps=50, logprobs=None):
+    """src/inference.py:48-89.  logprobs=K (0 .. 20): the LLM also computes per-token log-probabilities (USDMForCausalLM.generate) and the
+    cumulative log-probability of each of the three rounds goes to stderr; nothing else changes."""
     bad_words_ids_unit2text = _bad("u2t", 32000, 42003)
     bad_words_ids_text2text = _bad("t2t", 32002, 42003)
     bad_words_ids_text2unit = _bad("t2u", 0, 32002, exclude=[28705])
@@ -87,17 +89,21 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
     user_wav = load_audio_16k(user_path) if isinstance(user_path, str) else user_path
     user_unit = ''.join([f'<|unit{i}|>' for i in unit_extractor.predict(torch.as_tensor(user_wav, dtype=torch.float32).to(device), 35 - 1).cpu().tolist()])
 
-    def run(model_input, bad, eos):
+    def run(model_input, bad, eos, name):
         ids = torch.LongTensor(tokenizer(model_input).input_ids).to(device).unsqueeze(0)
-        return model.generate(input_ids=ids, max_length=tokenizer.model_max_length, do_sample=True, bad_words_ids=bad,
-                              top_p=1.0, top_k=1, temperature=1.0, eos_token_id=eos)
+        out = model.generate(input_ids=ids, max_length=tokenizer.model_max_length, do_sample=True, bad_words_ids=bad,
+                             top_p=1.0, top_k=1, temperature=1.0, eos_token_id=eos, logprobs=logprobs)
+        lp = model.last_logprobs
+        if lp is not None:
+            print(f"{name}: {lp.token_logprobs.numel()} tokens, cumulative log-probability {lp.cumulative:.4f}", file=sys.stderr)
+        return out
 
-    outputs = run(default_template(user_unit=user_unit), bad_words_ids_unit2text, tokenizer("\n").input_ids[-1])
+    outputs = run(default_template(user_unit=user_unit), bad_words_ids_unit2text, tokenizer("\n").input_ids[-1], "unit-to-text")
     user_text = strip_exact_multiple(tokenizer.decode(outputs[0]).split("<|correspond|>")[-1], ["\n", " "])
     outputs = run(default_template(user_unit=user_unit, user_text=user_text), bad_words_ids_text2text,
-                  tokenizer("<|correspond|>").input_ids[-1])
+                  tokenizer("<|correspond|>").input_ids[-1], "text-to-text")
     agent_text = strip_exact_multiple(tokenizer.decode(outputs[0]).split("\n")[-1], ["\n", " ", "<|correspond|>"])
-    outputs = run(default_template(user_unit=user_unit, user_text=user_text, agent_text=agent_text), bad_words_ids_text2unit, 28705)
+    outputs = run(default_template(user_unit=user_unit, user_text=user_text, agent_text=agent_text), bad_words_ids_text2unit, 28705, "text-to-unit")
     agent_unit = tokenizer.decode(outputs[0]).split("<|correspond|>")[-1]
 
     matches = [int(x) for x in pattern.findall(agent_unit)]
@@ -158,13 +164,16 @@ def main(argv=None):
     parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["bf16", "fp8"],
                         help="KV cache of the LLM: bf16 (default) or fp8 (e4m3 rows, one power-of-two scale per token and kv head; opt-in, "
                              "switches prefix reuse between the three rounds off).")
+    parser.add_argument('--logprobs', type=int, default=None, choices=range(21), metavar="K",
+                        help="Also compute per-token log-probabilities on the device (K = 0 .. 20 most likely ids per token) and print the "
+                             "cumulative log-probability of each of the three LLM rounds to stderr.")
     args = parser.parse_args(argv)
 
     device = torch.device("cuda")
     model, unit_extractor, voicebox, vocoder, tokenizer = load_models(args.model_cache_dir, device, quantization=args.quantization,
                                                                          kv_cache_dtype=args.kv_cache_dtype)
     try:
-        sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path)
+        sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path, logprobs=args.logprobs)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)
         print(f"Error while sampling: {e}")
         return 1

@@ -108,6 +108,51 @@ def stop_index(toks, stops, min_new):
     return next((i + 1 for i, t in enumerate(toks) if t in stops and i + 1 >= min_new), None)
 
 
+def check_logprobs(logprobs):
+    """generate()'s / SamplingParams' logprobs: None (off) or the number K of most likely ids reported per token, 0 .. 20 (vLLM's
+    cap; 0 = the picked token only)."""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= ops.LOGPROBS_MAX_K:
+        raise ValueError(f"logprobs must be None or an integer 0 .. {ops.LOGPROBS_MAX_K}, got {logprobs!r}")
+    return logprobs
+
+
+class TokenLogprobs:
+    """Log-probabilities of one generated sequence of n tokens (host tensors): token_logprobs [n] f32 and ranks [n] i32 of the picked
+    tokens, top_ids [n][K] i32 / top_logprobs [n][K] f32 in descending log-probability (exact ties: lowest id first), cumulative = the
+    float64 sum of token_logprobs.  lp(i) = x_i - logsumexp(x) over the ban-masked logits row the token was picked from: the model's
+    distribution over the allowed ids, before temperature / top-k / top-p (usdm_logprobs)."""
+    __slots__ = ("token_logprobs", "ranks", "top_ids", "top_logprobs", "cumulative")
+
+    def __init__(self, token_logprobs, ranks, top_ids, top_logprobs):
+        self.token_logprobs, self.ranks, self.top_ids, self.top_logprobs = token_logprobs, ranks, top_ids, top_logprobs
+        self.cumulative = float(token_logprobs.double().sum())
+
+    def trimmed(self, n, k):
+        """The first n tokens with the k most likely ids each (a request served inside a group whose step carries a larger K)"""
+        return TokenLogprobs(self.token_logprobs[:n], self.ranks[:n], self.top_ids[:n, :k], self.top_logprobs[:n, :k])
+
+
+def logprob_buffers(device, max_out, B=None):
+    """The four output buffers of usdm_logprobs for one sequence (B=None: plus its rows-written count) or B batch slots, sized for
+    K = 20 so that K never re-allocates; the kernel addresses the top lists as [max_out][K]."""
+    lead = () if B is None else (B,)
+    z = lambda n, dt: torch.zeros(*lead, n, dtype=dt, device=device)
+    bufs = dict(tok_lp=z(max_out, torch.float32), tok_rank=z(max_out, torch.int32), top_id=z(max_out * ops.LOGPROBS_MAX_K, torch.int32),
+                top_lp=z(max_out * ops.LOGPROBS_MAX_K, torch.float32))
+    if B is None:
+        bufs["count"] = torch.zeros(1, dtype=torch.int32, device=device)
+    return bufs
+
+
+def read_logprobs(bufs, n, K, b=None):
+    """Rows 0 .. n-1 of a sequence's log-probability buffers (slot b of a batch's) as a TokenLogprobs on the host."""
+    row = (lambda t: t) if b is None else (lambda t: t[b])
+    top = lambda t: row(t)[:n * K].view(n, K).cpu()
+    return TokenLogprobs(row(bufs["tok_lp"])[:n].cpu(), row(bufs["tok_rank"])[:n].cpu(), top(bufs["top_id"]), top(bufs["top_lp"]))
+
+
 class _Segments:
     """A plan under construction as the list of its segments: launches are added to .plan; cut() ends that plan, with a host call
     to run after it (a collective, the logits hook) or without (the boundary between a peer-to-peer put and its get), and starts
@@ -271,6 +316,8 @@ class USDMForCausalLM:
         self.logits_hook = None   # generate(_logits_hook=f): f() runs between the lm_head launch and the sampling pick of every step
         self.keep_logits = False  # debug/tests: keep the fp32 (bf16-valued) logits of the last step
         self.last_logits = None
+        self._lp = None           # log-probability rows of the single sequence (logprob_buffers; allocated at first use)
+        self.last_logprobs = None  # generate(logprobs=K): TokenLogprobs of the last call (generate_batch: a list); None when not asked
 
     # ------------------------------------------------------------------ weights
     def _shard(self, sd_get):
@@ -495,15 +542,24 @@ class USDMForCausalLM:
         rec.cut()
         launch(2)
 
-    def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None):
+    def _lp_buffers(self):
+        if self._lp is None:
+            self._lp = logprob_buffers(self.device, self.max_out)
+        return self._lp
+
+    def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None, logprobs=None):
         """lm_head GEMV + token choice, for the single sequence (slot=None), a batch slot's prefill, and the batched step
         (slot = the batch's "all" view, batch_gemv = its projection launcher).  sampling=None: ban-masked arg-max (the reference's
         top_k=1 path); sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block sample_params
         (written per request by generate(): plans and graphs do not depend on temperature / top-k / top-p / seed).
         Under tensor parallelism the ranks' arg-max partials, or (sampled) their Vloc ban-masked logits, are gathered first - in the
         kernels on a peer-to-peer model, else through the group; the sampler then runs unchanged over the full row on every rank with
-        the same seed and step: every rank draws the same token."""
+        the same seed and step: every rank draws the same token.
+        logprobs=K (sampled picks only): usdm_logprobs right after the pick, on the row it drew from (after the hook: as the hook left
+        it; tensor parallel: the gathered row, on every rank), into the sequence's / the slots' log-probability buffers."""
         c, H = self.cfg, self.cfg["hidden_size"]
+        if logprobs is not None and not sampling:
+            raise ValueError("log-probabilities need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
         sl = slot or self   # where the picked token, the decode state and the next input row live (self = the single sequence)
         single = sl is self
         B = 0 if single else sl.batch
@@ -530,6 +586,7 @@ class USDMForCausalLM:
         st = ops.decode_state(sl.st_next, sl.st_out, sl.st_step, sl.st_pos, advance_pos=advance_pos, batch=B, done=sl.st_done, eos=sl.st_eos)
         # the picked token's embedding row is written straight into the decode step's input vector
         out = dict(embed=self.W["embed"], h_out=sl.h_dec, Hd=H)
+        lp = None if logprobs is None else dict(self._lp_buffers() if single else sl.lp, K=logprobs)      # (the plan is named at the launch: rec.cut() below starts a new one)
         if tp_sampled:
             row = sl.logits_row     # a batch: [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
             if p2p is not None:
@@ -539,10 +596,14 @@ class USDMForCausalLM:
                 rec.cut(lambda: self._gather_partials([row], [logits]))
             seg = dict(nseg=self.tp_size, seg_stride=B * self.Vloc, seg_len=self.Vloc) if B else {}
             ops.sample_final(row, st, V=c["vocab_size"], dev_params=sl.sample_params, plan=rec.plan, **seg, **out)
+            if lp:
+                ops.logprobs(row, st, V=c["vocab_size"], plan=rec.plan, **seg, **lp)
         elif sampling:
             if sampling == "hook":      # Python logits processors (usdm_amd.serving): a host call between the two kernels
                 rec.cut(lambda: self.logits_hook())
             ops.sample_final(logits, st, dev_params=sl.sample_params, plan=rec.plan, **out)
+            if lp:
+                ops.logprobs(logits, st, V=self.v1 - self.v0, plan=rec.plan, **lp)
         elif p2p is not None:
             # vocab-parallel pick across ranks in ONE launch (pairs exchanged peer to peer; advances the exchange epoch)
             site = 2 * c["num_hidden_layers"]
@@ -616,7 +677,7 @@ class USDMForCausalLM:
             land(w["down"], act, I, 2 * l + 1, **down_kw)
         return h, pend
 
-    def _build_prefill(self, S, sampling=None, slot=None, past=0):
+    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None):
         """Prefill of S new tokens at positions past .. past+S-1 (past > 0: the KV cache already holds the first `past`
         tokens of the same sequence; only the single-sequence cache keeps the V^T that makes this possible)."""
         dev, bf = self.device, torch.bfloat16
@@ -658,7 +719,7 @@ class USDMForCausalLM:
                           o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=rec.plan)
 
         self._layers(rec, gemm, attn, h, qkv, ao, act, "reduce" if self.tp_path else "fused", n=S * H, parts=(part, part))
-        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot)
+        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs)
         return rec.finish(), io
 
     def _build_decode_p2p(self, sampling=None):
@@ -667,7 +728,7 @@ class USDMForCausalLM:
             raise ValueError("_build_decode_p2p needs a model with a P2PComm")
         return self._build_decode(sampling)
 
-    def _build_decode(self, sampling=None):
+    def _build_decode(self, sampling=None, logprobs=None):
         """One decode step of the single sequence.  Tensor parallel with a P2PComm: the launch sequence of the single-GPU step over
         this rank's shards, o_proj / down_proj carry the exchange (_layers, way "p2p"); returned as segments cut at every exchange,
         which a real rank runs back to back inside one hipGraph."""
@@ -729,7 +790,7 @@ class USDMForCausalLM:
         if chain:     # the last layer's chain has no next qkv to wait for
             flush()
         # (pend: the last down-projection's sum goes into the final norm + lm_head)
-        self._lm_head_and_pick(rec, h, True, sampling, x_delta=pend, skip=skp)
+        self._lm_head_and_pick(rec, h, True, sampling, x_delta=pend, skip=skp, logprobs=logprobs)
         return rec.finish()
 
     @staticmethod
@@ -811,7 +872,18 @@ class USDMForCausalLM:
         self._batches[B] = bb
         return bb
 
-    def _build_decode_batch(self, B, sampling=False):
+    def _batch_lp(self, B):
+        """The slots' log-probability buffers, next to bb["out"] (allocated at first use); no rows-written count: batch slots have
+        no device-side `done` word, every step writes its row and the host ignores rows past a request's end."""
+        bb = self._batch_buffers(B)
+        if "lp" not in bb:
+            bb["lp"] = bb["all"].lp = logprob_buffers(self.device, self.max_out, B)
+            for b, sl in enumerate(bb["slots"]):
+                sl.lp = {k: v[b] for k, v in bb["lp"].items()}
+            bb["decode_lp"] = {}
+        return bb["lp"]
+
+    def _build_decode_batch(self, B, sampling=False, logprobs=None):
         """One decode step of B sequences: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
         sampling: the pick is usdm_sample_final's batched form - every slot draws with its OWN knobs (bb["sp"][b]: temperature,
         top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1."""
@@ -856,7 +928,7 @@ class USDMForCausalLM:
                             counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=rec.plan)
 
         self._layers(rec, gemv, attn, h, qkv, ao, act, "reduce" if tp else "fused", n=B * H, parts=parts, down_kw={} if tp else dict(ks=ks))
-        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv)
+        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs)
         segs = rec.finish()
         return segs if tp else segs[0]
 
@@ -879,37 +951,51 @@ class USDMForCausalLM:
         return self.MAX_BATCH if all(k % 256 == 0 for k in ks) else 4
 
     @torch.no_grad()
-    def generate_batch(self, input_ids_list, max_new_tokens, bad_words_ids=None, eos_token_id=None, min_new_tokens=0, group=None):
+    def generate_batch(self, input_ids_list, max_new_tokens, bad_words_ids=None, eos_token_id=None, min_new_tokens=0, group=None,
+                       logprobs=None):
         """Greedy generation of several utterances in lockstep (the serving-side batching of inference_vllm.py:109-125): up to
         `group` (default 16) sequences per step, longer lists run in groups.  Each prompt is prefilled on its own; every decode
         step then streams the weights once for the whole group.  Groups of <= 4 run on the VALU kernel and equal generate() per
         sequence bit for bit; larger groups run on the matrix cores (usdm_gemv_batch form 1): the same rounding points, K summed
-        in another order - equal to the oracle up to its near-ties, not bit-identical with generate()."""
+        in another order - equal to the oracle up to its near-ties, not bit-identical with generate().
+        logprobs=K (0 .. 20): self.last_logprobs is then the list of the sequences' TokenLogprobs (see generate())."""
+        lpk = check_logprobs(logprobs)
         group = self.max_batch() if group is None else max(1, min(int(group), self.max_batch()))
-        outs = []
+        outs, self.last_logprobs = [], (None if lpk is None else [])
         for g0 in range(0, len(input_ids_list), group):
-            outs += self._generate_group(input_ids_list[g0:g0 + group], max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens)
+            outs += self._generate_group(input_ids_list[g0:g0 + group], max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, lpk)
         return outs
 
-    def _batch_step(self, B, sampling=False):
-        """The replayable decode step of the B slots, greedy or sampled (built at first use)."""
+    def _batch_step(self, B, sampling=False, logprobs=None):
+        """The replayable decode step of the B slots, greedy or sampled (built at first use); logprobs=K: the sampled step followed by
+        usdm_logprobs, a plan of its own per K."""
         bb = self._batch_buffers(B)
+        if logprobs is not None:
+            self._batch_lp(B)
+            if logprobs not in bb["decode_lp"]:
+                bb["decode_lp"][logprobs] = self._graphed(self._build_decode_batch(B, sampling=True, logprobs=logprobs))
+            return bb["decode_lp"][logprobs]
         key = "decode_sampled" if sampling else "decode"
         if bb[key] is None:
             bb[key] = self._graphed(self._build_decode_batch(B, sampling=sampling))
         return bb[key]
 
-    def _admit(self, B, b, ids, sampling=False):
+    def _admit(self, B, b, ids, sampling=False, logprobs=None):
         """Admit a prompt (ids [L]) into slot b of the B slots: its step / position counters, then the per-item prefill into the
-        slot's cache, which also picks the first token (sampled too when the batch runs on the sampling step)."""
+        slot's cache, which also picks the first token (sampled too when the batch runs on the sampling step; logprobs=K: with row 0
+        of the slot's log-probabilities)."""
         bb, L = self._batch_buffers(B), int(ids.shape[0])
         bb["step"][b] = 0
         bb["pos"][b] = L
-        segs, io = bb["prefill"].get_or_build((L, b, sampling), lambda: self._build_prefill(L, True if sampling else None, slot=bb["slots"][b]))
+        if logprobs is not None:
+            self._batch_lp(B)
+            sampling = True
+        key = (L, b, sampling) if logprobs is None else (L, b, sampling, logprobs)
+        segs, io = bb["prefill"].get_or_build(key, lambda: self._build_prefill(L, True if sampling else None, slot=bb["slots"][b], logprobs=logprobs))
         io["ids"].copy_(ids)
         self._run_segs(segs)
 
-    def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens):
+    def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None):
         B = len(ids_list)
         for ids in ids_list:
             if ids.dim() != 2 or ids.shape[0] != 1:
@@ -919,10 +1005,14 @@ class USDMForCausalLM:
         L0 = [int(ids.shape[1]) for ids in ids_list]
         max_new = min(max_new_tokens, self.ctx_max - max(L0), self.max_out)
         if max_new <= 0:
+            if logprobs is not None:
+                self.last_logprobs += [None] * B
             return [ids.clone() for ids in ids_list]
         for b, ids in enumerate(ids_list):
-            self._admit(B, b, ids[0])
-        decode = self._batch_step(B)
+            if logprobs is not None:      # greedy on the sampling step: top_k = 1 (the arg-max path has no logits row)
+                ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
+            self._admit(B, b, ids[0], logprobs=logprobs)
+        decode = self._batch_step(B, logprobs=logprobs)
         eos = stop_ids(eos_token_id)
         produced, chunk = 1, 8
         ends = [None] * B
@@ -941,6 +1031,8 @@ class USDMForCausalLM:
         for b, ids in enumerate(ids_list):
             n = ends[b] if ends[b] is not None else min(produced, max_new)
             res.append(torch.cat([ids[0], torch.tensor(toks[b][:n], dtype=torch.long, device=ids.device)]).unsqueeze(0))
+            if logprobs is not None:
+                self.last_logprobs.append(read_logprobs(bb["lp"], n, logprobs, b))
         return res
 
     # ------------------------------------------------------------------ generate
@@ -960,7 +1052,7 @@ class USDMForCausalLM:
         self._ban_cache.put(key, (bad_words_ids, t))
         return t
 
-    def _setup_call(self, input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=None):
+    def _setup_call(self, input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=None, logprobs=None):
         """Per-call device state of generate(): prompt ids into the (cached) prefill plan, ban mask, position / step counters,
         device-side EOS list.  Returns (prefill segments, the EOS ids the device checks)."""
         L0 = input_ids.shape[1]
@@ -969,8 +1061,10 @@ class USDMForCausalLM:
                 self._shard_logits, self.last_logits = self.last_logits, self.logits_row
             elif not sampling and self.last_logits is self.logits_row:
                 self.last_logits = self._shard_logits
-        key = (L0 - past, past, sampling)
-        segs, io = self._prefill_plans.get_or_build(key, lambda: self._build_prefill(L0 - past, sampling, past=past))
+        key = (L0 - past, past, sampling) if logprobs is None else (L0 - past, past, sampling, logprobs)
+        segs, io = self._prefill_plans.get_or_build(key, lambda: self._build_prefill(L0 - past, sampling, past=past, logprobs=logprobs))
+        if logprobs is not None:
+            self._lp_buffers()["count"].zero_()      # rows written so far (usdm_logprobs keys its write on it: the device-side EOS)
         io["ids"].copy_(input_ids[0, past:])
         self._kv_ids, self._vt_upto = None, L0      # (set again once this call's decode steps are known)
         if ban_mask is not None:      # a ready-made [vocab] 0/1 mask (usdm_amd.serving: static logits processors)
@@ -988,11 +1082,16 @@ class USDMForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids=None, max_length=None, do_sample=False, bad_words_ids=None, top_p=1.0, top_k=None,
                  temperature=1.0, eos_token_id=None, max_new_tokens=None, min_new_tokens=0, seed=None, ban_mask=None,
-                 _logits_hook=None, **unused):
+                 _logits_hook=None, logprobs=None, **unused):
         """Generation with the call shape of src/inference.py:63-83.  Greedy when do_sample is False or top_k == 1 (what the
         reference passes: arg-max of the ban-masked logits).  Otherwise temperature / top-k / top-p sampling on the device
         (usdm_sample_final).  `seed` keys its Philox stream; seed=None draws a fresh one from torch's global CPU generator,
-        so calls differ from each other as HF sampling does and are reproducible under torch.manual_seed."""
+        so calls differ from each other as HF sampling does and are reproducible under torch.manual_seed.
+        logprobs=K (0 .. 20; None = off): self.last_logprobs is then the TokenLogprobs of the returned tokens, the first one (picked by
+        the prefill) included - computed on the device inside the step (usdm_logprobs), before temperature / top-k / top-p.  A greedy
+        call then runs on the sampling step with top_k = 1 (the arg-max path never materialises a logits row); its ids are the same."""
+        lpk = check_logprobs(logprobs)
+        self.last_logprobs = None
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1, as the reference calls it)")
         sampling = False
@@ -1009,9 +1108,12 @@ class USDMForCausalLM:
                 seed = self._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
             sampling = True
             ops.set_sample_params(self.sample_params, temperature, int(top_k or 0), top_p, seed)
-        elif temperature != 1.0 or top_p != 1.0:
-            if not do_sample:
+        else:
+            if (temperature != 1.0 or top_p != 1.0) and not do_sample:
                 raise ValueError("temperature / top_p only apply with do_sample=True")
+            if lpk is not None:
+                sampling = True
+                ops.set_sample_params(self.sample_params, 1.0, 1, 1.0, 0)
         L0 = input_ids.shape[1]
         if max_new_tokens is None:
             if max_length is None:
@@ -1035,11 +1137,13 @@ class USDMForCausalLM:
             if past > self._vt_upto:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers
                 a0 = self._vt_upto
                 self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
-        segs, dev_eos = self._setup_call(input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask)
+        segs, dev_eos = self._setup_call(input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,
+                                          logprobs=lpk)
         self._run_segs(segs)  # prefill + first token
-        if sampling not in self._decodes:      # (the hooked step has host code inside: never captured)
-            self._decodes[sampling] = self._graphed(self._build_decode(sampling), enabled=False if sampling == "hook" else None)
-        self._decode = self._decodes[sampling]
+        dkey = sampling if lpk is None else (sampling, lpk)      # the step with log-probabilities: a plan / graph of its own per K
+        if dkey not in self._decodes:      # (the hooked step has host code inside: never captured)
+            self._decodes[dkey] = self._graphed(self._build_decode(sampling, logprobs=lpk), enabled=False if sampling == "hook" else None)
+        self._decode = self._decodes[dkey]
         eos = stop_ids(eos_token_id)
         produced, done, chunk = 1, False, 8
         toks = []
@@ -1069,5 +1173,7 @@ class USDMForCausalLM:
         if self.reuse_prefix:   # ids whose K/V now sit in the cache: the prompt and every generated token that was fed back
             fed = self.st_out[:produced - 1].tolist() if produced > 1 else []
             self._kv_ids = ids_host + fed
+        if lpk is not None:
+            self.last_logprobs = read_logprobs(self._lp, len(toks), lpk)
         out = torch.cat([input_ids[0], torch.tensor(toks, dtype=torch.long, device=input_ids.device)])
         return out.unsqueeze(0)

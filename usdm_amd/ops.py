@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogprobArgs, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -393,6 +393,45 @@ def sample_final(logits, st, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, pro
         raise ValueError("sample_final: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
     a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
     _go(plan, "usdm_sample_final", lib.usdm_sample_final, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
+
+
+LOGPROBS_MAX_K = 20     # vLLM's cap on SamplingParams.logprobs
+
+
+def logprobs(logits, st, *, K, tok_lp, tok_rank, top_id=None, top_lp=None, count=None, V=None, nseg=1, seg_stride=0, seg_len=0, plan=None):
+    """usdm_logprobs, launched after the sample_final of the same step on the same row: log-probability and rank of the token that
+    was just picked into tok_lp / tok_rank [max_out] at row step - 1, and (K > 0) the K most likely ids and their log-probabilities
+    into top_id / top_lp, which the kernel addresses as [max_out][K].  Batched state: every output is [B][...] with its dim-0 stride.
+    count (int32 [B]): rows written so far, required with a device-side `done` word (see include/usdm_hip.h).
+    V / nseg / seg_stride / seg_len as in sample_final (usdm_logprobs_seg)."""
+    _need_cuda(logits, tok_lp, tok_rank, top_id, top_lp, count)
+    B = max(1, st.batch)
+    a = LogprobArgs()
+    a.logits, a.V, a.K = _ptr(logits), logits.shape[-1] if V is None else V, int(K)
+    a.tok_lp, a.tok_rank, a.top_id, a.top_lp, a.count = _ptr(tok_lp), _ptr(tok_rank), _ptr(top_id), _ptr(top_lp), _ptr(count)
+    for name, t, dt, per in (("tok_lp", tok_lp, torch.float32, 1), ("tok_rank", tok_rank, torch.int32, 1),
+                             ("top_id", top_id, torch.int32, a.K), ("top_lp", top_lp, torch.float32, a.K)):
+        if t is None or not 0 <= a.K <= LOGPROBS_MAX_K:
+            continue      # (the library refuses a missing output and K outside 0 .. 20)
+        rows = t if B == 1 else t[0]
+        if t.dtype != dt or not rows.is_contiguous() or rows.numel() < st.max_out * per or (B > 1 and (t.shape[0] < B or t.stride(0) < st.max_out * per)):
+            raise ValueError(f"logprobs: {name} must be {dt} with room for [max_out = {st.max_out}][{per}] values per sequence")
+    if count is not None and (count.dtype != torch.int32 or count.numel() < B):
+        raise ValueError("logprobs: count must be int32 [batch]")
+    a.tok_bs = tok_lp.stride(0) if (B > 1 and tok_lp is not None) else 0
+    a.top_bs = top_id.stride(0) if (B > 1 and top_id is not None) else 0
+    if B > 1 and (tok_rank is not None and tok_rank.stride(0) != a.tok_bs or top_lp is not None and top_lp.stride(0) != a.top_bs):
+        raise ValueError("logprobs: tok_lp / tok_rank and top_id / top_lp must share their per-sequence strides")
+    if seg_len > 0:
+        if nseg < 1 or not logits.is_contiguous() or logits.shape[-1] != seg_len or logits.numel() < (nseg - 1) * seg_stride + B * seg_len:
+            raise ValueError("segmented logprobs: logits must be a contiguous [nseg][B][seg_len] tensor")
+        a.logits_bs = seg_len
+        _go(plan, "usdm_logprobs_seg", lib.usdm_logprobs_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len), C_.byref(st))
+        return
+    if logits.dim() > 2 or a.V > logits.shape[-1]:
+        raise ValueError("logprobs: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
+    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
+    _go(plan, "usdm_logprobs", lib.usdm_logprobs, C_.byref(a), C_.byref(st))
 
 
 def logits_p2p(logits, Vloc, st, p2p, site0, row_out, phase=0, plan=None):

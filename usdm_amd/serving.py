@@ -19,7 +19,11 @@ How requests are executed
     shards) and draws from it with the same seed and step, so every rank picks the same token; a seed left to the server is
     rank 0's draw on every rank.  Processors that depend on the history are not supported there (they would see one shard);
   * processors that really depend on the token history run as Python between the lm_head launch and the pick of every step
-    (eager launches: correct, not fast).
+    (eager launches: correct, not fast);
+  * SamplingParams(logprobs=K), K = 0 .. 20: per-token log-probabilities computed on the device inside the step (usdm_logprobs, right
+    after the pick, on the row it drew from): lp(i) = x_i - logsumexp(x) over the ban-masked logits, i.e. the model's distribution
+    over the allowed ids BEFORE temperature / top-k / top-p.  One asking request puts its whole group on the log-probability step
+    (K = the group's maximum, trimmed per request on the host); a greedy request then runs on the sampling step with top_k = 1.
 """
 import os
 from collections import deque
@@ -27,7 +31,7 @@ from collections import deque
 import torch
 
 from . import ops
-from .llm import USDMForCausalLM, check_quantization, stop_index
+from .llm import USDMForCausalLM, check_logprobs, check_quantization, read_logprobs, stop_index
 from .quant import check_kv_cache_dtype
 
 MAX_SLOTS = 16      # usdm_gemv_batch streams the weights once per step for up to 16 sequences (matrix-core form above 4)
@@ -39,7 +43,8 @@ class SamplingParams:
     """The subset of vllm.SamplingParams the reference and its demo use (inference_vllm.py:109-123)."""
 
     def __init__(self, n=1, temperature=1.0, top_p=1.0, top_k=-1, max_tokens=16, min_tokens=0, stop_token_ids=None,
-                 logits_processors=None, seed=None, skip_special_tokens=True, ignore_eos=False, static_logits_mask=None, **unused):
+                 logits_processors=None, seed=None, skip_special_tokens=True, ignore_eos=False, static_logits_mask=None, logprobs=None,
+                 prompt_logprobs=None, **unused):
         if not isinstance(n, int) or n < 1:
             raise ValueError("n must be a positive integer")
         if temperature < 0 or not (0 < top_p <= 1) or (top_k < -1 or top_k == 0):
@@ -50,6 +55,11 @@ class SamplingParams:
         self.logits_processors = list(logits_processors or [])
         self.seed, self.skip_special_tokens, self.ignore_eos = seed, skip_special_tokens, ignore_eos
         self.static_logits_mask = static_logits_mask      # None: probe the processors; True / False: caller's word
+        # logprobs (vllm's name): None, or the number of most likely ids reported per generated token next to the picked one, 0 .. 20
+        self.logprobs = check_logprobs(logprobs)
+        if prompt_logprobs is not None:
+            raise NotImplementedError("prompt_logprobs is not supported (it needs the lm_head over every prompt row); logprobs= covers "
+                                      "the generated tokens")
         if self.n > 1 and self.greedy:
             raise ValueError("n must be 1 when using greedy sampling (the n completions would be identical)")   # as vllm
 
@@ -58,10 +68,45 @@ class SamplingParams:
         return self.temperature == 0.0 or self.top_k == 1
 
 
+class Logprob:
+    """vllm.sequence.Logprob: log-probability, rank (1 = most likely) and text of one candidate token."""
+    __slots__ = ("logprob", "rank", "decoded_token")
+
+    def __init__(self, logprob, rank=None, decoded_token=None):
+        self.logprob, self.rank, self.decoded_token = logprob, rank, decoded_token
+
+    def __eq__(self, other):
+        return isinstance(other, Logprob) and (self.logprob, self.rank, self.decoded_token) == (other.logprob, other.rank, other.decoded_token)
+
+    def __repr__(self):
+        return f"Logprob(logprob={self.logprob}, rank={self.rank}, decoded_token={self.decoded_token!r})"
+
+
+def assemble_logprobs(token_ids, tok_lp, tok_rank, top_id, top_lp, k, tokenizer=None):
+    """vLLM's CompletionOutput.logprobs / .cumulative_logprob from the device's rows (sequences or tensors; top_id / top_lp are [n][>= k]
+    in descending log-probability, id -1 = padding): per generated token a dict {token_id: Logprob} holding the picked token and the k
+    most likely ones - k entries when the pick is among them, else k + 1 - and the float64 sum of the picked tokens' log-probabilities.
+    Entry j of the top list has rank j + 1 (its position; among exactly tied logits that is the lowest-id-first order, while the
+    picked token carries vLLM's rank: 1 + the number of strictly greater logits)."""
+    lst = lambda t: t.tolist() if hasattr(t, "tolist") else list(t)
+    tok_lp, tok_rank, top_id, top_lp = lst(tok_lp), lst(tok_rank), lst(top_id), lst(top_lp)
+    text = (lambda i: tokenizer.decode([i])) if tokenizer is not None else (lambda i: None)
+    out, total = [], 0.0
+    for t, tok in enumerate(token_ids):
+        d = {int(tok): Logprob(float(tok_lp[t]), int(tok_rank[t]), text(int(tok)))}
+        for j in range(k):
+            i = int(top_id[t][j])
+            if i >= 0 and i != tok:
+                d[i] = Logprob(float(top_lp[t][j]), j + 1, text(i))
+        out.append(d)
+        total += float(tok_lp[t])
+    return out, total
+
+
 class CompletionOutput:
-    def __init__(self, index, text, token_ids, finish_reason, stop_reason=None):
+    def __init__(self, index, text, token_ids, finish_reason, stop_reason=None, cumulative_logprob=None, logprobs=None):
         self.index, self.text, self.token_ids, self.finish_reason, self.stop_reason = index, text, token_ids, finish_reason, stop_reason
-        self.cumulative_logprob, self.logprobs = None, None
+        self.cumulative_logprob, self.logprobs = cumulative_logprob, logprobs
 
     def __repr__(self):
         return f"CompletionOutput(index={self.index}, text={self.text!r}, token_ids={self.token_ids}, finish_reason={self.finish_reason})"
@@ -207,8 +252,8 @@ class LLM:
                 groups.setdefault(bytes(r["mask"].cpu().numpy().tobytes()), []).append(r)
         for grp in groups.values():
             if len(grp) >= 2:
-                for r, toks, why in self._run_batched(grp):
-                    done[r["i"]] = (toks, why)
+                for r, toks, why, lp in self._run_batched(grp):
+                    done[r["i"]] = (toks, why, lp)
         for r in reqs:
             if r["i"] not in done:
                 done[r["i"]] = self._run_single(r)
@@ -223,9 +268,10 @@ class LLM:
     def _run_single(self, r):
         sp, llm = r["sp"], self.llm
         if r["max_new"] <= 0:
-            return [], "length"
+            return [], "length", None
         ids = torch.tensor([r["ids"]], dtype=torch.long, device=llm.device)
-        kw = dict(input_ids=ids, max_new_tokens=r["max_new"], eos_token_id=sorted(r["stops"]) or None, min_new_tokens=sp.min_tokens)
+        kw = dict(input_ids=ids, max_new_tokens=r["max_new"], eos_token_id=sorted(r["stops"]) or None, min_new_tokens=sp.min_tokens,
+                  logprobs=sp.logprobs)
         sampled = not sp.greedy
         if sampled:
             kw.update(do_sample=True, temperature=sp.temperature, top_p=sp.top_p, top_k=(sp.top_k if sp.top_k > 0 else None), seed=r["seed"])
@@ -248,15 +294,19 @@ class LLM:
             out = llm.generate(_logits_hook=hook, **kw)
         toks = out[0, len(r["ids"]):].tolist()
         why = "stop" if (toks and toks[-1] in r["stops"] and len(toks) >= sp.min_tokens) else "length"
-        return toks, why
+        return toks, why, llm.last_logprobs
 
     # ------------------------------------------------------------------ continuous batching over the decode slots
     def _run_batched(self, grp):
         llm = self.llm
         nslots = min(self.max_slots, llm.max_batch(), SMALL_SLOTS if len(grp) <= SMALL_SLOTS else MAX_SLOTS)
         bb = llm._batch_buffers(nslots)
-        sampled = any(not r["sp"].greedy for r in grp)       # one sampled request -> the whole group runs on the sampling graph
-        decode = llm._batch_step(nslots, sampling=sampled)
+        # one request with log-probabilities -> the whole group runs on the log-probability step (the sampling step + usdm_logprobs),
+        # with the group's largest K; every request's rows are trimmed to its own K on the host
+        ks = [r["sp"].logprobs for r in grp if r["sp"].logprobs is not None]
+        lpk = max(ks) if ks else None
+        sampled = lpk is not None or any(not r["sp"].greedy for r in grp)       # one sampled request -> the whole group runs on the sampling graph
+        decode = llm._batch_step(nslots, sampling=sampled, logprobs=lpk)
         self.stats["sampled_in_batch"] = self.stats.get("sampled_in_batch", 0) + sum(not r["sp"].greedy for r in grp)
         for b in range(nslots):                               # idle slots: harmless greedy knobs
             ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
@@ -272,7 +322,7 @@ class LLM:
                         ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
                     else:
                         ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"])
-                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), sampling=sampled)      # (+ first token)
+                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), sampling=sampled, logprobs=lpk)      # (+ first token)
                     slots[b] = dict(r=r, produced=1)
                     self.stats["admissions"] += 1
             active = [b for b in range(nslots) if slots[b] is not None]
@@ -290,7 +340,11 @@ class LLM:
                 end = stop_index(seq, r["stops"], r["sp"].min_tokens)
                 if end is not None or s["produced"] >= r["max_new"]:
                     n = end if end is not None else r["max_new"]
-                    results.append((r, seq[:n], "stop" if end is not None and end <= n else "length"))
+                    # the slot's rows are read HERE, before a refill restarts its step at 0 and overwrites them; rows decoded past
+                    # the stop, up to the end of the chunk, are dropped with their tokens
+                    k = r["sp"].logprobs
+                    lp = read_logprobs(bb["lp"], len(seq[:n]), lpk, b).trimmed(len(seq[:n]), k) if k is not None else None
+                    results.append((r, seq[:n], "stop" if end is not None and end <= n else "length", lp))
                     slots[b] = None
                     freed = True
                 else:
@@ -311,9 +365,15 @@ class LLM:
         return results
 
     # ------------------------------------------------------------------ detokenise
-    def _finish(self, r, toks, why):
+    def _finish(self, r, toks, why, lp=None):
         text = ""
         if self.tokenizer is not None:
             text = self.tokenizer.decode(toks, skip_special_tokens=r["sp"].skip_special_tokens)
         stop_reason = toks[-1] if (why == "stop" and toks) else None
-        return CompletionOutput(r["i"][1], text, toks, why, stop_reason)
+        k = r["sp"].logprobs
+        if k is None:
+            return CompletionOutput(r["i"][1], text, toks, why, stop_reason)
+        if lp is None:      # (no room for a single token)
+            return CompletionOutput(r["i"][1], text, toks, why, stop_reason, 0.0, [])
+        lps, total = assemble_logprobs(toks, lp.token_logprobs, lp.ranks, lp.top_ids, lp.top_logprobs, k, self.tokenizer)
+        return CompletionOutput(r["i"][1], text, toks, why, stop_reason, total, lps)
