@@ -465,6 +465,41 @@ int usdm_logprobs_seg(const usdm_logprob_args* args, int32_t nseg, int64_t seg_s
                       usdm_stream_t stream);
 int usdm_sizeof_logprob_args(void);
 
+/* Repetition / frequency / presence penalties of the step whose token usdm_sample_final is ABOUT to pick, applied in place to the
+ * ban-masked f32 row it will read (before a host logits hook, which sees the penalised row).  State per sequence: table[V], one
+ * int32 per id: c(i) = how often id i was generated so far in this call in bits 0 .. 29, in_prompt(i) in bit 30 (the caller zeroes
+ * the table per request and sets bit 30 of every prompt id).  One launch
+ *   1. counts the token picked by the previous step, out_tokens[*st->step - 1] - st->id_offset, when *st->step >= 1;
+ *   2. rewrites x of every id i < V, each line one f32 operation (no contraction):
+ *        seen = in_prompt(i) or c(i) > 0
+ *        x = seen ? (x < 0 ? x * r : x / r) : x       repetition (HF RepetitionPenaltyLogitsProcessor; vLLM: prompt + output)
+ *        x = x - (f * float(c(i)))                    frequency  (vLLM: output tokens only)
+ *        x = x - (p * (c(i) > 0 ? 1.0f : 0.0f))       presence   (vLLM: output tokens only)
+ *      -inf stays -inf, NaN stays NaN.  With the neutral knobs r = 1, f = 0, p = 0 the row is not touched (the token is still counted).
+ * The knobs are a DEVICE block, one per sequence, rewritten by the host per request: plans and graphs never depend on the values.
+ * Ranges (vLLM): r in (0, 2], f and p in [-2, 2]; usdm_penalty_params_init fills a host block and refuses anything else, NaN
+ * included.  (A device block outside the ranges, such as a zero-filled one, is taken as neutral.)
+ * count [batch] (device, *st->step at the last counting; the caller zeroes it with st->step): a token is counted only while
+ * count[b] < *st->step, and count[b] = *st->step afterwards, so a replay at the same step counts nothing.  REQUIRED with a device-side
+ * st->done, and the launch then returns at once when done[b] != 0.  NULL: every launch with *st->step >= 1 counts.
+ * At every pick c is exactly the histogram of out_tokens[0 .. *st->step - 1]. */
+typedef struct usdm_penalty_params { float repetition, frequency, presence; int32_t reserved; } usdm_penalty_params;
+typedef struct usdm_penalty_args {
+  float* logits; int32_t V;
+  int64_t logits_bs;        /* batched (st->batch > 1): sequence b's row is logits + b * logits_bs */
+  int32_t* table;
+  int64_t table_bs;         /* batched: sequence b's table is table + b * table_bs (>= V) */
+  const usdm_penalty_params* dev_params;   /* [batch], 16-byte aligned */
+  int32_t* count;
+} usdm_penalty_args;
+int usdm_penalize(const usdm_penalty_args* args, const usdm_decode_state* st, usdm_stream_t stream);
+/* The same over a row of nseg segments, addressed as usdm_sample_final_seg addresses it (ids >= V never read or written). */
+int usdm_penalize_seg(const usdm_penalty_args* args, int32_t nseg, int64_t seg_stride, int32_t seg_len, const usdm_decode_state* st,
+                      usdm_stream_t stream);
+int usdm_penalty_params_init(usdm_penalty_params* out, float repetition, float frequency, float presence);
+int usdm_sizeof_penalty_args(void);
+int usdm_sizeof_penalty_params(void);
+
 /* out[r][:] = table[ids[r]][:] (bf16 rows; ids == NULL -> single row from *next_token) */
 int usdm_embed_rows(const void* table, const int64_t* ids, const int32_t* next_token, int32_t n, int32_t Hd,
                     void* out, usdm_stream_t stream);

@@ -28,6 +28,9 @@ lib.usdm_gemv_mxfp4.restype = C.c_int        # (the MXFP4 entry points: likewise
 lib.usdm_dequant_mxfp4.restype = C.c_int
 lib.usdm_logprobs.restype = C.c_int          # (the log-probability entry points: likewise)
 lib.usdm_logprobs_seg.restype = C.c_int
+lib.usdm_penalize.restype = C.c_int          # (the penalty entry points: likewise)
+lib.usdm_penalize_seg.restype = C.c_int
+lib.usdm_penalty_params_init.restype = C.c_int
 _exp = None
 
 
@@ -196,6 +199,17 @@ class LogprobArgs(C.Structure):
     ]
 
 
+class PenaltyParams(C.Structure):
+    _fields_ = [("repetition", C.c_float), ("frequency", C.c_float), ("presence", C.c_float), ("reserved", C.c_int32)]
+
+
+class PenaltyArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("V", C.c_int32), ("logits_bs", C.c_int64), ("table", C.c_void_p), ("table_bs", C.c_int64),
+        ("dev_params", C.c_void_p), ("count", C.c_void_p),
+    ]
+
+
 class RopeArgs(C.Structure):
     _fields_ = [
         ("qkv", C.c_void_p), ("ld", C.c_int64), ("S", C.c_int32), ("pos0", C.c_int32), ("Hq", C.c_int32),
@@ -239,10 +253,13 @@ def _selfcheck():
                       ("vb_solver", VbSolverArgs), ("gemv", GemvArgs), ("decode_state", DecodeState),
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
-                      ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs)):
+                      ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
+                      ("penalty", PenaltyArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")
+    if lib.usdm_sizeof_penalty_params() != C.sizeof(PenaltyParams):
+        raise ImportError("ABI mismatch: usdm_penalty_params")
 
 
 _selfcheck()

@@ -78,9 +78,10 @@ def _bad(name, *a, **k):
 
 @torch.inference_mode()
 def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, output_path,
-           reference_mel=None, n_timesteps=50, logprobs=None):
+           reference_mel=None, n_timesteps=50, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
     """src/inference.py:48-89.  logprobs=K (0 .. 20): the LLM also computes per-token log-probabilities (USDMForCausalLM.generate) and the
-    cumulative log-probability of each of the three rounds goes to stderr; nothing else changes."""
+    cumulative log-probability of each of the three rounds goes to stderr; nothing else changes.
+    repetition_penalty / presence_penalty / frequency_penalty: passed to all three rounds (USDMForCausalLM.generate; on the device)."""
     bad_words_ids_unit2text = _bad("u2t", 32000, 42003)
     bad_words_ids_text2text = _bad("t2t", 32002, 42003)
     bad_words_ids_text2unit = _bad("t2u", 0, 32002, exclude=[28705])
@@ -92,7 +93,8 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
     def run(model_input, bad, eos, name):
         ids = torch.LongTensor(tokenizer(model_input).input_ids).to(device).unsqueeze(0)
         out = model.generate(input_ids=ids, max_length=tokenizer.model_max_length, do_sample=True, bad_words_ids=bad,
-                             top_p=1.0, top_k=1, temperature=1.0, eos_token_id=eos, logprobs=logprobs)
+                             top_p=1.0, top_k=1, temperature=1.0, eos_token_id=eos, logprobs=logprobs,
+                             repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
         lp = model.last_logprobs
         if lp is not None:
             print(f"{name}: {lp.token_logprobs.numel()} tokens, cumulative log-probability {lp.cumulative:.4f}", file=sys.stderr)
@@ -167,13 +169,25 @@ def main(argv=None):
     parser.add_argument('--logprobs', type=int, default=None, choices=range(21), metavar="K",
                         help="Also compute per-token log-probabilities on the device (K = 0 .. 20 most likely ids per token) and print the "
                              "cumulative log-probability of each of the three LLM rounds to stderr.")
+    parser.add_argument('--repetition_penalty', type=float, default=1.0,
+                        help="Repetition penalty of the three LLM rounds, in (0, 2]; 1 = off (HF generate / vLLM: ids of the prompt and the output).")
+    parser.add_argument('--presence_penalty', type=float, default=0.0,
+                        help="Presence penalty of the three LLM rounds, in [-2, 2]; 0 = off (vLLM: ids generated so far).")
+    parser.add_argument('--frequency_penalty', type=float, default=0.0,
+                        help="Frequency penalty of the three LLM rounds, in [-2, 2]; 0 = off (vLLM: per occurrence among the ids generated so far).")
     args = parser.parse_args(argv)
+    from .llm import check_penalties
+    try:
+        check_penalties(args.repetition_penalty, args.presence_penalty, args.frequency_penalty)
+    except ValueError as e:
+        parser.error(str(e))
 
     device = torch.device("cuda")
     model, unit_extractor, voicebox, vocoder, tokenizer = load_models(args.model_cache_dir, device, quantization=args.quantization,
                                                                          kv_cache_dtype=args.kv_cache_dtype)
     try:
-        sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path, logprobs=args.logprobs)
+        sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path, logprobs=args.logprobs,
+               repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)
         print(f"Error while sampling: {e}")
         return 1

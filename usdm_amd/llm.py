@@ -118,6 +118,36 @@ def check_logprobs(logprobs):
     return logprobs
 
 
+def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """generate()'s / SamplingParams' penalty knobs -> None when all are neutral (no penalty plan is built), else the tuple
+    (repetition, frequency, presence) in usdm_penalty_params' order.  Ranges as vLLM's: repetition in (0, 2], the other two in
+    [-2, 2]; anything else, NaN included, is a ValueError (the library's own check: usdm_penalty_params_init)."""
+    p = ops.penalty_params(repetition_penalty, frequency_penalty, presence_penalty)
+    knobs = (p.repetition, p.frequency, p.presence)
+    return None if knobs == ops.PENALTY_NEUTRAL else knobs
+
+
+def penalty_buffers(device, V, B=None):
+    """usdm_penalize's state for one sequence (B=None: plus its tokens-counted word) or B batch slots: the table of V words per
+    sequence (count of generated occurrences, bit 30 = in the prompt) and the device block of the knobs (zero-filled = neutral)."""
+    lead = () if B is None else (B,)
+    bufs = dict(table=torch.zeros(*lead, V, dtype=torch.int32, device=device), dev_params=ops.penalty_params_tensor(device, B or 1).view(*lead, -1))
+    if B is None:
+        bufs["count"] = torch.zeros(1, dtype=torch.int32, device=device)
+    return bufs
+
+
+def seed_penalties(bufs, prompt_ids, knobs):
+    """A new request for this sequence / slot: its knobs, an empty table with every prompt id flagged (prompt ids whose K/V were
+    reused from the cache included), nothing counted yet.  Plain torch calls, outside the captured graphs."""
+    ops.set_penalty_params(bufs["dev_params"], *(knobs or ops.PENALTY_NEUTRAL))
+    tbl = bufs["table"]
+    tbl.zero_()
+    tbl[prompt_ids.to(tbl.device, torch.long)] = ops.PENALTY_PROMPT_BIT
+    if "count" in bufs:
+        bufs["count"].zero_()
+
+
 class TokenLogprobs:
     """Log-probabilities of one generated sequence of n tokens (host tensors): token_logprobs [n] f32 and ranks [n] i32 of the picked
     tokens, top_ids [n][K] i32 / top_logprobs [n][K] f32 in descending log-probability (exact ties: lowest id first), cumulative = the
@@ -318,6 +348,7 @@ class USDMForCausalLM:
         self.last_logits = None
         self._lp = None           # log-probability rows of the single sequence (logprob_buffers; allocated at first use)
         self.last_logprobs = None  # generate(logprobs=K): TokenLogprobs of the last call (generate_batch: a list); None when not asked
+        self._pen = None          # penalty state of the single sequence (penalty_buffers; allocated at first use)
 
     # ------------------------------------------------------------------ weights
     def _shard(self, sd_get):
@@ -547,7 +578,13 @@ class USDMForCausalLM:
             self._lp = logprob_buffers(self.device, self.max_out)
         return self._lp
 
-    def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None, logprobs=None):
+    def _pen_buffers(self):
+        if self._pen is None:
+            self._pen = penalty_buffers(self.device, self.cfg["vocab_size"])
+        return self._pen
+
+    def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None, logprobs=None,
+                          penalties=False):
         """lm_head GEMV + token choice, for the single sequence (slot=None), a batch slot's prefill, and the batched step
         (slot = the batch's "all" view, batch_gemv = its projection launcher).  sampling=None: ban-masked arg-max (the reference's
         top_k=1 path); sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block sample_params
@@ -556,10 +593,16 @@ class USDMForCausalLM:
         kernels on a peer-to-peer model, else through the group; the sampler then runs unchanged over the full row on every rank with
         the same seed and step: every rank draws the same token.
         logprobs=K (sampled picks only): usdm_logprobs right after the pick, on the row it drew from (after the hook: as the hook left
-        it; tensor parallel: the gathered row, on every rank), into the sequence's / the slots' log-probability buffers."""
+        it; tensor parallel: the gathered row, on every rank), into the sequence's / the slots' log-probability buffers.
+        penalties (sampled picks only): usdm_penalize on the row the sampler will read, BEFORE the hook and the pick - it counts the
+        previous step's token into the sequence's / the slots' table and applies the knobs of their device block (tensor parallel: on
+        the gathered row, on every rank; the table holds global ids and is the same on all ranks, so every rank still draws the
+        same token).  The hook, the log-probabilities and last_logits see the penalised row."""
         c, H = self.cfg, self.cfg["hidden_size"]
         if logprobs is not None and not sampling:
             raise ValueError("log-probabilities need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
+        if penalties and not sampling:
+            raise ValueError("penalties need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
         sl = slot or self   # where the picked token, the decode state and the next input row live (self = the single sequence)
         single = sl is self
         B = 0 if single else sl.batch
@@ -587,6 +630,7 @@ class USDMForCausalLM:
         # the picked token's embedding row is written straight into the decode step's input vector
         out = dict(embed=self.W["embed"], h_out=sl.h_dec, Hd=H)
         lp = None if logprobs is None else dict(self._lp_buffers() if single else sl.lp, K=logprobs)      # (the plan is named at the launch: rec.cut() below starts a new one)
+        pen = (self._pen_buffers() if single else sl.pen) if penalties else None
         if tp_sampled:
             row = sl.logits_row     # a batch: [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
             if p2p is not None:
@@ -595,10 +639,14 @@ class USDMForCausalLM:
             else:
                 rec.cut(lambda: self._gather_partials([row], [logits]))
             seg = dict(nseg=self.tp_size, seg_stride=B * self.Vloc, seg_len=self.Vloc) if B else {}
+            if pen:
+                ops.penalize(row, st, V=c["vocab_size"], plan=rec.plan, **seg, **pen)
             ops.sample_final(row, st, V=c["vocab_size"], dev_params=sl.sample_params, plan=rec.plan, **seg, **out)
             if lp:
                 ops.logprobs(row, st, V=c["vocab_size"], plan=rec.plan, **seg, **lp)
         elif sampling:
+            if pen:
+                ops.penalize(logits, st, V=self.v1 - self.v0, plan=rec.plan, **pen)
             if sampling == "hook":      # Python logits processors (usdm_amd.serving): a host call between the two kernels
                 rec.cut(lambda: self.logits_hook())
             ops.sample_final(logits, st, dev_params=sl.sample_params, plan=rec.plan, **out)
@@ -677,7 +725,7 @@ class USDMForCausalLM:
             land(w["down"], act, I, 2 * l + 1, **down_kw)
         return h, pend
 
-    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None):
+    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None, penalties=False):
         """Prefill of S new tokens at positions past .. past+S-1 (past > 0: the KV cache already holds the first `past`
         tokens of the same sequence; only the single-sequence cache keeps the V^T that makes this possible)."""
         dev, bf = self.device, torch.bfloat16
@@ -719,7 +767,7 @@ class USDMForCausalLM:
                           o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=rec.plan)
 
         self._layers(rec, gemm, attn, h, qkv, ao, act, "reduce" if self.tp_path else "fused", n=S * H, parts=(part, part))
-        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs)
+        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs, penalties=penalties)
         return rec.finish(), io
 
     def _build_decode_p2p(self, sampling=None):
@@ -728,7 +776,7 @@ class USDMForCausalLM:
             raise ValueError("_build_decode_p2p needs a model with a P2PComm")
         return self._build_decode(sampling)
 
-    def _build_decode(self, sampling=None, logprobs=None):
+    def _build_decode(self, sampling=None, logprobs=None, penalties=False):
         """One decode step of the single sequence.  Tensor parallel with a P2PComm: the launch sequence of the single-GPU step over
         this rank's shards, o_proj / down_proj carry the exchange (_layers, way "p2p"); returned as segments cut at every exchange,
         which a real rank runs back to back inside one hipGraph."""
@@ -790,7 +838,7 @@ class USDMForCausalLM:
         if chain:     # the last layer's chain has no next qkv to wait for
             flush()
         # (pend: the last down-projection's sum goes into the final norm + lm_head)
-        self._lm_head_and_pick(rec, h, True, sampling, x_delta=pend, skip=skp, logprobs=logprobs)
+        self._lm_head_and_pick(rec, h, True, sampling, x_delta=pend, skip=skp, logprobs=logprobs, penalties=penalties)
         return rec.finish()
 
     @staticmethod
@@ -883,7 +931,18 @@ class USDMForCausalLM:
             bb["decode_lp"] = {}
         return bb["lp"]
 
-    def _build_decode_batch(self, B, sampling=False, logprobs=None):
+    def _batch_pen(self, B):
+        """The slots' penalty state (allocated at first use); no tokens-counted word: batch slots have no device-side `done` word,
+        every step counts the token of the step before."""
+        bb = self._batch_buffers(B)
+        if "pen" not in bb:
+            bb["pen"] = bb["all"].pen = penalty_buffers(self.device, self.cfg["vocab_size"], B)
+            for b, sl in enumerate(bb["slots"]):
+                sl.pen = {k: v[b] for k, v in bb["pen"].items()}
+            bb["decode_pen"] = {}
+        return bb["pen"]
+
+    def _build_decode_batch(self, B, sampling=False, logprobs=None, penalties=False):
         """One decode step of B sequences: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
         sampling: the pick is usdm_sample_final's batched form - every slot draws with its OWN knobs (bb["sp"][b]: temperature,
         top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1."""
@@ -928,7 +987,7 @@ class USDMForCausalLM:
                             counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=rec.plan)
 
         self._layers(rec, gemv, attn, h, qkv, ao, act, "reduce" if tp else "fused", n=B * H, parts=parts, down_kw={} if tp else dict(ks=ks))
-        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs)
+        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs, penalties=penalties)
         segs = rec.finish()
         return segs if tp else segs[0]
 
@@ -952,24 +1011,40 @@ class USDMForCausalLM:
 
     @torch.no_grad()
     def generate_batch(self, input_ids_list, max_new_tokens, bad_words_ids=None, eos_token_id=None, min_new_tokens=0, group=None,
-                       logprobs=None):
+                       logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
         """Greedy generation of several utterances in lockstep (the serving-side batching of inference_vllm.py:109-125): up to
         `group` (default 16) sequences per step, longer lists run in groups.  Each prompt is prefilled on its own; every decode
         step then streams the weights once for the whole group.  Groups of <= 4 run on the VALU kernel and equal generate() per
         sequence bit for bit; larger groups run on the matrix cores (usdm_gemv_batch form 1): the same rounding points, K summed
         in another order - equal to the oracle up to its near-ties, not bit-identical with generate().
-        logprobs=K (0 .. 20): self.last_logprobs is then the list of the sequences' TokenLogprobs (see generate())."""
+        logprobs=K (0 .. 20): self.last_logprobs is then the list of the sequences' TokenLogprobs (see generate()).
+        repetition_penalty / presence_penalty / frequency_penalty: one value for all sequences or a list with one per sequence (see
+        generate()); a group with a non-neutral knob runs on the penalised sampling step, its other sequences with neutral knobs."""
         lpk = check_logprobs(logprobs)
+        n = len(input_ids_list)
+        per = [k if isinstance(k, (list, tuple)) else [k] * n for k in (repetition_penalty, presence_penalty, frequency_penalty)]
+        if any(len(k) != n for k in per):
+            raise ValueError("a penalty is one value for all sequences or a list with one value per sequence")
+        pens = [check_penalties(*k) for k in zip(*per)]
         group = self.max_batch() if group is None else max(1, min(int(group), self.max_batch()))
         outs, self.last_logprobs = [], (None if lpk is None else [])
-        for g0 in range(0, len(input_ids_list), group):
-            outs += self._generate_group(input_ids_list[g0:g0 + group], max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, lpk)
+        for g0 in range(0, n, group):
+            outs += self._generate_group(input_ids_list[g0:g0 + group], max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, lpk,
+                                         pens[g0:g0 + group])
         return outs
 
-    def _batch_step(self, B, sampling=False, logprobs=None):
+    def _batch_step(self, B, sampling=False, logprobs=None, penalties=False):
         """The replayable decode step of the B slots, greedy or sampled (built at first use); logprobs=K: the sampled step followed by
-        usdm_logprobs, a plan of its own per K."""
+        usdm_logprobs, a plan of its own per K; penalties: the sampled step with usdm_penalize in front of the pick, a plan of its
+        own (per K too)."""
         bb = self._batch_buffers(B)
+        if penalties:
+            self._batch_pen(B)
+            if logprobs is not None:
+                self._batch_lp(B)
+            if logprobs not in bb["decode_pen"]:
+                bb["decode_pen"][logprobs] = self._graphed(self._build_decode_batch(B, sampling=True, logprobs=logprobs, penalties=True))
+            return bb["decode_pen"][logprobs]
         if logprobs is not None:
             self._batch_lp(B)
             if logprobs not in bb["decode_lp"]:
@@ -980,10 +1055,11 @@ class USDMForCausalLM:
             bb[key] = self._graphed(self._build_decode_batch(B, sampling=sampling))
         return bb[key]
 
-    def _admit(self, B, b, ids, sampling=False, logprobs=None):
+    def _admit(self, B, b, ids, sampling=False, logprobs=None, penalties=None):
         """Admit a prompt (ids [L]) into slot b of the B slots: its step / position counters, then the per-item prefill into the
         slot's cache, which also picks the first token (sampled too when the batch runs on the sampling step; logprobs=K: with row 0
-        of the slot's log-probabilities)."""
+        of the slot's log-probabilities).  penalties = the request's knobs (repetition, frequency, presence) when the batch runs on
+        the penalised step - ops.PENALTY_NEUTRAL for a request without: the slot's table is reset and seeded from the prompt."""
         bb, L = self._batch_buffers(B), int(ids.shape[0])
         bb["step"][b] = 0
         bb["pos"][b] = L
@@ -991,12 +1067,18 @@ class USDMForCausalLM:
             self._batch_lp(B)
             sampling = True
         key = (L, b, sampling) if logprobs is None else (L, b, sampling, logprobs)
-        segs, io = bb["prefill"].get_or_build(key, lambda: self._build_prefill(L, True if sampling else None, slot=bb["slots"][b], logprobs=logprobs))
+        if penalties is not None:
+            self._batch_pen(B)
+            seed_penalties(bb["slots"][b].pen, ids, penalties)
+            sampling, key = True, (L, b, True, logprobs, "penalties")
+        segs, io = bb["prefill"].get_or_build(key, lambda: self._build_prefill(L, True if sampling else None, slot=bb["slots"][b], logprobs=logprobs,
+                                                                               penalties=penalties is not None))
         io["ids"].copy_(ids)
         self._run_segs(segs)
 
-    def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None):
+    def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None, pens=None):
         B = len(ids_list)
+        pen = pens is not None and any(k is not None for k in pens)      # one penalised sequence: the group runs on the penalised step
         for ids in ids_list:
             if ids.dim() != 2 or ids.shape[0] != 1:
                 raise ValueError("every prompt must be a LongTensor of shape [1, L]")
@@ -1009,10 +1091,10 @@ class USDMForCausalLM:
                 self.last_logprobs += [None] * B
             return [ids.clone() for ids in ids_list]
         for b, ids in enumerate(ids_list):
-            if logprobs is not None:      # greedy on the sampling step: top_k = 1 (the arg-max path has no logits row)
+            if logprobs is not None or pen:      # greedy on the sampling step: top_k = 1 (the arg-max path has no logits row)
                 ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
-            self._admit(B, b, ids[0], logprobs=logprobs)
-        decode = self._batch_step(B, logprobs=logprobs)
+            self._admit(B, b, ids[0], logprobs=logprobs, penalties=(pens[b] or ops.PENALTY_NEUTRAL) if pen else None)
+        decode = self._batch_step(B, logprobs=logprobs, penalties=pen)
         eos = stop_ids(eos_token_id)
         produced, chunk = 1, 8
         ends = [None] * B
@@ -1052,7 +1134,8 @@ class USDMForCausalLM:
         self._ban_cache.put(key, (bad_words_ids, t))
         return t
 
-    def _setup_call(self, input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=None, logprobs=None):
+    def _setup_call(self, input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=None, logprobs=None,
+                    penalties=None):
         """Per-call device state of generate(): prompt ids into the (cached) prefill plan, ban mask, position / step counters,
         device-side EOS list.  Returns (prefill segments, the EOS ids the device checks)."""
         L0 = input_ids.shape[1]
@@ -1062,7 +1145,12 @@ class USDMForCausalLM:
             elif not sampling and self.last_logits is self.logits_row:
                 self.last_logits = self._shard_logits
         key = (L0 - past, past, sampling) if logprobs is None else (L0 - past, past, sampling, logprobs)
-        segs, io = self._prefill_plans.get_or_build(key, lambda: self._build_prefill(L0 - past, sampling, past=past, logprobs=logprobs))
+        if penalties is not None:
+            key = (L0 - past, past, sampling, logprobs, "penalties")
+            # the whole prompt is flagged, the ids whose K/V are reused from the cache included; zeroed together with st_step below
+            seed_penalties(self._pen_buffers(), input_ids[0], penalties)
+        segs, io = self._prefill_plans.get_or_build(key, lambda: self._build_prefill(L0 - past, sampling, past=past, logprobs=logprobs,
+                                                                                     penalties=penalties is not None))
         if logprobs is not None:
             self._lp_buffers()["count"].zero_()      # rows written so far (usdm_logprobs keys its write on it: the device-side EOS)
         io["ids"].copy_(input_ids[0, past:])
@@ -1082,15 +1170,21 @@ class USDMForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids=None, max_length=None, do_sample=False, bad_words_ids=None, top_p=1.0, top_k=None,
                  temperature=1.0, eos_token_id=None, max_new_tokens=None, min_new_tokens=0, seed=None, ban_mask=None,
-                 _logits_hook=None, logprobs=None, **unused):
+                 _logits_hook=None, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, **unused):
         """Generation with the call shape of src/inference.py:63-83.  Greedy when do_sample is False or top_k == 1 (what the
         reference passes: arg-max of the ban-masked logits).  Otherwise temperature / top-k / top-p sampling on the device
         (usdm_sample_final).  `seed` keys its Philox stream; seed=None draws a fresh one from torch's global CPU generator,
         so calls differ from each other as HF sampling does and are reproducible under torch.manual_seed.
         logprobs=K (0 .. 20; None = off): self.last_logprobs is then the TokenLogprobs of the returned tokens, the first one (picked by
         the prefill) included - computed on the device inside the step (usdm_logprobs), before temperature / top-k / top-p.  A greedy
-        call then runs on the sampling step with top_k = 1 (the arg-max path never materialises a logits row); its ids are the same."""
+        call then runs on the sampling step with top_k = 1 (the arg-max path never materialises a logits row); its ids are the same.
+        repetition_penalty r in (0, 2] (HF / vLLM: ids of the prompt and of the output so far), frequency_penalty and presence_penalty
+        in [-2, 2] (vLLM: ids of the output so far): applied on the device to the ban-masked row of every step before the hook and
+        the pick (usdm_penalize), so log-probabilities and last_logits are those of the penalised row.  With a
+        non-neutral knob a greedy call runs on the sampling step with top_k = 1 too, and its ids may differ from the plain call's:
+        that is the point.  All neutral (the default): no penalty plan is built, every launch is what it is without the arguments."""
         lpk = check_logprobs(logprobs)
+        pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         self.last_logprobs = None
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1, as the reference calls it)")
@@ -1111,7 +1205,7 @@ class USDMForCausalLM:
         else:
             if (temperature != 1.0 or top_p != 1.0) and not do_sample:
                 raise ValueError("temperature / top_p only apply with do_sample=True")
-            if lpk is not None:
+            if lpk is not None or pen is not None:
                 sampling = True
                 ops.set_sample_params(self.sample_params, 1.0, 1, 1.0, 0)
         L0 = input_ids.shape[1]
@@ -1138,11 +1232,14 @@ class USDMForCausalLM:
                 a0 = self._vt_upto
                 self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
         segs, dev_eos = self._setup_call(input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,
-                                          logprobs=lpk)
+                                          logprobs=lpk, penalties=pen)
         self._run_segs(segs)  # prefill + first token
         dkey = sampling if lpk is None else (sampling, lpk)      # the step with log-probabilities: a plan / graph of its own per K
+        if pen is not None:                                      # ... and the penalised step
+            dkey = (sampling, lpk, "penalties")
         if dkey not in self._decodes:      # (the hooked step has host code inside: never captured)
-            self._decodes[dkey] = self._graphed(self._build_decode(sampling, logprobs=lpk), enabled=False if sampling == "hook" else None)
+            self._decodes[dkey] = self._graphed(self._build_decode(sampling, logprobs=lpk, penalties=pen is not None),
+                                                enabled=False if sampling == "hook" else None)
         self._decode = self._decodes[dkey]
         eos = stop_ids(eos_token_id)
         produced, done, chunk = 1, False, 8

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogprobArgs, NormArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogprobArgs, NormArgs, PenaltyArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -432,6 +432,67 @@ def logprobs(logits, st, *, K, tok_lp, tok_rank, top_id=None, top_lp=None, count
         raise ValueError("logprobs: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
     a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
     _go(plan, "usdm_logprobs", lib.usdm_logprobs, C_.byref(a), C_.byref(st))
+
+
+PENALTY_PROMPT_BIT = 1 << 30     # usdm_penalize's table word: in_prompt(i) in bit 30, c(i) below it
+PENALTY_NEUTRAL = (1.0, 0.0, 0.0)   # repetition, frequency, presence: the knobs that change nothing
+
+
+def penalty_params_tensor(device, n=1):
+    """Device block holding n usdm_penalty_params (16 bytes each: repetition, frequency, presence, reserved); zero-filled = neutral."""
+    sz = C_.sizeof(_lib.PenaltyParams)
+    return torch.zeros(sz if n == 1 else (n, sz), dtype=torch.uint8, device=device)
+
+
+def penalty_params(repetition=1.0, frequency=0.0, presence=0.0):
+    """One host usdm_penalty_params, filled and range-checked by the library (usdm_penalty_params_init): repetition in (0, 2],
+    frequency and presence in [-2, 2]; anything else, NaN included, is a ValueError."""
+    p = _lib.PenaltyParams()
+    try:
+        r, f, q = float(repetition), float(frequency), float(presence)
+    except (TypeError, ValueError):
+        raise ValueError(f"penalties must be numbers, got {repetition!r}, {frequency!r}, {presence!r}") from None
+    if lib.usdm_penalty_params_init(C_.byref(p), C_.c_float(r), C_.c_float(f), C_.c_float(q)) != 0:
+        raise ValueError(lib.usdm_last_error().decode())
+    return p
+
+
+def set_penalty_params(block, repetition=1.0, frequency=0.0, presence=0.0):
+    """block: one 16-byte block (a row of penalty_params_tensor(device, n) for slot b of a batch)"""
+    block.copy_(torch.frombuffer(bytearray(bytes(penalty_params(repetition, frequency, presence))), dtype=torch.uint8))
+
+
+def penalize(logits, st, *, table, dev_params, count=None, V=None, nseg=1, seg_stride=0, seg_len=0, plan=None):
+    """usdm_penalize, launched before the sample_final of the same step on the row it will read: counts the token the previous step
+    picked into table (int32 [V], or [B][>= V] with a batched state) and applies the repetition / frequency / presence penalties of
+    dev_params (penalty_params_tensor) to the f32 row in place.  count (int32 [B]): the step at the last counting, required with a
+    device-side `done` word (see include/usdm_hip.h).  V / nseg / seg_stride / seg_len as in sample_final (usdm_penalize_seg)."""
+    _need_cuda(logits, table, dev_params, count)
+    B = max(1, st.batch)
+    a = PenaltyArgs()
+    a.logits, a.V = _ptr(logits), logits.shape[-1] if V is None else V
+    a.table, a.dev_params, a.count = _ptr(table), _ptr(dev_params), _ptr(count)
+    if logits.dtype != torch.float32:
+        raise ValueError("penalize: logits must be float32")
+    if table is not None:
+        rows = table if B == 1 else table[0]
+        if table.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < a.V or (B > 1 and (table.dim() != 2 or table.shape[0] < B)):
+            raise ValueError(f"penalize: table must be int32 with room for V = {a.V} words per sequence")
+        a.table_bs = table.stride(0) if B > 1 else 0
+    if dev_params is not None and (dev_params.dtype != torch.uint8 or not dev_params.is_contiguous() or dev_params.numel() < 16 * B):
+        raise ValueError("penalize: dev_params must be a penalty_params_tensor of [batch] blocks")
+    if count is not None and (count.dtype != torch.int32 or count.numel() < B):
+        raise ValueError("penalize: count must be int32 [batch]")
+    if seg_len > 0:
+        if nseg < 1 or not logits.is_contiguous() or logits.shape[-1] != seg_len or logits.numel() < (nseg - 1) * seg_stride + B * seg_len:
+            raise ValueError("segmented penalize: logits must be a contiguous [nseg][B][seg_len] tensor")
+        a.logits_bs = seg_len
+        _go(plan, "usdm_penalize_seg", lib.usdm_penalize_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len), C_.byref(st))
+        return
+    if logits.dim() > 2 or a.V > logits.shape[-1] or logits.stride(-1) != 1:
+        raise ValueError("penalize: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
+    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
+    _go(plan, "usdm_penalize", lib.usdm_penalize, C_.byref(a), C_.byref(st))
 
 
 def logits_p2p(logits, Vloc, st, p2p, site0, row_out, phase=0, plan=None):

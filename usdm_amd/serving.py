@@ -18,8 +18,12 @@ How requests are executed
   * under tensor parallelism both forms sample as well: every rank gathers the full ban-masked logits row (the ranks' lm_head
     shards) and draws from it with the same seed and step, so every rank picks the same token; a seed left to the server is
     rank 0's draw on every rank.  Processors that depend on the history are not supported there (they would see one shard);
-  * processors that really depend on the token history run as Python between the lm_head launch and the pick of every step
-    (eager launches: correct, not fast);
+  * SamplingParams(repetition_penalty=, presence_penalty=, frequency_penalty=) - the history-dependent processors every HF / vLLM
+    user reaches for - run on the device inside the step (usdm_penalize, in front of the pick): graph-captured,
+    continuously batched and tensor parallel like any other request.  One penalised request puts its whole group on the penalised
+    step, which is also the sampling step; the other slots carry neutral knobs, which leave every bit of their rows alone;
+  * other processors that really depend on the token history run as Python between the lm_head launch and the pick of every step
+    (eager launches: correct, not fast); with penalties they get both, the processors seeing the penalised row;
   * SamplingParams(logprobs=K), K = 0 .. 20: per-token log-probabilities computed on the device inside the step (usdm_logprobs, right
     after the pick, on the row it drew from): lp(i) = x_i - logsumexp(x) over the ban-masked logits, i.e. the model's distribution
     over the allowed ids BEFORE temperature / top-k / top-p.  One asking request puts its whole group on the log-probability step
@@ -31,7 +35,7 @@ from collections import deque
 import torch
 
 from . import ops
-from .llm import USDMForCausalLM, check_logprobs, check_quantization, read_logprobs, stop_index
+from .llm import USDMForCausalLM, check_logprobs, check_penalties, check_quantization, read_logprobs, stop_index
 from .quant import check_kv_cache_dtype
 
 MAX_SLOTS = 16      # usdm_gemv_batch streams the weights once per step for up to 16 sequences (matrix-core form above 4)
@@ -44,7 +48,7 @@ class SamplingParams:
 
     def __init__(self, n=1, temperature=1.0, top_p=1.0, top_k=-1, max_tokens=16, min_tokens=0, stop_token_ids=None,
                  logits_processors=None, seed=None, skip_special_tokens=True, ignore_eos=False, static_logits_mask=None, logprobs=None,
-                 prompt_logprobs=None, **unused):
+                 prompt_logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, **unused):
         if not isinstance(n, int) or n < 1:
             raise ValueError("n must be a positive integer")
         if temperature < 0 or not (0 < top_p <= 1) or (top_k < -1 or top_k == 0):
@@ -57,6 +61,10 @@ class SamplingParams:
         self.static_logits_mask = static_logits_mask      # None: probe the processors; True / False: caller's word
         # logprobs (vllm's name): None, or the number of most likely ids reported per generated token next to the picked one, 0 .. 20
         self.logprobs = check_logprobs(logprobs)
+        # vllm's penalties: repetition in (0, 2] over prompt + output ids, presence / frequency in [-2, 2] over output ids (usdm_penalize)
+        self.penalties = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)      # None: all neutral
+        self.repetition_penalty, self.presence_penalty, self.frequency_penalty = (
+            float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
         if prompt_logprobs is not None:
             raise NotImplementedError("prompt_logprobs is not supported (it needs the lm_head over every prompt row); logprobs= covers "
                                       "the generated tokens")
@@ -271,7 +279,8 @@ class LLM:
             return [], "length", None
         ids = torch.tensor([r["ids"]], dtype=torch.long, device=llm.device)
         kw = dict(input_ids=ids, max_new_tokens=r["max_new"], eos_token_id=sorted(r["stops"]) or None, min_new_tokens=sp.min_tokens,
-                  logprobs=sp.logprobs)
+                  logprobs=sp.logprobs, repetition_penalty=sp.repetition_penalty, presence_penalty=sp.presence_penalty,
+                  frequency_penalty=sp.frequency_penalty)
         sampled = not sp.greedy
         if sampled:
             kw.update(do_sample=True, temperature=sp.temperature, top_p=sp.top_p, top_k=(sp.top_k if sp.top_k > 0 else None), seed=r["seed"])
@@ -305,8 +314,14 @@ class LLM:
         # with the group's largest K; every request's rows are trimmed to its own K on the host
         ks = [r["sp"].logprobs for r in grp if r["sp"].logprobs is not None]
         lpk = max(ks) if ks else None
-        sampled = lpk is not None or any(not r["sp"].greedy for r in grp)       # one sampled request -> the whole group runs on the sampling graph
-        decode = llm._batch_step(nslots, sampling=sampled, logprobs=lpk)
+        # one penalised request -> the whole group runs on the penalised step (usdm_penalize + the sampling step); the other
+        # requests and the idle slots carry neutral knobs
+        pen = any(r["sp"].penalties is not None for r in grp)
+        sampled = lpk is not None or pen or any(not r["sp"].greedy for r in grp)       # one sampled request -> the whole group runs on the sampling graph
+        decode = llm._batch_step(nslots, sampling=sampled, logprobs=lpk, penalties=pen)
+        if pen:
+            for b in range(nslots):
+                ops.set_penalty_params(bb["pen"]["dev_params"][b])
         self.stats["sampled_in_batch"] = self.stats.get("sampled_in_batch", 0) + sum(not r["sp"].greedy for r in grp)
         for b in range(nslots):                               # idle slots: harmless greedy knobs
             ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
@@ -322,7 +337,8 @@ class LLM:
                         ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
                     else:
                         ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"])
-                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), sampling=sampled, logprobs=lpk)      # (+ first token)
+                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), sampling=sampled, logprobs=lpk,
+                               penalties=(sp.penalties or ops.PENALTY_NEUTRAL) if pen else None)      # (+ first token)
                     slots[b] = dict(r=r, produced=1)
                     self.stats["admissions"] += 1
             active = [b for b in range(nslots) if slots[b] is not None]
@@ -346,6 +362,8 @@ class LLM:
                     lp = read_logprobs(bb["lp"], len(seq[:n]), lpk, b).trimmed(len(seq[:n]), k) if k is not None else None
                     results.append((r, seq[:n], "stop" if end is not None and end <= n else "length", lp))
                     slots[b] = None
+                    if pen:      # the idle slot keeps decoding garbage: with neutral knobs
+                        ops.set_penalty_params(bb["pen"]["dev_params"][b])
                     freed = True
                 else:
                     need = max(need, 1)
