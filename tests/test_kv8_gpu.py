@@ -334,7 +334,7 @@ def test_fp8_kv_batched_request_running_into_the_context_limit(dev):
     from oracle import mistral_oracle as MO
     from tests._greedy_compare import check_against_oracle
     from tests._kv8_reference import kv8_greedy_generate
-    from usdm_amd.llm import USDMForCausalLM
+    from usdm_amd.llm import USDMForCausalLM, step_kind
     from usdm_amd.serving import LLM, SamplingParams
     sd = MO.random_state_dict(SMALL, seed=47)
     m = USDMForCausalLM.from_state_dict(sd, SMALL, dev, ctx_max=128, kv_cache_dtype="fp8")
@@ -355,7 +355,7 @@ def test_fp8_kv_batched_request_running_into_the_context_limit(dev):
     bb = m._batch_buffers(4)
     before = [bb[k].clone() for k in ("kc", "vc", "ke", "ve")]
     bb["pos"].fill_(128); bb["step"].zero_()
-    bb["decode"].run()
+    bb["steps"][step_kind()].run()
     torch.cuda.synchronize()
     for k, t in zip(("kc", "vc", "ke", "ve"), before):
         assert torch.equal(t, bb[k]), k

@@ -87,13 +87,14 @@ def test_device_penalties_equal_the_hooked_reference(dev, sampled, knobs):
 
 
 def test_neutral_knobs_are_the_plain_call_and_build_nothing(dev):
+    from usdm_amd.llm import step_kind
     m, ids = _model(dev), _prompt(dev)
     kw = dict(input_ids=ids, max_new_tokens=12, bad_words_ids=BAD)
     plain = m.generate(**kw)
     keys = set(m._decodes)
     out = m.generate(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, **kw)
-    assert torch.equal(out, plain) and set(m._decodes) == keys == {False} and m._pen is None
-    assert not any("penalties" in k for k in m._prefill_plans)
+    assert torch.equal(out, plain) and set(m._decodes) == keys == {step_kind()} and m._pen is None
+    assert not any(k[4] for k in m._prefill_plans)
     outs = m.generate_batch([ids, _prompt(dev, 23, 2)], 6, bad_words_ids=BAD, repetition_penalty=[1.0, 1.0], frequency_penalty=0.0)
     assert "pen" not in m._batches[2] and torch.equal(outs[0][0, :46], plain[0, :46])
     for bad in (dict(repetition_penalty=0.0), dict(repetition_penalty=2.5), dict(presence_penalty=3.0), dict(frequency_penalty=float("nan"))):

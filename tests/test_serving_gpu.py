@@ -170,7 +170,7 @@ def test_batched_request_running_into_the_context_limit(dev):
     would be another head's / slot's rows) while its neighbours keep decoding and a queued request takes over its slot."""
     from oracle import mistral_oracle as MO
     from tests._greedy_compare import check_against_oracle
-    from usdm_amd.llm import USDMForCausalLM
+    from usdm_amd.llm import USDMForCausalLM, step_kind
     from usdm_amd.serving import LLM, SamplingParams
     sd = MO.random_state_dict(SMALL, seed=47)
     m = USDMForCausalLM.from_state_dict(sd, SMALL, dev, ctx_max=128)
@@ -192,7 +192,7 @@ def test_batched_request_running_into_the_context_limit(dev):
     bb = m._batch_buffers(4)
     before = bb["kc"].clone()
     bb["pos"].fill_(128); bb["step"].zero_()
-    bb["decode"].run()
+    bb["steps"][step_kind()].run()
     torch.cuda.synchronize()
     assert torch.equal(before, bb["kc"])
 

@@ -28,7 +28,7 @@ def test_tp_batched_code_path_single_rank_rccl(dev, B):
     residual-add kernel, gathered pick) on a 1-rank group: the same arithmetic as the fused epilogues -> identical tokens."""
     import torch.distributed as dist
     from oracle import mistral_oracle as MO
-    from usdm_amd.llm import USDMForCausalLM
+    from usdm_amd.llm import USDMForCausalLM, step_kind
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29541")
     created = False
@@ -41,7 +41,7 @@ def test_tp_batched_code_path_single_rank_rccl(dev, B):
         a = USDMForCausalLM.from_state_dict(sd, CFG, dev, ctx_max=128).generate_batch(ps, max_new_tokens=14, bad_words_ids=BAD)
         m = USDMForCausalLM.from_state_dict(sd, CFG, dev, ctx_max=128, tp_segments=True, group=dist.group.WORLD)
         b = m.generate_batch(ps, max_new_tokens=14, bad_words_ids=BAD)
-        dec = m._batches[B]["decode"]
+        dec = m._batches[B]["steps"][step_kind()]
         print(f"B={B}: TP batched step graph captured: {dec.graph is not None} (fallback reason: {dec.failed})")
         for x, y in zip(a, b):
             assert torch.equal(x, y)

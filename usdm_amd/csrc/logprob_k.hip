@@ -15,19 +15,14 @@
 //   last collect the <= 20 kept keys, order them by counting, write the row
 // Histogram bins are replicated 32 times (lane % 32): a pass whose keys share a few bins (the exponent byte) would otherwise
 // serialise 64 LDS atomics per wave instruction on one address.  Every sum is an integer sum and every per-id quantity depends on the
-// id's value only, so the same logical row gives bit-identical output run to run, single or batched, contiguous or segmented.
-//
-// (fkey and the segmented addressing repeat sample_k.hip's, which this feature leaves untouched.)
-#include "common.h"
+// id's value only, so the same logical row gives bit-identical output run to run, single or batched, contiguous or segmented
+// (logits_row.h).
+#include "logits_row.h"
 #include "../../include/usdm_hip.h"
 
 namespace {
 constexpr int NT = 1024, NW = NT / 64, REP = 32, KMAX = 20;
 
-__device__ __forceinline__ unsigned fkey(float x) {   // order-preserving float -> uint
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 __device__ __forceinline__ float fkey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 // composite key of (id, logit): larger = more likely, then lower id.  -0.0 is folded into +0.0 first (equal values must tie)
 __device__ __forceinline__ unsigned long long ckey(int i, float x) {
@@ -55,33 +50,13 @@ __global__ __launch_bounds__(NT) void logprob_kernel(usdm_logprob_args a, usdm_d
   const int tok = st.next_token[b] - st.id_offset;
   const bool tok_ok = tok >= 0 && tok < V;
 
-  auto LG = [&](int i) -> float {   // logit of id i (0 <= i < V)
-    if constexpr (SEG) {
-      unsigned q = __umulhi((unsigned)i, seg_magic);
-      if (q * (unsigned)seg_len > (unsigned)i) --q;
-      return a.logits[(int64_t)q * seg_stride + (i - (int)q * seg_len)];
-    } else {
-      return a.logits[i];
-    }
-  };
+  const logits_row_view rv{seg_stride, seg_len, seg_magic};
   auto each = [&](auto&& f) {   // f(i, logit of i) for i = tid, tid + NT, ... < V
-    if constexpr (SEG) {
-      unsigned q = __umulhi((unsigned)tid, seg_magic);
-      if (q * (unsigned)seg_len > (unsigned)tid) --q;
-      int r = tid - (int)q * seg_len;
-      const float* ptr = a.logits + (int64_t)q * seg_stride + r;
-      for (int i = tid; i < V; i += NT) {
-        f(i, *ptr);
-        ptr += NT; r += NT;
-        while (r >= seg_len) { r -= seg_len; ptr += seg_stride - seg_len; }
-      }
-    } else {
-      for (int i = tid; i < V; i += NT) f(i, a.logits[i]);
-    }
+    row_each<SEG, NT>(a.logits, V, tid, rv, [&](int i, const float* px) { f(i, *px); });
   };
 
   // ---- pass 1: max, and how many ids beat the picked one
-  const float xt = tok_ok ? LG(tok) : -INFINITY;
+  const float xt = tok_ok ? row_at<SEG>(a.logits, tok, rv) : -INFINITY;
   float m = -INFINITY;
   unsigned gt = 0;
   each([&](int, float x) {
@@ -201,7 +176,7 @@ int check_logprobs(const usdm_logprob_args* pa, const usdm_decode_state* st, con
 
 extern "C" int usdm_logprobs(const usdm_logprob_args* pa, const usdm_decode_state* st, usdm_stream_t stream) {
   if (int rc = check_logprobs(pa, st, "usdm_logprobs")) return rc;
-  const int nb = st->batch > 1 ? st->batch : 1;
+  const int nb = logits_rows(st->batch);
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= pa->V && pa->tok_bs >= st->max_out && (pa->K == 0 || pa->top_bs >= (int64_t)st->max_out * pa->K)),
                  "usdm_logprobs: the batched form needs logits_bs >= V, tok_bs >= max_out and top_bs >= max_out * K");
   hipLaunchKernelGGL(logprob_kernel<false>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (int64_t)0, 0, 0u);
@@ -212,14 +187,11 @@ extern "C" int usdm_logprobs(const usdm_logprob_args* pa, const usdm_decode_stat
 extern "C" int usdm_logprobs_seg(const usdm_logprob_args* pa, int32_t nseg, int64_t seg_stride, int32_t seg_len,
                                  const usdm_decode_state* st, usdm_stream_t stream) {
   if (int rc = check_logprobs(pa, st, "usdm_logprobs_seg")) return rc;
-  const int nb = st->batch > 1 ? st->batch : 1;
-  USDM_CHECK_ARG(nseg >= 1 && seg_len >= 2 && seg_len <= (1 << 20) && (int64_t)nseg * seg_len >= pa->V,
-                 "usdm_logprobs_seg: nseg segments of seg_len ids must cover V");
+  const int nb = logits_rows(st->batch);
+  if (int rc = check_logits_seg("usdm_logprobs_seg", nseg, seg_stride, seg_len, pa->V, pa->logits_bs, nb)) return rc;
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= seg_len && pa->tok_bs >= st->max_out && (pa->K == 0 || pa->top_bs >= (int64_t)st->max_out * pa->K)),
                  "usdm_logprobs_seg: the batched form needs logits_bs >= seg_len, tok_bs >= max_out and top_bs >= max_out * K");
-  USDM_CHECK_ARG(nseg == 1 || seg_stride >= pa->logits_bs * (nb - 1) + seg_len, "usdm_logprobs_seg: segments overlap");
-  const unsigned magic = (unsigned)((((uint64_t)1 << 32) + (uint64_t)seg_len - 1) / (uint64_t)seg_len);
-  hipLaunchKernelGGL(logprob_kernel<true>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, seg_stride, (int)seg_len, magic);
+  hipLaunchKernelGGL(logprob_kernel<true>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, seg_stride, (int)seg_len, logits_seg_magic(seg_len));
   USDM_LAUNCH_CHECK();
   return 0;
 }

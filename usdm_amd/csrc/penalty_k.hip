@@ -18,10 +18,8 @@
 // is therefore exactly the histogram of out_tokens[0 .. *step - 1].
 //
 // One workgroup of 1024 threads per sequence (the read of `count` and its update are separated by a __syncthreads()), one pass over
-// the V logits and table words (L2-resident, 2 x 168 KB at V = 42003).
-//
-// (The segmented addressing repeats sample_k.hip's, which this feature leaves untouched.)
-#include "common.h"
+// the V logits and table words (L2-resident, 2 x 168 KB at V = 42003); the row is contiguous or segmented (logits_row.h).
+#include "logits_row.h"
 #include "../../include/usdm_hip.h"
 
 namespace {
@@ -51,7 +49,7 @@ __global__ __launch_bounds__(NT) void penalty_kernel(usdm_penalty_args a, usdm_d
     return;
   }
   float* row = a.logits + (int64_t)b * a.logits_bs;
-  auto one = [&](int i, float* px) {
+  row_each<SEG, NT>(row, V, tid, logits_row_view{seg_stride, seg_len, seg_magic}, [&](int i, float* px) {
     int t = tbl[i];
     if (i == last) {
       t += 1;
@@ -63,20 +61,7 @@ __global__ __launch_bounds__(NT) void penalty_kernel(usdm_penalty_args a, usdm_d
     x = x - (f * (float)c);
     x = x - (p * (c > 0 ? 1.0f : 0.0f));
     *px = x;
-  };
-  if constexpr (SEG) {   // id i sits at (i / seg_len) * seg_stride + i % seg_len: divide once, then walk, stepping over the gaps
-    unsigned q = __umulhi((unsigned)tid, seg_magic);
-    if (q * (unsigned)seg_len > (unsigned)tid) --q;
-    int rr = tid - (int)q * seg_len;
-    float* ptr = row + (int64_t)q * seg_stride + rr;
-    for (int i = tid; i < V; i += NT) {
-      one(i, ptr);
-      ptr += NT; rr += NT;
-      while (rr >= seg_len) { rr -= seg_len; ptr += seg_stride - seg_len; }
-    }
-  } else {
-    for (int i = tid; i < V; i += NT) one(i, row + i);
-  }
+  });
 }
 
 int check_penalize(const usdm_penalty_args* pa, const usdm_decode_state* st, const char* who) {
@@ -92,7 +77,7 @@ int check_penalize(const usdm_penalty_args* pa, const usdm_decode_state* st, con
 
 extern "C" int usdm_penalize(const usdm_penalty_args* pa, const usdm_decode_state* st, usdm_stream_t stream) {
   if (int rc = check_penalize(pa, st, "usdm_penalize")) return rc;
-  const int nb = st->batch > 1 ? st->batch : 1;
+  const int nb = logits_rows(st->batch);
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= pa->V && pa->table_bs >= pa->V),
                  "usdm_penalize: the batched form needs logits_bs >= V and table_bs >= V");
   hipLaunchKernelGGL(penalty_kernel<false>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (int64_t)0, 0, 0u);
@@ -103,14 +88,11 @@ extern "C" int usdm_penalize(const usdm_penalty_args* pa, const usdm_decode_stat
 extern "C" int usdm_penalize_seg(const usdm_penalty_args* pa, int32_t nseg, int64_t seg_stride, int32_t seg_len,
                                  const usdm_decode_state* st, usdm_stream_t stream) {
   if (int rc = check_penalize(pa, st, "usdm_penalize_seg")) return rc;
-  const int nb = st->batch > 1 ? st->batch : 1;
-  USDM_CHECK_ARG(nseg >= 1 && seg_len >= 2 && seg_len <= (1 << 20) && (int64_t)nseg * seg_len >= pa->V,
-                 "usdm_penalize_seg: nseg segments of seg_len ids must cover V");
+  const int nb = logits_rows(st->batch);
+  if (int rc = check_logits_seg("usdm_penalize_seg", nseg, seg_stride, seg_len, pa->V, pa->logits_bs, nb)) return rc;
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= seg_len && pa->table_bs >= pa->V),
                  "usdm_penalize_seg: the batched form needs logits_bs >= seg_len and table_bs >= V");
-  USDM_CHECK_ARG(nseg == 1 || seg_stride >= pa->logits_bs * (nb - 1) + seg_len, "usdm_penalize_seg: segments overlap");
-  const unsigned magic = (unsigned)((((uint64_t)1 << 32) + (uint64_t)seg_len - 1) / (uint64_t)seg_len);
-  hipLaunchKernelGGL(penalty_kernel<true>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, seg_stride, (int)seg_len, magic);
+  hipLaunchKernelGGL(penalty_kernel<true>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, seg_stride, (int)seg_len, logits_seg_magic(seg_len));
   USDM_LAUNCH_CHECK();
   return 0;
 }

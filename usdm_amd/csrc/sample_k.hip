@@ -10,16 +10,11 @@
 //   top-p  : radix select over the ascending exp(x - max) keys with FIXED-POINT mass histograms (u64 LDS atomics are
 //            associative, so the kept set does not depend on thread scheduling); ties are kept or dropped as a block;
 //   draw   : u * kept_mass located by an exclusive scan over contiguous index ranges (index order, deterministic).
-#include "common.h"
+#include "logits_row.h"
 #include "../../include/usdm_hip.h"
 
 namespace {
 constexpr int NT = 1024;
-
-__device__ __forceinline__ unsigned fkey(float x) {   // order-preserving float -> uint
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __device__ __forceinline__ void philox_round(unsigned (&c)[4], const unsigned (&k)[2]) {
   const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
@@ -48,10 +43,8 @@ __device__ float block_max(float v, float* sred) {
   return m;
 }
 
-// SEG = false: the row of sequence b is contiguous (usdm_sample_final).  SEG = true: it is made of rank-major segments of seg_len
-// ids, seg_stride elements apart (usdm_sample_final_seg); id i sits at (i / seg_len) * seg_stride + i % seg_len, the quotient by a
-// multiply-high with seg_magic = ceil(2^32 / seg_len) and one correction (exact for i, seg_len < 2^20).  Every sum below is an
-// integer sum and every per-id quantity depends on the id's value only, so both forms give bit-identical results on the same row.
+// SEG: the row of sequence b is contiguous (usdm_sample_final) or segmented (usdm_sample_final_seg), see logits_row.h.  Every sum
+// below is an integer sum and every per-id quantity depends on the id's value only.
 template <bool SEG>
 __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, usdm_decode_state st, const bf16_t* E, int Hd,
                                                            bf16_t* h_out, int64_t seg_stride, int seg_len, unsigned seg_magic,
@@ -80,31 +73,10 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     if (a.top_k < 0) a.top_k = 0;
   }
   const float invT = 1.0f / a.temperature;   // HF divides; x / T and x * (1 / T) differ by <= 1 ulp, below the logits' bf16 grain
-  auto LG = [&](int i) -> float {   // logit of id i (0 <= i < V)
-    if constexpr (SEG) {
-      unsigned q = __umulhi((unsigned)i, seg_magic);
-      if (q * (unsigned)seg_len > (unsigned)i) --q;
-      return a.logits[(int64_t)q * seg_stride + (i - (int)q * seg_len)];
-    } else {
-      return a.logits[i];
-    }
-  };
-  // f(i, logit of i) for i = tid, tid + NT, ... < V.  The segmented form divides once and then walks a pointer, stepping over the
-  // gap between two segments when it crosses one (seg_len >= NT: at most one step per iteration)
-  auto each = [&](auto&& f) {
-    if constexpr (SEG) {
-      unsigned q = __umulhi((unsigned)tid, seg_magic);
-      if (q * (unsigned)seg_len > (unsigned)tid) --q;
-      int r = tid - (int)q * seg_len;
-      const float* ptr = a.logits + (int64_t)q * seg_stride + r;
-      for (int i = tid; i < V; i += NT) {
-        f(i, *ptr);
-        ptr += NT; r += NT;
-        while (r >= seg_len) { r -= seg_len; ptr += seg_stride - seg_len; }
-      }
-    } else {
-      for (int i = tid; i < V; i += NT) f(i, a.logits[i]);
-    }
+  const logits_row_view rv{seg_stride, seg_len, seg_magic};
+  auto LG = [&](int i) -> float { return row_at<SEG>(a.logits, i, rv); };
+  auto each = [&](auto&& f) {   // f(i, logit of i) for i = tid, tid + NT, ... < V
+    row_each<SEG, NT>(a.logits, V, tid, rv, [&](int i, const float* px) { f(i, *px); });
   };
 
   // ---- top-k: key of the k-th largest scaled logit (all keys >= it are kept, ties included: `scores < kth` is removed)
@@ -296,7 +268,7 @@ int check_sample(const usdm_sample_args* pa, const usdm_decode_state* st, const 
 extern "C" int usdm_sample_final(const usdm_sample_args* pa, const usdm_decode_state* st, const void* embed_table, int32_t Hd,
                                  void* h_out, usdm_stream_t stream) {
   if (int rc = check_sample(pa, st, embed_table, Hd, h_out, "usdm_sample_final")) return rc;
-  const int nb = st->batch > 1 ? st->batch : 1;
+  const int nb = logits_rows(st->batch);
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= pa->V && pa->dev_params), "usdm_sample_final: the batched form needs logits_bs >= V and dev_params[batch]");
   hipLaunchKernelGGL(sample_final_kernel<false>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (const bf16_t*)embed_table, Hd,
                      (bf16_t*)h_out, (int64_t)0, 0, 0u, pa->logits_bs);
@@ -308,14 +280,11 @@ extern "C" int usdm_sample_final_seg(const usdm_sample_args* pa, int32_t nseg, i
                                      const usdm_decode_state* st, const void* embed_table, int32_t Hd, void* h_out,
                                      usdm_stream_t stream) {
   if (int rc = check_sample(pa, st, embed_table, Hd, h_out, "usdm_sample_final_seg")) return rc;
-  const int nb = st->batch > 1 ? st->batch : 1;
-  USDM_CHECK_ARG(nseg >= 1 && seg_len >= 2 && seg_len <= (1 << 20) && (int64_t)nseg * seg_len >= pa->V,
-                 "usdm_sample_final_seg: nseg segments of seg_len ids must cover V");
+  const int nb = logits_rows(st->batch);
+  if (int rc = check_logits_seg("usdm_sample_final_seg", nseg, seg_stride, seg_len, pa->V, pa->logits_bs, nb)) return rc;
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= seg_len && pa->dev_params), "usdm_sample_final_seg: the batched form needs logits_bs >= seg_len and dev_params[batch]");
-  USDM_CHECK_ARG(nseg == 1 || seg_stride >= pa->logits_bs * (nb - 1) + seg_len, "usdm_sample_final_seg: segments overlap");
-  const unsigned magic = (unsigned)((((uint64_t)1 << 32) + (uint64_t)seg_len - 1) / (uint64_t)seg_len);
   hipLaunchKernelGGL(sample_final_kernel<true>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (const bf16_t*)embed_table, Hd,
-                     (bf16_t*)h_out, seg_stride, (int)seg_len, magic, (int64_t)pa->V);
+                     (bf16_t*)h_out, seg_stride, (int)seg_len, logits_seg_magic(seg_len), (int64_t)pa->V);
   USDM_LAUNCH_CHECK();
   return 0;
 }

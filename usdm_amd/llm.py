@@ -27,6 +27,7 @@ attention reads its unquantized K / V from per-plan scratch.  Half the cache byt
 """
 import math
 import os
+from collections import namedtuple
 
 import torch
 
@@ -125,6 +126,18 @@ def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_pena
     p = ops.penalty_params(repetition_penalty, frequency_penalty, presence_penalty)
     knobs = (p.repetition, p.frequency, p.presence)
     return None if knobs == ops.PENALTY_NEUTRAL else knobs
+
+
+StepKind = namedtuple("StepKind", "sampling logprobs penalties")
+
+
+def step_kind(sampling=None, logprobs=None, penalties=False):
+    """Which variant of a step (the prefill's pick, the decode step) runs: the key of every cache of built plans, in the builders'
+    argument order.  sampling: False = the ban-masked arg-max, True = usdm_sample_final, "hook" = Python logits processors in front
+    of it; logprobs: None or K; penalties: whether usdm_penalize runs.  Log-probabilities and penalties work on the logits row, which
+    only the sampling step materialises, so either turns a greedy step into the sampling step (run with top_k = 1: the same ids)."""
+    sampling = "hook" if sampling == "hook" else bool(sampling)
+    return StepKind(sampling or logprobs is not None or bool(penalties), logprobs, bool(penalties))
 
 
 def penalty_buffers(device, V, B=None):
@@ -573,15 +586,12 @@ class USDMForCausalLM:
         rec.cut()
         launch(2)
 
-    def _lp_buffers(self):
-        if self._lp is None:
+    def _pick_state(self, kind):
+        """What a step of this kind needs beyond the sampler's state, for the single sequence (allocated at first use)."""
+        if kind.logprobs is not None and self._lp is None:
             self._lp = logprob_buffers(self.device, self.max_out)
-        return self._lp
-
-    def _pen_buffers(self):
-        if self._pen is None:
+        if kind.penalties and self._pen is None:
             self._pen = penalty_buffers(self.device, self.cfg["vocab_size"])
-        return self._pen
 
     def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None, logprobs=None,
                           penalties=False):
@@ -629,8 +639,10 @@ class USDMForCausalLM:
         st = ops.decode_state(sl.st_next, sl.st_out, sl.st_step, sl.st_pos, advance_pos=advance_pos, batch=B, done=sl.st_done, eos=sl.st_eos)
         # the picked token's embedding row is written straight into the decode step's input vector
         out = dict(embed=self.W["embed"], h_out=sl.h_dec, Hd=H)
-        lp = None if logprobs is None else dict(self._lp_buffers() if single else sl.lp, K=logprobs)      # (the plan is named at the launch: rec.cut() below starts a new one)
-        pen = (self._pen_buffers() if single else sl.pen) if penalties else None
+        if single:
+            self._pick_state(step_kind(sampling, logprobs, penalties))
+        lp = None if logprobs is None else dict(self._lp if single else sl.lp, K=logprobs)      # (the plan is named at the launch: rec.cut() below starts a new one)
+        pen = (self._pen if single else sl.pen) if penalties else None
         if tp_sampled:
             row = sl.logits_row     # a batch: [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
             if p2p is not None:
@@ -770,12 +782,6 @@ class USDMForCausalLM:
         self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs, penalties=penalties)
         return rec.finish(), io
 
-    def _build_decode_p2p(self, sampling=None):
-        """The decode step of a peer-to-peer model (_build_decode builds it: way "p2p")."""
-        if self.p2p is None:
-            raise ValueError("_build_decode_p2p needs a model with a P2PComm")
-        return self._build_decode(sampling)
-
     def _build_decode(self, sampling=None, logprobs=None, penalties=False):
         """One decode step of the single sequence.  Tensor parallel with a P2PComm: the launch sequence of the single-GPU step over
         this rank's shards, o_proj / down_proj carry the exchange (_layers, way "p2p"); returned as segments cut at every exchange,
@@ -880,8 +886,8 @@ class USDMForCausalLM:
         bb = dict(kc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=cdt, device=dev),
                   vc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=cdt, device=dev),
                   nxt=i32(B), step=i32(B), pos=i32(B), out=i32(B, self.max_out), h=torch.zeros(B, H, dtype=bf, device=dev),
-                  pv=torch.zeros(B, self.nparts, dtype=torch.float32, device=dev), pi=i32(B, self.nparts), prefill=LRU(16), decode=None,
-                  decode_sampled=None, logits=torch.zeros(B, self.Vloc, dtype=torch.float32, device=dev),
+                  pv=torch.zeros(B, self.nparts, dtype=torch.float32, device=dev), pi=i32(B, self.nparts), prefill=LRU(16), steps={},
+                  logits=torch.zeros(B, self.Vloc, dtype=torch.float32, device=dev),
                   sp=ops.sample_params_tensor(dev, B).view(B, -1))
         if self.tp_path:
             # tensor parallel: pv / pi hold THIS rank's partials; the decode step gathers them rank-major into pvg / pig
@@ -920,27 +926,22 @@ class USDMForCausalLM:
         self._batches[B] = bb
         return bb
 
-    def _batch_lp(self, B):
-        """The slots' log-probability buffers, next to bb["out"] (allocated at first use); no rows-written count: batch slots have
-        no device-side `done` word, every step writes its row and the host ignores rows past a request's end."""
-        bb = self._batch_buffers(B)
-        if "lp" not in bb:
-            bb["lp"] = bb["all"].lp = logprob_buffers(self.device, self.max_out, B)
+    def _batch_pick_state(self, B, kind):
+        """The B slots' buffers with what a step of this kind needs beyond the sampler's state (allocated at first use): bb["lp"], the
+        slots' log-probability buffers next to bb["out"], and bb["pen"], their penalty state; every slot views its own row as sl.lp /
+        sl.pen.  No rows-written / tokens-counted word: batch slots have no device-side `done` word, every step writes its row and
+        counts the token of the step before, and the host ignores rows past a request's end."""
+        bb, new = self._batch_buffers(B), {}
+        if kind.logprobs is not None and "lp" not in bb:
+            new["lp"] = logprob_buffers(self.device, self.max_out, B)
+        if kind.penalties and "pen" not in bb:
+            new["pen"] = penalty_buffers(self.device, self.cfg["vocab_size"], B)
+        for name, bufs in new.items():
+            bb[name] = bufs
+            setattr(bb["all"], name, bufs)
             for b, sl in enumerate(bb["slots"]):
-                sl.lp = {k: v[b] for k, v in bb["lp"].items()}
-            bb["decode_lp"] = {}
-        return bb["lp"]
-
-    def _batch_pen(self, B):
-        """The slots' penalty state (allocated at first use); no tokens-counted word: batch slots have no device-side `done` word,
-        every step counts the token of the step before."""
-        bb = self._batch_buffers(B)
-        if "pen" not in bb:
-            bb["pen"] = bb["all"].pen = penalty_buffers(self.device, self.cfg["vocab_size"], B)
-            for b, sl in enumerate(bb["slots"]):
-                sl.pen = {k: v[b] for k, v in bb["pen"].items()}
-            bb["decode_pen"] = {}
-        return bb["pen"]
+                setattr(sl, name, {k: v[b] for k, v in bufs.items()})
+        return bb
 
     def _build_decode_batch(self, B, sampling=False, logprobs=None, penalties=False):
         """One decode step of B sequences: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
@@ -1033,52 +1034,33 @@ class USDMForCausalLM:
                                          pens[g0:g0 + group])
         return outs
 
-    def _batch_step(self, B, sampling=False, logprobs=None, penalties=False):
-        """The replayable decode step of the B slots, greedy or sampled (built at first use); logprobs=K: the sampled step followed by
-        usdm_logprobs, a plan of its own per K; penalties: the sampled step with usdm_penalize in front of the pick, a plan of its
-        own (per K too)."""
-        bb = self._batch_buffers(B)
-        if penalties:
-            self._batch_pen(B)
-            if logprobs is not None:
-                self._batch_lp(B)
-            if logprobs not in bb["decode_pen"]:
-                bb["decode_pen"][logprobs] = self._graphed(self._build_decode_batch(B, sampling=True, logprobs=logprobs, penalties=True))
-            return bb["decode_pen"][logprobs]
-        if logprobs is not None:
-            self._batch_lp(B)
-            if logprobs not in bb["decode_lp"]:
-                bb["decode_lp"][logprobs] = self._graphed(self._build_decode_batch(B, sampling=True, logprobs=logprobs))
-            return bb["decode_lp"][logprobs]
-        key = "decode_sampled" if sampling else "decode"
-        if bb[key] is None:
-            bb[key] = self._graphed(self._build_decode_batch(B, sampling=sampling))
-        return bb[key]
+    def _batch_step(self, B, kind):
+        """The replayable decode step of the B slots (built at first use), a plan / graph of its own per kind: greedy, sampled, the
+        sampled step followed by usdm_logprobs (per K), and each of the latter two with usdm_penalize in front of the pick."""
+        bb = self._batch_pick_state(B, kind)
+        if kind not in bb["steps"]:
+            bb["steps"][kind] = self._graphed(self._build_decode_batch(B, *kind))
+        return bb["steps"][kind]
 
-    def _admit(self, B, b, ids, sampling=False, logprobs=None, penalties=None):
-        """Admit a prompt (ids [L]) into slot b of the B slots: its step / position counters, then the per-item prefill into the
-        slot's cache, which also picks the first token (sampled too when the batch runs on the sampling step; logprobs=K: with row 0
-        of the slot's log-probabilities).  penalties = the request's knobs (repetition, frequency, presence) when the batch runs on
-        the penalised step - ops.PENALTY_NEUTRAL for a request without: the slot's table is reset and seeded from the prompt."""
-        bb, L = self._batch_buffers(B), int(ids.shape[0])
+    def _admit(self, B, b, ids, kind, knobs=None):
+        """Admit a prompt (ids [L]) into slot b of the B slots, whose batch runs on the step `kind`: its step / position counters,
+        then the per-item prefill into the slot's cache, which also picks the first token as that step would (sampled; with row 0 of
+        the slot's log-probabilities).  On the penalised step the slot's table is reset and seeded from the prompt, with the request's
+        knobs (repetition, frequency, presence; None: a request without, neutral)."""
+        bb, L = self._batch_pick_state(B, kind), int(ids.shape[0])
         bb["step"][b] = 0
         bb["pos"][b] = L
-        if logprobs is not None:
-            self._batch_lp(B)
-            sampling = True
-        key = (L, b, sampling) if logprobs is None else (L, b, sampling, logprobs)
-        if penalties is not None:
-            self._batch_pen(B)
-            seed_penalties(bb["slots"][b].pen, ids, penalties)
-            sampling, key = True, (L, b, True, logprobs, "penalties")
-        segs, io = bb["prefill"].get_or_build(key, lambda: self._build_prefill(L, True if sampling else None, slot=bb["slots"][b], logprobs=logprobs,
-                                                                               penalties=penalties is not None))
+        if kind.penalties:
+            seed_penalties(bb["slots"][b].pen, ids, knobs)
+        segs, io = bb["prefill"].get_or_build((L, b, *kind), lambda: self._build_prefill(L, kind.sampling or None, slot=bb["slots"][b],
+                                                                                         logprobs=kind.logprobs, penalties=kind.penalties))
         io["ids"].copy_(ids)
         self._run_segs(segs)
 
     def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None, pens=None):
         B = len(ids_list)
-        pen = pens is not None and any(k is not None for k in pens)      # one penalised sequence: the group runs on the penalised step
+        # one penalised sequence: the group runs on the penalised step
+        kind = step_kind(logprobs=logprobs, penalties=pens is not None and any(k is not None for k in pens))
         for ids in ids_list:
             if ids.dim() != 2 or ids.shape[0] != 1:
                 raise ValueError("every prompt must be a LongTensor of shape [1, L]")
@@ -1091,10 +1073,10 @@ class USDMForCausalLM:
                 self.last_logprobs += [None] * B
             return [ids.clone() for ids in ids_list]
         for b, ids in enumerate(ids_list):
-            if logprobs is not None or pen:      # greedy on the sampling step: top_k = 1 (the arg-max path has no logits row)
+            if kind.sampling:      # greedy on the sampling step: top_k = 1
                 ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
-            self._admit(B, b, ids[0], logprobs=logprobs, penalties=(pens[b] or ops.PENALTY_NEUTRAL) if pen else None)
-        decode = self._batch_step(B, logprobs=logprobs, penalties=pen)
+            self._admit(B, b, ids[0], kind, knobs=pens[b] if kind.penalties else None)
+        decode = self._batch_step(B, kind)
         eos = stop_ids(eos_token_id)
         produced, chunk = 1, 8
         ends = [None] * B
@@ -1137,22 +1119,24 @@ class USDMForCausalLM:
     def _setup_call(self, input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=None, logprobs=None,
                     penalties=None):
         """Per-call device state of generate(): prompt ids into the (cached) prefill plan, ban mask, position / step counters,
-        device-side EOS list.  Returns (prefill segments, the EOS ids the device checks)."""
-        L0 = input_ids.shape[1]
+        device-side EOS list; penalties = the knobs (repetition, frequency, presence) of a penalised call.  Returns (prefill
+        segments, the EOS ids the device checks).  (The call shape is the lockstep harnesses' too, which step several logical
+        ranks through it: it takes the three values, not the kind.)"""
+        kind = step_kind(sampling, logprobs, penalties is not None)
+        L0, sampling = input_ids.shape[1], kind.sampling
         if self.tp_path:      # keep_logits: a sampled call exposes the gathered row, a greedy one this rank's shard
             if sampling and self.last_logits is not self.logits_row:
                 self._shard_logits, self.last_logits = self.last_logits, self.logits_row
             elif not sampling and self.last_logits is self.logits_row:
                 self.last_logits = self._shard_logits
-        key = (L0 - past, past, sampling) if logprobs is None else (L0 - past, past, sampling, logprobs)
-        if penalties is not None:
-            key = (L0 - past, past, sampling, logprobs, "penalties")
+        self._pick_state(kind)
+        if kind.penalties:
             # the whole prompt is flagged, the ids whose K/V are reused from the cache included; zeroed together with st_step below
-            seed_penalties(self._pen_buffers(), input_ids[0], penalties)
-        segs, io = self._prefill_plans.get_or_build(key, lambda: self._build_prefill(L0 - past, sampling, past=past, logprobs=logprobs,
-                                                                                     penalties=penalties is not None))
-        if logprobs is not None:
-            self._lp_buffers()["count"].zero_()      # rows written so far (usdm_logprobs keys its write on it: the device-side EOS)
+            seed_penalties(self._pen, input_ids[0], penalties)
+        segs, io = self._prefill_plans.get_or_build((L0 - past, past, *kind), lambda: self._build_prefill(L0 - past, sampling, past=past,
+                                                                                                          logprobs=kind.logprobs, penalties=kind.penalties))
+        if kind.logprobs is not None:
+            self._lp["count"].zero_()      # rows written so far (usdm_logprobs keys its write on it: the device-side EOS)
         io["ids"].copy_(input_ids[0, past:])
         self._kv_ids, self._vt_upto = None, L0      # (set again once this call's decode steps are known)
         if ban_mask is not None:      # a ready-made [vocab] 0/1 mask (usdm_amd.serving: static logits processors)
@@ -1205,9 +1189,9 @@ class USDMForCausalLM:
         else:
             if (temperature != 1.0 or top_p != 1.0) and not do_sample:
                 raise ValueError("temperature / top_p only apply with do_sample=True")
-            if lpk is not None or pen is not None:
-                sampling = True
-                ops.set_sample_params(self.sample_params, 1.0, 1, 1.0, 0)
+        kind = step_kind(sampling, lpk, pen is not None)
+        if kind.sampling and not sampling:      # greedy on the sampling step: top_k = 1
+            ops.set_sample_params(self.sample_params, 1.0, 1, 1.0, 0)
         L0 = input_ids.shape[1]
         if max_new_tokens is None:
             if max_length is None:
@@ -1231,16 +1215,12 @@ class USDMForCausalLM:
             if past > self._vt_upto:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers
                 a0 = self._vt_upto
                 self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
-        segs, dev_eos = self._setup_call(input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,
+        segs, dev_eos = self._setup_call(input_ids, past, kind.sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,
                                           logprobs=lpk, penalties=pen)
         self._run_segs(segs)  # prefill + first token
-        dkey = sampling if lpk is None else (sampling, lpk)      # the step with log-probabilities: a plan / graph of its own per K
-        if pen is not None:                                      # ... and the penalised step
-            dkey = (sampling, lpk, "penalties")
-        if dkey not in self._decodes:      # (the hooked step has host code inside: never captured)
-            self._decodes[dkey] = self._graphed(self._build_decode(sampling, logprobs=lpk, penalties=pen is not None),
-                                                enabled=False if sampling == "hook" else None)
-        self._decode = self._decodes[dkey]
+        if kind not in self._decodes:      # a plan / graph of its own per kind (the hooked step has host code inside: never captured)
+            self._decodes[kind] = self._graphed(self._build_decode(*kind), enabled=False if kind.sampling == "hook" else None)
+        self._decode = self._decodes[kind]
         eos = stop_ids(eos_token_id)
         produced, done, chunk = 1, False, 8
         toks = []

@@ -368,6 +368,23 @@ def set_sample_params(t, temperature, top_k, top_p, seed):
     t.copy_(torch.frombuffer(bytearray(bytes(p)), dtype=torch.uint8))
 
 
+def _logits_row(who, a, logits, st, V, nseg, seg_stride, seg_len):
+    """The f32 logits row(s) of a pick kernel (csrc/logits_row.h): checks the tensor, fills a.logits / a.V / a.logits_bs and returns
+    whether the segmented entry point (usdm_*_seg) is the one to call."""
+    a.logits, a.V = _ptr(logits), logits.shape[-1] if V is None else V
+    if logits.dtype != torch.float32 or logits.stride(-1) != 1:
+        raise ValueError(f"{who}: logits must be float32 with unit inner stride")
+    if seg_len > 0:
+        if nseg < 1 or not logits.is_contiguous() or logits.shape[-1] != seg_len or logits.numel() < (nseg - 1) * seg_stride + max(1, st.batch) * seg_len:
+            raise ValueError(f"segmented {who}: logits must be a contiguous [nseg][B][seg_len] tensor")
+        a.logits_bs = seg_len
+        return True
+    if logits.dim() > 2 or a.V > logits.shape[-1]:
+        raise ValueError(f"{who}: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
+    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
+    return False
+
+
 def sample_final(logits, st, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, probs_out=None, embed=None, h_out=None, Hd=0,
                  dev_params=None, V=None, nseg=1, seg_stride=0, seg_len=0, plan=None):
     """usdm_sample_final: temperature / top-k / top-p sampling of one token from ban-masked f32 logits.
@@ -378,20 +395,15 @@ def sample_final(logits, st, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, pro
     sequence b's id i is read at (i // seg_len) * seg_stride + b * seg_len + i % seg_len; probs_out is [B][V]."""
     _need_cuda(logits, probs_out, embed, h_out, dev_params)
     a = SampleArgs()
-    a.logits, a.V, a.temperature, a.top_k, a.top_p = _ptr(logits), logits.shape[-1] if V is None else V, temperature, top_k, top_p
+    seg = _logits_row("sample_final", a, logits, st, V, nseg, seg_stride, seg_len)
+    a.temperature, a.top_k, a.top_p = temperature, top_k, top_p
     a.seed, a.probs_out, a.dev_params = seed, _ptr(probs_out), _ptr(dev_params)
     if probs_out is not None and probs_out.numel() < max(1, st.batch) * a.V:
         raise ValueError("sample_final: probs_out holds fewer than batch * V values")
-    if seg_len > 0:
-        if nseg < 1 or not logits.is_contiguous() or logits.shape[-1] != seg_len or logits.numel() < (nseg - 1) * seg_stride + max(1, st.batch) * seg_len:
-            raise ValueError("segmented sample_final: logits must be a contiguous [nseg][B][seg_len] tensor")
-        a.logits_bs = seg_len
+    if seg:
         _go(plan, "usdm_sample_final_seg", lib.usdm_sample_final_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride),
             C_.c_int32(seg_len), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
         return
-    if logits.dim() > 2 or a.V > logits.shape[-1]:
-        raise ValueError("sample_final: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
-    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
     _go(plan, "usdm_sample_final", lib.usdm_sample_final, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
 
 
@@ -407,7 +419,8 @@ def logprobs(logits, st, *, K, tok_lp, tok_rank, top_id=None, top_lp=None, count
     _need_cuda(logits, tok_lp, tok_rank, top_id, top_lp, count)
     B = max(1, st.batch)
     a = LogprobArgs()
-    a.logits, a.V, a.K = _ptr(logits), logits.shape[-1] if V is None else V, int(K)
+    seg = _logits_row("logprobs", a, logits, st, V, nseg, seg_stride, seg_len)
+    a.K = int(K)
     a.tok_lp, a.tok_rank, a.top_id, a.top_lp, a.count = _ptr(tok_lp), _ptr(tok_rank), _ptr(top_id), _ptr(top_lp), _ptr(count)
     for name, t, dt, per in (("tok_lp", tok_lp, torch.float32, 1), ("tok_rank", tok_rank, torch.int32, 1),
                              ("top_id", top_id, torch.int32, a.K), ("top_lp", top_lp, torch.float32, a.K)):
@@ -422,15 +435,9 @@ def logprobs(logits, st, *, K, tok_lp, tok_rank, top_id=None, top_lp=None, count
     a.top_bs = top_id.stride(0) if (B > 1 and top_id is not None) else 0
     if B > 1 and (tok_rank is not None and tok_rank.stride(0) != a.tok_bs or top_lp is not None and top_lp.stride(0) != a.top_bs):
         raise ValueError("logprobs: tok_lp / tok_rank and top_id / top_lp must share their per-sequence strides")
-    if seg_len > 0:
-        if nseg < 1 or not logits.is_contiguous() or logits.shape[-1] != seg_len or logits.numel() < (nseg - 1) * seg_stride + B * seg_len:
-            raise ValueError("segmented logprobs: logits must be a contiguous [nseg][B][seg_len] tensor")
-        a.logits_bs = seg_len
+    if seg:
         _go(plan, "usdm_logprobs_seg", lib.usdm_logprobs_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len), C_.byref(st))
         return
-    if logits.dim() > 2 or a.V > logits.shape[-1]:
-        raise ValueError("logprobs: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
-    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
     _go(plan, "usdm_logprobs", lib.usdm_logprobs, C_.byref(a), C_.byref(st))
 
 
@@ -470,10 +477,8 @@ def penalize(logits, st, *, table, dev_params, count=None, V=None, nseg=1, seg_s
     _need_cuda(logits, table, dev_params, count)
     B = max(1, st.batch)
     a = PenaltyArgs()
-    a.logits, a.V = _ptr(logits), logits.shape[-1] if V is None else V
+    seg = _logits_row("penalize", a, logits, st, V, nseg, seg_stride, seg_len)
     a.table, a.dev_params, a.count = _ptr(table), _ptr(dev_params), _ptr(count)
-    if logits.dtype != torch.float32:
-        raise ValueError("penalize: logits must be float32")
     if table is not None:
         rows = table if B == 1 else table[0]
         if table.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < a.V or (B > 1 and (table.dim() != 2 or table.shape[0] < B)):
@@ -483,15 +488,9 @@ def penalize(logits, st, *, table, dev_params, count=None, V=None, nseg=1, seg_s
         raise ValueError("penalize: dev_params must be a penalty_params_tensor of [batch] blocks")
     if count is not None and (count.dtype != torch.int32 or count.numel() < B):
         raise ValueError("penalize: count must be int32 [batch]")
-    if seg_len > 0:
-        if nseg < 1 or not logits.is_contiguous() or logits.shape[-1] != seg_len or logits.numel() < (nseg - 1) * seg_stride + B * seg_len:
-            raise ValueError("segmented penalize: logits must be a contiguous [nseg][B][seg_len] tensor")
-        a.logits_bs = seg_len
+    if seg:
         _go(plan, "usdm_penalize_seg", lib.usdm_penalize_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len), C_.byref(st))
         return
-    if logits.dim() > 2 or a.V > logits.shape[-1] or logits.stride(-1) != 1:
-        raise ValueError("penalize: logits must be [V] or [B][>= V] (a segmented row needs seg_len)")
-    a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
     _go(plan, "usdm_penalize", lib.usdm_penalize, C_.byref(a), C_.byref(st))
 
 

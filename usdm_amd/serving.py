@@ -35,7 +35,7 @@ from collections import deque
 import torch
 
 from . import ops
-from .llm import USDMForCausalLM, check_logprobs, check_penalties, check_quantization, read_logprobs, stop_index
+from .llm import USDMForCausalLM, check_logprobs, check_penalties, check_quantization, read_logprobs, step_kind, stop_index
 from .quant import check_kv_cache_dtype
 
 MAX_SLOTS = 16      # usdm_gemv_batch streams the weights once per step for up to 16 sequences (matrix-core form above 4)
@@ -317,8 +317,8 @@ class LLM:
         # one penalised request -> the whole group runs on the penalised step (usdm_penalize + the sampling step); the other
         # requests and the idle slots carry neutral knobs
         pen = any(r["sp"].penalties is not None for r in grp)
-        sampled = lpk is not None or pen or any(not r["sp"].greedy for r in grp)       # one sampled request -> the whole group runs on the sampling graph
-        decode = llm._batch_step(nslots, sampling=sampled, logprobs=lpk, penalties=pen)
+        kind = step_kind(any(not r["sp"].greedy for r in grp), lpk, pen)       # one sampled request -> the whole group runs on the sampling graph
+        decode = llm._batch_step(nslots, kind)
         if pen:
             for b in range(nslots):
                 ops.set_penalty_params(bb["pen"]["dev_params"][b])
@@ -337,8 +337,7 @@ class LLM:
                         ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
                     else:
                         ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"])
-                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), sampling=sampled, logprobs=lpk,
-                               penalties=(sp.penalties or ops.PENALTY_NEUTRAL) if pen else None)      # (+ first token)
+                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), kind, knobs=sp.penalties)      # (+ first token)
                     slots[b] = dict(r=r, produced=1)
                     self.stats["admissions"] += 1
             active = [b for b in range(nslots) if slots[b] is not None]
