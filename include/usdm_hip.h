@@ -408,9 +408,14 @@ int usdm_argmax_final_seg(const float* part_val, const int32_t* part_idx, int32_
  * top_k = 0 and top_p = 1 switch the filters off.  Ties at a filter boundary are kept or dropped as a block (HF's
  * unstable sort picks arbitrarily).  probs_out (optional, [V]) receives the filtered, renormalised distribution.
  * If no id has positive mass (every logit banned or NaN) the arg-max of the finite logits is taken, else id 0: the
- * kernel never emits an id outside [0, V). */
+ * kernel never emits an id outside [0, V).
+ * min_p (HF MinPLogitsWarper, vLLM; 0 = off): after temperature, top-k and top-p an id is dropped when p_i < min_p * p_max.  The
+ * ratio p_i / p_max = exp(x_i / T - max / T) does not change under renormalisation and the maximum survives top-k and top-p, so the
+ * kept set is the intersection of the top-k test, the top-p test and e_i >= min_p, e_i being the f32 softmax numerator of the other
+ * stages; draw and probs_out honour it.  With top_k = 1 it changes nothing. */
 typedef struct usdm_sample_params {   /* the per-request knobs (vLLM SamplingParams of inference_vllm.py:42-66) */
-  float temperature; int32_t top_k; float top_p; int32_t reserved;
+  float temperature; int32_t top_k; float top_p;
+  float min_p;   /* in [0, 1]; zero bits = off.  A device value outside the range (NaN included) is taken as 0 */
   uint64_t seed;
 } usdm_sample_params;
 typedef struct usdm_sample_args {
@@ -425,6 +430,7 @@ typedef struct usdm_sample_args {
    * words [b] and writes h_out + b * Hd; its Philox counter is ITS step, so its tokens equal those of the single-sequence call
    * (per-slot sampling inside a continuous batch: src/inference_vllm.py:109-123 passes one SamplingParams per request). */
   int64_t logits_bs;
+  float min_p;   /* [0, 1], 0 = off (dev_params: the block's) */
 } usdm_sample_args;
 int usdm_sample_final(const usdm_sample_args* args, const usdm_decode_state* st, const void* embed_table_bf16, int32_t Hd,
                       void* h_out_bf16, usdm_stream_t stream);
@@ -499,6 +505,41 @@ int usdm_penalize_seg(const usdm_penalty_args* args, int32_t nseg, int64_t seg_s
 int usdm_penalty_params_init(usdm_penalty_params* out, float repetition, float frequency, float presence);
 int usdm_sizeof_penalty_args(void);
 int usdm_sizeof_penalty_params(void);
+
+/* Additive logit bias and the n-gram ban of the step whose token usdm_sample_final is ABOUT to pick, applied in place to the
+ * ban-masked f32 row it will read, in front of usdm_penalize (HF's and vLLM's order: bias, then penalties), a host logits hook and
+ * the pick.  One workgroup per sequence, two phases with a barrier between them:
+ *   1. bias (OpenAI / vLLM logit_bias, HF SequenceBiasLogitsProcessor with single-token keys): for t < n_bias
+ *        x[bias_id[t]] = x[bias_id[t]] + bias_val[t]          one f32 add; -inf stays -inf, NaN stays NaN
+ *      The ids of a sequence are distinct (the caller's duty); entries outside [0, V) are ignored.  n_bias <= bias_max <= 1024.
+ *   2. n-gram ban (HF NoRepeatNGramLogitsProcessor, no_repeat_ngram_size = n >= 1): the history is the prompt followed by the tokens
+ *      generated so far, hist[j] = j < P ? prompt[j] : out_tokens[j - P] - st->id_offset, of length Lh = P + *st->step, read where it
+ *      lives (no copy is kept).  When Lh >= n: for every j in 0 .. Lh - n with hist[j .. j+n-2] equal to the last n - 1 tokens,
+ *        x[hist[j+n-1]] = -inf
+ *      (n = 1: the tail is empty and every id of the history is banned).  An id that is both biased and banned ends at -inf.  The
+ *      prefill's pick has *st->step = 0: its history is the prompt.  *st->step above st->max_out counts as max_out.
+ * Per-sequence state, all DEVICE memory rewritten by the host per request, so plans and graphs never depend on the values:
+ * dev_params[b] = {ngram n (<= 0: off), prompt_len P (0 .. prompt_max), n_bias}, the rows bias_id / bias_val and the row prompt.
+ * A sequence with n_bias = 0 and n <= 0 (a zero-filled block) neither reads nor writes its row.  With a device-side st->done the
+ * launch returns at once when done[b] != 0. */
+typedef struct usdm_logit_edit_params { int32_t ngram, prompt_len, n_bias, reserved; } usdm_logit_edit_params;
+typedef struct usdm_logit_edit_args {
+  float* logits; int32_t V;
+  int64_t logits_bs;        /* batched (st->batch > 1): sequence b's row is logits + b * logits_bs */
+  const usdm_logit_edit_params* dev_params;   /* [batch], 16-byte aligned */
+  const int32_t* bias_id; const float* bias_val;
+  int32_t bias_max;         /* entries a bias row holds, 0 .. 1024 (0: the rows may be NULL) */
+  int64_t bias_bs;          /* batched: sequence b's bias rows are bias_id + b * bias_bs, bias_val + b * bias_bs (>= bias_max) */
+  const int32_t* prompt;
+  int32_t prompt_max;       /* ids a prompt row holds (0: the row may be NULL) */
+  int64_t prompt_bs;        /* batched: sequence b's prompt row is prompt + b * prompt_bs (>= prompt_max) */
+} usdm_logit_edit_args;
+int usdm_logit_edit(const usdm_logit_edit_args* args, const usdm_decode_state* st, usdm_stream_t stream);
+/* The same over a row of nseg segments, addressed as usdm_sample_final_seg addresses it (ids >= V never read or written). */
+int usdm_logit_edit_seg(const usdm_logit_edit_args* args, int32_t nseg, int64_t seg_stride, int32_t seg_len, const usdm_decode_state* st,
+                        usdm_stream_t stream);
+int usdm_sizeof_logit_edit_args(void);
+int usdm_sizeof_logit_edit_params(void);
 
 /* out[r][:] = table[ids[r]][:] (bf16 rows; ids == NULL -> single row from *next_token) */
 int usdm_embed_rows(const void* table, const int64_t* ids, const int32_t* next_token, int32_t n, int32_t Hd,

@@ -31,6 +31,8 @@ lib.usdm_logprobs_seg.restype = C.c_int
 lib.usdm_penalize.restype = C.c_int          # (the penalty entry points: likewise)
 lib.usdm_penalize_seg.restype = C.c_int
 lib.usdm_penalty_params_init.restype = C.c_int
+lib.usdm_logit_edit.restype = C.c_int        # (the logit-edit entry points: likewise)
+lib.usdm_logit_edit_seg.restype = C.c_int
 _exp = None
 
 
@@ -181,13 +183,14 @@ class P2pDev(C.Structure):
 
 
 class SampleParams(C.Structure):
-    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("seed", C.c_uint64)]
 
 
 class SampleArgs(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p), ("V", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
         ("seed", C.c_uint64), ("probs_out", C.c_void_p), ("dev_params", C.c_void_p), ("logits_bs", C.c_int64),
+        ("min_p", C.c_float),
     ]
 
 
@@ -207,6 +210,18 @@ class PenaltyArgs(C.Structure):
     _fields_ = [
         ("logits", C.c_void_p), ("V", C.c_int32), ("logits_bs", C.c_int64), ("table", C.c_void_p), ("table_bs", C.c_int64),
         ("dev_params", C.c_void_p), ("count", C.c_void_p),
+    ]
+
+
+class LogitEditParams(C.Structure):
+    _fields_ = [("ngram", C.c_int32), ("prompt_len", C.c_int32), ("n_bias", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LogitEditArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("V", C.c_int32), ("logits_bs", C.c_int64), ("dev_params", C.c_void_p),
+        ("bias_id", C.c_void_p), ("bias_val", C.c_void_p), ("bias_max", C.c_int32), ("bias_bs", C.c_int64),
+        ("prompt", C.c_void_p), ("prompt_max", C.c_int32), ("prompt_bs", C.c_int64),
     ]
 
 
@@ -254,12 +269,14 @@ def _selfcheck():
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
-                      ("penalty", PenaltyArgs)):
+                      ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")
     if lib.usdm_sizeof_penalty_params() != C.sizeof(PenaltyParams):
         raise ImportError("ABI mismatch: usdm_penalty_params")
+    if lib.usdm_sizeof_logit_edit_params() != C.sizeof(LogitEditParams):
+        raise ImportError("ABI mismatch: usdm_logit_edit_params")
 
 
 _selfcheck()

@@ -1,4 +1,4 @@
-// The f32 logits row of one sequence as the pick kernels (sample_k.hip, logprob_k.hip, penalty_k.hip) address it, plus the host-side
+// The f32 logits row of one sequence as the pick kernels (sample_k.hip, logprob_k.hip, penalty_k.hip, edit_k.hip) address it, plus the host-side
 // checks of its shape.
 //
 // SEG = false: the row is contiguous, id i sits at row[i].  SEG = true: it is made of rank-major segments of seg_len ids, seg_stride
@@ -20,16 +20,20 @@ struct logits_row_view {   // built inside the kernel from its three scalar para
   unsigned seg_magic;
 };
 
-template <bool SEG>
-__device__ __forceinline__ float row_at(const float* row, int i, const logits_row_view& v) {   // logit of id i (0 <= i < V)
+// where id i (0 <= i < V) sits (P = const float*, or float* for a kernel that writes in place)
+template <bool SEG, typename P>
+__device__ __forceinline__ P row_ptr(P row, int i, const logits_row_view& v) {
   if constexpr (SEG) {
     unsigned q = __umulhi((unsigned)i, v.seg_magic);
     if (q * (unsigned)v.seg_len > (unsigned)i) --q;
-    return row[(int64_t)q * v.seg_stride + (i - (int)q * v.seg_len)];
+    return row + ((int64_t)q * v.seg_stride + (i - (int)q * v.seg_len));
   } else {
-    return row[i];
+    return row + i;
   }
 }
+
+template <bool SEG>
+__device__ __forceinline__ float row_at(const float* row, int i, const logits_row_view& v) { return *row_ptr<SEG>(row, i, v); }   // logit of id i
 
 // f(i, pointer to id i) for i = tid, tid + NT, ... < V (P = const float*, or float* for a kernel that writes in place).  The segmented
 // form divides once and then walks a pointer, stepping over the gap between two segments when it crosses one (seg_len >= NT: at most

@@ -9,6 +9,7 @@
 //   top-k  : radix select (4 x 8 bits) of the k-th largest key with integer histograms;
 //   top-p  : radix select over the ascending exp(x - max) keys with FIXED-POINT mass histograms (u64 LDS atomics are
 //            associative, so the kept set does not depend on thread scheduling); ties are kept or dropped as a block;
+//   min-p  : HF MinPLogitsWarper / vLLM: ids with p_i < min_p * p_max are dropped, by raising the top-p stage's key threshold;
 //   draw   : u * kept_mass located by an exclusive scan over contiguous index ranges (index order, deterministic).
 #include "logits_row.h"
 #include "../../include/usdm_hip.h"
@@ -71,6 +72,7 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     if (!(a.temperature > 0.f)) a.temperature = 1.0f;
     if (!(a.top_p > 0.f) || a.top_p > 1.0f) a.top_p = 1.0f;
     if (a.top_k < 0) a.top_k = 0;
+    a.min_p = (a.dev_params->min_p >= 0.f && a.dev_params->min_p <= 1.0f) ? a.dev_params->min_p : 0.f;   // (NaN fails both)
   }
   const float invT = 1.0f / a.temperature;   // HF divides; x / T and x * (1 / T) differ by <= 1 ulp, below the logits' bf16 grain
   const logits_row_view rv{seg_stride, seg_len, seg_magic};
@@ -164,6 +166,9 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     }
     pkey = prefix;
   }
+  // ---- min-p: drop e_i < min_p (e_i = p_i / p_max; the maximum has e = 1 and survives top-k and top-p, so the kept set is the
+  // intersection).  Keys of positive floats are ordered like the floats, so the f32 test e >= min_p is one more bound on the key
+  if (a.min_p > 0.f) pkey = max(pkey, __float_as_uint(a.min_p));
   // ---- draw: contiguous index ranges, exclusive scan of the kept fixed-point masses
   const int per = (V + NT - 1) / NT;
   const int i0 = tid * per, i1 = min(V, i0 + per);
@@ -259,6 +264,7 @@ int check_sample(const usdm_sample_args* pa, const usdm_decode_state* st, const 
   USDM_CHECK_ARG(pa && pa->logits && pa->V > 0 && pa->V <= (1 << 20), "%s: logits / V", who);
   USDM_CHECK_ARG(pa->dev_params || (pa->temperature > 0.f && pa->top_p > 0.f && pa->top_p <= 1.0f && pa->top_k >= 0),
                  "%s: temperature > 0, 0 < top_p <= 1, top_k >= 0 (0 = off)", who);
+  USDM_CHECK_ARG(pa->dev_params || (pa->min_p >= 0.f && pa->min_p <= 1.0f), "%s: min_p must be in [0, 1] (0 = off)", who);
   USDM_CHECK_ARG(st && st->next_token && st->out_tokens && st->step && st->pos, "%s: decode state", who);
   USDM_CHECK_ARG(!embed_table || (h_out && Hd > 0 && Hd % 8 == 0), "%s: embedding output missing", who);
   return 0;

@@ -78,10 +78,12 @@ def _bad(name, *a, **k):
 
 @torch.inference_mode()
 def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, output_path,
-           reference_mel=None, n_timesteps=50, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+           reference_mel=None, n_timesteps=50, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+           min_p=0.0, logit_bias=None, no_repeat_ngram_size=0):
     """src/inference.py:48-89.  logprobs=K (0 .. 20): the LLM also computes per-token log-probabilities (USDMForCausalLM.generate) and the
     cumulative log-probability of each of the three rounds goes to stderr; nothing else changes.
-    repetition_penalty / presence_penalty / frequency_penalty: passed to all three rounds (USDMForCausalLM.generate; on the device)."""
+    repetition_penalty / presence_penalty / frequency_penalty: passed to all three rounds (USDMForCausalLM.generate; on the device).
+    min_p / logit_bias / no_repeat_ngram_size: likewise (the rounds pick with top_k = 1, where min_p changes nothing)."""
     bad_words_ids_unit2text = _bad("u2t", 32000, 42003)
     bad_words_ids_text2text = _bad("t2t", 32002, 42003)
     bad_words_ids_text2unit = _bad("t2u", 0, 32002, exclude=[28705])
@@ -94,7 +96,8 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
         ids = torch.LongTensor(tokenizer(model_input).input_ids).to(device).unsqueeze(0)
         out = model.generate(input_ids=ids, max_length=tokenizer.model_max_length, do_sample=True, bad_words_ids=bad,
                              top_p=1.0, top_k=1, temperature=1.0, eos_token_id=eos, logprobs=logprobs,
-                             repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+                             repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                             min_p=min_p, logit_bias=logit_bias, no_repeat_ngram_size=no_repeat_ngram_size)
         lp = model.last_logprobs
         if lp is not None:
             print(f"{name}: {lp.token_logprobs.numel()} tokens, cumulative log-probability {lp.cumulative:.4f}", file=sys.stderr)
@@ -121,6 +124,23 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
                                reference_mel=reference_mel, reference_unit=reference_unit)
     write(output_path, vocoder.h.sampling_rate, audio)
     return audio
+
+
+def parse_logit_bias(text):
+    """--logit_bias: a JSON object {"token id": bias} -> {int id: bias} (None: no bias); anything else is a ValueError."""
+    if text is None:
+        return None
+    import json
+    try:
+        obj = json.loads(text)
+    except ValueError as e:
+        raise ValueError(f"logit_bias is not JSON: {e}") from None
+    if not isinstance(obj, dict):
+        raise ValueError("logit_bias must be a JSON object {\"token id\": bias}")
+    try:
+        return {int(k): v for k, v in obj.items()}
+    except ValueError:
+        raise ValueError("logit_bias: every key must be an integer token id") from None
 
 
 def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None, kv_cache_dtype=None):
@@ -175,10 +195,21 @@ def main(argv=None):
                         help="Presence penalty of the three LLM rounds, in [-2, 2]; 0 = off (vLLM: ids generated so far).")
     parser.add_argument('--frequency_penalty', type=float, default=0.0,
                         help="Frequency penalty of the three LLM rounds, in [-2, 2]; 0 = off (vLLM: per occurrence among the ids generated so far).")
+    parser.add_argument('--min_p', type=float, default=0.0,
+                        help="min-p of the three LLM rounds, in [0, 1]; 0 = off (HF / vLLM: drops ids with p < min_p * p_max; the rounds "
+                             "pick with top_k = 1, where it changes nothing).")
+    parser.add_argument('--no_repeat_ngram_size', type=int, default=0,
+                        help="HF no_repeat_ngram_size of the three LLM rounds: no n-gram of this size occurs twice in prompt + output; 0 = off.")
+    parser.add_argument('--logit_bias', type=str, default=None, metavar="JSON",
+                        help='Additive logit bias of the three LLM rounds as a JSON object {"token id": bias}, at most 1024 entries, '
+                             'values clamped to [-100, 100] (OpenAI / vLLM).')
     args = parser.parse_args(argv)
-    from .llm import check_penalties
+    from .llm import check_edits, check_min_p, check_penalties
     try:
         check_penalties(args.repetition_penalty, args.presence_penalty, args.frequency_penalty)
+        check_min_p(args.min_p)
+        logit_bias = parse_logit_bias(args.logit_bias)
+        check_edits(logit_bias, args.no_repeat_ngram_size)
     except ValueError as e:
         parser.error(str(e))
 
@@ -187,7 +218,8 @@ def main(argv=None):
                                                                          kv_cache_dtype=args.kv_cache_dtype)
     try:
         sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path, logprobs=args.logprobs,
-               repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty)
+               repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty,
+               min_p=args.min_p, logit_bias=logit_bias, no_repeat_ngram_size=args.no_repeat_ngram_size)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)
         print(f"Error while sampling: {e}")
         return 1

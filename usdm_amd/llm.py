@@ -128,16 +128,68 @@ def check_penalties(repetition_penalty=1.0, presence_penalty=0.0, frequency_pena
     return None if knobs == ops.PENALTY_NEUTRAL else knobs
 
 
-StepKind = namedtuple("StepKind", "sampling logprobs penalties")
+def check_min_p(min_p):
+    """generate()'s / SamplingParams' min_p (HF MinPLogitsWarper, vLLM): a number in [0, 1], 0 = off."""
+    try:
+        v = float(min_p)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(min_p, bool) or not 0.0 <= v <= 1.0:
+        raise ValueError(f"min_p must be a number in [0, 1] (0 = off), got {min_p!r}")
+    return v
 
 
-def step_kind(sampling=None, logprobs=None, penalties=False):
+LOGIT_BIAS_CLAMP = 100.0      # vLLM's and OpenAI's range of a logit_bias value
+
+
+def check_edits(logit_bias=None, no_repeat_ngram_size=0, vocab=None):
+    """generate()'s / SamplingParams' logit_bias and no_repeat_ngram_size -> None when both are neutral (no edit plan is built), else
+    (bias, n): bias a tuple of (id, value) pairs in ascending id order, the values clamped to [-100, 100] (vLLM's and OpenAI's
+    range), n the n-gram size (0 = off).  logit_bias: None or a dict of at most 1024 integer ids in [0, vocab) (vocab=None: the
+    caller does not know it yet, >= 0) to finite numbers; no_repeat_ngram_size: None or an integer >= 0.  Anything else is a
+    ValueError."""
+    n = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"no_repeat_ngram_size must be None or an integer >= 0, got {no_repeat_ngram_size!r}")
+    if logit_bias is None:
+        logit_bias = {}
+    if not isinstance(logit_bias, dict):
+        raise ValueError(f"logit_bias must be None or a dict {{token id: bias}}, got {type(logit_bias).__name__}")
+    if len(logit_bias) > ops.LOGIT_BIAS_MAX:
+        raise ValueError(f"logit_bias holds {len(logit_bias)} entries, at most {ops.LOGIT_BIAS_MAX} are supported")
+    bias = []
+    for i, v in logit_bias.items():
+        if isinstance(i, bool) or not isinstance(i, int) or i < 0 or (vocab is not None and i >= vocab):
+            raise ValueError(f"logit_bias: token id {i!r} is not an integer in [0, {'vocab' if vocab is None else vocab})")
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if isinstance(v, bool) or not math.isfinite(f):
+            raise ValueError(f"logit_bias: the bias of token {i} must be a finite number, got {v!r}")
+        bias.append((i, max(-LOGIT_BIAS_CLAMP, min(LOGIT_BIAS_CLAMP, f))))
+    return (tuple(sorted(bias)), n) if (bias or n) else None
+
+
+def _per_sequence(value, n):
+    """A generate_batch knob: one value (a number, a dict, None) for all n sequences, or a list with one per sequence."""
+    per = list(value) if isinstance(value, (list, tuple)) else [value] * n
+    if len(per) != n:
+        raise ValueError("a sampling knob is one value for all sequences or a list with one value per sequence")
+    return per
+
+
+StepKind = namedtuple("StepKind", "sampling logprobs penalties edits", defaults=(False,))
+
+
+def step_kind(sampling=None, logprobs=None, penalties=False, edits=False):
     """Which variant of a step (the prefill's pick, the decode step) runs: the key of every cache of built plans, in the builders'
     argument order.  sampling: False = the ban-masked arg-max, True = usdm_sample_final, "hook" = Python logits processors in front
-    of it; logprobs: None or K; penalties: whether usdm_penalize runs.  Log-probabilities and penalties work on the logits row, which
-    only the sampling step materialises, so either turns a greedy step into the sampling step (run with top_k = 1: the same ids)."""
+    of it; logprobs: None or K; penalties: whether usdm_penalize runs; edits: whether usdm_logit_edit (logit bias, n-gram ban) runs.
+    Log-probabilities, penalties and edits work on the logits row, which only the sampling step materialises, so each turns a greedy
+    step into the sampling step (run with top_k = 1: the same ids)."""
     sampling = "hook" if sampling == "hook" else bool(sampling)
-    return StepKind(sampling or logprobs is not None or bool(penalties), logprobs, bool(penalties))
+    return StepKind(sampling or logprobs is not None or bool(penalties) or bool(edits), logprobs, bool(penalties), bool(edits))
 
 
 def penalty_buffers(device, V, B=None):
@@ -159,6 +211,31 @@ def seed_penalties(bufs, prompt_ids, knobs):
     tbl[prompt_ids.to(tbl.device, torch.long)] = ops.PENALTY_PROMPT_BIT
     if "count" in bufs:
         bufs["count"].zero_()
+
+
+def edit_buffers(device, ctx_max, B=None):
+    """usdm_logit_edit's state for one sequence (B=None) or B batch slots: the device block of the knobs (zero-filled = neutral), the
+    bias rows of ops.LOGIT_BIAS_MAX entries and the prompt row of ctx_max ids."""
+    lead = () if B is None else (B,)
+    return dict(dev_params=ops.edit_params_tensor(device, B or 1).view(*lead, -1),
+                bias_id=torch.zeros(*lead, ops.LOGIT_BIAS_MAX, dtype=torch.int32, device=device),
+                bias_val=torch.zeros(*lead, ops.LOGIT_BIAS_MAX, dtype=torch.float32, device=device),
+                prompt=torch.zeros(*lead, ctx_max, dtype=torch.int32, device=device))
+
+
+def seed_edits(bufs, prompt_ids, knobs):
+    """A new request for this sequence / slot: its bias list, n-gram size and prompt (ids whose K/V were reused from the cache
+    included); knobs = check_edits()'s (bias, n) or None: a request without, neutral.  Plain torch calls, outside the captured graphs."""
+    bias, n = knobs or ((), 0)
+    P = int(prompt_ids.shape[0]) if n else 0      # (the bias needs no history)
+    if P > bufs["prompt"].shape[-1]:
+        raise ValueError(f"the prompt of {P} ids does not fit the prompt row of {bufs['prompt'].shape[-1]}")
+    if bias:
+        bufs["bias_id"][:len(bias)] = torch.tensor([i for i, _ in bias], dtype=torch.int32)
+        bufs["bias_val"][:len(bias)] = torch.tensor([v for _, v in bias], dtype=torch.float32)
+    if P:
+        bufs["prompt"][:P] = prompt_ids.to(bufs["prompt"].device, torch.int32)
+    ops.set_edit_params(bufs["dev_params"], n, P, len(bias))
 
 
 class TokenLogprobs:
@@ -362,6 +439,7 @@ class USDMForCausalLM:
         self._lp = None           # log-probability rows of the single sequence (logprob_buffers; allocated at first use)
         self.last_logprobs = None  # generate(logprobs=K): TokenLogprobs of the last call (generate_batch: a list); None when not asked
         self._pen = None          # penalty state of the single sequence (penalty_buffers; allocated at first use)
+        self._edt = None          # logit-edit state of the single sequence (edit_buffers; allocated at first use)
 
     # ------------------------------------------------------------------ weights
     def _shard(self, sd_get):
@@ -592,9 +670,11 @@ class USDMForCausalLM:
             self._lp = logprob_buffers(self.device, self.max_out)
         if kind.penalties and self._pen is None:
             self._pen = penalty_buffers(self.device, self.cfg["vocab_size"])
+        if kind.edits and self._edt is None:
+            self._edt = edit_buffers(self.device, self.ctx_max)
 
     def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None, logprobs=None,
-                          penalties=False):
+                          penalties=False, edits=False):
         """lm_head GEMV + token choice, for the single sequence (slot=None), a batch slot's prefill, and the batched step
         (slot = the batch's "all" view, batch_gemv = its projection launcher).  sampling=None: ban-masked arg-max (the reference's
         top_k=1 path); sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block sample_params
@@ -607,12 +687,17 @@ class USDMForCausalLM:
         penalties (sampled picks only): usdm_penalize on the row the sampler will read, BEFORE the hook and the pick - it counts the
         previous step's token into the sequence's / the slots' table and applies the knobs of their device block (tensor parallel: on
         the gathered row, on every rank; the table holds global ids and is the same on all ranks, so every rank still draws the
-        same token).  The hook, the log-probabilities and last_logits see the penalised row."""
+        same token).  The hook, the log-probabilities and last_logits see the penalised row.
+        edits (sampled picks only): usdm_logit_edit directly in front of usdm_penalize (HF's and vLLM's order: bias, then penalties) -
+        the logit bias and the n-gram ban of the sequence's / the slots' edit state (tensor parallel: on the gathered row, on every
+        rank, with global ids).  Everything after it sees the edited row."""
         c, H = self.cfg, self.cfg["hidden_size"]
         if logprobs is not None and not sampling:
             raise ValueError("log-probabilities need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
         if penalties and not sampling:
             raise ValueError("penalties need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
+        if edits and not sampling:
+            raise ValueError("logit edits need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
         sl = slot or self   # where the picked token, the decode state and the next input row live (self = the single sequence)
         single = sl is self
         B = 0 if single else sl.batch
@@ -640,9 +725,10 @@ class USDMForCausalLM:
         # the picked token's embedding row is written straight into the decode step's input vector
         out = dict(embed=self.W["embed"], h_out=sl.h_dec, Hd=H)
         if single:
-            self._pick_state(step_kind(sampling, logprobs, penalties))
+            self._pick_state(step_kind(sampling, logprobs, penalties, edits))
         lp = None if logprobs is None else dict(self._lp if single else sl.lp, K=logprobs)      # (the plan is named at the launch: rec.cut() below starts a new one)
         pen = (self._pen if single else sl.pen) if penalties else None
+        edt = (self._edt if single else sl.edt) if edits else None
         if tp_sampled:
             row = sl.logits_row     # a batch: [rank][sequence][Vloc] gathered, one draw per sequence over its nseg = tp segments
             if p2p is not None:
@@ -651,12 +737,16 @@ class USDMForCausalLM:
             else:
                 rec.cut(lambda: self._gather_partials([row], [logits]))
             seg = dict(nseg=self.tp_size, seg_stride=B * self.Vloc, seg_len=self.Vloc) if B else {}
+            if edt:
+                ops.logit_edit(row, st, V=c["vocab_size"], plan=rec.plan, **seg, **edt)
             if pen:
                 ops.penalize(row, st, V=c["vocab_size"], plan=rec.plan, **seg, **pen)
             ops.sample_final(row, st, V=c["vocab_size"], dev_params=sl.sample_params, plan=rec.plan, **seg, **out)
             if lp:
                 ops.logprobs(row, st, V=c["vocab_size"], plan=rec.plan, **seg, **lp)
         elif sampling:
+            if edt:
+                ops.logit_edit(logits, st, V=self.v1 - self.v0, plan=rec.plan, **edt)
             if pen:
                 ops.penalize(logits, st, V=self.v1 - self.v0, plan=rec.plan, **pen)
             if sampling == "hook":      # Python logits processors (usdm_amd.serving): a host call between the two kernels
@@ -737,7 +827,7 @@ class USDMForCausalLM:
             land(w["down"], act, I, 2 * l + 1, **down_kw)
         return h, pend
 
-    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None, penalties=False):
+    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None, penalties=False, edits=False):
         """Prefill of S new tokens at positions past .. past+S-1 (past > 0: the KV cache already holds the first `past`
         tokens of the same sequence; only the single-sequence cache keeps the V^T that makes this possible)."""
         dev, bf = self.device, torch.bfloat16
@@ -779,10 +869,10 @@ class USDMForCausalLM:
                           o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=rec.plan)
 
         self._layers(rec, gemm, attn, h, qkv, ao, act, "reduce" if self.tp_path else "fused", n=S * H, parts=(part, part))
-        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs, penalties=penalties)
+        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs, penalties=penalties, edits=edits)
         return rec.finish(), io
 
-    def _build_decode(self, sampling=None, logprobs=None, penalties=False):
+    def _build_decode(self, sampling=None, logprobs=None, penalties=False, edits=False):
         """One decode step of the single sequence.  Tensor parallel with a P2PComm: the launch sequence of the single-GPU step over
         this rank's shards, o_proj / down_proj carry the exchange (_layers, way "p2p"); returned as segments cut at every exchange,
         which a real rank runs back to back inside one hipGraph."""
@@ -844,7 +934,7 @@ class USDMForCausalLM:
         if chain:     # the last layer's chain has no next qkv to wait for
             flush()
         # (pend: the last down-projection's sum goes into the final norm + lm_head)
-        self._lm_head_and_pick(rec, h, True, sampling, x_delta=pend, skip=skp, logprobs=logprobs, penalties=penalties)
+        self._lm_head_and_pick(rec, h, True, sampling, x_delta=pend, skip=skp, logprobs=logprobs, penalties=penalties, edits=edits)
         return rec.finish()
 
     @staticmethod
@@ -928,14 +1018,17 @@ class USDMForCausalLM:
 
     def _batch_pick_state(self, B, kind):
         """The B slots' buffers with what a step of this kind needs beyond the sampler's state (allocated at first use): bb["lp"], the
-        slots' log-probability buffers next to bb["out"], and bb["pen"], their penalty state; every slot views its own row as sl.lp /
-        sl.pen.  No rows-written / tokens-counted word: batch slots have no device-side `done` word, every step writes its row and
+        slots' log-probability buffers next to bb["out"], bb["pen"], their penalty state, and bb["edt"], their logit-edit state; every
+        slot views its own row as sl.lp / sl.pen / sl.edt.
+        No rows-written / tokens-counted word: batch slots have no device-side `done` word, every step writes its row and
         counts the token of the step before, and the host ignores rows past a request's end."""
         bb, new = self._batch_buffers(B), {}
         if kind.logprobs is not None and "lp" not in bb:
             new["lp"] = logprob_buffers(self.device, self.max_out, B)
         if kind.penalties and "pen" not in bb:
             new["pen"] = penalty_buffers(self.device, self.cfg["vocab_size"], B)
+        if kind.edits and "edt" not in bb:
+            new["edt"] = edit_buffers(self.device, self.ctx_max, B)
         for name, bufs in new.items():
             bb[name] = bufs
             setattr(bb["all"], name, bufs)
@@ -943,7 +1036,7 @@ class USDMForCausalLM:
                 setattr(sl, name, {k: v[b] for k, v in bufs.items()})
         return bb
 
-    def _build_decode_batch(self, B, sampling=False, logprobs=None, penalties=False):
+    def _build_decode_batch(self, B, sampling=False, logprobs=None, penalties=False, edits=False):
         """One decode step of B sequences: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
         sampling: the pick is usdm_sample_final's batched form - every slot draws with its OWN knobs (bb["sp"][b]: temperature,
         top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1."""
@@ -988,7 +1081,7 @@ class USDMForCausalLM:
                             counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=rec.plan)
 
         self._layers(rec, gemv, attn, h, qkv, ao, act, "reduce" if tp else "fused", n=B * H, parts=parts, down_kw={} if tp else dict(ks=ks))
-        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs, penalties=penalties)
+        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs, penalties=penalties, edits=edits)
         segs = rec.finish()
         return segs if tp else segs[0]
 
@@ -1012,7 +1105,8 @@ class USDMForCausalLM:
 
     @torch.no_grad()
     def generate_batch(self, input_ids_list, max_new_tokens, bad_words_ids=None, eos_token_id=None, min_new_tokens=0, group=None,
-                       logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+                       logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None,
+                       no_repeat_ngram_size=0):
         """Greedy generation of several utterances in lockstep (the serving-side batching of inference_vllm.py:109-125): up to
         `group` (default 16) sequences per step, longer lists run in groups.  Each prompt is prefilled on its own; every decode
         step then streams the weights once for the whole group.  Groups of <= 4 run on the VALU kernel and equal generate() per
@@ -1020,47 +1114,57 @@ class USDMForCausalLM:
         in another order - equal to the oracle up to its near-ties, not bit-identical with generate().
         logprobs=K (0 .. 20): self.last_logprobs is then the list of the sequences' TokenLogprobs (see generate()).
         repetition_penalty / presence_penalty / frequency_penalty: one value for all sequences or a list with one per sequence (see
-        generate()); a group with a non-neutral knob runs on the penalised sampling step, its other sequences with neutral knobs."""
+        generate()); a group with a non-neutral knob runs on the penalised sampling step, its other sequences with neutral knobs.
+        logit_bias / no_repeat_ngram_size: one dict / integer for all sequences or a list with one per sequence, likewise (the step
+        with usdm_logit_edit).  min_p is accepted and range-checked for symmetry with generate(): these picks are greedy (top_k = 1),
+        where it changes nothing."""
         lpk = check_logprobs(logprobs)
         n = len(input_ids_list)
-        per = [k if isinstance(k, (list, tuple)) else [k] * n for k in (repetition_penalty, presence_penalty, frequency_penalty)]
-        if any(len(k) != n for k in per):
-            raise ValueError("a penalty is one value for all sequences or a list with one value per sequence")
-        pens = [check_penalties(*k) for k in zip(*per)]
+        pens = [check_penalties(*k) for k in zip(*(_per_sequence(k, n) for k in (repetition_penalty, presence_penalty, frequency_penalty)))]
+        for v in _per_sequence(min_p, n):
+            check_min_p(v)
+        V = self.cfg["vocab_size"]
+        edits = [check_edits(lb, ng, V) for lb, ng in zip(_per_sequence(logit_bias, n), _per_sequence(no_repeat_ngram_size, n))]
         group = self.max_batch() if group is None else max(1, min(int(group), self.max_batch()))
         outs, self.last_logprobs = [], (None if lpk is None else [])
         for g0 in range(0, n, group):
             outs += self._generate_group(input_ids_list[g0:g0 + group], max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, lpk,
-                                         pens[g0:g0 + group])
+                                         pens[g0:g0 + group], edits[g0:g0 + group])
         return outs
 
     def _batch_step(self, B, kind):
         """The replayable decode step of the B slots (built at first use), a plan / graph of its own per kind: greedy, sampled, the
-        sampled step followed by usdm_logprobs (per K), and each of the latter two with usdm_penalize in front of the pick."""
+        sampled step followed by usdm_logprobs (per K), and each of the latter two with usdm_logit_edit and / or usdm_penalize in front
+        of the pick."""
         bb = self._batch_pick_state(B, kind)
         if kind not in bb["steps"]:
             bb["steps"][kind] = self._graphed(self._build_decode_batch(B, *kind))
         return bb["steps"][kind]
 
-    def _admit(self, B, b, ids, kind, knobs=None):
+    def _admit(self, B, b, ids, kind, knobs=None, edits=None):
         """Admit a prompt (ids [L]) into slot b of the B slots, whose batch runs on the step `kind`: its step / position counters,
         then the per-item prefill into the slot's cache, which also picks the first token as that step would (sampled; with row 0 of
         the slot's log-probabilities).  On the penalised step the slot's table is reset and seeded from the prompt, with the request's
-        knobs (repetition, frequency, presence; None: a request without, neutral)."""
+        knobs (repetition, frequency, presence; None: a request without, neutral); on the step with logit edits the slot's edit state
+        is written from the prompt and the request's check_edits() value (None: neutral)."""
         bb, L = self._batch_pick_state(B, kind), int(ids.shape[0])
         bb["step"][b] = 0
         bb["pos"][b] = L
         if kind.penalties:
             seed_penalties(bb["slots"][b].pen, ids, knobs)
+        if kind.edits:
+            seed_edits(bb["slots"][b].edt, ids, edits)
         segs, io = bb["prefill"].get_or_build((L, b, *kind), lambda: self._build_prefill(L, kind.sampling or None, slot=bb["slots"][b],
-                                                                                         logprobs=kind.logprobs, penalties=kind.penalties))
+                                                                                         logprobs=kind.logprobs, penalties=kind.penalties,
+                                                                                         edits=kind.edits))
         io["ids"].copy_(ids)
         self._run_segs(segs)
 
-    def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None, pens=None):
+    def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None, pens=None, edits=None):
         B = len(ids_list)
-        # one penalised sequence: the group runs on the penalised step
-        kind = step_kind(logprobs=logprobs, penalties=pens is not None and any(k is not None for k in pens))
+        # one penalised / edited sequence: the group runs on the penalised / edited step
+        kind = step_kind(logprobs=logprobs, penalties=pens is not None and any(k is not None for k in pens),
+                         edits=edits is not None and any(k is not None for k in edits))
         for ids in ids_list:
             if ids.dim() != 2 or ids.shape[0] != 1:
                 raise ValueError("every prompt must be a LongTensor of shape [1, L]")
@@ -1075,7 +1179,7 @@ class USDMForCausalLM:
         for b, ids in enumerate(ids_list):
             if kind.sampling:      # greedy on the sampling step: top_k = 1
                 ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
-            self._admit(B, b, ids[0], kind, knobs=pens[b] if kind.penalties else None)
+            self._admit(B, b, ids[0], kind, knobs=pens[b] if kind.penalties else None, edits=edits[b] if kind.edits else None)
         decode = self._batch_step(B, kind)
         eos = stop_ids(eos_token_id)
         produced, chunk = 1, 8
@@ -1117,12 +1221,13 @@ class USDMForCausalLM:
         return t
 
     def _setup_call(self, input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=None, logprobs=None,
-                    penalties=None):
+                    penalties=None, edits=None):
         """Per-call device state of generate(): prompt ids into the (cached) prefill plan, ban mask, position / step counters,
-        device-side EOS list; penalties = the knobs (repetition, frequency, presence) of a penalised call.  Returns (prefill
+        device-side EOS list; penalties = the knobs (repetition, frequency, presence) of a penalised call, edits = check_edits()'s
+        (bias, n) of a call with a logit bias or an n-gram ban.  Returns (prefill
         segments, the EOS ids the device checks).  (The call shape is the lockstep harnesses' too, which step several logical
         ranks through it: it takes the three values, not the kind.)"""
-        kind = step_kind(sampling, logprobs, penalties is not None)
+        kind = step_kind(sampling, logprobs, penalties is not None, edits is not None)
         L0, sampling = input_ids.shape[1], kind.sampling
         if self.tp_path:      # keep_logits: a sampled call exposes the gathered row, a greedy one this rank's shard
             if sampling and self.last_logits is not self.logits_row:
@@ -1133,8 +1238,11 @@ class USDMForCausalLM:
         if kind.penalties:
             # the whole prompt is flagged, the ids whose K/V are reused from the cache included; zeroed together with st_step below
             seed_penalties(self._pen, input_ids[0], penalties)
+        if kind.edits:
+            seed_edits(self._edt, input_ids[0], edits)      # (the whole prompt, likewise)
         segs, io = self._prefill_plans.get_or_build((L0 - past, past, *kind), lambda: self._build_prefill(L0 - past, sampling, past=past,
-                                                                                                          logprobs=kind.logprobs, penalties=kind.penalties))
+                                                                                                          logprobs=kind.logprobs, penalties=kind.penalties,
+                                                                                                          edits=kind.edits))
         if kind.logprobs is not None:
             self._lp["count"].zero_()      # rows written so far (usdm_logprobs keys its write on it: the device-side EOS)
         io["ids"].copy_(input_ids[0, past:])
@@ -1154,7 +1262,8 @@ class USDMForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids=None, max_length=None, do_sample=False, bad_words_ids=None, top_p=1.0, top_k=None,
                  temperature=1.0, eos_token_id=None, max_new_tokens=None, min_new_tokens=0, seed=None, ban_mask=None,
-                 _logits_hook=None, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, **unused):
+                 _logits_hook=None, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
+                 logit_bias=None, no_repeat_ngram_size=0, **unused):
         """Generation with the call shape of src/inference.py:63-83.  Greedy when do_sample is False or top_k == 1 (what the
         reference passes: arg-max of the ban-masked logits).  Otherwise temperature / top-k / top-p sampling on the device
         (usdm_sample_final).  `seed` keys its Philox stream; seed=None draws a fresh one from torch's global CPU generator,
@@ -1166,9 +1275,16 @@ class USDMForCausalLM:
         in [-2, 2] (vLLM: ids of the output so far): applied on the device to the ban-masked row of every step before the hook and
         the pick (usdm_penalize), so log-probabilities and last_logits are those of the penalised row.  With a
         non-neutral knob a greedy call runs on the sampling step with top_k = 1 too, and its ids may differ from the plain call's:
-        that is the point.  All neutral (the default): no penalty plan is built, every launch is what it is without the arguments."""
+        that is the point.  All neutral (the default): no penalty plan is built, every launch is what it is without the arguments.
+        min_p in [0, 1] (HF MinPLogitsWarper / vLLM; sampled calls): after temperature, top-k and top-p, ids with p < min_p * p_max
+        are dropped (inside usdm_sample_final: no other plan; a greedy pick keeps the maximum anyway).
+        logit_bias {id: bias} (at most 1024 ids, values clamped to [-100, 100]) and no_repeat_ngram_size n (HF
+        NoRepeatNGramLogitsProcessor over prompt + output) run on the device in front of the penalties (usdm_logit_edit; DESIGN.md 8h-2);
+        a greedy call then runs on the sampling step with top_k = 1.  Both neutral (None / 0): no edit plan, no buffers."""
         lpk = check_logprobs(logprobs)
         pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        min_p = check_min_p(min_p)
+        edt = check_edits(logit_bias, no_repeat_ngram_size, self.cfg["vocab_size"])
         self.last_logprobs = None
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1, as the reference calls it)")
@@ -1178,18 +1294,18 @@ class USDMForCausalLM:
                 seed = self._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
             sampling, self.logits_hook = "hook", _logits_hook
             ops.set_sample_params(self.sample_params, temperature if do_sample else 1.0, int(top_k or 0) if do_sample else 1,
-                                  top_p if do_sample else 1.0, seed)
+                                  top_p if do_sample else 1.0, seed, min_p=min_p if do_sample else 0.0)
         elif do_sample and top_k != 1:
             if not (temperature > 0) or not (0 < top_p <= 1):
                 raise ValueError("temperature must be > 0 and top_p in (0, 1]")
             if seed is None:
                 seed = self._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
             sampling = True
-            ops.set_sample_params(self.sample_params, temperature, int(top_k or 0), top_p, seed)
+            ops.set_sample_params(self.sample_params, temperature, int(top_k or 0), top_p, seed, min_p=min_p)
         else:
             if (temperature != 1.0 or top_p != 1.0) and not do_sample:
                 raise ValueError("temperature / top_p only apply with do_sample=True")
-        kind = step_kind(sampling, lpk, pen is not None)
+        kind = step_kind(sampling, lpk, pen is not None, edt is not None)
         if kind.sampling and not sampling:      # greedy on the sampling step: top_k = 1
             ops.set_sample_params(self.sample_params, 1.0, 1, 1.0, 0)
         L0 = input_ids.shape[1]
@@ -1216,7 +1332,7 @@ class USDMForCausalLM:
                 a0 = self._vt_upto
                 self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
         segs, dev_eos = self._setup_call(input_ids, past, kind.sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,
-                                          logprobs=lpk, penalties=pen)
+                                          logprobs=lpk, penalties=pen, edits=edt)
         self._run_segs(segs)  # prefill + first token
         if kind not in self._decodes:      # a plan / graph of its own per kind (the hooked step has host code inside: never captured)
             self._decodes[kind] = self._graphed(self._build_decode(*kind), enabled=False if kind.sampling == "hook" else None)

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogprobArgs, NormArgs, PenaltyArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -357,14 +357,14 @@ def argmax_final(part_val, part_idx, nparts, st, embed=None, h_out=None, Hd=0, n
 
 
 def sample_params_tensor(device, n=1):
-    """Device block holding n usdm_sample_params (24 bytes each: temperature, top_k, top_p, reserved, seed)."""
+    """Device block holding n usdm_sample_params (24 bytes each: temperature, top_k, top_p, min_p, seed)."""
     sz = C_.sizeof(_lib.SampleParams)
     return torch.zeros(sz if n == 1 else (n, sz), dtype=torch.uint8, device=device)
 
 
-def set_sample_params(t, temperature, top_k, top_p, seed):
+def set_sample_params(t, temperature, top_k, top_p, seed, min_p=0.0):
     """t: one 24-byte block (a row of sample_params_tensor(device, n) for slot b of a batch)"""
-    p = _lib.SampleParams(float(temperature), int(top_k), float(top_p), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+    p = _lib.SampleParams(float(temperature), int(top_k), float(top_p), float(min_p), int(seed) & 0xFFFFFFFFFFFFFFFF)
     t.copy_(torch.frombuffer(bytearray(bytes(p)), dtype=torch.uint8))
 
 
@@ -385,9 +385,9 @@ def _logits_row(who, a, logits, st, V, nseg, seg_stride, seg_len):
     return False
 
 
-def sample_final(logits, st, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, probs_out=None, embed=None, h_out=None, Hd=0,
+def sample_final(logits, st, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, min_p=0.0, probs_out=None, embed=None, h_out=None, Hd=0,
                  dev_params=None, V=None, nseg=1, seg_stride=0, seg_len=0, plan=None):
-    """usdm_sample_final: temperature / top-k / top-p sampling of one token from ban-masked f32 logits.
+    """usdm_sample_final: temperature / top-k / top-p / min-p sampling of one token from ban-masked f32 logits.
     dev_params (sample_params_tensor): the knobs are read from device memory instead (graph-replayable per request).
     Batched state (decode_state(batch=B)): logits [B][V], dev_params [B][24], h_out [B][Hd]; one workgroup per sequence.
     V: ids drawn from (default logits.shape[-1]; a gathered tensor-parallel row is longer than the vocabulary by the last rank's
@@ -396,7 +396,7 @@ def sample_final(logits, st, *, temperature=1.0, top_k=0, top_p=1.0, seed=0, pro
     _need_cuda(logits, probs_out, embed, h_out, dev_params)
     a = SampleArgs()
     seg = _logits_row("sample_final", a, logits, st, V, nseg, seg_stride, seg_len)
-    a.temperature, a.top_k, a.top_p = temperature, top_k, top_p
+    a.temperature, a.top_k, a.top_p, a.min_p = temperature, top_k, top_p, min_p
     a.seed, a.probs_out, a.dev_params = seed, _ptr(probs_out), _ptr(dev_params)
     if probs_out is not None and probs_out.numel() < max(1, st.batch) * a.V:
         raise ValueError("sample_final: probs_out holds fewer than batch * V values")
@@ -492,6 +492,55 @@ def penalize(logits, st, *, table, dev_params, count=None, V=None, nseg=1, seg_s
         _go(plan, "usdm_penalize_seg", lib.usdm_penalize_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len), C_.byref(st))
         return
     _go(plan, "usdm_penalize", lib.usdm_penalize, C_.byref(a), C_.byref(st))
+
+
+LOGIT_BIAS_MAX = 1024     # bias entries per sequence: one per thread of usdm_logit_edit's workgroup
+
+
+def edit_params_tensor(device, n=1):
+    """Device block holding n usdm_logit_edit_params (16 bytes each: ngram, prompt_len, n_bias, reserved); zero-filled = neutral."""
+    sz = C_.sizeof(_lib.LogitEditParams)
+    return torch.zeros(sz if n == 1 else (n, sz), dtype=torch.uint8, device=device)
+
+
+def set_edit_params(block, ngram=0, prompt_len=0, n_bias=0):
+    """block: one 16-byte block (a row of edit_params_tensor(device, n) for slot b of a batch)"""
+    if ngram < 0 or prompt_len < 0 or not 0 <= n_bias <= LOGIT_BIAS_MAX:
+        raise ValueError(f"set_edit_params: ngram >= 0, prompt_len >= 0, n_bias 0 .. {LOGIT_BIAS_MAX}; got {ngram}, {prompt_len}, {n_bias}")
+    p = _lib.LogitEditParams(min(int(ngram), 2 ** 31 - 1), int(prompt_len), int(n_bias), 0)
+    block.copy_(torch.frombuffer(bytearray(bytes(p)), dtype=torch.uint8))
+
+
+def logit_edit(logits, st, *, dev_params, bias_id=None, bias_val=None, prompt=None, V=None, nseg=1, seg_stride=0, seg_len=0, plan=None):
+    """usdm_logit_edit, launched before the penalize / sample_final of the same step on the row they will read: adds the sequence's
+    logit bias (bias_id int32 / bias_val f32, [<= 1024] or [B][<= 1024]; the first n_bias entries count) and writes -inf over the ids
+    HF's no_repeat_ngram_size bans, the history being prompt (int32 [>= prompt_len] or [B][...]) followed by the state's out_tokens.
+    dev_params: edit_params_tensor.  V / nseg / seg_stride / seg_len as in sample_final (usdm_logit_edit_seg)."""
+    _need_cuda(logits, dev_params, bias_id, bias_val, prompt)
+    B = max(1, st.batch)
+    a = LogitEditArgs()
+    seg = _logits_row("logit_edit", a, logits, st, V, nseg, seg_stride, seg_len)
+    a.dev_params, a.bias_id, a.bias_val, a.prompt = _ptr(dev_params), _ptr(bias_id), _ptr(bias_val), _ptr(prompt)
+    if dev_params is not None and (dev_params.dtype != torch.uint8 or not dev_params.is_contiguous() or dev_params.numel() < 16 * B):
+        raise ValueError("logit_edit: dev_params must be an edit_params_tensor of [batch] blocks")
+    if (bias_id is None) != (bias_val is None):
+        raise ValueError("logit_edit: bias_id and bias_val go together")
+
+    def rows_of(name, t, dt):      # -> (entries per sequence, per-sequence stride)
+        if t is None:
+            return 0, 0
+        rows = t if B == 1 else t[0]
+        if t.dtype != dt or not rows.is_contiguous() or (B > 1 and (t.dim() != 2 or t.shape[0] < B)):
+            raise ValueError(f"logit_edit: {name} must be {dt}, [n] or [batch][n] with contiguous rows")
+        return rows.numel(), (t.stride(0) if B > 1 else 0)
+    a.bias_max, a.bias_bs = rows_of("bias_id", bias_id, torch.int32)
+    if rows_of("bias_val", bias_val, torch.float32) != (a.bias_max, a.bias_bs) or a.bias_max > LOGIT_BIAS_MAX:
+        raise ValueError(f"logit_edit: bias_id and bias_val must have the same shape, at most {LOGIT_BIAS_MAX} entries per sequence")
+    a.prompt_max, a.prompt_bs = rows_of("prompt", prompt, torch.int32)
+    if seg:
+        _go(plan, "usdm_logit_edit_seg", lib.usdm_logit_edit_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len), C_.byref(st))
+        return
+    _go(plan, "usdm_logit_edit", lib.usdm_logit_edit, C_.byref(a), C_.byref(st))
 
 
 def logits_p2p(logits, Vloc, st, p2p, site0, row_out, phase=0, plan=None):

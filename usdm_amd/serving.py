@@ -22,6 +22,9 @@ How requests are executed
     user reaches for - run on the device inside the step (usdm_penalize, in front of the pick): graph-captured,
     continuously batched and tensor parallel like any other request.  One penalised request puts its whole group on the penalised
     step, which is also the sampling step; the other slots carry neutral knobs, which leave every bit of their rows alone;
+  * SamplingParams(min_p=, logit_bias=, no_repeat_ngram_size=) run on the device too: min_p inside the sampler, per slot, next to
+    top-k and top-p; the logit bias and HF's n-gram ban in usdm_logit_edit, in front of the penalties.  One request
+    with a bias or an n-gram size puts its group on the step with that launch; the other slots' neutral blocks leave their rows alone;
   * other processors that really depend on the token history run as Python between the lm_head launch and the pick of every step
     (eager launches: correct, not fast); with penalties they get both, the processors seeing the penalised row;
   * SamplingParams(logprobs=K), K = 0 .. 20: per-token log-probabilities computed on the device inside the step (usdm_logprobs, right
@@ -35,7 +38,7 @@ from collections import deque
 import torch
 
 from . import ops
-from .llm import USDMForCausalLM, check_logprobs, check_penalties, check_quantization, read_logprobs, step_kind, stop_index
+from .llm import USDMForCausalLM, check_edits, check_logprobs, check_min_p, check_penalties, check_quantization, read_logprobs, step_kind, stop_index
 from .quant import check_kv_cache_dtype
 
 MAX_SLOTS = 16      # usdm_gemv_batch streams the weights once per step for up to 16 sequences (matrix-core form above 4)
@@ -48,7 +51,8 @@ class SamplingParams:
 
     def __init__(self, n=1, temperature=1.0, top_p=1.0, top_k=-1, max_tokens=16, min_tokens=0, stop_token_ids=None,
                  logits_processors=None, seed=None, skip_special_tokens=True, ignore_eos=False, static_logits_mask=None, logprobs=None,
-                 prompt_logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, **unused):
+                 prompt_logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None,
+                 no_repeat_ngram_size=0, **unused):
         if not isinstance(n, int) or n < 1:
             raise ValueError("n must be a positive integer")
         if temperature < 0 or not (0 < top_p <= 1) or (top_k < -1 or top_k == 0):
@@ -65,6 +69,11 @@ class SamplingParams:
         self.penalties = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)      # None: all neutral
         self.repetition_penalty, self.presence_penalty, self.frequency_penalty = (
             float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
+        # min_p in [0, 1] (inside usdm_sample_final); logit_bias {id: bias in [-100, 100] after clamping} and HF's no_repeat_ngram_size
+        # (usdm_logit_edit).  The ids' upper bound is the model's vocabulary: checked when the request is served
+        self.min_p = check_min_p(min_p)
+        self.edits = check_edits(logit_bias, no_repeat_ngram_size)      # None: both neutral
+        self.logit_bias, self.no_repeat_ngram_size = (dict(logit_bias) if logit_bias else None), int(no_repeat_ngram_size or 0)
         if prompt_logprobs is not None:
             raise NotImplementedError("prompt_logprobs is not supported (it needs the lm_head over every prompt row); logprobs= covers "
                                       "the generated tokens")
@@ -224,6 +233,7 @@ class LLM:
                 text = prompts[i]
                 ids = list(self.tokenizer(text).input_ids)
             sp = sps[i]
+            check_edits(sp.logit_bias, sp.no_repeat_ngram_size, V)      # (ids against this model's vocabulary)
             mask = sp.static_logits_mask
             if mask is None or mask is True:
                 m = static_mask_of(sp.logits_processors, V, dev)
@@ -280,7 +290,7 @@ class LLM:
         ids = torch.tensor([r["ids"]], dtype=torch.long, device=llm.device)
         kw = dict(input_ids=ids, max_new_tokens=r["max_new"], eos_token_id=sorted(r["stops"]) or None, min_new_tokens=sp.min_tokens,
                   logprobs=sp.logprobs, repetition_penalty=sp.repetition_penalty, presence_penalty=sp.presence_penalty,
-                  frequency_penalty=sp.frequency_penalty)
+                  frequency_penalty=sp.frequency_penalty, min_p=sp.min_p, logit_bias=sp.logit_bias, no_repeat_ngram_size=sp.no_repeat_ngram_size)
         sampled = not sp.greedy
         if sampled:
             kw.update(do_sample=True, temperature=sp.temperature, top_p=sp.top_p, top_k=(sp.top_k if sp.top_k > 0 else None), seed=r["seed"])
@@ -317,8 +327,12 @@ class LLM:
         # one penalised request -> the whole group runs on the penalised step (usdm_penalize + the sampling step); the other
         # requests and the idle slots carry neutral knobs
         pen = any(r["sp"].penalties is not None for r in grp)
-        kind = step_kind(any(not r["sp"].greedy for r in grp), lpk, pen)       # one sampled request -> the whole group runs on the sampling graph
+        edt = any(r["sp"].edits is not None for r in grp)      # likewise: the step with usdm_logit_edit
+        kind = step_kind(any(not r["sp"].greedy for r in grp), lpk, pen, edt)       # one sampled request -> the whole group runs on the sampling graph
         decode = llm._batch_step(nslots, kind)
+        if edt:
+            for b in range(nslots):
+                ops.set_edit_params(bb["edt"]["dev_params"][b])
         if pen:
             for b in range(nslots):
                 ops.set_penalty_params(bb["pen"]["dev_params"][b])
@@ -336,8 +350,8 @@ class LLM:
                     if sp.greedy:
                         ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
                     else:
-                        ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"])
-                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), kind, knobs=sp.penalties)      # (+ first token)
+                        ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"], min_p=sp.min_p)
+                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), kind, knobs=sp.penalties, edits=sp.edits)      # (+ first token)
                     slots[b] = dict(r=r, produced=1)
                     self.stats["admissions"] += 1
             active = [b for b in range(nslots) if slots[b] is not None]
@@ -363,6 +377,8 @@ class LLM:
                     slots[b] = None
                     if pen:      # the idle slot keeps decoding garbage: with neutral knobs
                         ops.set_penalty_params(bb["pen"]["dev_params"][b])
+                    if edt:
+                        ops.set_edit_params(bb["edt"]["dev_params"][b])
                     freed = True
                 else:
                     need = max(need, 1)
