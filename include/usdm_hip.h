@@ -471,6 +471,34 @@ int usdm_logprobs_seg(const usdm_logprob_args* args, int32_t nseg, int64_t seg_s
                       usdm_stream_t stream);
 int usdm_sizeof_logprob_args(void);
 
+/* Log-probabilities of tokens the caller SUPPLIED: a chunk of f32 logits rows of a prompt scored against the prompt's own next ids.
+ * Row r (0 <= r < rows) of the chunk, at logits + r * logits_bs, is prompt row row0 + r (the lm_head over the hidden state of that
+ * position); its target is ids[row0 + r + 1], and every output is indexed by the TARGET's row t = row0 + r + 1:
+ *   tok_lp[t], tok_rank[t]     log p(ids[t] | ids[< t]) and its vLLM rank
+ *   top_id / top_lp            [t][K], as usdm_logprobs writes them (K = 0: not written, may be NULL)
+ * so the caller's buffers hold n_ids rows (n_ids * K for the top lists); rows outside row0 + 1 .. row0 + rows are not touched.
+ * The quantities and the arithmetic are usdm_logprobs' (2^40 fixed-point sum, f64 log, one rounding to f32; radix select on unique
+ * (value, id) keys): the same row and target give the same bits from both.  A target id outside [0, V) is reported with lp -inf
+ * (and the rank of -inf); a row with no finite logit gives -inf everywhere, never NaN.  Nothing is banned or edited: the rows are
+ * the raw model's distribution over all V ids (vLLM's prompt_logprobs).  One workgroup per row; no host synchronisation.
+ * Refused: null pointers, K outside 0 .. 20, V outside 1 .. 2^20, rows < 1, row0 < 0, row0 + rows + 1 > n_ids, logits_bs < V. */
+typedef struct usdm_prompt_logprob_args {
+  const float* logits; int32_t V; int32_t K;
+  int64_t logits_bs;          /* elements between two rows of the chunk */
+  const int64_t* ids;         /* the prompt's ids (device) */
+  int32_t n_ids;
+  int32_t row0, rows;         /* first prompt row of the chunk, rows in the chunk */
+  float* tok_lp; int32_t* tok_rank; int32_t* top_id; float* top_lp;
+} usdm_prompt_logprob_args;
+int usdm_prompt_logprobs(const usdm_prompt_logprob_args* args, usdm_stream_t stream);
+/* The same over rows of nseg segments (the vocab-parallel lm_head: the ranks' [rows][seg_len] chunks gathered rank-major): id i of
+ * row r is read at logits + (i / seg_len) * seg_stride + r * logits_bs + i % seg_len; ids >= V are never read.  Needs
+ * 2 <= seg_len <= 2^20, nseg * seg_len >= V, logits_bs >= seg_len and seg_stride >= logits_bs * (rows - 1) + seg_len.  Bit-identical
+ * with usdm_prompt_logprobs on the same logical rows. */
+int usdm_prompt_logprobs_seg(const usdm_prompt_logprob_args* args, int32_t nseg, int64_t seg_stride, int32_t seg_len,
+                             usdm_stream_t stream);
+int usdm_sizeof_prompt_logprob_args(void);
+
 /* Repetition / frequency / presence penalties of the step whose token usdm_sample_final is ABOUT to pick, applied in place to the
  * ban-masked f32 row it will read (before a host logits hook, which sees the penalised row).  State per sequence: table[V], one
  * int32 per id: c(i) = how often id i was generated so far in this call in bits 0 .. 29, in_prompt(i) in bit 30 (the caller zeroes

@@ -28,6 +28,8 @@ lib.usdm_gemv_mxfp4.restype = C.c_int        # (the MXFP4 entry points: likewise
 lib.usdm_dequant_mxfp4.restype = C.c_int
 lib.usdm_logprobs.restype = C.c_int          # (the log-probability entry points: likewise)
 lib.usdm_logprobs_seg.restype = C.c_int
+lib.usdm_prompt_logprobs.restype = C.c_int   # (the scoring entry points: likewise)
+lib.usdm_prompt_logprobs_seg.restype = C.c_int
 lib.usdm_penalize.restype = C.c_int          # (the penalty entry points: likewise)
 lib.usdm_penalize_seg.restype = C.c_int
 lib.usdm_penalty_params_init.restype = C.c_int
@@ -202,6 +204,14 @@ class LogprobArgs(C.Structure):
     ]
 
 
+class PromptLogprobArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("V", C.c_int32), ("K", C.c_int32), ("logits_bs", C.c_int64),
+        ("ids", C.c_void_p), ("n_ids", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32),
+        ("tok_lp", C.c_void_p), ("tok_rank", C.c_void_p), ("top_id", C.c_void_p), ("top_lp", C.c_void_p),
+    ]
+
+
 class PenaltyParams(C.Structure):
     _fields_ = [("repetition", C.c_float), ("frequency", C.c_float), ("presence", C.c_float), ("reserved", C.c_int32)]
 
@@ -269,7 +279,7 @@ def _selfcheck():
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
-                      ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs)):
+                      ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

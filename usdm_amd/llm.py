@@ -330,8 +330,14 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
 
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
-                 p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None):
+                 p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None, score_rows=256):
         check_quantization(quantization, fp8_matrix_cores)
+        # score(): prompt rows per lm_head GEMM + usdm_prompt_logprobs launch.  256 is reasoned, not measured: one 1024-thread workgroup per
+        # row is about one round of the 256 CUs, and a 256 x 42003 x 4 B = 43 MB chunk should stay cache-resident between the GEMM's write
+        # and the kernel's 2 - 9 read passes (tools/score_rate.py sweeps it)
+        if isinstance(score_rows, bool) or not isinstance(score_rows, int) or score_rows < 16 or score_rows % 16:
+            raise ValueError(f"score_rows must be a positive multiple of 16, got {score_rows!r}")
+        self.score_rows = score_rows
         if quantization is not None and (tp_size > 1 or tp_segments or p2p is not None):
             raise NotImplementedError(f"quantization={quantization!r} runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) takes bf16 weights")
         self.kv_cache_dtype = check_kv_cache_dtype(kv_cache_dtype)
@@ -440,6 +446,13 @@ class USDMForCausalLM:
         self.last_logprobs = None  # generate(logprobs=K): TokenLogprobs of the last call (generate_batch: a list); None when not asked
         self._pen = None          # penalty state of the single sequence (penalty_buffers; allocated at first use)
         self._edt = None          # logit-edit state of the single sequence (edit_buffers; allocated at first use)
+        # score(): plans keyed (S, past, j0, K) in a cache of their own (scoring never evicts generate()'s prefill plans), the output
+        # rows [ctx_max] / [ctx_max][20] and the bf16 copy of a quantized lm_head, all allocated at first use
+        self._score_plans = LRU(8)
+        self._score_out = None
+        self._head_bf16 = None
+        self.keep_score_logits = False   # debug/tests: keep the fp32 (bf16-valued) logits of every scored row
+        self.last_score_logits = None    # ... of the last score() call: [rows scored][V] (tensor parallel: the gathered logical rows)
 
     # ------------------------------------------------------------------ weights
     def _shard(self, sd_get):
@@ -827,9 +840,11 @@ class USDMForCausalLM:
             land(w["down"], act, I, 2 * l + 1, **down_kw)
         return h, pend
 
-    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None, penalties=False, edits=False):
-        """Prefill of S new tokens at positions past .. past+S-1 (past > 0: the KV cache already holds the first `past`
-        tokens of the same sequence; only the single-sequence cache keeps the V^T that makes this possible)."""
+    def _prefill_rows(self, S, slot=None, past=0):
+        """The launches every plan over a prompt's rows begins with: embedding, the layers, K/V rows into the cache (of the slot, or of
+        the single sequence), for S new tokens at positions past .. past+S-1 (past > 0: the KV cache already holds the first `past`
+        tokens of the same sequence; only the single-sequence cache keeps the V^T that makes this possible).  Returns (rec, io, h, xn):
+        the open plan, its input ids, the final hidden state of every row [S][H] and the [S][H] scratch of the normalised rows."""
         dev, bf = self.device, torch.bfloat16
         H, d, L, Hq, Hkv, I, nq = self._dims()
         Spad = (S + 63) // 64 * 64
@@ -869,7 +884,65 @@ class USDMForCausalLM:
                           o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=rec.plan)
 
         self._layers(rec, gemm, attn, h, qkv, ao, act, "reduce" if self.tp_path else "fused", n=S * H, parts=(part, part))
+        return rec, io, h, xn
+
+    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None, penalties=False, edits=False):
+        """Prefill of S new tokens at positions past .. past+S-1 (_prefill_rows), then the lm_head over the LAST row and the pick of the
+        first generated token."""
+        rec, io, h, _ = self._prefill_rows(S, slot=slot, past=past)
         self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs, penalties=penalties, edits=edits)
+        return rec.finish(), io
+
+    def _score_head(self):
+        """The bf16 [v1 - v0][H] operand of score()'s lm_head GEMMs: the weight itself, or (fp8 / mxfp4 models, whose lm_head is fp8) its
+        dequantization, done ONCE at first use into a tensor of its own that the model keeps (344 MB on the 7B): dq_scratch is sized
+        for the largest layer matrix, which is smaller than the lm_head, and is rewritten by every layer of every prefill."""
+        W = self.W["lm_head"]
+        if not isinstance(W, Fp8Weight):
+            return W
+        if self._head_bf16 is None:
+            self._head_bf16 = torch.empty(W.N, W.K, dtype=torch.bfloat16, device=self.device)
+            ops.dequant_fp8(W, self._head_bf16)
+        return self._head_bf16
+
+    def _build_score(self, S, past, j0, K):
+        """The plan of score(): _prefill_rows over S new tokens at positions past .. past+S-1, one usdm_norm (the final RMSNorm) over
+        all S rows, then per chunk of score_rows rows over the new-token rows j0 .. S-2 one lm_head usdm_gemm into an f32 chunk
+        [score_rows][Vloc, padded to 4] (round_bf16: the bf16-valued logits the lm_head GEMV writes and HF's bf16 head produces) and one
+        usdm_prompt_logprobs against io["ids"] (local row j's target is ids[j + 1]; outputs at the target's local row).  No ban mask,
+        no penalties, no edits, no pick, no decode-state write, no host sync.  Tensor parallel: every rank's chunk is gathered rank-major
+        into [tp][score_rows][Vloc] (the plan is cut at the collective) and every rank runs usdm_prompt_logprobs_seg on it with the
+        global ids.  keep_score_logits: every chunk is also copied into io["logits"] [S - 1 - j0][V]."""
+        dev, c, H, V = self.device, self.cfg, self.cfg["hidden_size"], self.cfg["vocab_size"]
+        rec, io, h, xn = self._prefill_rows(S, past=past)
+        R, Vn, tp = self.score_rows, self.v1 - self.v0, self.tp_size if self.tp_path else 1
+        ldl = (self.Vloc + 3) // 4 * 4      # row stride of the chunk: 16-byte rows, so that the GEMM's epilogue stores float4s
+        Zf = lambda *s: rec.plan.hold(torch.zeros(*s, device=dev, dtype=torch.float32))
+        chunk = Zf(R, ldl)
+        gathered = Zf(tp, R, ldl) if self.tp_path else None
+        head = self._score_head()
+        if self._score_out is None:
+            n, kk = self.ctx_max, self.ctx_max * ops.LOGPROBS_MAX_K
+            self._score_out = dict(tok_lp=torch.zeros(n, dtype=torch.float32, device=dev), tok_rank=torch.zeros(n, dtype=torch.int32, device=dev),
+                                   top_id=torch.zeros(kk, dtype=torch.int32, device=dev), top_lp=torch.zeros(kk, dtype=torch.float32, device=dev))
+        keep = Zf(S - 1 - j0, ldl if not self.tp_path else tp * self.Vloc) if self.keep_score_logits else None
+        io.update(logits=None if keep is None else keep[:, :V], keep=self.keep_score_logits)
+        ops.norm(h, self.W["norm"], None, rows=S, C=H, eps=c["rms_norm_eps"], rms=True, round_bf16=True, out16=xn, plan=rec.plan)
+        for j in range(j0, S - 1, R):
+            rows = min(R, S - 1 - j)
+            ops.gemm(xn[j:], head, M=rows, N=Vn, Kc=H, round_bf16=True, out32=chunk, ldc=ldl, plan=rec.plan)
+            if self.tp_path:
+                def gather(j=j, rows=rows):
+                    self._gather_partials([gathered], [chunk])
+                    if keep is not None:      # the logical rows: the ranks' Vloc slots side by side (the last rank's padding is past V)
+                        keep[j - j0:j - j0 + rows] = gathered[:, :rows, :self.Vloc].transpose(0, 1).reshape(rows, tp * self.Vloc)
+                rec.cut(gather)
+                ops.prompt_logprobs(gathered[:, :, :self.Vloc], io["ids"], row0=j, rows=rows, K=K, V=V, nseg=tp, seg_stride=R * ldl, seg_len=self.Vloc,
+                                    plan=rec.plan, **self._score_out)
+            else:
+                if keep is not None:
+                    ops.copy_bytes(keep[j - j0], chunk, rows * ldl * 4, plan=rec.plan)
+                ops.prompt_logprobs(chunk, io["ids"], row0=j, rows=rows, K=K, V=V, plan=rec.plan, **self._score_out)
         return rec.finish(), io
 
     def _build_decode(self, sampling=None, logprobs=None, penalties=False, edits=False):
@@ -959,6 +1032,57 @@ class USDMForCausalLM:
                 plan.calls += s.calls
                 plan.hold(*s.keep)
         return GraphedPlan(plan)
+
+    @torch.no_grad()
+    def score(self, input_ids, top_logprobs=0, start=1):
+        """Log-probabilities of tokens that were GIVEN: TokenLogprobs whose row i describes token start + i of input_ids [1, L] given
+        the tokens in front of it, for start <= start + i < L (log p(token_t | tokens_<t), its rank, and the top_logprobs most likely ids
+        of that position, 0 .. 20; None = 0), with .cumulative as generate(logprobs=) reports it.  Nothing is generated: one prefill over
+        the rows, the lm_head as GEMMs over chunks of score_rows rows and usdm_prompt_logprobs per chunk, all on the device.
+        The distribution is the RAW model's over all vocab_size ids - no ban mask, no penalties, no bias, no temperature: vLLM's
+        definition of prompt log-probabilities (generate(logprobs=) reports the ban-masked row it picked from instead).
+        With reuse_prefix on, cached rows of a common prefix are reused up to start - 1 tokens under generate()'s rule ("exact": rows a
+        prefill wrote), and the call leaves the prompt's ids behind as cached prefill-written rows: N candidates behind one prefix
+        prefill and score their own rows only.  With the fp8 KV cache nothing is reused.
+        last_logits, last_logprobs, the sampler's, the penalties' and the edits' state are not touched.
+        keep_score_logits = True (debug / tests): last_score_logits is then the [L - start][vocab_size] f32 logits rows scored."""
+        K = check_logprobs(top_logprobs) or 0
+        if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1)")
+        L = int(input_ids.shape[1])
+        if L < 2 or L > self.ctx_max:
+            raise ValueError(f"score() needs 2 <= L <= ctx_max = {self.ctx_max} tokens, got {L}")
+        if isinstance(start, bool) or not isinstance(start, int) or not 1 <= start <= L - 1:
+            raise ValueError(f"start must be an integer 1 .. L - 1 = {L - 1}, got {start!r}")
+        past, ids_host = 0, None
+        if self.reuse_prefix:
+            ids_host = input_ids[0].tolist()
+            if self._kv_ids is not None:
+                n = min(start - 1, len(self._kv_ids))
+                while past < n and ids_host[past] == self._kv_ids[past]:
+                    past += 1
+                if self.reuse_prefix == "exact":
+                    past = min(past, self._vt_upto)      # rows beyond that were appended by decode steps
+                if past < 16:
+                    past = 0
+            if past > self._vt_upto:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers
+                a0 = self._vt_upto
+                self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
+        S, j0 = L - past, start - 1 - past
+        key = (S, past, j0, K)
+        hit = self._score_plans.get(key)
+        if hit is None or hit[1]["keep"] != self.keep_score_logits:
+            hit = self._score_plans.put(key, self._build_score(*key))
+        segs, io = hit
+        io["ids"].copy_(input_ids[0, past:])
+        self._kv_ids, self._vt_upto = None, L
+        self._run_segs(segs)
+        if self.reuse_prefix:      # every row of the prompt now sits in the cache, written by prefill launches
+            self._kv_ids = ids_host
+        self.last_score_logits = io["logits"]
+        o = self._score_out
+        top = lambda t: t[:S * K].view(S, K)[j0 + 1:].cpu()
+        return TokenLogprobs(o["tok_lp"][j0 + 1:S].cpu(), o["tok_rank"][j0 + 1:S].cpu(), top(o["top_id"]), top(o["top_lp"]))
 
     # ------------------------------------------------------------------ batched decode (SURVEY.md §8f-2)
     class _Slot:

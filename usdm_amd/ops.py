@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -439,6 +439,46 @@ def logprobs(logits, st, *, K, tok_lp, tok_rank, top_id=None, top_lp=None, count
         _go(plan, "usdm_logprobs_seg", lib.usdm_logprobs_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len), C_.byref(st))
         return
     _go(plan, "usdm_logprobs", lib.usdm_logprobs, C_.byref(a), C_.byref(st))
+
+
+def prompt_logprobs(logits, ids, *, row0, K, tok_lp, tok_rank, top_id=None, top_lp=None, rows=None, V=None, nseg=1, seg_stride=0, seg_len=0,
+                    plan=None):
+    """usdm_prompt_logprobs: log-probabilities of tokens that were GIVEN.  logits: a chunk of f32 rows, [rows][>= V] with any row
+    stride (or one row [V]); row r is prompt row row0 + r, its target ids[row0 + r + 1] (ids: the prompt's int64 ids on the device).
+    Outputs are indexed by the target's row t = row0 + r + 1: tok_lp / tok_rank [>= n_ids], top_id / top_lp addressed as [n_ids][K].
+    seg_len > 0 (usdm_prompt_logprobs_seg): logits is [nseg][rows][seg_len] with any row stride, the ranks' chunks gathered rank-major,
+    seg_stride elements between two segments; V: the ids scored over (default logits.shape[-1])."""
+    _need_cuda(logits, ids, tok_lp, tok_rank, top_id, top_lp)
+    if logits.dtype != torch.float32 or logits.stride(-1) != 1 or ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError("prompt_logprobs: logits must be float32 with unit inner stride, ids a contiguous int64 [n_ids]")
+    a = PromptLogprobArgs()
+    a.logits, a.V, a.K = _ptr(logits), (logits.shape[-1] if V is None else V), int(K)
+    a.ids, a.n_ids, a.row0 = _ptr(ids), ids.numel(), int(row0)
+    if seg_len > 0:
+        if logits.dim() != 3 or logits.shape[0] != nseg or logits.shape[2] != seg_len or logits.stride(0) != seg_stride:
+            raise ValueError("segmented prompt_logprobs: logits must be [nseg][rows][seg_len] with seg_stride elements between segments")
+        a.rows, a.logits_bs = (logits.shape[1] if rows is None else rows), logits.stride(1)
+        if a.rows > logits.shape[1]:
+            raise ValueError("segmented prompt_logprobs: more rows than the chunk holds")
+    else:
+        if logits.dim() > 2 or a.V > logits.shape[-1]:
+            raise ValueError("prompt_logprobs: logits must be [V] or [rows][>= V] (a segmented chunk needs seg_len)")
+        have = logits.shape[0] if logits.dim() == 2 else 1
+        a.rows = have if rows is None else rows
+        a.logits_bs = logits.stride(0) if logits.dim() == 2 else logits.numel()
+        if a.rows > have:
+            raise ValueError("prompt_logprobs: more rows than the chunk holds")
+    a.tok_lp, a.tok_rank, a.top_id, a.top_lp = _ptr(tok_lp), _ptr(tok_rank), _ptr(top_id), _ptr(top_lp)
+    for name, t, dt, per in (("tok_lp", tok_lp, torch.float32, 1), ("tok_rank", tok_rank, torch.int32, 1),
+                             ("top_id", top_id, torch.int32, a.K), ("top_lp", top_lp, torch.float32, a.K)):
+        if t is None or not 0 <= a.K <= LOGPROBS_MAX_K:
+            continue      # (the library refuses a missing output and K outside 0 .. 20)
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < a.n_ids * per:
+            raise ValueError(f"prompt_logprobs: {name} must be {dt} with room for [n_ids = {a.n_ids}][{per}] values")
+    if seg_len > 0:
+        _go(plan, "usdm_prompt_logprobs_seg", lib.usdm_prompt_logprobs_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len))
+        return
+    _go(plan, "usdm_prompt_logprobs", lib.usdm_prompt_logprobs, C_.byref(a))
 
 
 PENALTY_PROMPT_BIT = 1 << 30     # usdm_penalize's table word: in_prompt(i) in bit 30, c(i) below it

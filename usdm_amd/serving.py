@@ -27,6 +27,8 @@ How requests are executed
     with a bias or an n-gram size puts its group on the step with that launch; the other slots' neutral blocks leave their rows alone;
   * other processors that really depend on the token history run as Python between the lm_head launch and the pick of every step
     (eager launches: correct, not fast); with penalties they get both, the processors seeing the penalised row;
+  * LLM.score(prompt_token_ids, top_logprobs=K, start=...) scores tokens that were GIVEN (vLLM's prompt_logprobs, as an entry point of
+    its own: nothing is generated): one prefill, the lm_head over every scored row, usdm_prompt_logprobs on the device (DESIGN.md 8g-2);
   * SamplingParams(logprobs=K), K = 0 .. 20: per-token log-probabilities computed on the device inside the step (usdm_logprobs, right
     after the pick, on the row it drew from): lp(i) = x_i - logsumexp(x) over the ban-masked logits, i.e. the model's distribution
     over the allowed ids BEFORE temperature / top-k / top-p.  One asking request puts its whole group on the log-probability step
@@ -75,8 +77,9 @@ class SamplingParams:
         self.edits = check_edits(logit_bias, no_repeat_ngram_size)      # None: both neutral
         self.logit_bias, self.no_repeat_ngram_size = (dict(logit_bias) if logit_bias else None), int(no_repeat_ngram_size or 0)
         if prompt_logprobs is not None:
-            raise NotImplementedError("prompt_logprobs is not supported (it needs the lm_head over every prompt row); logprobs= covers "
-                                      "the generated tokens")
+            raise NotImplementedError("prompt_logprobs is not supported as a SamplingParams field (it needs the lm_head over every prompt row, "
+                                      "which a generating request does not run); logprobs= covers the generated tokens - to score given "
+                                      "tokens use LLM.score() / USDMForCausalLM.score()")
         if self.n > 1 and self.greedy:
             raise ValueError("n must be 1 when using greedy sampling (the n completions would be identical)")   # as vllm
 
@@ -127,6 +130,25 @@ class CompletionOutput:
 
     def __repr__(self):
         return f"CompletionOutput(index={self.index}, text={self.text!r}, token_ids={self.token_ids}, finish_reason={self.finish_reason})"
+
+
+class ScoreOutput:
+    """One scored prompt (LLM.score): prompt_token_ids, prompt_logprobs in vLLM's shape - None for the `start` leading tokens that were
+    not scored, then per token the dict {token_id: Logprob} of assemble_logprobs - and cumulative_logprob, the float64 sum over the
+    scored tokens."""
+
+    def __init__(self, prompt, prompt_token_ids, prompt_logprobs, cumulative_logprob):
+        self.prompt, self.prompt_token_ids, self.prompt_logprobs, self.cumulative_logprob = prompt, prompt_token_ids, prompt_logprobs, cumulative_logprob
+
+    def __repr__(self):
+        return f"ScoreOutput(tokens={len(self.prompt_token_ids)}, cumulative_logprob={self.cumulative_logprob})"
+
+
+def assemble_score(prompt_token_ids, start, lp, k, tokenizer=None, prompt=None):
+    """ScoreOutput of a prompt whose tokens start .. L-1 were scored into the TokenLogprobs (or any object with its four row fields) lp."""
+    ids = list(prompt_token_ids)
+    rows, total = assemble_logprobs(ids[start:], lp.token_logprobs, lp.ranks, lp.top_ids, lp.top_logprobs, k, tokenizer)
+    return ScoreOutput(prompt, ids, [None] * start + rows, total)
 
 
 class RequestOutput:
@@ -280,6 +302,38 @@ class LLM:
             if r["i"][1] == 0:
                 outs.append(RequestOutput(r["rid"], r["text"], r["ids"], []))
             outs[-1].outputs.append(self._finish(r, *done[r["i"]]))
+        return outs
+
+    @torch.no_grad()
+    def score(self, prompts=None, prompt_token_ids=None, top_logprobs=0, start=None):
+        """Log-probabilities of GIVEN tokens (what vLLM reports as prompt_logprobs): one ScoreOutput per prompt, whose tokens
+        start .. L-1 are scored given the tokens in front of them over the raw model's distribution (USDMForCausalLM.score), with the
+        top_logprobs (0 .. 20) most likely ids of every scored position.  start: None = 1 (everything but the first token), an integer for
+        all prompts or a list with one per prompt - the length of a shared context when candidates behind it are compared.  Nothing is
+        generated and no SamplingParams apply.  The prompts run one after another on the single-sequence path (prefill is compute-bound;
+        with prefix reuse on, prompts that share a prefix of >= 16 tokens up to start - 1 prefill their own rows only)."""
+        if prompts is None and prompt_token_ids is None:
+            raise ValueError("prompts or prompt_token_ids is required")
+        if isinstance(prompts, str):
+            prompts = [prompts]
+        if prompt_token_ids is not None and prompt_token_ids and isinstance(prompt_token_ids[0], int):
+            prompt_token_ids = [prompt_token_ids]
+        n = len(prompts) if prompt_token_ids is None else len(prompt_token_ids)
+        k = check_logprobs(top_logprobs) or 0
+        starts = list(start) if isinstance(start, (list, tuple)) else [1 if start is None else start] * n
+        if len(starts) != n:
+            raise ValueError("start is one value for all prompts or a list with one value per prompt")
+        outs = []
+        for i in range(n):
+            text = prompts[i] if prompts is not None else None
+            if prompt_token_ids is not None:
+                ids = list(prompt_token_ids[i])
+            else:
+                if self.tokenizer is None:
+                    raise ValueError("text prompts need a tokenizer")
+                ids = list(self.tokenizer(text).input_ids)
+            lp = self.llm.score(torch.tensor([ids], dtype=torch.long, device=self.llm.device), top_logprobs=k, start=starts[i])
+            outs.append(assemble_score(ids, starts[i], lp, k, self.tokenizer, text))
         return outs
 
     # ------------------------------------------------------------------ one request on the single-sequence graph
