@@ -178,7 +178,8 @@ extern "C" int usdm_aa_snake(const usdm_snake_args* pa, usdm_stream_t stream) {
 
 extern "C" int usdm_sum3_scale(const float* a, const float* b, const float* c, float scale, int64_t n,
                                float* out32, void* out16, usdm_stream_t stream) {
-  USDM_CHECK_ARG(a && b && c && n > 0 && n % 4 == 0 && (out32 || out16), "usdm_sum3_scale: bad args");
+  USDM_CHECK_ARG(a && b && c && (out32 || out16), "usdm_sum3_scale: null args");
+  USDM_CHECK_ARG(n > 0 && n % 4 == 0, "usdm_sum3_scale: n=%lld must be a positive multiple of 4", (long long)n);
   const int64_t n4 = n / 4;
   hipLaunchKernelGGL(sum3_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, a, b, c, scale, n4, out32,
                      (bf16_t*)out16);
@@ -231,6 +232,7 @@ __global__ void stft_mag_kernel(const float* __restrict__ ri, int64_t ld, int nb
 extern "C" int usdm_stft_frames(const float* x, int32_t n, int32_t n_fft, int32_t hop, int32_t pad, const float* window,
                                 float* frames, int32_t T, usdm_stream_t stream) {
   USDM_CHECK_ARG(x && window && frames && n > pad && T > 0, "usdm_stft_frames: bad args (signal must be longer than the reflect pad)");
+  USDM_CHECK_ARG(n_fft > 0 && hop > 0, "usdm_stft_frames: n_fft=%d and hop=%d must be positive", n_fft, hop);
   USDM_CHECK_ARG((int64_t)(T - 1) * hop + n_fft <= (int64_t)n + 2 * pad, "usdm_stft_frames: T frames exceed the padded signal");
   hipLaunchKernelGGL(stft_frames_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, x, n, n_fft, hop, pad, window, frames, T);
   USDM_LAUNCH_CHECK();

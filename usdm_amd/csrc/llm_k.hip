@@ -1377,7 +1377,8 @@ extern "C" int usdm_argmax_final(const float* part_val, const int32_t* part_idx,
 
 extern "C" int usdm_embed_rows(const void* table, const int64_t* ids, const int32_t* next_token, int32_t n, int32_t Hd,
                                void* out, usdm_stream_t stream) {
-  USDM_CHECK_ARG(table && out && (ids || next_token) && n > 0 && Hd % 8 == 0, "usdm_embed_rows: bad args");
+  USDM_CHECK_ARG(table && out && (ids || next_token) && n > 0, "usdm_embed_rows: bad args");
+  USDM_CHECK_ARG(Hd % 8 == 0, "usdm_embed_rows: Hd=%d must be a multiple of 8 (16-byte row copies)", Hd);
   hipLaunchKernelGGL(embed_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)table, ids, next_token, n, Hd,
                      (bf16_t*)out);
   USDM_LAUNCH_CHECK();

@@ -105,6 +105,7 @@ extern "C" int usdm_vb_build_input(const usdm_vb_input_args* pa, usdm_stream_t s
   const usdm_vb_input_args& a = *pa;
   USDM_CHECK_ARG(a.B_in > 0 && (a.dup == 1 || a.dup == 2) && a.S > 0 && a.E % 8 == 0 && a.ldo >= a.E + 2 * a.F && a.ldo % 8 == 0,
                  "usdm_vb_build_input: bad sizes");
+  USDM_CHECK_ARG(a.F >= 0 && a.null_id >= 0, "usdm_vb_build_input: F=%d and null_id=%d must not be negative", a.F, a.null_id);
   USDM_CHECK_ARG(!a.use_cond || a.cond, "usdm_vb_build_input: cond missing");
   USDM_CHECK_ARG(a.out_dtype == USDM_BF16 || a.out_dtype == USDM_F32, "usdm_vb_build_input: out_dtype");
   if (a.out_dtype == USDM_F32) hipLaunchKernelGGL(vb_build_input_kernel<float>, dim3(a.S, a.B_in * a.dup), dim3(256), 0, (hipStream_t)stream, a);

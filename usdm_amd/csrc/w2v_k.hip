@@ -188,6 +188,7 @@ extern "C" int usdm_softmax_segments(float* x, int32_t rows, int32_t nseg, int32
 extern "C" int usdm_kmeans_argmin(const float* x, int32_t T, int32_t D, const float* dots, int64_t ldd, const float* csq,
                                   int32_t n_units, int64_t* ids, float* margin, usdm_stream_t stream) {
   USDM_CHECK_ARG(x && dots && csq && ids && T > 0 && D > 0 && n_units > 0, "usdm_kmeans_argmin: bad args");
+  USDM_CHECK_ARG(ldd >= n_units, "usdm_kmeans_argmin: ldd=%lld is shorter than a row of n_units=%d", (long long)ldd, n_units);
   hipLaunchKernelGGL(kmeans_argmin_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, x, D, dots, ldd, csq, n_units, ids, margin);
   USDM_LAUNCH_CHECK();
   return 0;
