@@ -1124,6 +1124,7 @@ static int gemm_impl(const usdm_gemm_args* pa, usdm_stream_t stream, int* tile_o
   if (a.tile_sel > 0) sel = (a.tile_sel & 0xff) - 1;   // benchmarking / test override (usdm_gemm_args.tile_sel; ops.gemm fills it from USDM_GEMM_TILE)
   if (a.taps != 1 && sel >= 4 && !(sel >= 12 && pp_taps)) sel = (sel == 6 || sel == 10) ? 1 : ((sel == 5 || sel == 7 || sel == 8) ? 2 : 0);   // DMA tiles are single-tap
   if (sel == 13 && (a.transpose_out || a.epi != USDM_EPI_PLAIN)) sel = 12;   // the 288-row tiles have row-major epilogues only
+  if (a.dtype == USDM_F32 && sel >= 12) sel = 2;      // the ping-pong tiles are bf16 only (reachable through tile_sel alone): report the 64x64 tile that runs
   if (!tile_out && (a.stats_out || a.ln_mode)) {      // folded LayerNorm: implemented in the epilogues of the ping-pong tiles only (see usdm_gemm_args)
     USDM_CHECK_ARG(sel >= 12 && sel <= 14 && a.dtype == USDM_BF16 && a.epi == USDM_EPI_PLAIN && !a.transpose_out && !a.round_bf16 &&
                        a.N % 128 == 0 && a.groups == 1 && (a.ldc & 3) == 0,
