@@ -569,6 +569,55 @@ int usdm_logit_edit_seg(const usdm_logit_edit_args* args, int32_t nseg, int64_t 
 int usdm_sizeof_logit_edit_args(void);
 int usdm_sizeof_logit_edit_params(void);
 
+/* Beam search, the pick of the batched decode step of B = st->batch beams in lockstep (1 .. 16; batch 0 counts as 1), in place of usdm_sample_final.
+ * Rows b < nlive of the ban-masked f32 logits are live (nlive = 1 on the first step, where all beams are still the prompt: this
+ * replaces HF's -1e9 initial scores; else nlive = B).  Per live row lp_b(i) = x_i - logsumexp(x) with exactly usdm_logprobs'
+ * arithmetic (max, 2^40 fixed-point sum, f64 log, one rounding to f32; banned ids -inf) and s(b, i) = score[b] + lp_b(i), one f32
+ * addition.  Selected are the KC = max(2, 1 + n_eos) * B largest s (HF's beams_to_keep) under the TOTAL order: value descending,
+ * then flat index b * V + i ascending, -0.0 folded into +0.0; composite (value, index) keys are unique, so the selection is exact.
+ * Written, for t = step[0] (t >= log_rows or t >= st->max_out: the launch changes nothing):
+ *   log_score / log_token / log_parent [t][KC]   the candidates in that order (token = id + st->id_offset)
+ *   next_token[b], parent[b], score[b], out_tokens[b][t], h_out[b] = embed_table[next_token[b]]   for b < B: the first B candidates
+ *                                                whose token is none of the n_eos ids eos[0 ..] (HF's running beams of the next
+ *                                                iteration; at most n_eos * nlive of the KC are EOS, so B always remain)
+ *   step[b] + 1 and (st->advance_pos) pos[b] + 1 for all b < B
+ * Every sum is an integer sum and every per-id quantity depends on the value only: bit-identical run to run, and two live rows with
+ * equal logits and equal scores give bit-equal candidates.  Two launches: one workgroup per live row, one merging workgroup.
+ * Refused: B outside 1 .. 16, n_eos outside 0 .. 3, KC > 32, V < KC or V > 2^20, nlive outside {1, B}, logits_bs < V, a missing
+ * pointer, log_rows < 1. */
+#define USDM_BEAM_MAX_KC 32
+typedef struct usdm_beam_args {
+  const float* logits; int32_t V;
+  int64_t logits_bs;           /* beam b's row is logits + b * logits_bs (>= V) */
+  float* score;                /* [B] running scores, read and rewritten */
+  int32_t* parent;             /* [B] out: the beam each new running beam continues */
+  int32_t nlive, n_eos;
+  const int32_t* eos;          /* [3] device: the EOS ids (the first n_eos are read) */
+  float* log_score; int32_t* log_token; int32_t* log_parent;   /* [log_rows][KC] */
+  int32_t log_rows;
+  float* cand_score; int32_t* cand_index;   /* scratch [B][KC]: the rows' own best KC (value, id), between the two launches */
+} usdm_beam_args;
+int usdm_beam_step(const usdm_beam_args* args, const usdm_decode_state* st, const void* embed_table_bf16, int32_t Hd, void* h_out_bf16,
+                   usdm_stream_t stream);
+int usdm_sizeof_beam_args(void);
+
+/* Reorder of the beams' KV rows by parent, in place: for every array a < n_arrays, block k < nblk (layer x kv head) and row r in
+ * [*lo, pos[0]), slot b's row becomes what slot parent[b]'s row was BEFORE the launch, for all b < B at once; parent may be any map
+ * (identity, cycles, several children of one parent).  A byte copy: array a is base[a] + b * slot_bytes[a] + k * ctx_max *
+ * row_bytes[a] + r * row_bytes[a], so bf16 rows (256 B), e4m3 rows (128 B) and their int8 exponents (1 B) are the same kernel.
+ * One thread owns a byte offset in ALL slots: it loads the sources of every slot with parent[b] != b, then stores them, so no
+ * staging copy is needed.  parent, lo and pos are read from device memory (the launch is capturable); rows outside [lo, pos),
+ * slots >= B and slots with parent[b] == b or outside [0, B) are not written.  lo < 0 counts as 0, pos[0] > ctx_max as ctx_max.
+ * Refused: B outside 1 .. 16, n_arrays outside 1 .. 4, a null base, row_bytes < 1, a row_bytes >= 16 that is no multiple of 16 or
+ * whose base / slot_bytes are not 16-byte aligned, slot_bytes < nblk * ctx_max * row_bytes. */
+typedef struct usdm_kv_reorder_args {
+  void* base[4]; int64_t slot_bytes[4]; int32_t row_bytes[4];
+  int32_t n_arrays, nblk, ctx_max, B;
+  const int32_t* parent; const int32_t* lo; const int32_t* pos;
+} usdm_kv_reorder_args;
+int usdm_kv_reorder(const usdm_kv_reorder_args* args, usdm_stream_t stream);
+int usdm_sizeof_kv_reorder_args(void);
+
 /* out[r][:] = table[ids[r]][:] (bf16 rows; ids == NULL -> single row from *next_token) */
 int usdm_embed_rows(const void* table, const int64_t* ids, const int32_t* next_token, int32_t n, int32_t Hd,
                     void* out, usdm_stream_t stream);

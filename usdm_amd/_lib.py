@@ -35,6 +35,8 @@ lib.usdm_penalize_seg.restype = C.c_int
 lib.usdm_penalty_params_init.restype = C.c_int
 lib.usdm_logit_edit.restype = C.c_int        # (the logit-edit entry points: likewise)
 lib.usdm_logit_edit_seg.restype = C.c_int
+lib.usdm_beam_step.restype = C.c_int         # (the beam-search entry points: likewise)
+lib.usdm_kv_reorder.restype = C.c_int
 _exp = None
 
 
@@ -235,6 +237,23 @@ class LogitEditArgs(C.Structure):
     ]
 
 
+class BeamArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("V", C.c_int32), ("logits_bs", C.c_int64), ("score", C.c_void_p), ("parent", C.c_void_p),
+        ("nlive", C.c_int32), ("n_eos", C.c_int32), ("eos", C.c_void_p),
+        ("log_score", C.c_void_p), ("log_token", C.c_void_p), ("log_parent", C.c_void_p), ("log_rows", C.c_int32),
+        ("cand_score", C.c_void_p), ("cand_index", C.c_void_p),
+    ]
+
+
+class KvReorderArgs(C.Structure):
+    _fields_ = [
+        ("base", C.c_void_p * 4), ("slot_bytes", C.c_int64 * 4), ("row_bytes", C.c_int32 * 4),
+        ("n_arrays", C.c_int32), ("nblk", C.c_int32), ("ctx_max", C.c_int32), ("B", C.c_int32),
+        ("parent", C.c_void_p), ("lo", C.c_void_p), ("pos", C.c_void_p),
+    ]
+
+
 class RopeArgs(C.Structure):
     _fields_ = [
         ("qkv", C.c_void_p), ("ld", C.c_int64), ("S", C.c_int32), ("pos0", C.c_int32), ("Hq", C.c_int32),
@@ -279,7 +298,8 @@ def _selfcheck():
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
-                      ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs)):
+                      ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs), ("beam", BeamArgs),
+                      ("kv_reorder", KvReorderArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

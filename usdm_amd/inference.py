@@ -79,11 +79,13 @@ def _bad(name, *a, **k):
 @torch.inference_mode()
 def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, output_path,
            reference_mel=None, n_timesteps=50, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-           min_p=0.0, logit_bias=None, no_repeat_ngram_size=0):
+           min_p=0.0, logit_bias=None, no_repeat_ngram_size=0, num_beams=None):
     """src/inference.py:48-89.  logprobs=K (0 .. 20): the LLM also computes per-token log-probabilities (USDMForCausalLM.generate) and the
     cumulative log-probability of each of the three rounds goes to stderr; nothing else changes.
     repetition_penalty / presence_penalty / frequency_penalty: passed to all three rounds (USDMForCausalLM.generate; on the device).
-    min_p / logit_bias / no_repeat_ngram_size: likewise (the rounds pick with top_k = 1, where min_p changes nothing)."""
+    min_p / logit_bias / no_repeat_ngram_size: likewise (the rounds pick with top_k = 1, where min_p changes nothing).
+    num_beams=N > 1: the three rounds run beam search on the device instead (USDMForCausalLM.generate(num_beams=N): the best
+    hypothesis, HF's defaults length_penalty = 1 and early_stopping = False); its score goes to stderr.  Not with the knobs above."""
     bad_words_ids_unit2text = _bad("u2t", 32000, 42003)
     bad_words_ids_text2text = _bad("t2t", 32002, 42003)
     bad_words_ids_text2unit = _bad("t2u", 0, 32002, exclude=[28705])
@@ -94,6 +96,10 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
 
     def run(model_input, bad, eos, name):
         ids = torch.LongTensor(tokenizer(model_input).input_ids).to(device).unsqueeze(0)
+        if num_beams is not None and num_beams > 1:
+            out = model.generate(input_ids=ids, max_length=tokenizer.model_max_length, bad_words_ids=bad, eos_token_id=eos, num_beams=num_beams)
+            print(f"{name}: beam search over {num_beams} beams, score {float(model.last_beam_scores[0]):.4f}", file=sys.stderr)
+            return out
         out = model.generate(input_ids=ids, max_length=tokenizer.model_max_length, do_sample=True, bad_words_ids=bad,
                              top_p=1.0, top_k=1, temperature=1.0, eos_token_id=eos, logprobs=logprobs,
                              repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
@@ -141,6 +147,20 @@ def parse_logit_bias(text):
         return {int(k): v for k, v in obj.items()}
     except ValueError:
         raise ValueError("logit_bias: every key must be an integer token id") from None
+
+
+def check_num_beams(args):
+    """--num_beams: None or 1 (off), or 2 .. 16 with every other generation flag at its default.  ValueError otherwise."""
+    n = args.num_beams
+    if n is None or n == 1:
+        return
+    from .ops import beam_candidates
+    beam_candidates(n, 1)      # (every round has one EOS id)
+    flags = dict(logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, no_repeat_ngram_size=0,
+                 logit_bias=None)
+    used = [f"--{k}" for k, v in flags.items() if getattr(args, k) != v]
+    if used:
+        raise ValueError(f"--num_beams cannot be combined with {', '.join(used)}: beam search ranks the model's own log-probabilities")
 
 
 def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None, kv_cache_dtype=None):
@@ -203,9 +223,14 @@ def main(argv=None):
     parser.add_argument('--logit_bias', type=str, default=None, metavar="JSON",
                         help='Additive logit bias of the three LLM rounds as a JSON object {"token id": bias}, at most 1024 entries, '
                              'values clamped to [-100, 100] (OpenAI / vLLM).')
+    parser.add_argument('--num_beams', type=int, default=None, metavar="N",
+                        help="Beam search over N beams (2 .. 16) in the three LLM rounds instead of the greedy pick, on the device (HF "
+                             "generate(num_beams=N): length_penalty 1, early_stopping False, the best hypothesis).  An error together with "
+                             "--logprobs, the penalties, --min_p, --no_repeat_ngram_size or --logit_bias.")
     args = parser.parse_args(argv)
     from .llm import check_edits, check_min_p, check_penalties
     try:
+        check_num_beams(args)
         check_penalties(args.repetition_penalty, args.presence_penalty, args.frequency_penalty)
         check_min_p(args.min_p)
         logit_bias = parse_logit_bias(args.logit_bias)
@@ -219,7 +244,7 @@ def main(argv=None):
     try:
         sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path, logprobs=args.logprobs,
                repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty,
-               min_p=args.min_p, logit_bias=logit_bias, no_repeat_ngram_size=args.no_repeat_ngram_size)
+               min_p=args.min_p, logit_bias=logit_bias, no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)
         print(f"Error while sampling: {e}")
         return 1

@@ -437,6 +437,9 @@ class USDMForCausalLM:
         self._decode = None
         self._decodes = {}
         self._batches = {}
+        self._beams = {}          # beam search: the buffers, prefill plans and step of (num_beams, n_eos), built at first use (_beam_buffers)
+        self.last_beam_scores = None   # generate(num_beams > 1): HF's sequences_scores of the returned sequences (float32 tensor [n])
+        self.last_beam_rows, self.last_beam_replay = None, None   # ... its recorded logits rows (tests: _beam_keep_rows) and its beam.BeamReplay
         self._ban_cache = LRU(8)
         self.stats = {}
         self.logits_hook = None   # generate(_logits_hook=f): f() runs between the lm_head launch and the sampling pick of every step
@@ -687,7 +690,7 @@ class USDMForCausalLM:
             self._edt = edit_buffers(self.device, self.ctx_max)
 
     def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None, logprobs=None,
-                          penalties=False, edits=False):
+                          penalties=False, edits=False, beam=None):
         """lm_head GEMV + token choice, for the single sequence (slot=None), a batch slot's prefill, and the batched step
         (slot = the batch's "all" view, batch_gemv = its projection launcher).  sampling=None: ban-masked arg-max (the reference's
         top_k=1 path); sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block sample_params
@@ -703,7 +706,10 @@ class USDMForCausalLM:
         same token).  The hook, the log-probabilities and last_logits see the penalised row.
         edits (sampled picks only): usdm_logit_edit directly in front of usdm_penalize (HF's and vLLM's order: bias, then penalties) -
         the logit bias and the n-gram ban of the sequence's / the slots' edit state (tensor parallel: on the gathered row, on every
-        rank, with global ids).  Everything after it sees the edited row."""
+        rank, with global ids).  Everything after it sees the edited row.
+        beam (the buffers of _beam_buffers; one GPU, no hook, no penalties, no edits, no log-probabilities): the pick is the beam
+        search's (_beam_pick) over ALL rows of those buffers - from the batched step (slot = their "all" view) with every row live,
+        from the prompt's prefill into slot 0 (slot = that slot) with row 0 live."""
         c, H = self.cfg, self.cfg["hidden_size"]
         if logprobs is not None and not sampling:
             raise ValueError("log-probabilities need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
@@ -757,6 +763,8 @@ class USDMForCausalLM:
             ops.sample_final(row, st, V=c["vocab_size"], dev_params=sl.sample_params, plan=rec.plan, **seg, **out)
             if lp:
                 ops.logprobs(row, st, V=c["vocab_size"], plan=rec.plan, **seg, **lp)
+        elif beam is not None:
+            self._beam_pick(rec, beam, nlive=B or 1, advance_pos=advance_pos)
         elif sampling:
             if edt:
                 ops.logit_edit(logits, st, V=self.v1 - self.v0, plan=rec.plan, **edt)
@@ -1091,8 +1099,13 @@ class USDMForCausalLM:
         batch, st_done, st_eos = 0, None, None
 
     def _batch_buffers(self, B):
-        if B in self._batches:
-            return self._batches[B]
+        if B not in self._batches:
+            self._batches[B] = self._new_batch_buffers(B)
+        return self._batches[B]
+
+    def _new_batch_buffers(self, B):
+        """The buffers of B slots in lockstep (caches, decode state, logits rows) and their per-slot / whole-batch views; the caller
+        keeps them (generate_batch: self._batches[B]; beam search: its own, self._beams)."""
         c, dev, bf = self.cfg, self.device, torch.bfloat16
         L, d, H = c["num_hidden_layers"], c["head_dim"], c["hidden_size"]
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
@@ -1137,7 +1150,6 @@ class USDMForCausalLM:
         al.part_val_loc, al.part_idx_loc = bb["pv"], bb["pi"]
         al.part_val, al.part_idx = (bb["pvg"], bb["pig"]) if self.tp_path else (bb["pv"], bb["pi"])
         al.logits, al.sample_params, al.logits_row = bb["logits"], bb["sp"], bb.get("lg")
-        self._batches[B] = bb
         return bb
 
     def _batch_pick_state(self, B, kind):
@@ -1160,13 +1172,15 @@ class USDMForCausalLM:
                 setattr(sl, name, {k: v[b] for k, v in bufs.items()})
         return bb
 
-    def _build_decode_batch(self, B, sampling=False, logprobs=None, penalties=False, edits=False):
+    def _build_decode_batch(self, B, sampling=False, logprobs=None, penalties=False, edits=False, beam=None):
         """One decode step of B sequences: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
         sampling: the pick is usdm_sample_final's batched form - every slot draws with its OWN knobs (bb["sp"][b]: temperature,
-        top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1."""
+        top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1.
+        beam (the buffers of _beam_buffers): the step of a beam search over those buffers instead - the pick is usdm_beam_step over
+        the B rows, followed by usdm_kv_reorder; returned as its two segments (the pick's end is where an eager run can look)."""
         dev, bf = self.device, torch.bfloat16
         H, d, L, Hq, Hkv, I, nq = self._dims()
-        bb = self._batch_buffers(B)
+        bb = self._batch_buffers(B) if beam is None else beam
         rec = _Segments()
         Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
         h, qkv, ao, act = bb["h"], Z(B, nq), Z(B, Hq * d), Z(B, I)
@@ -1205,9 +1219,10 @@ class USDMForCausalLM:
                             counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=rec.plan)
 
         self._layers(rec, gemv, attn, h, qkv, ao, act, "reduce" if tp else "fused", n=B * H, parts=parts, down_kw={} if tp else dict(ks=ks))
-        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs, penalties=penalties, edits=edits)
+        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs, penalties=penalties, edits=edits,
+                               beam=beam)
         segs = rec.finish()
-        return segs if tp else segs[0]
+        return segs if (tp or beam is not None) else segs[0]
 
     MAX_BATCH = 16      # sequences per decode step (usdm_gemv_batch: VALU form up to 4, matrix-core form up to 16)
 
@@ -1327,6 +1342,115 @@ class USDMForCausalLM:
                 self.last_logprobs.append(read_logprobs(bb["lp"], n, logprobs, b))
         return res
 
+    # ------------------------------------------------------------------ beam search
+    def _beam_buffers(self, B, n_eos):
+        """The state of a search with B beams and n_eos EOS ids, in a cache of its own (generate_batch's slots and plans are not
+        touched): the B slots of _new_batch_buffers plus the running scores, the parents, the EOS ids, `lo` (first cache row the
+        reorder moves), usdm_beam_step's scratch and its step log [max_out][KC]; per prompt length one prefill plan, and the step."""
+        key = (B, n_eos)
+        if key not in self._beams:
+            dev, KC = self.device, ops.beam_candidates(B, n_eos)
+            bm = self._new_batch_buffers(B)
+            i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+            f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+            bm.update(n_eos=n_eos, KC=KC, score=f32(B), parent=i32(B), eos=i32(ops.BEAM_MAX_EOS), lo=i32(1), cand_score=f32(B, KC),
+                      cand_index=i32(B, KC), log_score=f32(self.max_out, KC), log_token=i32(self.max_out, KC),
+                      log_parent=i32(self.max_out, KC), beam_graph=None, beam_eager=None)
+            self._beams[key] = bm
+        return self._beams[key]
+
+    def _beam_pick(self, rec, bm, nlive, advance_pos):
+        """usdm_beam_step over the rows of the beam buffers, a segment boundary, usdm_kv_reorder of every cache array by the parents
+        the pick just wrote.  (The boundary costs nothing: a captured step joins its segments into one hipGraph.)"""
+        H, d, L, Hq, Hkv, I, nq = self._dims()
+        al = bm["all"]
+        st = ops.decode_state(al.st_next, al.st_out, al.st_step, al.st_pos, advance_pos=advance_pos, batch=al.batch)
+        ops.beam_step(bm["logits"], st, V=self.v1 - self.v0, score=bm["score"], parent=bm["parent"], nlive=nlive, eos=bm["eos"],
+                      n_eos=bm["n_eos"], log_score=bm["log_score"], log_token=bm["log_token"], log_parent=bm["log_parent"],
+                      cand_score=bm["cand_score"], cand_index=bm["cand_index"], embed=self.W["embed"], h_out=bm["h"], Hd=H, plan=rec.plan)
+        rec.plan.hold(st)
+        rec.cut()
+        arrays = [bm["kc"], bm["vc"]] + ([bm["ke"], bm["ve"]] if self.kv8 else [])
+        ops.kv_reorder(arrays, bm["parent"], bm["lo"], bm["pos"], B=al.batch, nblk=L * Hkv, ctx_max=self.ctx_max, plan=rec.plan)
+
+    def _generate_beam(self, input_ids, max_new_tokens, B, n, length_penalty, early_stopping, eos_list, pad_token_id, bad_words_ids,
+                       ban_mask, keep_rows=False, on_step=None):
+        """generate(num_beams=B): one prefill of the prompt into slot 0, whose pick is usdm_beam_step with row 0 live and whose
+        usdm_kv_reorder (lo = 0, every parent 0) hands the prompt's rows to all slots; then per token ONE captured graph: the batched
+        decode step of the B slots, usdm_beam_step, usdm_kv_reorder of the rows behind the prompt (lo = prompt length).  Every 8
+        steps the host reads the new rows of the step log and replays HF's finished-beam bookkeeping on them (beam.BeamReplay);
+        steps the device ran past HF's stopping point are not fed.
+        keep_rows / on_step (tests; either one runs the step's two segments as plain launches instead of the graph): copy every step's
+        [B][V] logits rows to self.last_beam_rows; call on_step(phase, bm) with phase "pick" between the pick and the reorder and "step"
+        after it.  self.last_beam_replay keeps the BeamReplay (the step log's tokens and parents as the host saw them)."""
+        from .beam import BeamReplay
+        bm = self._beam_buffers(B, len(eos_list))
+        L0, V = int(input_ids.shape[1]), self.v1 - self.v0
+        if ban_mask is not None:
+            self.ban.copy_(ban_mask.to(torch.uint8)[self.v0:self.v1])
+        else:
+            self.ban.copy_(self._ban_mask(bad_words_ids))
+        bm["eos"].copy_(torch.tensor((eos_list + [0] * ops.BEAM_MAX_EOS)[:ops.BEAM_MAX_EOS], dtype=torch.int32))
+        bm["pos"].fill_(L0)
+        bm["step"].zero_()
+        bm["score"].zero_()
+        bm["lo"].zero_()
+        segs, io = bm["prefill"].get_or_build(L0, lambda: self._build_beam_prefill(L0, bm))
+        io["ids"].copy_(input_ids[0])
+        rows = [] if keep_rows else None
+        hooked = keep_rows or on_step is not None
+
+        def run(step_segs):      # a list of segments (the prefill; the eager step) or the captured step
+            if not hooked:
+                return self._run_segs(step_segs) if isinstance(step_segs, list) else step_segs.run()
+            *head, last = step_segs
+            self._run_segs(head)
+            if rows is not None:
+                rows.append(bm["logits"][:, :V].cpu().numpy().copy())
+            if on_step is not None:
+                on_step("pick", bm)
+            last.run()
+            if on_step is not None:
+                on_step("step", bm)
+
+        run(segs)      # prefill + first pick + the prompt's rows to every slot
+        bm["lo"].fill_(L0)
+        if hooked:
+            if bm["beam_eager"] is None:
+                bm["beam_eager"] = self._build_decode_batch(B, True, beam=bm)
+            step = bm["beam_eager"]
+        else:
+            if bm["beam_graph"] is None:
+                bm["beam_graph"] = self._graphed(self._build_decode_batch(B, True, beam=bm))
+            step = bm["beam_graph"]
+        rp = BeamReplay(B, eos_list, max_new_tokens, length_penalty, early_stopping)
+        produced, fed, chunk = 1, 0, 8
+        while True:
+            log = [bm[k][fed:produced].cpu().numpy() for k in ("log_score", "log_token", "log_parent")]      # host sync point
+            over = False
+            for r in range(produced - fed):
+                over = rp.feed(log[0][r], log[1][r], log[2][r])
+                if over:
+                    break
+            fed = produced
+            if over or produced >= max_new_tokens:
+                break
+            for _ in range(min(chunk, max_new_tokens - produced)):
+                run(step)
+                produced += 1
+        seqs, scores = rp.results(n, pad_token_id)
+        self.last_beam_scores = torch.from_numpy(scores)
+        self.last_beam_rows = None if rows is None else rows[:rp.steps]
+        self.last_beam_replay = rp
+        gen = torch.tensor(seqs, dtype=torch.long, device=input_ids.device).view(n, -1)
+        return torch.cat([input_ids[0].expand(n, -1), gen], 1)
+
+    def _build_beam_prefill(self, L, bm):
+        """The prompt's prefill into slot 0 of the beam buffers, the lm_head over its last row into logits row 0, and the first pick."""
+        rec, io, h, _ = self._prefill_rows(L, slot=bm["slots"][0])
+        self._lm_head_and_pick(rec, h[L - 1], False, True, slot=bm["slots"][0], beam=bm)
+        return rec.finish(), io
+
     # ------------------------------------------------------------------ generate
     def _ban_mask(self, bad_words_ids):
         if not bad_words_ids:
@@ -1387,7 +1511,8 @@ class USDMForCausalLM:
     def generate(self, input_ids=None, max_length=None, do_sample=False, bad_words_ids=None, top_p=1.0, top_k=None,
                  temperature=1.0, eos_token_id=None, max_new_tokens=None, min_new_tokens=0, seed=None, ban_mask=None,
                  _logits_hook=None, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
-                 logit_bias=None, no_repeat_ngram_size=0, **unused):
+                 logit_bias=None, no_repeat_ngram_size=0, num_beams=None, num_return_sequences=None, length_penalty=1.0,
+                 early_stopping=False, pad_token_id=None, _beam_keep_rows=False, _beam_on_step=None, **unused):
         """Generation with the call shape of src/inference.py:63-83.  Greedy when do_sample is False or top_k == 1 (what the
         reference passes: arg-max of the ban-masked logits).  Otherwise temperature / top-k / top-p sampling on the device
         (usdm_sample_final).  `seed` keys its Philox stream; seed=None draws a fresh one from torch's global CPU generator,
@@ -1404,14 +1529,46 @@ class USDMForCausalLM:
         are dropped (inside usdm_sample_final: no other plan; a greedy pick keeps the maximum anyway).
         logit_bias {id: bias} (at most 1024 ids, values clamped to [-100, 100]) and no_repeat_ngram_size n (HF
         NoRepeatNGramLogitsProcessor over prompt + output) run on the device in front of the penalties (usdm_logit_edit; DESIGN.md 8h-2);
-        a greedy call then runs on the sampling step with top_k = 1.  Both neutral (None / 0): no edit plan, no buffers."""
+        a greedy call then runs on the sampling step with top_k = 1.  Both neutral (None / 0): no edit plan, no buffers.
+        num_beams=B in 2 .. 16 (B <= max_batch(); None / 1: this call is what it is without the argument, no beam buffers and no
+        beam plans are built): beam search on the device (usdm_beam_step, usdm_kv_reorder) with the semantics of the
+        installed transformers' generate(num_beams=B, do_sample=False, renormalize_logits=True): num_return_sequences=n <= B (default
+        1), length_penalty (default 1.0), early_stopping False / True / "never", at most 3 eos ids with max(2, 1 + n_eos) * B <= 32.
+        The log-probabilities are normalised over the ALLOWED ids (banned lm_head rows are never streamed), which is HF's
+        renormalize_logits=True; without bad_words_ids / ban_mask it is plain HF.  Returns [n][Lmax]: the prompt and each hypothesis,
+        padded with pad_token_id (default: the first eos id); self.last_beam_scores holds HF's sequences_scores (float32 [n]).
+        Not combined with (NotImplementedError): do_sample, logprobs, the penalties, logit_bias / no_repeat_ngram_size, min_p,
+        _logits_hook, min_new_tokens > 0, tensor parallelism.  The single sequence's KV cache and its prefix reuse are not touched."""
         lpk = check_logprobs(logprobs)
         pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         min_p = check_min_p(min_p)
         edt = check_edits(logit_bias, no_repeat_ngram_size, self.cfg["vocab_size"])
-        self.last_logprobs = None
+        self.last_logprobs = self.last_beam_scores = None
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1, as the reference calls it)")
+        if num_beams is not None and num_beams != 1:
+            from .beam import check_beam_args, check_beam_call
+            eos_list = list(dict.fromkeys(int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else
+                                                          ([] if eos_token_id is None else [eos_token_id]))))
+            B, n, length_penalty, early_stopping, _ = check_beam_args(num_beams, num_return_sequences, length_penalty, early_stopping,
+                                                                      len(eos_list), self.v1 - self.v0)
+            check_beam_call(do_sample, lpk, pen, edt, min_p, _logits_hook, min_new_tokens, self.tp_path)
+            if temperature != 1.0 or top_p != 1.0:
+                raise ValueError("temperature / top_p only apply with do_sample=True")
+            if B > self.max_batch():
+                raise ValueError(f"num_beams={B}: a decode step of this model takes at most {self.max_batch()} sequences")
+            L0 = input_ids.shape[1]
+            if max_new_tokens is None:
+                if max_length is None:
+                    raise ValueError("max_length or max_new_tokens is required")
+                max_new_tokens = max_length - L0
+            max_new_tokens = min(max_new_tokens, self.ctx_max - L0, self.max_out)
+            if max_new_tokens <= 0:
+                return input_ids.expand(n, -1).clone()
+            return self._generate_beam(input_ids, max_new_tokens, B, n, length_penalty, early_stopping, eos_list, pad_token_id,
+                                       bad_words_ids, ban_mask, keep_rows=_beam_keep_rows, on_step=_beam_on_step)
+        if num_return_sequences not in (None, 1):
+            raise ValueError("num_return_sequences > 1 needs num_beams > 1")
         sampling = False
         if _logits_hook is not None:      # arbitrary Python logits processors: eager steps, knobs still on the device
             if seed is None:

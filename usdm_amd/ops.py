@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, BeamArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -479,6 +479,74 @@ def prompt_logprobs(logits, ids, *, row0, K, tok_lp, tok_rank, top_id=None, top_
         _go(plan, "usdm_prompt_logprobs_seg", lib.usdm_prompt_logprobs_seg, C_.byref(a), C_.c_int32(nseg), C_.c_int64(seg_stride), C_.c_int32(seg_len))
         return
     _go(plan, "usdm_prompt_logprobs", lib.usdm_prompt_logprobs, C_.byref(a))
+
+
+BEAM_MAX_KC = 32        # candidates usdm_beam_step keeps per step: KC = max(2, 1 + n_eos) * B
+BEAM_MAX_EOS = 3
+
+
+def beam_candidates(B, n_eos):
+    """KC = max(2, 1 + n_eos) * B (HF's beams_to_keep), checked against usdm_beam_step's limits: 1 <= B <= 16, 0 <= n_eos <= 3,
+    KC <= 32.  ValueError otherwise."""
+    if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= 16:
+        raise ValueError(f"beam search runs 1 .. 16 beams, got {B!r}")
+    if not 0 <= n_eos <= BEAM_MAX_EOS:
+        raise ValueError(f"beam search takes 0 .. {BEAM_MAX_EOS} EOS ids, got {n_eos}")
+    KC = max(2, 1 + n_eos) * B
+    if KC > BEAM_MAX_KC:
+        raise ValueError(f"beam search keeps KC = max(2, 1 + n_eos) * num_beams = {KC} candidates per step, at most {BEAM_MAX_KC} are supported")
+    return KC
+
+
+def beam_step(logits, st, *, score, parent, nlive, eos, n_eos, log_score, log_token, log_parent, cand_score, cand_index, embed=None,
+              h_out=None, Hd=0, V=None, plan=None):
+    """usdm_beam_step: the beam-search pick of B = st.batch rows of ban-masked f32 logits [B][>= V].  score f32 [B] (read and
+    rewritten), parent i32 [B] (out), nlive 1 (first step) or B, eos i32 [>= 3] on the device with its first n_eos ids, the step log
+    log_score f32 / log_token i32 / log_parent i32 [rows][KC] with KC = beam_candidates(B, n_eos), scratch cand_score f32 / cand_index
+    i32 [B][KC].  V: ids ranked (default logits.shape[-1]).  Contiguous rows only: beam search runs on one GPU."""
+    _need_cuda(logits, score, parent, eos, log_score, log_token, log_parent, cand_score, cand_index, embed, h_out)
+    B = max(1, st.batch)
+    KC = beam_candidates(B, n_eos)
+    a = BeamArgs()
+    _logits_row("beam_step", a, logits, st, V, 1, 0, 0)
+    if a.V < KC:
+        raise ValueError(f"beam_step: V = {a.V} is smaller than the KC = {KC} candidates kept per step")
+    if nlive not in (1, B):
+        raise ValueError(f"beam_step: nlive must be 1 or B = {B}, got {nlive}")
+    for name, t, dt, n in (("score", score, torch.float32, B), ("parent", parent, torch.int32, B), ("eos", eos, torch.int32, BEAM_MAX_EOS),
+                           ("cand_score", cand_score, torch.float32, B * KC), ("cand_index", cand_index, torch.int32, B * KC),
+                           ("log_score", log_score, torch.float32, KC), ("log_token", log_token, torch.int32, KC),
+                           ("log_parent", log_parent, torch.int32, KC)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < n:
+            raise ValueError(f"beam_step: {name} must be a contiguous {dt} tensor of at least {n} values")
+    rows = min(t.numel() // KC for t in (log_score, log_token, log_parent))
+    a.score, a.parent, a.nlive, a.n_eos, a.eos = _ptr(score), _ptr(parent), int(nlive), int(n_eos), _ptr(eos)
+    a.log_score, a.log_token, a.log_parent, a.log_rows = _ptr(log_score), _ptr(log_token), _ptr(log_parent), rows
+    a.cand_score, a.cand_index = _ptr(cand_score), _ptr(cand_index)
+    _go(plan, "usdm_beam_step", lib.usdm_beam_step, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
+
+
+def kv_reorder(arrays, parent, lo, pos, *, B, nblk, ctx_max, plan=None):
+    """usdm_kv_reorder: rows [lo[0], pos[0]) of every block of slot b become those of slot parent[b], in place, for each tensor of
+    `arrays` (1 .. 4 of them): [>= B][nblk = layers x kv heads][ctx_max][row...] with contiguous slots, any element type (K / V caches,
+    bf16 or e4m3, and the fp8 cache's exponents [B][nblk][ctx_max]).  parent i32 [>= B], lo i32 [1], pos i32 [>= 1]: device memory."""
+    _need_cuda(parent, lo, pos, *arrays)
+    if not 1 <= len(arrays) <= 4:
+        raise ValueError("kv_reorder: 1 .. 4 arrays")
+    for t in (parent, lo, pos):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("kv_reorder: parent, lo and pos must be contiguous int32 tensors")
+    if parent.numel() < B or lo.numel() < 1 or pos.numel() < 1:
+        raise ValueError("kv_reorder: parent [B], lo [1], pos [>= 1]")
+    a = KvReorderArgs()
+    a.n_arrays, a.nblk, a.ctx_max, a.B = len(arrays), int(nblk), int(ctx_max), int(B)
+    a.parent, a.lo, a.pos = _ptr(parent), _ptr(lo), _ptr(pos)
+    for i, t in enumerate(arrays):
+        if t.shape[0] < B or not t[0].is_contiguous() or t[0].numel() % (nblk * ctx_max):
+            raise ValueError(f"kv_reorder: array {i} must be [>= B][nblk][ctx_max][row] with contiguous slots")
+        a.base[i], a.slot_bytes[i] = t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else t[0].numel()) * t.element_size()
+        a.row_bytes[i] = t[0].numel() // (nblk * ctx_max) * t.element_size()
+    _go(plan, "usdm_kv_reorder", lib.usdm_kv_reorder, C_.byref(a))
 
 
 PENALTY_PROMPT_BIT = 1 << 30     # usdm_penalize's table word: in_prompt(i) in bit 30, c(i) below it

@@ -151,6 +151,39 @@ def assemble_score(prompt_token_ids, start, lp, k, tokenizer=None, prompt=None):
     return ScoreOutput(prompt, ids, [None] * start + rows, total)
 
 
+class BeamSearchParams:
+    """vllm.sampling_params.BeamSearchParams(beam_width, max_tokens, ignore_eos=False, length_penalty=1.0), plus what a request of this
+    package carries next to it: stop_token_ids (at most 3 stop ids in all, the tokenizer's EOS included unless ignore_eos) and the
+    static -inf mask, as logits_processors that are one (static_mask_of) or a ready-made static_logits_mask [vocab] of 0 / 1."""
+
+    def __init__(self, beam_width, max_tokens, ignore_eos=False, temperature=0.0, length_penalty=1.0, stop_token_ids=None,
+                 logits_processors=None, static_logits_mask=None):
+        if temperature not in (0, 0.0):
+            raise NotImplementedError("beam search with a temperature is not supported (the search ranks exact log-probabilities)")
+        self.beam_width, self.max_tokens, self.ignore_eos, self.temperature = beam_width, int(max_tokens), bool(ignore_eos), 0.0
+        self.length_penalty = length_penalty
+        self.stop_token_ids, self.logits_processors, self.static_logits_mask = list(stop_token_ids or []), logits_processors, static_logits_mask
+
+
+class BeamSearchSequence:
+    """One hypothesis: tokens = prompt + generated ids (its stop id included), cum_logprob = the sum of its tokens' log-probabilities
+    (HF's sequences_scores x length ** length_penalty), text = the decoded generated ids (None without a tokenizer)"""
+
+    def __init__(self, tokens, cum_logprob, text=None):
+        self.tokens, self.cum_logprob, self.text = tokens, cum_logprob, text
+
+    def __repr__(self):
+        return f"BeamSearchSequence(tokens={self.tokens!r}, cum_logprob={self.cum_logprob!r}, text={self.text!r})"
+
+
+class BeamSearchOutput:
+    def __init__(self, sequences):
+        self.sequences = sequences
+
+    def __repr__(self):
+        return f"BeamSearchOutput(sequences={self.sequences!r})"
+
+
 class RequestOutput:
     def __init__(self, request_id, prompt, prompt_token_ids, outputs):
         self.request_id, self.prompt, self.prompt_token_ids, self.outputs, self.finished = request_id, prompt, prompt_token_ids, outputs, True
@@ -302,6 +335,47 @@ class LLM:
             if r["i"][1] == 0:
                 outs.append(RequestOutput(r["rid"], r["text"], r["ids"], []))
             outs[-1].outputs.append(self._finish(r, *done[r["i"]]))
+        return outs
+
+    @torch.no_grad()
+    def beam_search(self, prompts, params):
+        """vLLM's LLM.beam_search(prompts, BeamSearchParams): one BeamSearchOutput per prompt with its beam_width best hypotheses, best
+        first.  prompts: a text, a list of token ids, {"prompt": text} / {"prompt_token_ids": ids}, or a list of those.  One request
+        at a time, each one USDMForCausalLM.generate(num_beams=beam_width, num_return_sequences=beam_width, length_penalty=...,
+        early_stopping=False) over the request's static mask and stop ids; the hypotheses are ordered by HF's
+        length-normalised score, cum_logprob is the unnormalised sum."""
+        llm = self.llm
+        if isinstance(prompts, (str, dict)) or (isinstance(prompts, (list, tuple)) and prompts and isinstance(prompts[0], int)):
+            prompts = [prompts]
+        V, outs = llm.cfg["vocab_size"], []
+        mask = params.static_logits_mask
+        if mask is None or mask is True:
+            mask = static_mask_of(params.logits_processors, V, llm.device)
+            if mask is None and params.logits_processors:
+                raise NotImplementedError("beam search takes a static -inf mask only: these logits processors are not one")
+        stops = list(dict.fromkeys(int(t) for t in params.stop_token_ids))
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        if eos is not None and not params.ignore_eos and int(eos) not in stops:
+            stops.insert(0, int(eos))
+        for p in prompts:
+            if isinstance(p, dict):
+                p = p["prompt_token_ids"] if p.get("prompt_token_ids") is not None else p["prompt"]
+            if isinstance(p, str):
+                if self.tokenizer is None:
+                    raise ValueError("text prompts need a tokenizer")
+                p = self.tokenizer(p).input_ids
+            ids = [int(t) for t in p]
+            W = params.beam_width
+            out = llm.generate(input_ids=torch.tensor([ids], dtype=torch.long, device=llm.device), max_new_tokens=params.max_tokens,
+                               num_beams=W, num_return_sequences=W, length_penalty=params.length_penalty, eos_token_id=stops or None,
+                               ban_mask=mask, pad_token_id=-1)
+            self.stats["requests"] += 1
+            seqs = []
+            for row, sc in zip(out[:, len(ids):].tolist(), llm.last_beam_scores.tolist()):
+                toks = [t for t in row if t != -1]
+                text = self.tokenizer.decode(toks) if self.tokenizer is not None and hasattr(self.tokenizer, "decode") else None
+                seqs.append(BeamSearchSequence(ids + toks, float(sc) * max(1, len(toks)) ** float(params.length_penalty), text))
+            outs.append(BeamSearchOutput(seqs))
         return outs
 
     @torch.no_grad()
