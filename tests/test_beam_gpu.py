@@ -160,6 +160,37 @@ def test_first_step_reads_row_0_only(dev, V):
     assert d.parent.cpu().tolist() == [0] * B
 
 
+@pytest.mark.parametrize("score0", [0.0, -3.25])
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("V,B,n_eos", [(42003, 5, 3), (1000, 4, 0), (64, 5, 3)])      # KC = 20, 8, 20
+def test_row_scores_are_usdm_logprobs_bits(dev, V, B, n_eos, pattern, score0):
+    """one live row: the step's candidates are usdm_logprobs' top KC of that row, id for id, and their scores are its
+    log-probabilities plus one float32 addition, bit for bit (both kernels run the row passes of csrc/logprob_row.h)"""
+    from usdm_amd import ops
+    rows, scores = _rows(V, B, pattern, seed=1)
+    scores[0] = score0
+    KC, step = R.candidates(B, n_eos), 2
+    # the beam row orders by s = score + lp, usdm_logprobs by the logit: the two orders agree when logits that differ give sums that
+    # differ.  Over the KC + 1 largest logits in (logit descending, id ascending) order: equal logits, or a float64 gap above 2 tol
+    x = rows[0]
+    order = np.lexsort((np.arange(V), -x.astype(np.float64)))[:KC + 1]
+    s = np.float64(score0) + R.log_softmax64(x)[order]
+    assert np.isfinite(s).all()
+    same = x[order][:-1] == x[order][1:]
+    assert (same | (-np.diff(s) > 2 * tol_of(s)[:-1])).all(), "choose another seed for this case"
+    d = _Dev(dev, rows, scores, list(range(V - n_eos, V)))
+    i32 = lambda *sh: torch.full(sh, -7, dtype=torch.int32, device=dev)
+    nxt, lstep, lpos, out = i32(1), torch.ones(1, dtype=torch.int32, device=dev), i32(1), i32(MAX_OUT)      # step = 1: row 0
+    tok_lp, tok_rank = torch.zeros(MAX_OUT, device=dev), i32(MAX_OUT)
+    top_id, top_lp = i32(MAX_OUT * KC), torch.zeros(MAX_OUT * KC, device=dev)
+    ops.logprobs(d.logits[0], ops.decode_state(nxt, out, lstep, lpos), K=KC, V=V, tok_lp=tok_lp, tok_rank=tok_rank, top_id=top_id, top_lp=top_lp)
+    d.run(nlive=1)
+    assert torch.equal(d.log_token[step].cpu(), top_id[:KC].cpu())
+    want = np.float32(score0) + top_lp[:KC].cpu().numpy()      # float32 + float32
+    assert want.dtype == np.float32
+    assert d.log_score[step].cpu().numpy().view(np.int32).tolist() == want.view(np.int32).tolist()
+
+
 @pytest.mark.parametrize("V,B", [(42003, 2), (1000, 4), (64, 5)])
 def test_all_of_the_best_B_are_eos(dev, V, B):
     """EOS ids placed on the tokens of the first B candidates (at most 3 distinct ones): the running beams come from ranks B .. 2B-1"""

@@ -2,13 +2,11 @@
 // usdm_kv_reorder moves the beams' KV rows to their new owners afterwards.  Both read everything that changes per step (scores,
 // parents, positions, the EOS ids) from device memory, so the step stays one hipGraph.
 //
-// usdm_beam_step, launch 1 (beam_row_kernel): one workgroup of 1024 threads per LIVE row, passes over its V logits (L2-resident):
-//   1  max                         (registers, wave reductions)
-//   2  sum of exp(x - max)         as a 2^40 FIXED-POINT integer sum: usdm_logprobs' arithmetic, term for term (logprob_k.hip)
-//   3+ the row's own best KC       radix select, 8 bits per pass, of the KC-th largest COMPOSITE key (order key of s) << 24 | (2^24-1 - id)
-//                                  with s = score[b] + lp(x): the key is the key of the SUM, not of the logit, because two logits can
-//                                  round to one s and the total order then goes by the id
-//   last collect the kept keys, order them by counting, write (s, id) into the scratch [b][KC]
+// usdm_beam_step, launch 1 (beam_row_kernel): one workgroup of 1024 threads per LIVE row, the row passes of logprob_row.h over its V
+// logits (L2-resident), shared with usdm_prompt_logprobs: lp(x) has usdm_logprobs' bits (tests/test_beam_gpu.py and
+// tests/test_score_gpu.py pin the three kernels to each other), and the row's own best KC are selected under the composite key
+// (order key of s) << 24 | (2^24-1 - id) with s = score[b] + lp(x): the key is the key of the SUM, not of the logit, because two
+// logits can round to one s and the total order then goes by the id.  (s, id) go into the scratch [b][KC].
 // Launch 2 (beam_merge_kernel): one workgroup ranks the nlive * KC <= 512 scratch entries by (key of s) << 32 | (2^32-1 - flat index)
 // by counting, writes the first KC into the step log, walks them for the first B that are no EOS (HF's running beams of the next
 // iteration), advances the counters and copies the embedding rows.  The KC best of B * V are among the rows' own best KC, and within
@@ -17,122 +15,30 @@
 //
 // usdm_kv_reorder (kv_reorder_kernel): a byte copy; one thread owns one 16-byte (or, for rows under 16 bytes, 1-byte) offset in ALL
 // slots, loads the sources of every slot that changes owner and only then stores them: in place, any map, no staging copy.
-#include "logits_row.h"
+#include "logprob_row.h"
+#include "pick_commit.h"
 #include "../../include/usdm_hip.h"
 
 namespace {
-constexpr int NT = 1024, NW = NT / 64, REP = 32, KMAX = USDM_BEAM_MAX_KC, BMAX = 16, NTM = 512, NTR = 256;
-
-// composite key of (id, s): larger = better, then lower id.  -0.0 is folded into +0.0 first (equal values must tie)
-__device__ __forceinline__ unsigned long long ckey(int i, float s) {
-  return ((unsigned long long)fkey(s + 0.0f) << 24) | (unsigned long long)(0xFFFFFFu - (unsigned)i);
-}
-__device__ __forceinline__ float fkey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+constexpr int NT = LPR_NT, KMAX = USDM_BEAM_MAX_KC, BMAX = 16, NTM = 512, NTR = 256;
 
 __global__ __launch_bounds__(NT) void beam_row_kernel(usdm_beam_args a, int KC) {
-  __shared__ unsigned hist[256 * REP];
-  __shared__ unsigned long long cand[KMAX];
-  __shared__ float sredf[NW];
-  __shared__ unsigned sredu[NW];
-  __shared__ unsigned long long s_z, s_prefix;
-  __shared__ unsigned s_rem, s_cnt, s_n;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, V = a.V, K = KC;
+  __shared__ lpr_shared<KMAX> sh;
   const int b = blockIdx.x;                        // < nlive (the grid)
   a.logits += (int64_t)b * a.logits_bs;
   const float sc = a.score[b];
-
   const logits_row_view rv{0, 0, 0u};   // the contiguous row (beam search runs on one GPU: no segmented form)
-  auto each = [&](auto&& f) {   // f(i, logit of i) for i = tid, tid + NT, ... < V
-    row_each<false, NT>(a.logits, V, tid, rv, [&](int i, const float* px) { f(i, *px); });
-  };
-
-  // ---- pass 1: max
-  float m = -INFINITY;
-  each([&](int, float x) { m = fmaxf(m, x); });
-  m = wave_max(m);
-  if (lane == 0) sredf[wv] = m;
-  if (tid == 0) { s_z = 0; s_n = 0; }
+  unsigned none;                        // (no target: no rank count)
+  const float m = lpr_sum<false, false>(a.logits, a.V, rv, sh, 0.f, none);
   __syncthreads();
-  m = sredf[0];
-  for (int w = 1; w < NW; ++w) m = fmaxf(m, sredf[w]);
-
-  // ---- pass 2: Z = sum exp(x - max) in 2^40 fixed point (each term <= 2^40, V <= 2^20: no overflow)
-  {
-    unsigned long long z = 0;
-    each([&](int, float x) {
-      const float e = x == -INFINITY ? 0.f : expf(x == m ? 0.f : x - m);
-      z += e == e ? (unsigned long long)((double)e * 1099511627776.0) : 0ull;      // (a NaN logit: no conversion of NaN)
-    });
-    unsigned lo = (unsigned)z, hi = (unsigned)(z >> 32);
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long o = ((unsigned long long)__shfl_xor(hi, off, 64) << 32) | __shfl_xor(lo, off, 64);
-      z += o;
-      lo = (unsigned)z; hi = (unsigned)(z >> 32);
-    }
-    if (lane == 0) atomicAdd(&s_z, z);
-  }
-  __syncthreads();
-  const unsigned long long Z = s_z;
-  const double logZ = log((double)Z) - 40.0 * 0.69314718055994530942;
-  auto S = [&](float x) -> float {   // the candidate's score: one f32 addition on top of usdm_logprobs' lp (banned / empty row: -inf)
-    const float lp = (x == -INFINITY || Z == 0) ? -INFINITY : (float)((double)(x == m ? 0.f : x - m) - logZ);
-    return sc + lp;
-  };
-
-  // ---- the row's own best K: the K-th largest composite key
-  unsigned long long kth = 0, keep = 0;   // kept: (key & keep) >= kth; everything when V <= K
-  if (V > K) {
-    unsigned long long prefix = 0, mask = 0;
-    unsigned rem = (unsigned)K;
-    for (int shift = 48; shift >= 0; shift -= 8) {
-      for (int i = tid; i < 256 * REP; i += NT) hist[i] = 0;
-      __syncthreads();
-      each([&](int i, float x) {
-        const unsigned long long c = ckey(i, S(x));
-        if ((c & mask) == prefix) atomicAdd(&hist[(unsigned)((c >> shift) & 255) * REP + (tid & (REP - 1))], 1u);
-      });
-      __syncthreads();
-      // thread d < 256 owns digit d: its count, then the suffix sum over the digits >= d (descending keys come first)
-      unsigned tot = 0;
-      if (tid < 256)
-        for (int r = 0; r < REP; ++r) tot += hist[tid * REP + ((r + tid) & (REP - 1))];
-      unsigned incl = tot;
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = __shfl_down(incl, off, 64);
-        if (lane + off < 64) incl += o;
-      }
-      if (lane == 0) sredu[wv] = incl;
-      __syncthreads();
-      for (int w = wv + 1; w < 4; ++w) incl += sredu[w];
-      if (tid < 256 && incl >= rem && incl - tot < rem) {   // the K-th key has digit tid here: exactly one thread
-        s_prefix = prefix | ((unsigned long long)tid << shift);
-        s_rem = rem - (incl - tot);
-        s_cnt = tot;
-      }
-      __syncthreads();
-      prefix = s_prefix; rem = s_rem; mask |= 255ull << shift;
-      const bool whole = s_cnt == rem;   // every key of the boundary bin is kept: no need to look inside it
-      __syncthreads();
-      if (whole) break;
-    }
-    kth = prefix; keep = mask;
-  }
-  each([&](int i, float x) {
-    const unsigned long long c = ckey(i, S(x));
-    if ((c & keep) >= kth) {
-      const unsigned s = atomicAdd(&s_n, 1u);
-      if (s < KMAX) cand[s] = c;
-    }
+  const lpr_lse_t z = lpr_lse(sh, m);
+  // what is ranked: the candidate's score, one f32 addition on top of usdm_logprobs' lp (banned / empty row: -inf)
+  const auto S = [&](float x) { return sc + z.lp(x); };
+  const lpr_cut cut = a.V > KC ? lpr_select<false>(a.logits, a.V, KC, rv, sh, S) : lpr_cut{0, 0};
+  lpr_collect<false>(a.logits, a.V, KC, rv, sh, cut, S, [&](int r, int id, float s) {   // n = KC: the launcher refuses V < KC
+    a.cand_index[b * KC + r] = id;
+    a.cand_score[b * KC + r] = s;
   });
-  __syncthreads();
-  const int n = min((int)s_n, K);       // = K: the launcher refuses V < KC
-  if (tid < n) {
-    const unsigned long long c = cand[tid];
-    int r = 0;
-    for (int j = 0; j < n; ++j) r += cand[j] > c;   // keys are unique: a permutation of 0 .. n-1
-    a.cand_index[b * K + r] = (int)(0xFFFFFFu - (unsigned)(c & 0xFFFFFFu));
-    a.cand_score[b * K + r] = fkey_inv((unsigned)(c >> 24));
-  }
 }
 
 __global__ __launch_bounds__(NTM) void beam_merge_kernel(usdm_beam_args a, usdm_decode_state st, int B, int KC, const bf16_t* E, int Hd,
@@ -190,12 +96,8 @@ __global__ __launch_bounds__(NTM) void beam_merge_kernel(usdm_beam_args a, usdm_
   }
   __syncthreads();
   if (E) {
-    for (int q = 0; q < B; ++q) {
-      if (sel_tok[q] < 0) continue;
-      const u32x4* src = (const u32x4*)(E + (int64_t)sel_tok[q] * Hd);
-      u32x4* dst = (u32x4*)(h_out + (int64_t)q * Hd);
-      for (int i = tid; i < Hd / 8; i += NTM) dst[i] = src[i];
-    }
+    for (int q = 0; q < B; ++q)
+      if (sel_tok[q] >= 0) pick_embed_row<NTM>(E, sel_tok[q], Hd, h_out + (int64_t)q * Hd);
   }
 }
 

@@ -11,6 +11,7 @@
 #include "../../include/usdm_hip.h"
 #include "gemv_launch.h"
 #include "p2p.h"
+#include "pick_commit.h"
 
 #ifndef USDM_GEMV_X_FIRST
 #define USDM_GEMV_X_FIRST 1   // 0: the input vector is requested behind the first weight ring and read twice by the RMSNorm prologue (A/B builds)
@@ -521,44 +522,23 @@ __global__ void argmax_final_kernel(const float* pv, const int* pi, int nparts, 
   if (st.done && st.done[b]) return;
   pv += (int64_t)b * nparts; pi += (int64_t)b * nparts;
   float bv = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = PICK_NO_ID;
   for (int sg = 0; sg < nseg; ++sg)
     for (int i = threadIdx.x; i < nparts; i += 256) {
       const float v = pv[sg * seg_stride + i];
       const int id = pi[sg * seg_stride + i];
-      if (v > bv || (v == bv && id < bi)) { bv = v; bi = id; }
+      if (pick_better(v, id, bv, bi)) { bv = v; bi = id; }
     }
-  sv[threadIdx.x] = bv; si[threadIdx.x] = bi;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      const float v = sv[threadIdx.x + s];
-      const int id = si[threadIdx.x + s];
-      if (v > sv[threadIdx.x] || (v == sv[threadIdx.x] && id < si[threadIdx.x])) { sv[threadIdx.x] = v; si[threadIdx.x] = id; }
-    }
-    __syncthreads();
-  }
+  pick_block_best<256>(sv, si, bv, bi);
   if (threadIdx.x == 0) {
     // every id banned (no candidate anywhere): fall back to id 0 so that nothing indexes the embedding table out of range
-    const int tok = (si[0] == 0x7fffffff ? 0 : si[0]) + st.id_offset;
-    const int step = st.step[b];
-    st.next_token[b] = tok;
-    if (step < st.max_out) st.out_tokens[(int64_t)b * st.max_out + step] = tok;
-    st.step[b] = step + 1;
-    if (st.advance_pos) st.pos[b] = st.pos[b] + 1;
-    if (st.done && st.eos) {   // device-side EOS: eos = {count, min_new, ids...}
-      const int n = st.eos[0], mn = st.eos[1];
-      bool hit = false;
-      for (int i = 0; i < n && i < 6; ++i) hit |= (st.eos[2 + i] == tok);
-      if (hit && step + 1 >= mn) st.done[b] = 1;
-    }
+    const int tok = (si[0] == PICK_NO_ID ? 0 : si[0]) + st.id_offset;
+    pick_commit(st, b, st.step[b], tok);
     s_tok = tok;
   }
   if (E) {  // fused nn.Embedding lookup of the token the next decode step consumes
     __syncthreads();
-    const u32x4* src = (const u32x4*)(E + (int64_t)s_tok * Hd);
-    u32x4* dst = (u32x4*)(h_out + (int64_t)b * Hd);
-    for (int i = threadIdx.x; i < Hd / 8; i += 256) dst[i] = src[i];
+    pick_embed_row<256>(E, s_tok, Hd, h_out + (int64_t)b * Hd);
   }
 }
 

@@ -1,5 +1,5 @@
-// The f32 logits row of one sequence as the pick kernels (sample_k.hip, logprob_k.hip, penalty_k.hip, edit_k.hip) address it, plus the host-side
-// checks of its shape.
+// The f32 logits row of one sequence as the pick kernels (sample_k.hip, logprob_k.hip, penalty_k.hip, edit_k.hip, and through logprob_row.h
+// score_k.hip and beam_k.hip) address it, plus the host-side checks of its shape.
 //
 // SEG = false: the row is contiguous, id i sits at row[i].  SEG = true: it is made of rank-major segments of seg_len ids, seg_stride
 // elements apart (the *_seg entry points; under tensor parallelism every rank's lm_head slice is one segment); id i sits at

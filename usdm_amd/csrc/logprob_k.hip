@@ -17,6 +17,13 @@
 // serialise 64 LDS atomics per wave instruction on one address.  Every sum is an integer sum and every per-id quantity depends on the
 // id's value only, so the same logical row gives bit-identical output run to run, single or batched, contiguous or segmented
 // (logits_row.h).
+//
+// The row body below is this kernel's OWN: usdm_prompt_logprobs (score_k.hip) and usdm_beam_step (beam_k.hip) run the same passes
+// from logprob_row.h, and a fix to this arithmetic is made there AND here.  This kernel, written over that header, has the same
+// instructions in its loops, no scratch, the same LDS and 79 / 82 VGPRs (here: 82 / 82), but at K = 0 it measured 0.1 - 0.3 us
+// per launch slower than this form (18.3 - 18.6 against 18.0 - 18.4 us at one row, 19.2 - 19.3 against 19.0 - 19.1 us at 16), outside
+// this form's own spread, and it sits inside every captured log-probability step: profiles/pick_share.txt has the numbers.
+// tests/test_score_gpu.py and tests/test_beam_gpu.py pin the shared passes to this kernel's bits.
 #include "logits_row.h"
 #include "../../include/usdm_hip.h"
 

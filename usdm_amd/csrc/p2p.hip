@@ -1,6 +1,7 @@
 // Host side + standalone kernels of the one-shot peer-to-peer all-reduce (protocol: include/usdm_hip.h).
 // The fused form lives in the row-parallel GEMV's epilogue (llm_k.hip, gemv_kernel p2p_mode 1).
 #include "p2p.h"
+#include "pick_commit.h"
 #include <stdlib.h>
 
 struct usdm_p2p {
@@ -134,22 +135,13 @@ __global__ __launch_bounds__(256) void argmax_p2p_kernel(const float* pv, const 
   const int tid = threadIdx.x;
   if (phase != 2) {   // local arg-max over this rank's lm_head partials
     float bv = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = PICK_NO_ID;
     for (int i = tid; i < nparts; i += 256) {
       const float v = pv[i];
       const int id = pi[i];
-      if (v > bv || (v == bv && id < bi)) { bv = v; bi = id; }
+      if (pick_better(v, id, bv, bi)) { bv = v; bi = id; }
     }
-    sv[tid] = bv; si[tid] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (tid < s) {
-        const float v = sv[tid + s];
-        const int id = si[tid + s];
-        if (v > sv[tid] || (v == sv[tid] && id < si[tid])) { sv[tid] = v; si[tid] = id; }
-      }
-      __syncthreads();
-    }
+    pick_block_best<256>(sv, si, bv, bi);
   }
   if (tid < 64) {   // wave 0: lane r < world talks to rank r
     const int world = d->world, r = tid;
@@ -162,25 +154,11 @@ __global__ __launch_bounds__(256) void argmax_p2p_kernel(const float* pv, const 
     p2p_gran* mine = p2p_slot(d, d->rank, epoch, site, r < world ? r : 0);
     float v = p2p_get(d, mine, epoch, r < world, USDM_P2P_ERR_TIMEOUT_PICK, failed);
     int id = (int)p2p_get_bits(d, mine + 1, epoch, r < world, USDM_P2P_ERR_TIMEOUT_PICK, failed);
-    if (r >= world) { v = -INFINITY; id = 0x7fffffff; }
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(v, off, 64);
-      const int oi = __shfl_xor(id, off, 64);
-      if (ov > v || (ov == v && oi < id)) { v = ov; id = oi; }
-    }
+    if (r >= world) { v = -INFINITY; id = PICK_NO_ID; }
+    pick_wave_best(v, id);
     if (tid == 0) {
-      const int tok = (id == 0x7fffffff ? 0 : id) + st.id_offset;
-      const int step = st.step[0];
-      st.next_token[0] = tok;
-      if (step < st.max_out) st.out_tokens[step] = tok;
-      st.step[0] = step + 1;
-      if (st.advance_pos) st.pos[0] = st.pos[0] + 1;
-      if (st.done && st.eos) {
-        const int n = st.eos[0], mn = st.eos[1];
-        bool hit = false;
-        for (int i = 0; i < n && i < 6; ++i) hit |= (st.eos[2 + i] == tok);
-        if (hit && step + 1 >= mn) st.done[0] = 1;
-      }
+      const int tok = (id == PICK_NO_ID ? 0 : id) + st.id_offset;
+      pick_commit(st, 0, st.step[0], tok);
       s_tok = tok;
       // the step is complete on this rank: next epoch (kernels of the next step are stream-ordered behind this one)
       __hip_atomic_store(p2p_epoch_word(d), epoch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -189,9 +167,7 @@ __global__ __launch_bounds__(256) void argmax_p2p_kernel(const float* pv, const 
   if (phase == 1) return;
   if (E) {
     __syncthreads();
-    const u32x4* src = (const u32x4*)(E + (int64_t)s_tok * Hd);
-    u32x4* dst = (u32x4*)h_out;
-    for (int i = tid; i < Hd / 8; i += 256) dst[i] = src[i];
+    pick_embed_row<256>(E, s_tok, Hd, h_out);
   }
 }
 

@@ -12,6 +12,7 @@
 //   min-p  : HF MinPLogitsWarper / vLLM: ids with p_i < min_p * p_max are dropped, by raising the top-p stage's key threshold;
 //   draw   : u * kept_mass located by an exclusive scan over contiguous index ranges (index order, deterministic).
 #include "logits_row.h"
+#include "pick_commit.h"
 #include "../../include/usdm_hip.h"
 
 namespace {
@@ -62,10 +63,7 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
   const int b = blockIdx.x;
   a.logits += (int64_t)b * a.logits_bs;
   if (a.probs_out) a.probs_out += (int64_t)b * probs_bs;
-  st.next_token += b; st.step += b; st.pos += b; st.out_tokens += (int64_t)b * st.max_out;
-  if (st.done) st.done += b;
-  h_out += (int64_t)b * Hd;
-  if (st.done && *st.done) return;
+  if (st.done && st.done[b]) return;
   if (a.dev_params) {   // per-request knobs live in device memory: one captured graph for every request
     a.dev_params += b;
     a.temperature = a.dev_params->temperature; a.top_k = a.dev_params->top_k; a.top_p = a.dev_params->top_p; a.seed = a.dev_params->seed;
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     __syncthreads();
   }
   const unsigned long long Zk = sscan[NT - 1];
-  const int step = *st.step;
+  const int step = st.step[b];
   // top_k == 1 is the reference's "greedy" (do_sample=True, top_k=1): among exact ties take the lowest id, as usdm_argmax_final does
   const double u = a.top_k == 1 ? 0.0 : philox_uniform(a.seed, (unsigned)step);
   unsigned long long target = (unsigned long long)(u * (double)Zk);
@@ -212,21 +210,17 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     __shared__ float fbv[NT / 64];
     __shared__ int fbi[NT / 64];
     float bv = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = PICK_NO_ID;
     each([&](int i, float x) {
       if (x > bv) { bv = x; bi = i; }     // NaN and -inf never pass
     });
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
+    pick_wave_best(bv, bi);
     if ((tid & 63) == 0) { fbv[tid >> 6] = bv; fbi[tid >> 6] = bi; }
     __syncthreads();
     if (tid == 0) {
       for (int w = 1; w < NT / 64; ++w)
-        if (fbv[w] > bv || (fbv[w] == bv && fbi[w] < bi)) { bv = fbv[w]; bi = fbi[w]; }
-      s_tok = bi == 0x7fffffff ? 0 : bi;
+        if (pick_better(fbv[w], fbi[w], bv, bi)) { bv = fbv[w]; bi = fbi[w]; }
+      s_tok = bi == PICK_NO_ID ? 0 : bi;
     }
     __syncthreads();
   }
@@ -237,24 +231,8 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
       a.probs_out[i] = (e > 0.f && __float_as_uint(e) >= pkey) ? (float)((double)Q(e) * inv) : 0.f;
     });
   }
-  if (tid == 0) {
-    const int tok = s_tok + st.id_offset;
-    *st.next_token = tok;
-    if (step < st.max_out) st.out_tokens[step] = tok;
-    *st.step = step + 1;
-    if (st.advance_pos) *st.pos = *st.pos + 1;
-    if (st.done && st.eos) {   // device-side EOS: eos = {count, min_new, ids...}
-      const int n = st.eos[0], mn = st.eos[1];
-      bool hit = false;
-      for (int i = 0; i < n && i < 6; ++i) hit |= (st.eos[2 + i] == tok);
-      if (hit && step + 1 >= mn) *st.done = 1;
-    }
-  }
-  if (E) {
-    const u32x4* src = (const u32x4*)(E + (int64_t)(s_tok + st.id_offset) * Hd);
-    u32x4* dst = (u32x4*)h_out;
-    for (int i = tid; i < Hd / 8; i += NT) dst[i] = src[i];
-  }
+  if (tid == 0) pick_commit(st, b, step, s_tok + st.id_offset);
+  if (E) pick_embed_row<NT>(E, s_tok + st.id_offset, Hd, h_out + (int64_t)b * Hd);
 }
 }  // namespace
 
