@@ -1,5 +1,5 @@
 """Plain CPU references and input builders of tests/test_glue_gpu.py (the small kernels between the GEMMs and the attention:
-usdm_norm's untested paths, w2v_k.hip, vb_k.hip, bigvgan_k.hip and three entry points of llm_k.hip), checked themselves by
+usdm_norm's untested paths, w2v_k.hip, vb_k.hip, bigvgan_k.hip and three entry points of llm_k.hip / llm_attn_k.hip), checked themselves by
 tests/test_glue_cpu.py against the project's oracles and torch ops.
 
 Conventions
@@ -433,7 +433,7 @@ def frame_signal_ref(x, frame_len, hop, offset, T):
     return torch.where(ok, x[j.clamp(0, x.numel() - 1)], torch.zeros((), dtype=x.dtype))
 
 
-# ------------------------------------------------------------------------------------------------------------------ llm_k.hip
+# ------------------------------------------------------------------------------------------------- llm_k.hip, llm_attn_k.hip
 def residual_add_case(n):
     """h bf16 [n], delta f32 [n] with, from the front: exact bf16 ties in delta (1 + 2^-8 -> 1, -(1 + 3 * 2^-8) -> -(1 + 2^-6)),
     deltas a hair above 2^-8 on h = 1 (bf16(delta) = 2^-8 makes h + delta the tie 1 + 2^-8 -> 1; the unrounded sum goes up to

@@ -619,7 +619,7 @@ def test_frame_signal(dev):
     _same_bits(out.take(T, fl, "usdm_frame_signal"), ref, "frames")
 
 
-# ------------------------------------------------------------------------------------------------------------------ llm_k.hip
+# ------------------------------------------------------------------------------------------------- llm_k.hip, llm_attn_k.hip
 @pytest.mark.parametrize("Hd", [8, 72, 2400])
 def test_embed_rows(dev, Hd):
     """usdm_embed_rows: Hd = 8 (one vector), 72, 2400 (300 vectors on 256 threads); the ids path (n = 5: a repeated id, row 0, the last

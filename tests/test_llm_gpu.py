@@ -120,6 +120,51 @@ def test_attn_decode(dev, ctx):
             assert (y2.float() - out.float()).abs().max() <= 2 ** -7 * out.float().abs().max()
 
 
+def test_split_merges_agree_bit_for_bit(dev):
+    """The three merges of the context-split partials share csrc/attn_merge.h and must give the same bf16 bits on the same inputs:
+    (a) the combine launch, (b) the last-arriving workgroup of the attention launch (counters), (c) the first workgroups of the
+    o_proj launch (defer_merge + cmb_gran, then usdm_gemv with identity weights: its output is the merged vector exactly).
+    NS = 3 is the scalar tail alone, 21 = 16 + 4 + 1, 32 = 16 + 16; at pos 0 every split but the first is empty (pm = -1e30, pl = 0)."""
+    from oracle import mistral_oracle as MO
+    from usdm_amd import ops
+    bf = torch.bfloat16
+    Hq, Hkv, d, ctx_max = 32, 8, 128, 1024      # the hand-off form needs the 4096-output projection
+    n = Hq * d
+    cosf, sinf = MO.rope_tables(dict(head_dim=d, rope_theta=10000.0), torch.arange(ctx_max), bf)
+    cos, sin = cosf[:, :64].contiguous().to(dev), sinf[:, :64].contiguous().to(dev)
+    qkv = _r(((Hq + 2 * Hkv) * d,), 1).to(bf).to(dev)
+    kc, vc = _r((Hkv, ctx_max, d), 2).to(bf).to(dev), _r((Hkv, ctx_max, d), 3).to(bf).to(dev)
+    eye = torch.eye(n, dtype=bf, device=dev)
+    bits = lambda t: t.view(torch.int16)
+    for NS in (3, 21, 32):
+        for pos in (0, 700):
+            post = torch.tensor([pos], dtype=torch.int32, device=dev)
+
+            def run(**kw):
+                pm, pl, po = torch.zeros(Hq * NS, device=dev), torch.zeros(Hq * NS, device=dev), torch.zeros(Hq * NS * d, device=dev)
+                out = torch.full((n,), 7.0, dtype=bf, device=dev)
+                ops.attn_decode(qkv, post, cos, sin, kc.clone(), vc.clone(), pm, pl, po, out, Hq=Hq, Hkv=Hkv, ctx_max=ctx_max, NS=NS,
+                                scale=d ** -0.5, **kw)
+                return pm, pl, po, out
+
+            *_, out_a = run()
+            cnt = torch.zeros(Hkv, dtype=torch.int32, device=dev)
+            *_, out_b = run(counters=cnt)
+            assert not bool(cnt.any()), "the merge counters must be left zero"
+            gran = torch.full((Hq * 64,), (1 << 32) | 5, dtype=torch.int64, device=dev)      # tagged: the attention launch must clear them
+            pm, pl, po, out_0 = run(defer_merge=True, cmb_gran=gran)
+            assert not bool(gran.any()) and bool((out_0 == 7.0).all())
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            out_c = torch.zeros(n, dtype=bf, device=dev)
+            ops.gemv(eye, out_0, N=n, K=n, y16=out_c, merge=(pm, pl, po, NS), cmb=(gran, err))      # x pointer is ignored in merge mode
+            assert int(err.item()) == 0
+            lo_hi = gran.view(torch.int32).view(-1, 2)      # every granule tagged 1 and holding its two merged elements
+            assert bool((lo_hi[:, 1] == 1).all()) and torch.equal(bits(lo_hi[:, 0].contiguous()), bits(out_c))
+            assert bool(torch.isfinite(out_a.float()).all()) and bool((out_a != 7.0).any())
+            assert torch.equal(bits(out_a), bits(out_b)), f"NS {NS} pos {pos}: fused merge != combine launch"
+            assert torch.equal(bits(out_a), bits(out_c)), f"NS {NS} pos {pos}: o_proj hand-off merge != combine launch"
+
+
 def _compare_generate(dev, cfg, seed, L0, new, bad, eos=None):
     from oracle import mistral_oracle as MO
     from usdm_amd.llm import USDMForCausalLM

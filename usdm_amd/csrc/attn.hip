@@ -32,6 +32,31 @@ __device__ unsigned long long g_attn_trace[4096 * 8];
 #define ATR_T() 0ull
 #define ATR_ADD(i, t0) do { } while (0)
 #endif
+// end of a traced workgroup: its per-phase cycle sums, total and tile count (nothing in the product build)
+__device__ __forceinline__ void attn_trace_dump(int tid, const unsigned long long (&atr)[8], unsigned long long tstart, int ntiles) {
+#ifdef USDM_ATTN_TRACE
+  if (tid == 0) {
+    const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if (wg < 4096) {
+      for (int i = 0; i < 6; ++i) g_attn_trace[wg * 8 + i] = atr[i];
+      g_attn_trace[wg * 8 + 6] = ATR_T() - tstart;
+      g_attn_trace[wg * 8 + 7] = ntiles;
+    }
+  }
+#endif
+}
+
+// The head of the bidirectional ALiBi form's p-th (head, batch) pair in dispatch order (batches innermost), nh heads.  Speed only.
+// Heads are walked from the LAST (flattest slope: every key tile counts) to the first (steepest: most far tiles are skipped), so
+// that when the grid is a bit more than one round of workgroups the short ones are the stragglers' partners, not the long ones.
+// head_order 0 = flattest first ... steepest last (round 2); 1 = the two steepest heads FIRST, the next two LAST, flat heads in
+// between: a grid of a little more than one workgroup per CU (288 on 256) is dealt round-robin, so the CUs that receive a second
+// workgroup hold the first and the last workgroups of the launch - with order 1 both are short (steep slope: most key tiles
+// skipped), instead of a flat-slope one plus a steep one.
+__device__ __forceinline__ int attn_alibi_head(int p, int nh, int head_order) {
+  if (head_order == 0 || nh < 8) return nh - 1 - p;
+  return p < 2 ? p : (p >= nh - 2 ? p - (nh - 2) + 2 : nh - 1 - (p - 2));
+}
 
 // MODE 0: bidirectional + ALiBi + key-length mask ; 1: causal ; NW waves x 32 queries ; KS key-split groups: group g of NW
 // waves walks key tiles g, g+KS, ... of the SAME queries and the groups' (m, l, O) are merged at the end.  KS = 2 puts two
@@ -51,21 +76,11 @@ __global__ __launch_bounds__(NW * 64 * KS) void attn_kernel(const usdm_attn_args
 
   const int tid = threadIdx.x % NT, lane = tid & 63, wave = tid >> 6;
   const int lq = lane & 31, lh = lane >> 5;
-  // (head, batch) of this workgroup.  Bidirectional ALiBi attention: heads are walked from the LAST (flattest slope: every
-  // key tile counts) to the first (steepest: most far tiles are skipped below), batches innermost, so that when the grid is
-  // a bit more than one round of workgroups the short ones are the stragglers' partners, not the long ones.
+  // (head, batch) of this workgroup
   const int qb = blockIdx.x;
   const int lin = blockIdx.y + gridDim.y * blockIdx.z;
-  // MODE 0 head order (a.head_order; speed only): 0 = flattest first ... steepest last (round 2); 1 = the two steepest heads FIRST, the
-  // next two LAST, flat heads in between: a grid of a little more than one workgroup per CU (288 on 256) is dealt round-robin, so
-  // the CUs that receive a second workgroup hold the first and the last workgroups of the launch - with order 1 both are short
-  // (steep slope: most key tiles skipped), instead of a flat-slope one plus a steep one.
   int h = (int)blockIdx.y;
-  if (MODE == 0) {
-    const int nh = (int)gridDim.y, p = lin / (int)gridDim.z;           // position of this (head, batch) pair in dispatch order
-    if (a.head_order == 0 || nh < 8) h = nh - 1 - p;
-    else h = p < 2 ? p : (p >= nh - 2 ? p - (nh - 2) + 2 : nh - 1 - (p - 2));
-  }
+  if (MODE == 0) h = attn_alibi_head(lin / (int)gridDim.z, (int)gridDim.y, a.head_order);
   const int b = MODE == 0 ? lin % (int)gridDim.z : (int)blockIdx.z;
   const int hk = h / (a.Hq / a.Hkv);
   const int q0 = qb * QB + wave * 32;
@@ -318,16 +333,7 @@ __global__ __launch_bounds__(NW * 64 * KS) void attn_kernel(const usdm_attn_args
     __syncthreads();
     ATR_ADD(5, tph);
   }
-#ifdef USDM_ATTN_TRACE
-  if (tid == 0) {
-    const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (wg < 4096) {
-      for (int i = 0; i < 6; ++i) g_attn_trace[wg * 8 + i] = atr[i];
-      g_attn_trace[wg * 8 + 6] = ATR_T() - tstart;
-      g_attn_trace[wg * 8 + 7] = ntiles;
-    }
-  }
-#endif
+  attn_trace_dump(tid, atr, tstart, ntiles);
 
   if constexpr (KS > 1) {
     // ---- merge the key-split groups: groups 1.. park (m, l, O^T) in LDS, group 0 folds them in (same wave / lane)
@@ -409,10 +415,7 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const usdm_attn_args a)
   const int q16 = lane & 15, g = lane >> 4;
   const int qb = blockIdx.x;
   const int lin = blockIdx.y + gridDim.y * blockIdx.z;
-  const int nh = (int)gridDim.y, p = lin / (int)gridDim.z;
-  int h;
-  if (a.head_order == 0 || nh < 8) h = nh - 1 - p;
-  else h = p < 2 ? p : (p >= nh - 2 ? p - (nh - 2) + 2 : nh - 1 - (p - 2));
+  const int h = attn_alibi_head(lin / (int)gridDim.z, (int)gridDim.y, a.head_order);
   const int b = lin % (int)gridDim.z;
   const int q0 = qb * QB + wave * 16;
   const int kv_len = a.kv_len ? a.kv_len[b] : a.Skv;
@@ -602,16 +605,7 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const usdm_attn_args a)
     __syncthreads();
     ATR_ADD(5, tph);
   }
-#ifdef USDM_ATTN_TRACE
-  if (tid == 0) {
-    const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (wg < 4096) {
-      for (int i = 0; i < 6; ++i) g_attn_trace[wg * 8 + i] = atr[i];
-      g_attn_trace[wg * 8 + 6] = ATR_T() - tstart;
-      g_attn_trace[wg * 8 + 7] = ntiles;
-    }
-  }
-#endif
+  attn_trace_dump(tid, atr, tstart, ntiles);
   const float l_tot = quad_sum16(l_run);
   const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
   const int qr = q0 + q16;
@@ -648,7 +642,7 @@ extern "C" int usdm_attention(const usdm_attn_args* pa, usdm_stream_t stream) {
   usdm_attn_args a2 = a;
   if (a2.mode == 0 && a2.head_order == 0) a2.head_order = 1;      // default order of the bidirectional (Voicebox) form; -1 = flattest first
   else if (a2.head_order < 0) a2.head_order = 0;
-  const bool small = false;       // (2-wave workgroups and the key-split pairing measured no gain and are not instantiated: r02 / r03 notes)
+  // (2-wave workgroups and the key-split pairing measured no gain and are not built: profiles/r01_gemm_ablation.txt, r02 / r03 notes)
   dim3 grid(cdiv(a.Sq, 128), a.Hq, a.B), block(256);
   // 16-query waves (8 per workgroup) for the Voicebox form: MHA, d = 64, bidirectional (usdm_attn_args.variant = 1: the 32-query kernel)
   if (a.variant != 1 && a.dh == 64 && a.mode == 0 && a.Hq == a.Hkv) {
