@@ -684,6 +684,24 @@ int usdm_rope_cache_fp8(const usdm_rope_fp8_args* args, usdm_stream_t stream);
 int usdm_sizeof_attn_decode_fp8_args(void);
 int usdm_sizeof_rope_fp8_args(void);
 
+/* Prefix reuse where the prefill attention's V^T is per-plan scratch (batch slots, FP8 cache): rows 0 .. n-1 of ONE layer's cache
+ * of ONE sequence as the bf16 operands usdm_attention (mode 1) reads, in front of the rows the rope launch adds at offset n.
+ * bf16 cache (kexp = vexp = NULL): vt[h][d][r] = vcache[h][r][d]; K is read in place by the attention, kscr must be NULL.
+ * FP8 cache: kscr[h][r][:] and vt[h][:][r] are the exact dequantization byte x 2^e of the row (quant.dequantize_kv_rows; the values
+ * usdm_attn_decode_fp8 computes with).  Rows / columns >= n of the destinations and the caches are not written.
+ * 2 x Hkv x n x 256 bytes written (bf16 cache: half of that), 256 / 129 bytes read per row and array.
+ * Refused: a null kcache / vcache / vt, caches not 16-byte aligned, exponents / vt / kscr not 4-byte aligned, n < 1, n > ctx_max,
+ * vt_ld < n, kscr_ld < n, kscr with a bf16 cache, an FP8 cache without kscr or with one exponent array only. */
+typedef struct usdm_kv_expand_args {
+  const void* kcache; const void* vcache;  /* [Hkv][ctx_max][128], bf16 or e4m3 */
+  const int8_t* kexp; const int8_t* vexp;  /* FP8 cache: [Hkv][ctx_max]; NULL = bf16 cache */
+  void* kscr; int64_t kscr_ld;             /* FP8 only: bf16 [Hkv][kscr_ld][128], rows 0 .. n-1 are written */
+  void* vt;   int64_t vt_ld;               /* bf16 [Hkv][128][vt_ld], columns 0 .. n-1 are written */
+  int32_t Hkv, ctx_max, n;
+} usdm_kv_expand_args;
+int usdm_kv_expand(const usdm_kv_expand_args* args, usdm_stream_t stream);
+int usdm_sizeof_kv_expand_args(void);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot peer-to-peer all-reduce for the tensor-parallel decode step (replaces the single-GPU
  * model.generate of src/inference.py:116-123 when the 7B is sharded over the 8 GPUs of a node).  Messages are 4096 f32

@@ -37,6 +37,7 @@ lib.usdm_logit_edit.restype = C.c_int        # (the logit-edit entry points: lik
 lib.usdm_logit_edit_seg.restype = C.c_int
 lib.usdm_beam_step.restype = C.c_int         # (the beam-search entry points: likewise)
 lib.usdm_kv_reorder.restype = C.c_int
+lib.usdm_kv_expand.restype = C.c_int         # (the prefix-cache entry point: likewise)
 _exp = None
 
 
@@ -254,6 +255,14 @@ class KvReorderArgs(C.Structure):
     ]
 
 
+class KvExpandArgs(C.Structure):
+    _fields_ = [
+        ("kcache", C.c_void_p), ("vcache", C.c_void_p), ("kexp", C.c_void_p), ("vexp", C.c_void_p),
+        ("kscr", C.c_void_p), ("kscr_ld", C.c_int64), ("vt", C.c_void_p), ("vt_ld", C.c_int64),
+        ("Hkv", C.c_int32), ("ctx_max", C.c_int32), ("n", C.c_int32),
+    ]
+
+
 class RopeArgs(C.Structure):
     _fields_ = [
         ("qkv", C.c_void_p), ("ld", C.c_int64), ("S", C.c_int32), ("pos0", C.c_int32), ("Hq", C.c_int32),
@@ -299,7 +308,7 @@ def _selfcheck():
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
                       ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs), ("beam", BeamArgs),
-                      ("kv_reorder", KvReorderArgs)):
+                      ("kv_reorder", KvReorderArgs), ("kv_expand", KvExpandArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

@@ -116,6 +116,87 @@ __global__ __launch_bounds__(64) void rope_cache_fp8_kernel(const usdm_rope_args
   }
 }
 
+// ---- usdm_kv_expand: rows 0 .. n-1 of ONE layer's cache of ONE sequence -> the bf16 operands of the prefill attention (prefix
+// reuse where V^T is per-plan scratch: batch slots, FP8 cache).  Grid (ceil(n / 64), Hkv, FP8 ? 2 : 1), 256 threads; a workgroup
+// takes 64 keys x 128 d of one kv head.  z = 0: the V rows (FP8: dequantized exactly, fp8x8_to_bf16x8 with the row's 2^e, as the
+// decode kernels do) go through a padded LDS tile and leave as V^T, 8 keys = 16 bytes per store; z = 1 (FP8 only): the K rows,
+// dequantized likewise, go to kscr as they are.  Every global access is a 16-byte piece, except the columns of a last group of
+// fewer than 8 keys and destinations that are not 16-byte aligned (element / 4-byte stores).  Rows / columns >= n are neither read
+// nor written.
+constexpr int KVX_KEYS = 64, KVX_LD = 65;     // tile: [64 keys][64 dwords = 128 bf16], rows padded to 65 dwords (conflict-free both ways)
+__device__ __forceinline__ void kvx_store16(bf16_t* p, u32x4 v, bool al16) {
+  if (al16) { *(u32x4*)p = v; return; }
+#pragma unroll
+  for (int w = 0; w < 4; ++w) ((unsigned*)p)[w] = v[w];
+}
+template <bool FP8>
+__global__ __launch_bounds__(256) void kv_expand_kernel(const usdm_kv_expand_args a) {
+  __shared__ unsigned tile[KVX_KEYS][KVX_LD];
+  const int tid = threadIdx.x, kh = blockIdx.y;
+  const int r0 = blockIdx.x * KVX_KEYS;
+  const int64_t hrow = (int64_t)kh * a.ctx_max;
+  if (FP8 && blockIdx.z == 1) {      // K rows: 64 rows x 8 pieces of 16 e4m3 bytes -> 2 x 16 bytes of bf16 each
+    const bool al16 = ((uintptr_t)a.kscr & 15) == 0;
+    for (int p = tid; p < KVX_KEYS * 8; p += 256) {
+      const int r = r0 + (p >> 3), c = p & 7;
+      if (r >= a.n) break;
+      const u32x4 q = *(const u32x4*)((const uint8_t*)a.kcache + (hrow + r) * 128 + c * 16);
+      const float s = fp8_row_scale(a.kexp[hrow + r]);
+      bf16_t* dst = (bf16_t*)a.kscr + ((int64_t)kh * a.kscr_ld + r) * 128 + c * 16;
+      kvx_store16(dst, fp8x8_to_bf16x8(u32x2{q[0], q[1]}, s), al16);
+      kvx_store16(dst + 8, fp8x8_to_bf16x8(u32x2{q[2], q[3]}, s), al16);
+    }
+    return;
+  }
+  // V rows -> the tile (bf16 values, two per dword)
+  if constexpr (FP8) {
+    for (int p = tid; p < KVX_KEYS * 8; p += 256) {
+      const int k = p >> 3, c = p & 7;
+      if (r0 + k >= a.n) break;
+      const u32x4 q = *(const u32x4*)((const uint8_t*)a.vcache + (hrow + r0 + k) * 128 + c * 16);
+      const float s = fp8_row_scale(a.vexp[hrow + r0 + k]);
+      const u32x4 lo = fp8x8_to_bf16x8(u32x2{q[0], q[1]}, s), hi = fp8x8_to_bf16x8(u32x2{q[2], q[3]}, s);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) { tile[k][c * 8 + w] = lo[w]; tile[k][c * 8 + 4 + w] = hi[w]; }
+    }
+  } else {
+    for (int p = tid; p < KVX_KEYS * 16; p += 256) {
+      const int k = p >> 4, c = p & 15;
+      if (r0 + k >= a.n) break;
+      const u32x4 v = *(const u32x4*)((const bf16_t*)a.vcache + (hrow + r0 + k) * 128 + c * 8);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) tile[k][c * 4 + w] = v[w];
+    }
+  }
+  __syncthreads();
+  // the tile -> V^T: an item = (pair of d, group of 8 keys) = two 16-byte pieces, one per d
+  const bool al16 = ((uintptr_t)a.vt & 15) == 0 && a.vt_ld % 8 == 0;
+  bf16_t* vt = (bf16_t*)a.vt + (int64_t)kh * 128 * a.vt_ld;
+  for (int p = tid; p < 64 * 8; p += 256) {
+    const int kg = p & 7, dp = p >> 3;
+    const int kb = r0 + kg * 8;
+    if (kb >= a.n) continue;
+    const int nkeys = min(8, a.n - kb);
+    unsigned w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = j < nkeys ? tile[kg * 8 + j][dp] : 0u;
+    bf16_t* d0 = vt + (int64_t)(2 * dp) * a.vt_ld + kb;
+    bf16_t* d1 = d0 + a.vt_ld;
+    if (nkeys == 8 && al16) {
+      u32x4 e, o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        e[j] = (w[2 * j] & 0xffffu) | (w[2 * j + 1] << 16);
+        o[j] = (w[2 * j] >> 16) | (w[2 * j + 1] & 0xffff0000u);
+      }
+      *(u32x4*)d0 = e;
+      *(u32x4*)d1 = o;
+    } else {
+      for (int j = 0; j < nkeys; ++j) { d0[j] = (bf16_t)(w[j] & 0xffffu); d1[j] = (bf16_t)(w[j] >> 16); }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // The rope prologue, the scores of a key and the softmax statistics of a decode-attention step, once, for attn_decode_kernel and
 // attn_decode1_kernel: one kv head with its G query heads, d = 128.  What differs between the kernels - which keys a thread takes,
@@ -624,6 +705,27 @@ extern "C" int usdm_rope_cache_fp8(const usdm_rope_fp8_args* pa, usdm_stream_t s
   USDM_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int usdm_kv_expand(const usdm_kv_expand_args* pa, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->kcache && pa->vcache && pa->vt, "usdm_kv_expand: null args");
+  const usdm_kv_expand_args& a = *pa;
+  const bool fp8 = a.kexp || a.vexp;
+  USDM_CHECK_ARG(a.Hkv > 0 && a.ctx_max > 0 && a.n >= 1 && a.n <= a.ctx_max, "usdm_kv_expand: Hkv, ctx_max > 0 and 1 <= n <= ctx_max");
+  USDM_CHECK_ARG(((uintptr_t)a.vcache & 15) == 0 && ((uintptr_t)a.kcache & 15) == 0, "usdm_kv_expand: the caches must be 16-byte aligned");
+  USDM_CHECK_ARG(a.vt_ld >= a.n && ((uintptr_t)a.vt & 3) == 0, "usdm_kv_expand: vt_ld >= n, vt 4-byte aligned");
+  if (fp8) {
+    USDM_CHECK_ARG(a.kexp && a.vexp && a.kscr, "usdm_kv_expand: an fp8 cache comes with both exponent arrays and kscr");
+    USDM_CHECK_ARG(((uintptr_t)a.kexp & 3) == 0 && ((uintptr_t)a.vexp & 3) == 0, "usdm_kv_expand: the exponent arrays must be 4-byte aligned");
+    USDM_CHECK_ARG(a.kscr_ld >= a.n && ((uintptr_t)a.kscr & 3) == 0, "usdm_kv_expand: kscr_ld >= n, kscr 4-byte aligned");
+  } else {
+    USDM_CHECK_ARG(!a.kscr, "usdm_kv_expand: kscr belongs to the fp8 cache (the attention reads a bf16 cache's K rows in place)");
+  }
+  const dim3 grid((a.n + KVX_KEYS - 1) / KVX_KEYS, a.Hkv, fp8 ? 2 : 1);
+  if (fp8) hipLaunchKernelGGL(kv_expand_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(kv_expand_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int usdm_sizeof_kv_expand_args(void) { return (int)sizeof(usdm_kv_expand_args); }
 extern "C" int usdm_sizeof_rope_args(void) { return (int)sizeof(usdm_rope_args); }
 extern "C" int usdm_sizeof_rope_fp8_args(void) { return (int)sizeof(usdm_rope_fp8_args); }
 extern "C" int usdm_sizeof_attn_decode_args(void) { return (int)sizeof(usdm_attn_decode_args); }

@@ -163,7 +163,7 @@ def check_num_beams(args):
         raise ValueError(f"--num_beams cannot be combined with {', '.join(used)}: beam search ranks the model's own log-probabilities")
 
 
-def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None, kv_cache_dtype=None):
+def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None, kv_cache_dtype=None, enable_prefix_caching=False):
     """What the reference's __main__ does between argument parsing and sample() (src/inference.py:105-129), from LOCAL copies:
     hub names resolve inside model_cache_dir (huggingface_hub cache layout or plain <name>/ directories, checkpoints.py)."""
     import os
@@ -185,7 +185,8 @@ def load_models(model_cache_dir, dev=None, ctx_max=None, quantization=None, kv_c
     # kernels bound their key range (llm.py), so the cache may be longer than the window.  8192 = the USDM tokenizer's limit.
     want = ctx_max or min(int(getattr(tokenizer, "model_max_length", 4096) or 4096), 8192)
     model = USDMForCausalLM.from_pretrained(llm_dir, device=dev, torch_dtype=torch.bfloat16, ctx_max=want,
-                                            quantization=quantization, kv_cache_dtype=kv_cache_dtype).to(dev).eval()
+                                            quantization=quantization, kv_cache_dtype=kv_cache_dtype,
+                                            enable_prefix_caching=enable_prefix_caching).to(dev).eval()
     return model, unit_extractor, voicebox, vocoder, tokenizer
 
 
@@ -205,7 +206,10 @@ def main(argv=None):
                              "(e2m1 with a power-of-two scale per 32 elements, fp8 lm_head; about 11.5 %% weight error).")
     parser.add_argument('--kv_cache_dtype', type=str, default=None, choices=["bf16", "fp8"],
                         help="KV cache of the LLM: bf16 (default) or fp8 (e4m3 rows, one power-of-two scale per token and kv head; opt-in, "
-                             "switches prefix reuse between the three rounds off).")
+                             "switches prefix reuse between the three rounds off unless --enable_prefix_caching is given).")
+    parser.add_argument('--enable_prefix_caching', action='store_true',
+                        help="Prefix caching (vLLM's name; opt-in): batch slots reuse cached prompt rows, and with --kv_cache_dtype fp8 the three "
+                             "rounds reuse their prefix again (its rows are then read as the cache holds them: quantized).")
     parser.add_argument('--logprobs', type=int, default=None, choices=range(21), metavar="K",
                         help="Also compute per-token log-probabilities on the device (K = 0 .. 20 most likely ids per token) and print the "
                              "cumulative log-probability of each of the three LLM rounds to stderr.")
@@ -240,7 +244,8 @@ def main(argv=None):
 
     device = torch.device("cuda")
     model, unit_extractor, voicebox, vocoder, tokenizer = load_models(args.model_cache_dir, device, quantization=args.quantization,
-                                                                         kv_cache_dtype=args.kv_cache_dtype)
+                                                                         kv_cache_dtype=args.kv_cache_dtype,
+                                                                         enable_prefix_caching=args.enable_prefix_caching)
     try:
         sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path, logprobs=args.logprobs,
                repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty,

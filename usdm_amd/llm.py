@@ -23,7 +23,12 @@ fp8; the same contract and the same structure (usdm_gemv_mxfp4, usdm_dequant_mxf
 KV cache: bf16 rows.  kv_cache_dtype="fp8" (opt-in, independent of `quantization`): every cached row (one token, one kv head) is
 held as e4m3 bytes + one power-of-two exponent (quant.quantize_kv_rows), written by usdm_rope_cache_fp8 / usdm_attn_decode_fp8.
 The model is then exactly the bf16-cache model whose decode steps read the round-tripped rows K', V'; a prompt's own prefill
-attention reads its unquantized K / V from per-plan scratch.  Half the cache bytes per step and per slot; no prefix reuse; single GPU.
+attention reads its unquantized K / V from per-plan scratch.  Half the cache bytes per step and per slot; no prefix reuse unless
+enable_prefix_caching asks for it; single GPU.
+Prefix caching: enable_prefix_caching=True (opt-in; vLLM's keyword): a prompt admitted into a batch slot (generate_batch, serving.LLM,
+n > 1) reuses the prefill-written rows of the longest prefix any slot holds (usdm_amd/prefix.py; usdm_kv_reorder copies them between
+slots, usdm_kv_expand puts them into the prefill plan's scratch), bit-identical with the option off on a bf16 cache; an fp8-cache model
+then reuses its prefix on the single sequence too, reading the reused rows as the cache holds them.
 """
 import math
 import os
@@ -330,8 +335,17 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
 
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
-                 p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None, score_rows=256):
+                 p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None, score_rows=256,
+                 enable_prefix_caching=False):
         check_quantization(quantization, fp8_matrix_cores)
+        # enable_prefix_caching (vLLM's name; opt-in): batch slots reuse cached prompt rows (usdm_amd/prefix.py), and an
+        # fp8-cache model reuses its prefix on the single sequence too.  Off: no index, no buffer and no plan of it is built.
+        self.prefix_caching = bool(enable_prefix_caching)
+        if self.prefix_caching:
+            if tp_size > 1 or tp_segments or p2p is not None:
+                raise NotImplementedError("enable_prefix_caching runs on one GPU: tensor parallelism (tp_size > 1, tp_segments, p2p) is not supported")
+            if os.environ.get("USDM_PREFIX_REUSE", "exact") in ("0", "off"):
+                raise ValueError("enable_prefix_caching=True contradicts USDM_PREFIX_REUSE=0 (prefix reuse switched off)")
         # score(): prompt rows per lm_head GEMM + usdm_prompt_logprobs launch.  256 is reasoned, not measured: one 1024-thread workgroup per
         # row is about one round of the 256 CUs, and a 256 x 42003 x 4 B = 43 MB chunk should stay cache-resident between the GEMM's write
         # and the kernel's 2 - 9 read passes (tools/score_rate.py sweeps it)
@@ -569,9 +583,12 @@ class USDMForCausalLM:
         mode = os.environ.get("USDM_PREFIX_REUSE", "exact")
         self.reuse_prefix = {"0": False, "off": False, "1": True, "all": True}.get(mode, "exact")
         if self.kv8:
-            # fp8 cache: no reuse and no persistent V^T.  A reused prefix would have to be dequantized for the prefill attention and
-            # would no longer equal a recomputed prompt (which attends to its unquantized K / V); every call prefills its whole prompt.
-            self.reuse_prefix, self.vtc = False, None
+            # fp8 cache: no persistent V^T, and no reuse unless enable_prefix_caching asks for it.  A reused prefix is dequantized for the
+            # prefill attention (usdm_kv_expand into the plan's scratch) and no longer equals a recomputed prompt, which attends to its
+            # unquantized K / V: without the flag every call prefills its whole prompt.
+            self.vtc = None
+            if not self.prefix_caching:
+                self.reuse_prefix = False
         else:
             self.vtc = torch.zeros(L, self.Hkv, d, self.ctx_max, dtype=bf, device=dev)
         self._kv_ids, self._vt_upto = None, 0
@@ -851,18 +868,19 @@ class USDMForCausalLM:
     def _prefill_rows(self, S, slot=None, past=0):
         """The launches every plan over a prompt's rows begins with: embedding, the layers, K/V rows into the cache (of the slot, or of
         the single sequence), for S new tokens at positions past .. past+S-1 (past > 0: the KV cache already holds the first `past`
-        tokens of the same sequence; only the single-sequence cache keeps the V^T that makes this possible).  Returns (rec, io, h, xn):
+        tokens of the same sequence: the single bf16 sequence keeps their V^T, a slot or an fp8 cache gets them from usdm_kv_expand).  Returns (rec, io, h, xn):
         the open plan, its input ids, the final hidden state of every row [S][H] and the [S][H] scratch of the normalised rows."""
         dev, bf = self.device, torch.bfloat16
         H, d, L, Hq, Hkv, I, nq = self._dims()
-        Spad = (S + 63) // 64 * 64
+        scratch = slot is not None or self.kv8      # batch slots / fp8 cache: V^T (fp8: and the bf16 K rows) are scratch of this plan
+        # ... which then covers the cached rows in front of the new ones as well: every layer's usdm_kv_expand writes them (past > 0)
+        Spad = ((past if scratch else 0) + S + 63) // 64 * 64
         rec = _Segments()
         Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
         io = dict(ids=Z(S, dt=torch.int64))
         h, xn, qkv, ao, act = Z(S, H), Z(S, H), Z(S, nq), Z(S, Hq * d), Z(S, I)
-        vt = Z(Hkv, d, Spad) if (slot is not None or self.kv8) else None     # batch slots / fp8 cache: scratch V^T of this prompt only
-        kscr = Z(Hkv, Spad, d) if self.kv8 else None           # fp8 cache: the prompt's bf16 K rows (one scratch, reused by every layer)
-        assert past == 0 or (slot is None and not self.kv8)
+        vt = Z(Hkv, d, Spad) if scratch else None
+        kscr = Z(Hkv, Spad, d) if self.kv8 else None           # fp8 cache: the bf16 K rows (one scratch, reused by every layer)
         part = Z(S, H, dt=torch.float32) if self.tp_path else None
         ops.embed_rows(self.W["embed"], h, Hd=H, ids=io["ids"], n=S, plan=rec.plan)
 
@@ -877,16 +895,20 @@ class USDMForCausalLM:
 
         # Rows go to the cache of the slot or of the single sequence (fp8 cache: quantized).  The prompt's own attention reads K from
         # that cache, or (fp8 cache) the unquantized K rows from scratch, and V^T from this plan's scratch or the persistent V^T of the
-        # single sequence (the only one that can hold a prefix: past > 0)
+        # single bf16 sequence
         cs = slot if slot is not None else self
         k_ld = Spad if self.kv8 else self.ctx_max
         vt_ld = Spad if vt is not None else self.ctx_max
 
         def attn(l):
             vtl = vt if vt is not None else self.vtc[l]
+            kv8 = (cs.kexp[l], cs.vexp[l]) if self.kv8 else None
+            if past and scratch:      # the cached rows: V^T columns / K rows [0, past); beyond past + S the scratch stays zero
+                ops.kv_expand(cs.kcache[l], cs.vcache[l], vt, n=past, Hkv=Hkv, ctx_max=self.ctx_max, vt_ld=Spad, kv8=kv8, kscr=kscr,
+                              kscr_ld=Spad if self.kv8 else 0, plan=rec.plan)
             ops.rope_cache(qkv, self.cos, self.sin, cs.kcache[l], cs.vcache[l], ld=nq, S=S, pos0=past, Hq=Hq, Hkv=Hkv, ctx_max=self.ctx_max,
-                           max_pos=self.ctx_max, vt=vtl[:, :, past:], vt_ld=vt_ld, kv8=(cs.kexp[l], cs.vexp[l]) if self.kv8 else None,
-                           kscr=kscr, kscr_ld=Spad if self.kv8 else 0, plan=rec.plan)
+                           max_pos=self.ctx_max, vt=vtl[:, :, past:], vt_ld=vt_ld, kv8=kv8,
+                           kscr=kscr[:, past:] if self.kv8 else None, kscr_ld=Spad if self.kv8 else 0, plan=rec.plan)
             ops.attention(qkv, kscr if self.kv8 else cs.kcache[l], vtl, ao, mode=1, dh=d, B=1, Hq=Hq, Hkv=Hkv, Sq=S, Skv=past + S,
                           Skv_alloc=vt_ld, q_pos0=past, q_strides=(0, d, nq), k_strides=(0, k_ld * d, d), v_strides=(0, d * vt_ld, vt_ld),
                           o_strides=(0, Hq * d), scale=d ** -0.5, window=self.window, plan=rec.plan)
@@ -1051,7 +1073,8 @@ class USDMForCausalLM:
         definition of prompt log-probabilities (generate(logprobs=) reports the ban-masked row it picked from instead).
         With reuse_prefix on, cached rows of a common prefix are reused up to start - 1 tokens under generate()'s rule ("exact": rows a
         prefill wrote), and the call leaves the prompt's ids behind as cached prefill-written rows: N candidates behind one prefix
-        prefill and score their own rows only.  With the fp8 KV cache nothing is reused.
+        prefill and score their own rows only.  With the fp8 KV cache nothing is reused unless the model was built with
+        enable_prefix_caching=True; the reused rows are then read as the cache holds them, quantized.
         last_logits, last_logprobs, the sampler's, the penalties' and the edits' state are not touched.
         keep_score_logits = True (debug / tests): last_score_logits is then the [L - start][vocab_size] f32 logits rows scored."""
         K = check_logprobs(top_logprobs) or 0
@@ -1073,7 +1096,7 @@ class USDMForCausalLM:
                     past = min(past, self._vt_upto)      # rows beyond that were appended by decode steps
                 if past < 16:
                     past = 0
-            if past > self._vt_upto:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers
+            if past > self._vt_upto and self.vtc is not None:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers (fp8 cache: the plan's usdm_kv_expand covers them)
                 a0 = self._vt_upto
                 self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
         S, j0 = L - past, start - 1 - past
@@ -1256,7 +1279,10 @@ class USDMForCausalLM:
         generate()); a group with a non-neutral knob runs on the penalised sampling step, its other sequences with neutral knobs.
         logit_bias / no_repeat_ngram_size: one dict / integer for all sequences or a list with one per sequence, likewise (the step
         with usdm_logit_edit).  min_p is accepted and range-checked for symmetry with generate(): these picks are greedy (top_k = 1),
-        where it changes nothing."""
+        where it changes nothing.
+        On a model built with enable_prefix_caching=True every prompt reuses the rows of the longest prefix (>= 16 tokens) that a slot
+        of the group's buffers holds from an earlier prefill, and prefills the rest (_reuse_rows; self.stats counts prefix_hits,
+        prefix_rows_reused, prefix_copies, prefill_rows); bf16 cache: the same ids and log-probabilities, bit for bit."""
         lpk = check_logprobs(logprobs)
         n = len(input_ids_list)
         pens = [check_penalties(*k) for k in zip(*(_per_sequence(k, n) for k in (repetition_penalty, presence_penalty, frequency_penalty)))]
@@ -1285,7 +1311,9 @@ class USDMForCausalLM:
         then the per-item prefill into the slot's cache, which also picks the first token as that step would (sampled; with row 0 of
         the slot's log-probabilities).  On the penalised step the slot's table is reset and seeded from the prompt, with the request's
         knobs (repetition, frequency, presence; None: a request without, neutral); on the step with logit edits the slot's edit state
-        is written from the prompt and the request's check_edits() value (None: neutral)."""
+        is written from the prompt and the request's check_edits() value (None: neutral).
+        Returns (source slot, past): the rows [0, past) that were reused instead of prefilled and the slot they came from
+        (enable_prefix_caching, _reuse_rows); (None, 0) without the option or without a match."""
         bb, L = self._batch_pick_state(B, kind), int(ids.shape[0])
         bb["step"][b] = 0
         bb["pos"][b] = L
@@ -1293,11 +1321,51 @@ class USDMForCausalLM:
             seed_penalties(bb["slots"][b].pen, ids, knobs)
         if kind.edits:
             seed_edits(bb["slots"][b].edt, ids, edits)
-        segs, io = bb["prefill"].get_or_build((L, b, *kind), lambda: self._build_prefill(L, kind.sampling or None, slot=bb["slots"][b],
-                                                                                         logprobs=kind.logprobs, penalties=kind.penalties,
-                                                                                         edits=kind.edits))
-        io["ids"].copy_(ids)
+        src, past = self._reuse_rows(bb, B, b, ids) if self.prefix_caching else (None, 0)
+        S = L - past
+        segs, io = bb["prefill"].get_or_build((S, past, b, *kind), lambda: self._build_prefill(S, kind.sampling or None, slot=bb["slots"][b], past=past,
+                                                                                               logprobs=kind.logprobs, penalties=kind.penalties,
+                                                                                               edits=kind.edits))
+        io["ids"].copy_(ids[past:])
         self._run_segs(segs)
+        return src, past
+
+    def _prefix_index(self, bb, B):
+        """The slots' prefix index (usdm_amd/prefix.py) and the three device words of its usdm_kv_reorder copies, built at first use."""
+        if "prefix" not in bb:
+            from .prefix import PrefixIndex
+            from .serving import CHUNK
+            i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=self.device)
+            bb.update(prefix=PrefixIndex(B, self.ctx_max, CHUNK), px_parent=i32(B), px_lo=i32(1), px_pos=i32(1))
+        return bb["prefix"]
+
+    def _reuse_rows(self, bb, B, b, ids):
+        """enable_prefix_caching: the rows of the B slots that the prompt `ids`, about to be prefilled into slot b, can reuse ->
+        (source slot or None, past).  Rows [0, past) of another slot are copied into slot b (usdm_kv_reorder with parent[b] = source and
+        the identity elsewhere, lo = 0, pos = past: K, V and the fp8 cache's exponents in one launch); slot b's entry becomes the
+        prompt.  Counted in self.stats: prefix_hits, prefix_rows_reused, prefix_copies, prefill_rows."""
+        px, prompt = self._prefix_index(bb, B), ids.tolist()
+        src, past = px.match(prompt, b)
+        if src is not None and src != b:
+            parent = list(range(B))
+            parent[b] = src
+            bb["px_parent"].copy_(torch.tensor(parent, dtype=torch.int32))
+            bb["px_pos"].fill_(past)
+            arrays = [bb["kc"], bb["vc"]] + ([bb["ke"], bb["ve"]] if self.kv8 else [])
+            ops.kv_reorder(arrays, bb["px_parent"], bb["px_lo"], bb["px_pos"], B=B, nblk=self.cfg["num_hidden_layers"] * self.Hkv, ctx_max=self.ctx_max)
+        px.admit(b, prompt)
+        st = self.stats
+        for k, v in (("prefix_hits", int(past > 0)), ("prefix_rows_reused", past), ("prefix_copies", int(src is not None and src != b)),
+                     ("prefill_rows", len(prompt) - past)):
+            st[k] = st.get(k, 0) + v
+        return src, past
+
+    def reset_prefix_cache(self):
+        """vLLM's name: forget every reusable row, of the batch slots and of the single sequence (nothing on the device changes)."""
+        for bb in self._batches.values():
+            if "prefix" in bb:
+                bb["prefix"].reset()
+        self._kv_ids, self._vt_upto = None, 0
 
     def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None, pens=None, edits=None):
         B = len(ids_list)
@@ -1609,7 +1677,7 @@ class USDMForCausalLM:
                     past = min(past, self._vt_upto)      # rows beyond that were appended by decode steps
                 if past < 16:
                     past = 0
-            if past > self._vt_upto:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers
+            if past > self._vt_upto and self.vtc is not None:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers (fp8 cache: the plan's usdm_kv_expand covers them)
                 a0 = self._vt_upto
                 self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
         segs, dev_eos = self._setup_call(input_ids, past, kind.sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, BeamArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -547,6 +547,21 @@ def kv_reorder(arrays, parent, lo, pos, *, B, nblk, ctx_max, plan=None):
         a.base[i], a.slot_bytes[i] = t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else t[0].numel()) * t.element_size()
         a.row_bytes[i] = t[0].numel() // (nblk * ctx_max) * t.element_size()
     _go(plan, "usdm_kv_reorder", lib.usdm_kv_reorder, C_.byref(a))
+
+
+def kv_expand(kcache, vcache, vt, *, n, Hkv, ctx_max, vt_ld, kv8=None, kscr=None, kscr_ld=0, plan=None):
+    """usdm_kv_expand: rows 0 .. n-1 of one layer's cache of one sequence ([Hkv][ctx_max][128]) as the prefill attention's operands -
+    V^T into vt [Hkv][128][vt_ld], and with kv8=(kexp, vexp) (uint8 caches) the dequantized K rows into kscr [Hkv][kscr_ld][128]."""
+    _need_cuda(kcache, vcache, vt, kscr)
+    a = KvExpandArgs()
+    a.kcache, a.vcache, a.vt, a.vt_ld, a.kscr, a.kscr_ld = _ptr(kcache), _ptr(vcache), _ptr(vt), vt_ld, _ptr(kscr), kscr_ld
+    a.Hkv, a.ctx_max, a.n = Hkv, ctx_max, n
+    if kv8 is not None:
+        kexp, vexp = _kv8(kv8, kcache, vcache)
+        a.kexp, a.vexp = _ptr(kexp), _ptr(vexp)
+    elif kcache.dtype != torch.bfloat16 or vcache.dtype != torch.bfloat16:
+        raise TypeError("kv_expand: bf16 caches, or uint8 caches with kv8=(kexp, vexp)")
+    _go(plan, "usdm_kv_expand", lib.usdm_kv_expand, C_.byref(a))
 
 
 PENALTY_PROMPT_BIT = 1 << 30     # usdm_penalize's table word: in_prompt(i) in bit 30, c(i) below it

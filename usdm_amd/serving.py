@@ -32,7 +32,11 @@ How requests are executed
   * SamplingParams(logprobs=K), K = 0 .. 20: per-token log-probabilities computed on the device inside the step (usdm_logprobs, right
     after the pick, on the row it drew from): lp(i) = x_i - logsumexp(x) over the ban-masked logits, i.e. the model's distribution
     over the allowed ids BEFORE temperature / top-k / top-p.  One asking request puts its whole group on the log-probability step
-    (K = the group's maximum, trimmed per request on the host); a greedy request then runs on the sampling step with top_k = 1.
+    (K = the group's maximum, trimmed per request on the host); a greedy request then runs on the sampling step with top_k = 1;
+  * LLM(enable_prefix_caching=True) (vLLM's keyword; opt-in): a request admitted into a slot reuses the prefill-written
+    rows of the longest prefix (>= 16 tokens) that any slot holds - a slot still decoding included - and prefills the rest; rows of
+    another slot are copied on the device (usdm_kv_reorder), idle slots are parked behind their cached rows.  bf16 cache: every
+    request returns exactly what it returns with the option off.  stats: prefix_hits, prefix_rows_reused, prefill_rows.
 """
 import os
 from collections import deque
@@ -223,7 +227,8 @@ class LLM:
     download_dir), or `LLM(model=<USDMForCausalLM>, tokenizer=<tokenizer>)` around objects that are already loaded."""
 
     def __init__(self, model, tokenizer=None, download_dir=None, gpu_memory_utilization=0.9, max_model_len=None, device="cuda",
-                 dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None, **unused):
+                 dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None,
+                 enable_prefix_caching=False, **unused):
         # max_num_seqs (vllm's name): sequences decoded per step, 1..16.  <= 4: the VALU batch kernel (per slot bit-identical with the
         # single-request path); above: the matrix-core form (usdm_gemv_batch form 1)
         self.max_slots = max(1, min(int(max_num_seqs), MAX_SLOTS))
@@ -243,6 +248,8 @@ class LLM:
                                  f"quantization={model.quantization!r}")
             if fp8_matrix_cores and not model.fp8_matrix_cores:
                 raise ValueError("fp8_matrix_cores=True, but the model object was loaded with fp8_matrix_cores=False")
+            if enable_prefix_caching and not model.prefix_caching:
+                raise ValueError("enable_prefix_caching=True, but the model object was loaded with enable_prefix_caching=False")
             self.llm = model
         else:
             from .checkpoints import resolve_local
@@ -252,16 +259,30 @@ class LLM:
                 tokenizer = AutoTokenizer.from_pretrained(path, local_files_only=True)
             ctx = min(int(max_model_len or getattr(tokenizer, "model_max_length", 4096) or 4096), 8192)
             self.llm = USDMForCausalLM.from_pretrained(path, device=device, ctx_max=ctx, quantization=quantization,
-                                                       fp8_matrix_cores=fp8_matrix_cores, kv_cache_dtype=kv_cache_dtype)
+                                                       fp8_matrix_cores=fp8_matrix_cores, kv_cache_dtype=kv_cache_dtype,
+                                                       enable_prefix_caching=enable_prefix_caching)
         if isinstance(tokenizer, str):
             from transformers import AutoTokenizer
             tokenizer = AutoTokenizer.from_pretrained(tokenizer, local_files_only=True)
         self.tokenizer = tokenizer
         self.stats = dict(requests=0, batched_requests=0, admissions=0, max_active=0, batched_steps=0, hook_requests=0)
+        # enable_prefix_caching (vLLM's name): an admitted prompt reuses the rows of the longest prefix that any slot
+        # holds.  prefix_hits = admissions that reused rows, prefix_rows_reused / prefill_rows = rows reused / prefilled, prefix_copies =
+        # hits served from another slot (usdm_kv_reorder), prefix_hits_live = hits whose source slot was still decoding;
+        # admission_log = the last (slot, prompt ids) admissions in order (what a PrefixIndex replays)
+        self.prefix_caching = self.llm.prefix_caching
+        if self.prefix_caching:
+            self.stats.update(prefix_hits=0, prefix_rows_reused=0, prefill_rows=0, prefix_copies=0, prefix_hits_live=0)
+            self.admission_log = deque(maxlen=256)
         self._next_id = 0
 
     def get_tokenizer(self):
         return self.tokenizer
+
+    def reset_prefix_cache(self):
+        """vLLM's name: forget every cached prefix (enable_prefix_caching); later prompts prefill all their rows again."""
+        self.llm.reset_prefix_cache()
+        return True
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
@@ -308,7 +329,8 @@ class LLM:
                 seed = self.llm._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
             # n > 1 (vllm.SamplingParams.n): the request fans out into n sequences that share prompt, knobs and mask and draw from
             # the Philox streams seed, seed + 1, ...: completion j is exactly what a single request with seed + j returns, and the
-            # copies ride the continuous batch like any other requests (the prompt is prefilled once per copy)
+            # copies ride the continuous batch like any other requests (the prompt is prefilled once per copy; with
+            # enable_prefix_caching copies 2 .. n find it in copy 1's slot and prefill one row)
             for j in range(sp.n):
                 reqs.append(dict(i=(i, j), rid=str(self._next_id + i), text=text, ids=ids, sp=sp, mask=mask, stops=stops,
                                  seed=(seed + j) if seed is not None else None,
@@ -479,7 +501,15 @@ class LLM:
                         ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
                     else:
                         ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"], min_p=sp.min_p)
-                    llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), kind, knobs=sp.penalties, edits=sp.edits)      # (+ first token)
+                    src, past = llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), kind, knobs=sp.penalties, edits=sp.edits)      # (+ first token)
+                    if self.prefix_caching:
+                        st = self.stats
+                        st["prefix_hits"] += past > 0
+                        st["prefix_rows_reused"] += past
+                        st["prefill_rows"] += len(r["ids"]) - past
+                        st["prefix_copies"] += src is not None and src != b
+                        st["prefix_hits_live"] += src is not None and src != b and slots[src] is not None
+                        self.admission_log.append((b, tuple(r["ids"])))
                     slots[b] = dict(r=r, produced=1)
                     self.stats["admissions"] += 1
             active = [b for b in range(nslots) if slots[b] is not None]
@@ -487,7 +517,9 @@ class LLM:
             for b in range(nslots):                               # idle slots decode garbage into row 0 of their own cache
                 if slots[b] is None:
                     bb["step"][b] = 0
-                    bb["pos"][b] = 0
+                    # (enable_prefix_caching: behind the rows its index records, which the garbage would destroy - the idle slot's
+                    # attention then runs over those rows)
+                    bb["pos"][b] = llm._prefix_index(bb, nslots).park(b) if self.prefix_caching else 0
             # tokens already known (the prefill's first token) are checked before any further step is spent
             toks = bb["out"].tolist()                                # host sync = scheduling point
             need, freed = 0, False
