@@ -702,6 +702,67 @@ typedef struct usdm_kv_expand_args {
 int usdm_kv_expand(const usdm_kv_expand_args* args, usdm_stream_t stream);
 int usdm_sizeof_kv_expand_args(void);
 
+/* Speculative greedy decoding: decode attention for T = 1 .. 8 new tokens of ONE sequence (GQA G in {1, 2, 4},
+ * head_dim 128, bf16 cache).  Row i of qkv [T][qkv_ld] is the token at position *pos + i: its q and k are roped as usdm_attn_decode
+ * ropes them, its K / V rows are appended at *pos + i (bit-identical with T successive usdm_attn_decode calls) and out[i][Hq*128]
+ * is its attention over keys lo_i .. *pos + i (lo_i from `window` as in usdm_attn_decode); the step's own rows come from LDS as
+ * the bf16 values that are appended.  Every cached row is read once per launch for all T * G query rows of its kv head; scores and
+ * PV run on v_mfma_f32_16x16x32_bf16, softmax in fp32, P rounded to bf16.
+ * POSITION INVARIANCE: the result for the token at absolute position p (out row and appended rows) depends on p and the keys it
+ * sees only - not on T, its row index or *pos.  Splits are the FIXED key ranges [s * C, (s + 1) * C), key tiles of 64 are aligned
+ * to absolute indices, masked keys carry P = 0 exactly, and row p's partials are merged over splits 0 .. p / C in ascending order
+ * with the arithmetic of usdm_attn_decode's merge.  Grid (Hkv, ceil(ctx_max / C)); workgroups past the live context exit at once.
+ * Rows at positions >= ctx_max are neither appended nor computed (their out rows are not written).  *skip != 0: nothing is
+ * written.  Refused (error, no fall-back): T outside 1 .. 8, G outside {1, 2, 4}, a NULL pointer, caches not 16-byte aligned,
+ * qkv / out not 4-byte aligned, qkv_ld < (Hq + 2 Hkv) * 128 or odd, out_ld < Hq * 128, C no multiple of 64 or outside 64 .. 256,
+ * more than 64 splits, window < 0. */
+typedef struct usdm_attn_verify_args {
+  const void* qkv; int64_t qkv_ld;
+  const int32_t* pos;
+  int32_t T, Hq, Hkv, ctx_max;
+  int32_t C;                /* keys per split: a plan constant, a multiple of the key tile (64) */
+  int32_t window; float scale;
+  const uint16_t* cos; const uint16_t* sin;
+  void* kcache; void* vcache;          /* [Hkv][ctx_max][128] bf16 */
+  float* pm; float* pl; float* po;     /* scratch [T][Hq][NSP], [T][Hq][NSP], [T][Hq][NSP][128], NSP = ceil(ctx_max / C) */
+  void* out; int64_t out_ld;           /* bf16 [T][out_ld] */
+  const int32_t* skip;
+} usdm_attn_verify_args;
+int usdm_attn_verify(const usdm_attn_verify_args* args, usdm_stream_t stream);
+int usdm_sizeof_attn_verify_args(void);
+
+/* The end of a speculative step, in place of usdm_argmax_final: pick, accept, commit, propose, embed - one launch, one workgroup.
+ * Picks g_0 .. g_{T-1}: the arg-max of row i's partials part_val / part_idx [T][nparts] (ties to the lowest id, the reduction of
+ * usdm_argmax_final; no candidate -> id 0), token = id + st->id_offset.  drafts[i], i = 1 .. T-1, are the tokens that were fed as
+ * rows 1 .. T-1 (-1: none, never matches).  n = the number of leading i with drafts[i + 1] == g_i.
+ * Commit: with s = *st->step and lim = min(*limit, st->max_out), g_0 .. g_n go to out_tokens[s ..] until lim is reached or a stop id
+ * (st->eos = {count, min_new, ids}) is emitted with at least min_new tokens out; m = the number emitted.  done is set on that stop
+ * id or when s + m >= lim.  *step += m, *pos += m, next_token = the last emitted token; counters += {1, drafts >= 0 among the fed,
+ * m - 1}.  s >= lim on entry: done is set and nothing else changes.
+ * Propose (history = the prompt's ids + id_offset followed by out_tokens[0 .. *step), as usdm_logit_edit reads it): for n from
+ * params[0] (lookup_max, <= 16) down to params[1] (lookup_min, >= 1) the MOST RECENT earlier occurrence of the last n tokens
+ * (start j <= Lh - n - 1); drafts[i] = the token i - 1 places behind that occurrence's end, -1 where the history ends or nothing
+ * matched.  params[2] != 0 and script != NULL: drafts[i] = script[*step + i - 1] instead (tests, tools/spec_rate.py).  A draft
+ * whose id is outside [0, V) is -1.
+ * Finish: h_out[0] = E[next_token], h_out[i] = E[drafts[i]] (-1: the row of id 0) for the next step.
+ * propose_only != 0 (after the prefill, whose pick is already committed): only propose and finish.
+ * done != 0 on entry: the launch changes nothing.  Refused: T outside 1 .. 8, a batched state, a missing pointer, Hd % 8 != 0. */
+typedef struct usdm_spec_args {
+  const float* part_val; const int32_t* part_idx; int32_t nparts;
+  int32_t T;
+  int32_t* drafts;                 /* [8] device */
+  const int32_t* limit;            /* [1] device: max_new of the call */
+  const int32_t* prompt; const int32_t* prompt_len; int32_t prompt_max;   /* device: the prompt's ids, their count */
+  const int32_t* script;           /* [st->max_out] device or NULL */
+  const int32_t* params;           /* [4] device: lookup_max, lookup_min, use_script, reserved */
+  int32_t V;
+  int32_t* counters;               /* [3] device: steps, drafted, accepted */
+  int32_t propose_only;
+} usdm_spec_args;
+int usdm_spec_commit(const usdm_spec_args* args, const usdm_decode_state* st, const void* embed_table_bf16, int32_t Hd,
+                     void* h_out_bf16, usdm_stream_t stream);
+int usdm_sizeof_spec_args(void);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot peer-to-peer all-reduce for the tensor-parallel decode step (replaces the single-GPU
  * model.generate of src/inference.py:116-123 when the 7B is sharded over the 8 GPUs of a node).  Messages are 4096 f32

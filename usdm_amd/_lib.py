@@ -38,6 +38,8 @@ lib.usdm_logit_edit_seg.restype = C.c_int
 lib.usdm_beam_step.restype = C.c_int         # (the beam-search entry points: likewise)
 lib.usdm_kv_reorder.restype = C.c_int
 lib.usdm_kv_expand.restype = C.c_int         # (the prefix-cache entry point: likewise)
+lib.usdm_attn_verify.restype = C.c_int       # (the speculative-decoding entry points: likewise)
+lib.usdm_spec_commit.restype = C.c_int
 _exp = None
 
 
@@ -292,6 +294,25 @@ class RopeFp8Args(C.Structure):
     _fields_ = [("r", RopeArgs), ("kexp", C.c_void_p), ("vexp", C.c_void_p), ("kscr", C.c_void_p), ("kscr_ld", C.c_int64)]
 
 
+class AttnVerifyArgs(C.Structure):
+    _fields_ = [
+        ("qkv", C.c_void_p), ("qkv_ld", C.c_int64), ("pos", C.c_void_p),
+        ("T", C.c_int32), ("Hq", C.c_int32), ("Hkv", C.c_int32), ("ctx_max", C.c_int32), ("C", C.c_int32), ("window", C.c_int32),
+        ("scale", C.c_float),
+        ("cos", C.c_void_p), ("sin", C.c_void_p), ("kcache", C.c_void_p), ("vcache", C.c_void_p),
+        ("pm", C.c_void_p), ("pl", C.c_void_p), ("po", C.c_void_p), ("out", C.c_void_p), ("out_ld", C.c_int64), ("skip", C.c_void_p),
+    ]
+
+
+class SpecArgs(C.Structure):
+    _fields_ = [
+        ("part_val", C.c_void_p), ("part_idx", C.c_void_p), ("nparts", C.c_int32), ("T", C.c_int32),
+        ("drafts", C.c_void_p), ("limit", C.c_void_p),
+        ("prompt", C.c_void_p), ("prompt_len", C.c_void_p), ("prompt_max", C.c_int32),
+        ("script", C.c_void_p), ("params", C.c_void_p), ("V", C.c_int32), ("counters", C.c_void_p), ("propose_only", C.c_int32),
+    ]
+
+
 def check(rc, what=""):
     if rc != 0:
         raise UsdmError(f"{what} failed (rc={rc}): {lib.usdm_last_error().decode()}")
@@ -308,7 +329,7 @@ def _selfcheck():
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
                       ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs), ("beam", BeamArgs),
-                      ("kv_reorder", KvReorderArgs), ("kv_expand", KvExpandArgs)):
+                      ("kv_reorder", KvReorderArgs), ("kv_expand", KvExpandArgs), ("attn_verify", AttnVerifyArgs), ("spec", SpecArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

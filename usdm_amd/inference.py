@@ -79,13 +79,17 @@ def _bad(name, *a, **k):
 @torch.inference_mode()
 def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, output_path,
            reference_mel=None, n_timesteps=50, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-           min_p=0.0, logit_bias=None, no_repeat_ngram_size=0, num_beams=None):
+           min_p=0.0, logit_bias=None, no_repeat_ngram_size=0, num_beams=None, num_speculative_tokens=None, prompt_lookup_max=3,
+           prompt_lookup_min=1):
     """src/inference.py:48-89.  logprobs=K (0 .. 20): the LLM also computes per-token log-probabilities (USDMForCausalLM.generate) and the
     cumulative log-probability of each of the three rounds goes to stderr; nothing else changes.
     repetition_penalty / presence_penalty / frequency_penalty: passed to all three rounds (USDMForCausalLM.generate; on the device).
     min_p / logit_bias / no_repeat_ngram_size: likewise (the rounds pick with top_k = 1, where min_p changes nothing).
     num_beams=N > 1: the three rounds run beam search on the device instead (USDMForCausalLM.generate(num_beams=N): the best
-    hypothesis, HF's defaults length_penalty = 1 and early_stopping = False); its score goes to stderr.  Not with the knobs above."""
+    hypothesis, HF's defaults length_penalty = 1 and early_stopping = False); its score goes to stderr.  Not with the knobs above.
+    num_speculative_tokens=k (1 .. 7): the three rounds run speculative greedy decoding with n-gram drafts
+    (USDMForCausalLM.generate(num_speculative_tokens=k, prompt_lookup_max, prompt_lookup_min)); steps, drafts and accepted drafts of
+    each round go to stderr.  Not with the knobs above or num_beams."""
     bad_words_ids_unit2text = _bad("u2t", 32000, 42003)
     bad_words_ids_text2text = _bad("t2t", 32002, 42003)
     bad_words_ids_text2unit = _bad("t2u", 0, 32002, exclude=[28705])
@@ -103,7 +107,12 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
         out = model.generate(input_ids=ids, max_length=tokenizer.model_max_length, do_sample=True, bad_words_ids=bad,
                              top_p=1.0, top_k=1, temperature=1.0, eos_token_id=eos, logprobs=logprobs,
                              repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                             min_p=min_p, logit_bias=logit_bias, no_repeat_ngram_size=no_repeat_ngram_size)
+                             min_p=min_p, logit_bias=logit_bias, no_repeat_ngram_size=no_repeat_ngram_size,
+                             num_speculative_tokens=num_speculative_tokens, prompt_lookup_max=prompt_lookup_max,
+                             prompt_lookup_min=prompt_lookup_min)
+        if model.last_spec_stats is not None:
+            st = model.last_spec_stats
+            print(f"{name}: {st['steps']} speculative steps, {st['drafted']} drafts, {st['accepted']} accepted", file=sys.stderr)
         lp = model.last_logprobs
         if lp is not None:
             print(f"{name}: {lp.token_logprobs.numel()} tokens, cumulative log-probability {lp.cumulative:.4f}", file=sys.stderr)
@@ -231,9 +240,24 @@ def main(argv=None):
                         help="Beam search over N beams (2 .. 16) in the three LLM rounds instead of the greedy pick, on the device (HF "
                              "generate(num_beams=N): length_penalty 1, early_stopping False, the best hypothesis).  An error together with "
                              "--logprobs, the penalties, --min_p, --no_repeat_ngram_size or --logit_bias.")
+    parser.add_argument('--num_speculative_tokens', type=int, default=None, metavar="K",
+                        help="Speculative greedy decoding in the three LLM rounds: every step verifies K (1 .. 7) n-gram drafts taken from "
+                             "the round's own prompt and output (vLLM speculative_config method 'ngram').  The ids do not depend on the drafts.  "
+                             "An error together with --logprobs, the penalties, --min_p, --no_repeat_ngram_size, --logit_bias, --num_beams "
+                             "or --kv_cache_dtype fp8.")
+    parser.add_argument('--prompt_lookup_max', type=int, default=3, help="Longest n-gram the draft lookup matches (1 .. 16).")
+    parser.add_argument('--prompt_lookup_min', type=int, default=1, help="Shortest n-gram the draft lookup matches.")
     args = parser.parse_args(argv)
     from .llm import check_edits, check_min_p, check_penalties
+    from .spec import check_spec_args, check_spec_call
     try:
+        if check_spec_args(args.num_speculative_tokens, args.prompt_lookup_max, args.prompt_lookup_min) is not None:
+            try:
+                check_spec_call(False, args.logprobs, check_penalties(args.repetition_penalty, args.presence_penalty, args.frequency_penalty),
+                                check_edits(parse_logit_bias(args.logit_bias), args.no_repeat_ngram_size), args.min_p, None, args.num_beams,
+                                False, args.kv_cache_dtype == "fp8")
+            except NotImplementedError as e:
+                raise ValueError(str(e)) from None
         check_num_beams(args)
         check_penalties(args.repetition_penalty, args.presence_penalty, args.frequency_penalty)
         check_min_p(args.min_p)
@@ -249,7 +273,9 @@ def main(argv=None):
     try:
         sample(args.input_path, args.reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, args.output_path, logprobs=args.logprobs,
                repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty,
-               min_p=args.min_p, logit_bias=logit_bias, no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams)
+               min_p=args.min_p, logit_bias=logit_bias, no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams,
+               num_speculative_tokens=args.num_speculative_tokens, prompt_lookup_max=args.prompt_lookup_max,
+               prompt_lookup_min=args.prompt_lookup_min)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)
         print(f"Error while sampling: {e}")
         return 1

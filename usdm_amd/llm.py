@@ -463,6 +463,14 @@ class USDMForCausalLM:
         self.last_logprobs = None  # generate(logprobs=K): TokenLogprobs of the last call (generate_batch: a list); None when not asked
         self._pen = None          # penalty state of the single sequence (penalty_buffers; allocated at first use)
         self._edt = None          # logit-edit state of the single sequence (edit_buffers; allocated at first use)
+        # speculative greedy decoding: the device words of usdm_spec_commit, the rows, plan and graph per T, all built at
+        # first use (_spec_state); generate(num_speculative_tokens=None / 0) touches none of it
+        self._spec = None
+        self.last_spec_stats = None    # generate(num_speculative_tokens=k): dict(steps=, drafted=, accepted=) of the last call
+        # usdm_attn_verify's keys per split: a plan constant (fixed absolute key ranges).  Reasoned, not measured: 128 keys x 2 x 256 B
+        # = 64 KB per workgroup, 5 .. 28 splits x 8 kv heads over the 600 .. 3 500 rows of an utterance, at most one per CU; 256 where
+        # ctx_max / 128 would exceed the 64 splits the merge takes
+        self.spec_split = int(os.environ.get("USDM_SPEC_SPLIT", 128 if self.ctx_max <= 64 * 128 else 256))
         # score(): plans keyed (S, past, j0, K) in a cache of their own (scoring never evicts generate()'s prefill plans), the output
         # rows [ctx_max] / [ctx_max][20] and the bf16 copy of a quantized lm_head, all allocated at first use
         self._score_plans = LRU(8)
@@ -1247,6 +1255,89 @@ class USDMForCausalLM:
         segs = rec.finish()
         return segs if (tp or beam is not None) else segs[0]
 
+    # ------------------------------------------------------------------ speculative greedy decoding
+    def _spec_state(self, T=None):
+        """The device words of usdm_spec_commit for the single sequence (drafts, limit, prompt row, script, {lookup_max, lookup_min,
+        use_script}, the three counters) and, per T, the rows the step runs on: h [T][H] and the arg-max partials [T][nparts]."""
+        dev = self.device
+        if self._spec is None:
+            i32 = lambda n, v=0: torch.full((n,), v, dtype=torch.int32, device=dev)
+            self._spec = dict(drafts=i32(ops.SPEC_MAX_T, -1), limit=i32(1), prompt=i32(self.ctx_max), prompt_len=i32(1), script=i32(self.max_out, -1),
+                              params=i32(4), counters=i32(3), rows={}, steps={}, inits={})
+        sp = self._spec
+        if T is not None and T not in sp["rows"]:
+            sp["rows"][T] = dict(h=torch.zeros(T, self.cfg["hidden_size"], dtype=torch.bfloat16, device=dev),
+                                 pv=torch.full((T, self.nparts), float("-inf"), dtype=torch.float32, device=dev),
+                                 pi=torch.full((T, self.nparts), NO_CANDIDATE_IDX, dtype=torch.int32, device=dev))
+        return sp
+
+    def _spec_commit(self, T, plan, propose_only=False):
+        """usdm_spec_commit over the T rows of _spec_state: the end of the step, or (propose_only, after the prefill, whose pick is
+        already committed) the first drafts and the first T input rows."""
+        sp = self._spec_state(T)
+        r = sp["rows"][T]
+        st = ops.decode_state(self.st_next, self.st_out, self.st_step, self.st_pos, advance_pos=True, done=self.st_done, eos=self.st_eos)
+        ops.spec_commit(r["pv"], r["pi"], self.nparts, st, T=T, drafts=sp["drafts"], limit=sp["limit"], prompt=sp["prompt"],
+                        prompt_len=sp["prompt_len"], params=sp["params"], counters=sp["counters"], V=self.cfg["vocab_size"], script=sp["script"],
+                        embed=self.W["embed"], h_out=r["h"], Hd=self.cfg["hidden_size"], propose_only=propose_only, plan=plan)
+        plan.hold(st)
+
+    def _build_decode_spec(self, T):
+        """One speculative step of the single sequence: T rows (the token to continue from and T - 1 drafts of the SAME sequence) through
+        _layers with the batched projections of _build_decode_batch (weights streamed once; <= 4 rows on the VALU form, bit-identical
+        per row with the single step, 5 .. 8 on the matrix cores), usdm_attn_verify on the single sequence's caches (every cached row
+        read once for all rows), the lm_head in batched arg-max mode, usdm_spec_commit.  One plan, one graph per T."""
+        dev, bf = self.device, torch.bfloat16
+        H, d, L, Hq, Hkv, I, nq = self._dims()
+        r = self._spec_state(T)["rows"][T]
+        rec = _Segments()
+        Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
+        h, qkv, ao, act = r["h"], Z(T, nq), Z(T, Hq * d), Z(T, I)
+        nsp = ops.attn_verify_splits(self.ctx_max, self.spec_split)
+        pm, pl, po = Z(T * Hq * nsp, dt=torch.float32), Z(T * Hq * nsp, dt=torch.float32), Z(T * Hq * nsp * d, dt=torch.float32)
+        ksf = ops.gemv_batch_ks_floats(H, I) if T > 4 else 0
+        ks = (Z(ksf, dt=torch.float32), Z(-(-H // 16), dt=torch.int32)) if ksf else None
+        gemv_b = ops.gemv_fp8_mfma if (self.fp8_matrix_cores and T > 4) else ops.gemv_batch
+
+        def gemv(W, x, *, N, K, act=0, residual=None, y_bs=None, **kw):
+            gemv_b(W, x, nb=T, N=N, K=K, x_bs=K, y_bs=(N // 2 if act else N) if y_bs is None else y_bs, res_bs=N if residual is not None else 0,
+                   act=act, residual=residual, plan=rec.plan, **kw)
+
+        def attn(l):
+            ops.attn_verify(qkv, self.st_pos, self.cos, self.sin, self.kcache[l], self.vcache[l], pm, pl, po, ao, T=T, Hq=Hq, Hkv=Hkv,
+                            ctx_max=self.ctx_max, C=self.spec_split, scale=d ** -0.5, window=self.window, skip=self.st_done, plan=rec.plan)
+
+        self._layers(rec, gemv, attn, h, qkv, ao, act, "fused", n=T * H, down_kw=dict(ks=ks))
+        gemv(self.W["lm_head"], h, N=self.v1 - self.v0, K=H, norm_w=self.W["norm"], eps=self.cfg["rms_norm_eps"], ban=self.ban,
+             part_val=r["pv"], part_idx=r["pi"], idx_offset=self.v0, part_bs=self.nparts, y_bs=0)
+        self._spec_commit(T, rec.plan)
+        return rec.finish()[0]
+
+    def _spec_begin(self, T, input_ids, max_new, lookup_max, lookup_min, script):
+        """Per-call state of a speculative generate() behind its prefill (whose pick is committed: step = 1): limit, lookup
+        bounds, the prompt row, the script, zeroed counters; then the first drafts and input rows (usdm_spec_commit, propose_only).
+        Returns the replayable step."""
+        sp = self._spec_state(T)
+        L0 = int(input_ids.shape[1])
+        sp["limit"].fill_(int(max_new))
+        sp["prompt"][:L0] = input_ids[0].to(self.device, torch.int32)
+        sp["prompt_len"].fill_(L0)
+        sp["counters"].zero_()
+        sp["drafts"].fill_(-1)
+        if script is not None:
+            sc = torch.as_tensor(script).to(torch.int32).reshape(-1)[:self.max_out]
+            sp["script"].fill_(-1)
+            sp["script"][:sc.numel()] = sc.to(self.device)
+        sp["params"].copy_(torch.tensor([lookup_max, lookup_min, int(script is not None), 0], dtype=torch.int32))
+        if T not in sp["inits"]:
+            plan = ops.Plan()
+            self._spec_commit(T, plan, propose_only=True)
+            sp["inits"][T] = plan
+        sp["inits"][T].run()
+        if T not in sp["steps"]:
+            sp["steps"][T] = self._graphed(self._build_decode_spec(T))
+        return sp["steps"][T]
+
     MAX_BATCH = 16      # sequences per decode step (usdm_gemv_batch: VALU form up to 4, matrix-core form up to 16)
 
     def max_batch(self):
@@ -1519,6 +1610,32 @@ class USDMForCausalLM:
         self._lm_head_and_pick(rec, h[L - 1], False, True, slot=bm["slots"][0], beam=bm)
         return rec.finish(), io
 
+    def _generate_spec(self, input_ids, ids_host, max_new, spec, script, dev_eos, eos, min_new):
+        """The decode loop of generate(num_speculative_tokens=k) behind the prefill: the captured step is replayed in chunks and the
+        host reads step / done after each, since a replay emits 1 .. k + 1 tokens.  A chunk never holds more replays than the
+        remaining tokens could need at k + 1 per step, so no replay runs past the limit by the host's doing; replays past a
+        device-side stop change nothing."""
+        k, lookup_max, lookup_min = spec
+        T = k + 1
+        step = self._spec_begin(T, input_ids, max_new, lookup_max, lookup_min, script)
+        while True:
+            produced = min(int(self.st_step.item()), max_new)      # host sync point
+            toks = self.st_out[:produced].tolist()
+            end = stop_index(toks, eos, min_new)
+            if end is not None:
+                toks = toks[:end]
+                break
+            if produced >= max_new or int(self.st_done.item()):
+                break
+            for _ in range(max(1, min(8, -(-(max_new - produced) // T)))):
+                step.run()
+        if self.reuse_prefix:   # committed rows only: the prompt and every emitted token that was fed back and accepted
+            self._kv_ids = ids_host + (self.st_out[:produced - 1].tolist() if produced > 1 else [])
+        c = self._spec["counters"].tolist()
+        self.last_spec_stats = dict(steps=c[0], drafted=c[1], accepted=c[2])
+        out = torch.cat([input_ids[0], torch.tensor(toks, dtype=torch.long, device=input_ids.device)])
+        return out.unsqueeze(0)
+
     # ------------------------------------------------------------------ generate
     def _ban_mask(self, bad_words_ids):
         if not bad_words_ids:
@@ -1580,7 +1697,8 @@ class USDMForCausalLM:
                  temperature=1.0, eos_token_id=None, max_new_tokens=None, min_new_tokens=0, seed=None, ban_mask=None,
                  _logits_hook=None, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
                  logit_bias=None, no_repeat_ngram_size=0, num_beams=None, num_return_sequences=None, length_penalty=1.0,
-                 early_stopping=False, pad_token_id=None, _beam_keep_rows=False, _beam_on_step=None, **unused):
+                 early_stopping=False, pad_token_id=None, _beam_keep_rows=False, _beam_on_step=None, num_speculative_tokens=None,
+                 prompt_lookup_max=3, prompt_lookup_min=1, _spec_script=None, **unused):
         """Generation with the call shape of src/inference.py:63-83.  Greedy when do_sample is False or top_k == 1 (what the
         reference passes: arg-max of the ban-masked logits).  Otherwise temperature / top-k / top-p sampling on the device
         (usdm_sample_final).  `seed` keys its Philox stream; seed=None draws a fresh one from torch's global CPU generator,
@@ -1606,14 +1724,36 @@ class USDMForCausalLM:
         renormalize_logits=True; without bad_words_ids / ban_mask it is plain HF.  Returns [n][Lmax]: the prompt and each hypothesis,
         padded with pad_token_id (default: the first eos id); self.last_beam_scores holds HF's sequences_scores (float32 [n]).
         Not combined with (NotImplementedError): do_sample, logprobs, the penalties, logit_bias / no_repeat_ngram_size, min_p,
-        _logits_hook, min_new_tokens > 0, tensor parallelism.  The single sequence's KV cache and its prefix reuse are not touched."""
+        _logits_hook, min_new_tokens > 0, tensor parallelism.  The single sequence's KV cache and its prefix reuse are not touched.
+        num_speculative_tokens=k in 1 .. 7 (k + 1 <= max_batch(); None / 0: this call is what it is without the argument, no buffers
+        and no plan are built): speculative greedy decoding with n-gram drafts (vLLM's speculative_config method
+        "ngram").  Every step verifies k drafts of the sequence's own continuation in ONE pass over the weights and emits 1 .. k + 1
+        tokens; the drafts follow the most recent earlier occurrence of the last prompt_lookup_max .. prompt_lookup_min tokens of
+        prompt + output, found on the device.  The ids do not depend on the drafts (usdm_attn_verify is position-invariant by
+        construction); against the plain call they are equal up to near-ties of the logits, as generate_batch's are (k + 1 <= 4 rows
+        run the VALU projections, bit-identical per row with the single step; more rows the matrix cores).  self.last_spec_stats =
+        dict(steps=, drafted=, accepted=) counts the speculative steps, the drafts fed (ids, not the -1 of "no draft") and the drafts
+        accepted: tokens emitted by the steps = steps + accepted (the prefill's pick is the call's first token and no step).
+        _spec_script (tests, tools/spec_rate.py): an int sequence / tensor whose entry j replaces the lookup as the draft for output j.
+        Not combined with (NotImplementedError): sampling with top_k != 1, logprobs, the penalties, logit_bias / no_repeat_ngram_size,
+        min_p, _logits_hook, num_beams > 1, tensor parallelism, kv_cache_dtype="fp8".  Cache rows behind the committed position are
+        dead; prefix reuse after the call counts committed rows only."""
+        from .spec import check_spec_args, check_spec_call
+        spec = check_spec_args(num_speculative_tokens, prompt_lookup_max, prompt_lookup_min)
         lpk = check_logprobs(logprobs)
         pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         min_p = check_min_p(min_p)
         edt = check_edits(logit_bias, no_repeat_ngram_size, self.cfg["vocab_size"])
-        self.last_logprobs = self.last_beam_scores = None
+        self.last_logprobs = self.last_beam_scores = self.last_spec_stats = None
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1, as the reference calls it)")
+        if spec is not None:
+            check_spec_call(bool(do_sample) and top_k != 1, lpk, pen, edt, min_p, _logits_hook, num_beams, self.tp_path, self.kv8)
+            if spec[0] + 1 > self.max_batch():
+                raise ValueError(f"num_speculative_tokens={spec[0]}: a decode step of this model takes at most {self.max_batch()} rows")
+            if -(-self.ctx_max // self.spec_split) > 64 or self.spec_split % ops.ATTN_VERIFY_TILE or not 0 < self.spec_split <= ops.ATTN_VERIFY_CMAX:
+                raise ValueError(f"speculative decoding: ctx_max = {self.ctx_max} with {self.spec_split} keys per split (a multiple of "
+                                 f"{ops.ATTN_VERIFY_TILE} up to {ops.ATTN_VERIFY_CMAX}, at most 64 splits) is not supported")
         if num_beams is not None and num_beams != 1:
             from .beam import check_beam_args, check_beam_call
             eos_list = list(dict.fromkeys(int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else
@@ -1683,6 +1823,8 @@ class USDMForCausalLM:
         segs, dev_eos = self._setup_call(input_ids, past, kind.sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,
                                           logprobs=lpk, penalties=pen, edits=edt)
         self._run_segs(segs)  # prefill + first token
+        if spec is not None:
+            return self._generate_spec(input_ids, ids_host, max_new_tokens, spec, _spec_script, dev_eos, stop_ids(eos_token_id), min_new_tokens)
         if kind not in self._decodes:      # a plan / graph of its own per kind (the hooked step has host code inside: never captured)
             self._decodes[kind] = self._graphed(self._build_decode(*kind), enabled=False if kind.sampling == "hook" else None)
         self._decode = self._decodes[kind]

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnVerifyArgs, SpecArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -806,6 +806,39 @@ def attn_decode(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, Hq, Hkv,
         _go(plan, "usdm_attn_decode_fp8", lib.usdm_attn_decode_fp8, C_.byref(f))
         return
     _go(plan, "usdm_attn_decode", lib.usdm_attn_decode, C_.byref(a))
+
+
+SPEC_MAX_T = 8        # rows of a speculative step (usdm_attn_verify, usdm_spec_commit)
+ATTN_VERIFY_TILE = 64  # usdm_attn_verify's key tile: C is a multiple of it, at most ATTN_VERIFY_CMAX
+ATTN_VERIFY_CMAX = 256
+
+
+def attn_verify_splits(ctx_max, C):
+    """splits of usdm_attn_verify's grid and of its partial buffers [T][Hq][splits]"""
+    return -(-ctx_max // C)
+
+
+def attn_verify(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, T, Hq, Hkv, ctx_max, C, scale, window=0, skip=None, qkv_ld=None,
+                out_ld=None, plan=None):
+    """usdm_attn_verify: decode attention for T new tokens of one sequence (qkv [T][qkv_ld], out [T][out_ld], bf16 caches)."""
+    _need_cuda(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, skip)
+    a = AttnVerifyArgs()
+    a.qkv, a.qkv_ld, a.pos = _ptr(qkv), (Hq + 2 * Hkv) * 128 if qkv_ld is None else qkv_ld, _ptr(pos)
+    a.T, a.Hq, a.Hkv, a.ctx_max, a.C, a.window, a.scale = T, Hq, Hkv, ctx_max, C, int(window), scale
+    a.cos, a.sin, a.kcache, a.vcache = _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache)
+    a.pm, a.pl, a.po, a.out, a.out_ld, a.skip = _ptr(pm), _ptr(pl), _ptr(po), _ptr(out), Hq * 128 if out_ld is None else out_ld, _ptr(skip)
+    _go(plan, "usdm_attn_verify", lib.usdm_attn_verify, C_.byref(a))
+
+
+def spec_commit(part_val, part_idx, nparts, st, *, T, drafts, limit, prompt, prompt_len, params, counters, V, script=None, embed, h_out, Hd,
+                propose_only=False, plan=None):
+    """usdm_spec_commit: pick, accept, commit, propose and embed at the end of a speculative step (propose_only: after the prefill)."""
+    _need_cuda(part_val, part_idx, drafts, limit, prompt, prompt_len, params, counters, script, embed, h_out)
+    a = SpecArgs()
+    a.part_val, a.part_idx, a.nparts, a.T = _ptr(part_val), _ptr(part_idx), nparts, T
+    a.drafts, a.limit, a.prompt, a.prompt_len, a.prompt_max = _ptr(drafts), _ptr(limit), _ptr(prompt), _ptr(prompt_len), prompt.numel()
+    a.script, a.params, a.V, a.counters, a.propose_only = _ptr(script), _ptr(params), V, _ptr(counters), int(propose_only)
+    _go(plan, "usdm_spec_commit", lib.usdm_spec_commit, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
 
 
 def residual_add(h, delta, n, plan=None):

@@ -228,7 +228,7 @@ class LLM:
 
     def __init__(self, model, tokenizer=None, download_dir=None, gpu_memory_utilization=0.9, max_model_len=None, device="cuda",
                  dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None,
-                 enable_prefix_caching=False, **unused):
+                 enable_prefix_caching=False, speculative_config=None, **unused):
         # max_num_seqs (vllm's name): sequences decoded per step, 1..16.  <= 4: the VALU batch kernel (per slot bit-identical with the
         # single-request path); above: the matrix-core form (usdm_gemv_batch form 1)
         self.max_slots = max(1, min(int(max_num_seqs), MAX_SLOTS))
@@ -274,6 +274,16 @@ class LLM:
         if self.prefix_caching:
             self.stats.update(prefix_hits=0, prefix_rows_reused=0, prefill_rows=0, prefix_copies=0, prefix_hits_live=0)
             self.admission_log = deque(maxlen=256)
+        # speculative_config (vLLM's name and shape): {"method": "ngram", "num_speculative_tokens": k, "prompt_lookup_max": ..,
+        # "prompt_lookup_min": ..} - a greedy request with a static mask that is served alone runs on the speculative step
+        # (USDMForCausalLM.generate(num_speculative_tokens=k)); everything else runs as without the option
+        from .spec import check_spec_call, check_speculative_config
+        self.spec = check_speculative_config(speculative_config)
+        if self.spec is not None:
+            check_spec_call(tensor_parallel=self.llm.tp_path, kv_cache_fp8=self.llm.kv8)
+            if self.spec[0] + 1 > self.llm.max_batch():
+                raise ValueError(f"num_speculative_tokens={self.spec[0]}: a decode step of this model takes at most {self.llm.max_batch()} rows")
+            self.stats.update(spec_requests=0, spec_steps=0, spec_drafted=0, spec_accepted=0)
         self._next_id = 0
 
     def get_tokenizer(self):
@@ -444,7 +454,16 @@ class LLM:
         sampled = not sp.greedy
         if sampled:
             kw.update(do_sample=True, temperature=sp.temperature, top_p=sp.top_p, top_k=(sp.top_k if sp.top_k > 0 else None), seed=r["seed"])
-        if r["mask"] is not None:
+        spec = (self.spec is not None and r["mask"] is not None and not sampled and sp.logprobs is None and not sp.min_p
+                and sp.penalties is None and sp.edits is None)
+        if spec:        # a plain greedy request served alone: the speculative step
+            k, lmax, lmin = self.spec
+            out = llm.generate(ban_mask=r["mask"], num_speculative_tokens=k, prompt_lookup_max=lmax, prompt_lookup_min=lmin, **kw)
+            st = llm.last_spec_stats
+            self.stats["spec_requests"] += 1
+            for name in ("steps", "drafted", "accepted"):
+                self.stats["spec_" + name] += st[name]
+        elif r["mask"] is not None:
             out = llm.generate(ban_mask=r["mask"], **kw)
         else:       # history-dependent processors: Python between the lm_head launch and the pick of every step
             self.stats["hook_requests"] += 1
