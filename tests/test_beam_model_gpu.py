@@ -55,7 +55,7 @@ def _replay_recorded_rows(m, ids, B, **kw):
     tol = LR.kernel_tolerance() + 0.5 * float(np.spacing(np.float32(64.0)))      # one step: the lp and the f32 sum (|s| < 128)
     for t, st in enumerate(trace):
         assert rp.tokens[t] == st["cand_token"].tolist() and rp.parents[t] == st["cand_parent"].tolist(), t
-    log = m._beams[(B, 1)]["log_score"][:rp.steps].cpu().numpy().astype(np.float64)
+    log = m._beams[(B, 1)].log_score[:rp.steps].cpu().numpy().astype(np.float64)
     for t, st in enumerate(trace):
         fin = np.isfinite(st["cand_score"])
         assert np.abs(log[t][fin] - st["cand_score"][fin]).max() <= tol * (t + 1), (t, np.abs(log[t][fin] - st["cand_score"][fin]).max())
@@ -66,7 +66,7 @@ def _replay_recorded_rows(m, ids, B, **kw):
     for _ in range(2):      # the captured graph, twice: the same ids, the same bits
         out_g = m.generate(**call)
         assert torch.equal(out_g, out_e) and torch.equal(m.last_beam_scores.view(torch.int32), sc_e.view(torch.int32))
-    assert m._beams[(B, 1)]["beam_graph"].graph is not None
+    assert m._beams[(B, 1)].beam_graph.graph is not None
     return out_e, sc_e
 
 
@@ -102,13 +102,13 @@ def test_cache_rows_follow_their_beams(dev, kw):
 
     def on_step(phase, bm):
         if phase == "pick":
-            snap.update({k: bm[k].clone() for k in names})
+            snap.update({k: getattr(bm, k).clone() for k in names})
             return
-        pos, parent = int(bm["pos"][0].item()), bm["parent"].tolist()
+        pos, parent = int(bm.pos[0].item()), bm.parent.tolist()
         for k in names:
             for b in range(B):
-                assert torch.equal(bm[k][b][:, :, :pos], snap[k][parent[b]][:, :, :pos]), (k, b, pos)
-            assert torch.equal(bm[k][:, :, :, pos:], snap[k][:, :, :, pos:])      # rows past pos are not touched
+                assert torch.equal(getattr(bm, k)[b][:, :, :pos], snap[k][parent[b]][:, :, :pos]), (k, b, pos)
+            assert torch.equal(getattr(bm, k)[:, :, :, pos:], snap[k][:, :, :, pos:])      # rows past pos are not touched
         seen.append(parent)
 
     m.generate(input_ids=ids, max_new_tokens=MAX_NEW, num_beams=B, bad_words_ids=BAD, _beam_on_step=on_step)

@@ -151,7 +151,7 @@ def test_neutral_knobs_are_the_plain_call_and_build_nothing(dev):
         assert torch.equal(out, plain) and set(m._decodes) == keys == {step_kind()} and m._edt is None
     assert all(len(k) == 6 and not k[4] and not k[5] for k in m._prefill_plans)
     outs = m.generate_batch([ids, _prompt(dev, 23, 2)], 6, bad_words_ids=BAD, logit_bias=[None, {}], no_repeat_ngram_size=0, min_p=0.0)
-    assert "edt" not in m._batches[2] and torch.equal(outs[0][0, :46], plain[0, :46])
+    assert m._batches[2].edt is None and torch.equal(outs[0][0, :46], plain[0, :46])
     for bad, word in ((dict(min_p=1.5), "min_p"), (dict(min_p=float("nan")), "min_p"), (dict(no_repeat_ngram_size=-1), "no_repeat_ngram_size"),
                       (dict(no_repeat_ngram_size=1.5), "no_repeat_ngram_size"), (dict(logit_bias={1000: 1.0}), "logit_bias"),
                       (dict(logit_bias={-1: 1.0}), "logit_bias"), (dict(logit_bias={5: float("inf")}), "logit_bias"),

@@ -352,22 +352,22 @@ def test_fp8_kv_batched_request_running_into_the_context_limit(dev):
         check_against_oracle(p.tolist() + toks, ref, ref_logits, p.numel())
         assert len(toks) == n and o.outputs[0].finish_reason == "length"
     assert eng.stats["batched_requests"] == 5 and eng.stats["max_active"] == 4
-    bb = m._batch_buffers(4)
-    before = [bb[k].clone() for k in ("kc", "vc", "ke", "ve")]
-    bb["pos"].fill_(128); bb["step"].zero_()
-    bb["steps"][step_kind()].run()
+    ds = m.decode_slots(4)
+    before = [getattr(ds, k).clone() for k in ("kc", "vc", "ke", "ve")]
+    ds.pos.fill_(128); ds.step.zero_()
+    ds.steps[step_kind()].run()
     torch.cuda.synchronize()
     for k, t in zip(("kc", "vc", "ke", "ve"), before):
-        assert torch.equal(t, bb[k]), k
+        assert torch.equal(t, getattr(ds, k)), k
 
 
 def test_fp8_kv_cache_footprint(dev):
     from usdm_amd.llm import USDMForCausalLM
 
     def cache_bytes(m, B):
-        bb = m._batch_buffers(B)
+        ds = m.decode_slots(B)
         ts = [m.kcache, m.vcache, getattr(m, "vtc", None), getattr(m, "kexp", None), getattr(m, "vexp", None)]
-        ts += [bb.get(k) for k in ("kc", "vc", "ke", "ve")]
+        ts += [getattr(ds, k) for k in ("kc", "vc", "ke", "ve")]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
     a = USDMForCausalLM.random_init(SMALL, dev, seed=1, ctx_max=512, kv_cache_dtype="fp8")
     b = USDMForCausalLM.random_init(SMALL, dev, seed=1, ctx_max=512)

@@ -96,7 +96,7 @@ def test_neutral_knobs_are_the_plain_call_and_build_nothing(dev):
     assert torch.equal(out, plain) and set(m._decodes) == keys == {step_kind()} and m._pen is None
     assert not any(k[4] for k in m._prefill_plans)
     outs = m.generate_batch([ids, _prompt(dev, 23, 2)], 6, bad_words_ids=BAD, repetition_penalty=[1.0, 1.0], frequency_penalty=0.0)
-    assert "pen" not in m._batches[2] and torch.equal(outs[0][0, :46], plain[0, :46])
+    assert m._batches[2].pen is None and torch.equal(outs[0][0, :46], plain[0, :46])
     for bad in (dict(repetition_penalty=0.0), dict(repetition_penalty=2.5), dict(presence_penalty=3.0), dict(frequency_penalty=float("nan"))):
         with pytest.raises(ValueError, match="penalty"):
             m.generate(**kw, **bad)
@@ -151,7 +151,7 @@ def test_generate_batch_equals_generate_per_sequence(dev):
         alone = m.generate(input_ids=q, logprobs=K, repetition_penalty=r[b], frequency_penalty=f[b], presence_penalty=p[b], **kw)
         assert torch.equal(o, alone) and _same(lp, m.last_logprobs), b
         toks = o[0, q.shape[1]:].tolist()
-        assert np.array_equal(m._batches[4]["pen"]["table"][b].cpu().numpy(), P.table(1000, q[0].tolist(), toks[:-1])), b
+        assert np.array_equal(m._batches[4].pen["table"][b].cpu().numpy(), P.table(1000, q[0].tolist(), toks[:-1])), b
         differ += not torch.equal(o, m.generate(input_ids=q, **kw))
     assert torch.equal(outs[1], m.generate(input_ids=prompts[1], **kw))      # the neutral one is the plain one
     assert differ >= 1 and not torch.equal(outs[2], m.generate(input_ids=prompts[2], **kw))

@@ -5,7 +5,7 @@ import sys
 
 import pytest
 
-from usdm_amd.prefix import MIN_MATCH, PrefixIndex, common_prefix
+from usdm_amd.prefix import MIN_MATCH, PrefixIndex, common_prefix, reusable_past
 
 
 def _ids(n, base=0):
@@ -22,6 +22,35 @@ def test_common_prefix():
     assert common_prefix([1, 2, 3], [1, 2, 3, 4], 10) == 3
     assert common_prefix([1, 2, 3], [1, 2, 3], 2) == 2
     assert common_prefix([], [1], 5) == 0
+
+
+def test_reusable_past_floor_of_16_tokens():
+    assert reusable_past(_ids(40), _ids(15) + [777] * 30, 39, 45, True) == 0      # 15 common tokens: none
+    assert reusable_past(_ids(40), _ids(16) + [777] * 30, 39, 46, True) == 16     # 16: a match
+    assert reusable_past(_ids(40), _ids(40), 15, 40, False) == 0                  # a cap below the floor: none either
+
+
+def test_reusable_past_caps():
+    L, cached = 50, _ids(80)
+    assert reusable_past(_ids(L), cached, L - 1, 80, True) == 49       # generate(): the last token is always prefilled
+    assert reusable_past(_ids(L), _ids(30), L - 1, 30, True) == 30     # a shorter cached sequence: all of it
+    start = 41                                                        # score(): rows start - 1 .. L - 2 are scored, so at most start - 1 are skipped
+    assert reusable_past(_ids(L), cached, start - 1, 80, True) == 40
+    assert reusable_past(_ids(L), _ids(20) + [999] * 60, start - 1, 80, True) == 20      # the common prefix ends below the cap
+
+
+def test_reusable_past_exact_clamps_to_the_prefill_written_rows():
+    cached = _ids(60)      # 40 rows written by a prefill, 20 appended by decode steps
+    assert reusable_past(_ids(70), cached, 69, 40, True) == 40
+    assert reusable_past(_ids(70), cached, 69, 40, False) == 60
+    assert reusable_past(_ids(70), cached, 69, 10, True) == 0          # the clamp comes before the floor: 10 written rows are none
+    assert reusable_past(_ids(70), cached, 69, 10, False) == 60
+
+
+@pytest.mark.parametrize("cached", [None, [], ()])
+def test_reusable_past_without_a_cache(cached):
+    assert reusable_past(_ids(50), cached, 49, 0, True) == 0
+    assert reusable_past(_ids(50), cached, 49, 50, False) == 0
 
 
 def test_empty_index_matches_nothing():

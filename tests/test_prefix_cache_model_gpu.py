@@ -47,7 +47,7 @@ def test_three_chained_rounds_through_generate_batch(dev, sd, B):
         for b in range(B):
             assert oa[b].tolist() == ob[b].tolist(), (rnd, b)
             assert _same_logprobs(la[b], off.last_logprobs[b]), (rnd, b)
-        pasts = [k[1] for k in on._batches[B]["prefill"]]
+        pasts = [k[1] for k in on._batches[B].prefill]
         if rnd == 0:
             assert not any(pasts) and on.stats["prefix_hits"] == 0 and on.stats["prefill_rows"] == B * 90
         else:
@@ -56,9 +56,9 @@ def test_three_chained_rounds_through_generate_batch(dev, sd, B):
         assert all(p == 0 or p in earlier for p in pasts), (pasts, earlier)
         earlier |= {int(p.shape[1]) for p in prompts}
         prompts = [torch.cat([o, torch.tensor([_rand(g, extra)], dtype=torch.long, device=dev)], 1) for o in oa]
-    assert sorted({k[1] for k in on._batches[B]["prefill"]}) == [0, 90, 110]
+    assert sorted({k[1] for k in on._batches[B].prefill}) == [0, 90, 110]
     assert on.stats["prefix_rows_reused"] == B * (90 + 110) and on.stats["prefix_copies"] == 0      # every sequence found its rows in its own slot
-    assert all(k[1] == 0 for k in off._batches[B]["prefill"]) and "prefix" not in off._batches[B] and not off.stats
+    assert all(k[1] == 0 for k in off._batches[B].prefill) and off._batches[B].prefix is None and not off.stats
 
 
 # ------------------------------------------------------------------------------------------------------------------ serving
@@ -98,7 +98,7 @@ def test_serving_reuses_prefixes_across_slots_and_calls(dev, sd):
     assert st["prefix_hits"] >= 3 and st["prefix_copies"] > 0 and st["prefix_hits_live"] > 0
     # a second call whose prompts extend the first call's prompts: those the four slots hold now, in slot order (the first four
     # admissions go to slots 0 .. 3) - as prompt + what was generated + new tokens, or prompt + new tokens - and a fifth of slot 0's family
-    px = on.llm._batches[4]["prefix"]
+    px = on.llm._batches[4].prefix
     held = [list(e) for e in px.entries]
     assert all(h in prompts for h in held)
     more = [h + ra[prompts.index(h)].outputs[0].token_ids + _rand(g, 4) for h in held[:2]] + [held[2] + _rand(g, 6), held[3] + _rand(g, 11)]
@@ -113,7 +113,7 @@ def test_serving_reuses_prefixes_across_slots_and_calls(dev, sd):
     assert sum(p > 0 for _, p in pred[10:]) == 5, "an extending prompt of the second call found nothing"
     # idle slots: two requests on the four slots, unrelated to everything cached - slots 2 and 3 idle through the whole call, parked
     # behind their recorded rows ...
-    px = on.llm._batches[4]["prefix"]
+    px = on.llm._batches[4].prefix
     kept = [list(px.entries[2]), list(px.entries[3])]
     assert all(len(k) >= 16 for k in kept)
     two = [_rand(g, 45), _rand(g, 38)]
@@ -146,7 +146,7 @@ def test_n_copies_prefill_one_row_each(dev, sd):
     assert len({tuple(c.token_ids) for c in ra[0].outputs}) > 1, "the copies did not draw from their own streams"
     st = on.stats
     assert st["prefill_rows"] == 50 + 1 + 1 and st["prefix_rows_reused"] == 2 * 49 and st["prefix_copies"] == 2 and st["prefix_hits_live"] == 2
-    assert sorted(k[:2] for k in on.llm._batches[4]["prefill"]) == [(1, 49), (1, 49), (50, 0)]
+    assert sorted(k[:2] for k in on.llm._batches[4].prefill) == [(1, 49), (1, 49), (50, 0)]
 
 
 def test_model_object_without_the_flag_is_refused_by_the_engine(dev, sd):
@@ -163,10 +163,9 @@ def _roundtrip_rows(t, lo, hi):
 
 
 def _admit(m, bb_b, b, ids, kind):
-    from usdm_amd import ops
-    bb = m._batch_pick_state(bb_b, kind)
-    ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)      # greedy on the sampling step
-    return m._admit(bb_b, b, torch.tensor(ids, dtype=torch.long), kind), bb
+    ds = m.decode_slots(bb_b)
+    ds.require(kind)
+    return ds.admit(b, torch.tensor(ids, dtype=torch.long), kind), ds      # (sampling=None: greedy on the sampling step)
 
 
 def test_fp8_cache_contract_on_the_batch_slots(dev, sd):
@@ -183,37 +182,37 @@ def test_fp8_cache_contract_on_the_batch_slots(dev, sd):
     assert pa == pb == 0
     # 2. the rows A holds are the round-tripped rows of B
     for c8, ce, cb in (("kc", "ke", "kc"), ("vc", "ve", "vc")):
-        got = dequantize_kv_rows(ba[c8][0, :, :, :90].cpu(), ba[ce][0, :, :, :90].cpu())
-        want = roundtrip_kv_rows(bb[cb][0, :, :, :90].cpu())
+        got = dequantize_kv_rows(getattr(ba, c8)[0, :, :, :90].cpu(), getattr(ba, ce)[0, :, :, :90].cpu())
+        want = roundtrip_kv_rows(getattr(bb, cb)[0, :, :, :90].cpu())
         assert torch.equal(got.view(torch.int16), want.view(torch.int16)) and bool(want.any())
     # 3. B reads its rows as an fp8 cache would return them
     for name in ("kc", "vc"):
-        _roundtrip_rows(bb[name][0], 0, 90)
+        _roundtrip_rows(getattr(bb, name)[0], 0, 90)
     # 4. / 5. the prompt + 12 tokens: both reuse the 90 rows of their own slot; first token, its log-probability and the top 20 are equal
     p2 = p1 + _rand(g, 12)
     (sa, pa), _ = _admit(A, 2, 0, p2, kind)
     (sb, pb), _ = _admit(Bm, 2, 0, p2, kind)
     torch.cuda.synchronize()
     assert (sa, pa) == (sb, pb) == (0, 90)
-    assert any(k[:2] == (12, 90) for k in ba["prefill"]) and any(k[:2] == (12, 90) for k in bb["prefill"])
-    assert int(ba["out"][0, 0]) == int(bb["out"][0, 0])
-    la, lb = read_logprobs(ba["lp"], 1, 20, 0), read_logprobs(bb["lp"], 1, 20, 0)
+    assert any(k[:2] == (12, 90) for k in ba.prefill) and any(k[:2] == (12, 90) for k in bb.prefill)
+    assert int(ba.out[0, 0]) == int(bb.out[0, 0])
+    la, lb = read_logprobs(ba.lp, 1, 20, 0), read_logprobs(bb.lp, 1, 20, 0)
     assert torch.equal(la.token_logprobs, lb.token_logprobs) and torch.equal(la.top_ids, lb.top_ids) and torch.equal(la.top_logprobs, lb.top_logprobs)
     # 6. the rows A appended are the quantized rows B appended; the reused rows are untouched
     for c8, ce, cb in (("kc", "ke", "kc"), ("vc", "ve", "vc")):
-        q, e = quantize_kv_rows(bb[cb][0, :, :, 90:102].cpu())
-        assert torch.equal(ba[c8][0, :, :, 90:102].cpu(), q) and torch.equal(ba[ce][0, :, :, 90:102].cpu(), e)
+        q, e = quantize_kv_rows(getattr(bb, cb)[0, :, :, 90:102].cpu())
+        assert torch.equal(getattr(ba, c8)[0, :, :, 90:102].cpu(), q) and torch.equal(getattr(ba, ce)[0, :, :, 90:102].cpu(), e)
     # ... and once more through the other slot: rows, bytes and exponents copied from slot 0 (usdm_kv_reorder), three rows prefilled
     for name in ("kc", "vc"):
-        _roundtrip_rows(bb[name][0], 90, 102)
+        _roundtrip_rows(getattr(bb, name)[0], 90, 102)
     p3 = p2 + _rand(g, 3)
     (sa, pa), _ = _admit(A, 2, 1, p3, kind)
     (sb, pb), _ = _admit(Bm, 2, 1, p3, kind)
     torch.cuda.synchronize()
     assert (sa, pa) == (sb, pb) == (0, 102)
-    assert torch.equal(ba["kc"][1, :, :, :102], ba["kc"][0, :, :, :102]) and torch.equal(ba["ve"][1, :, :, :102], ba["ve"][0, :, :, :102])
-    assert int(ba["out"][1, 0]) == int(bb["out"][1, 0])
-    la, lb = read_logprobs(ba["lp"], 1, 20, 1), read_logprobs(bb["lp"], 1, 20, 1)
+    assert torch.equal(ba.kc[1, :, :, :102], ba.kc[0, :, :, :102]) and torch.equal(ba.ve[1, :, :, :102], ba.ve[0, :, :, :102])
+    assert int(ba.out[1, 0]) == int(bb.out[1, 0])
+    la, lb = read_logprobs(ba.lp, 1, 20, 1), read_logprobs(bb.lp, 1, 20, 1)
     assert torch.equal(la.token_logprobs, lb.token_logprobs) and torch.equal(la.top_ids, lb.top_ids) and torch.equal(la.top_logprobs, lb.top_logprobs)
 
 
@@ -277,7 +276,7 @@ def test_fp8_cache_without_the_flag_reuses_nothing(dev, sd):
     outs = m.generate_batch(two, 4)
     m.generate_batch([torch.cat([o, o[:, :2]], 1) for o in outs], 4)
     assert all(k[1] == 0 for k in m._prefill_plans) and all(k[1] == 0 for k in m._score_plans)
-    assert all(k[1] == 0 for k in m._batches[2]["prefill"]) and "prefix" not in m._batches[2]
+    assert all(k[1] == 0 for k in m._batches[2].prefill) and m._batches[2].prefix is None
 
 
 # ------------------------------------------------------------------------------------------------------------------ refusals

@@ -189,12 +189,12 @@ def test_batched_request_running_into_the_context_limit(dev):
         assert len(toks) == n and o.outputs[0].finish_reason == "length"
     assert eng.stats["batched_requests"] == 5 and eng.stats["max_active"] == 4
     # the guard inside usdm_attn_decode: a position at / past the end of the cache appends nothing and reads nothing out of range
-    bb = m._batch_buffers(4)
-    before = bb["kc"].clone()
-    bb["pos"].fill_(128); bb["step"].zero_()
-    bb["steps"][step_kind()].run()
+    ds = m.decode_slots(4)
+    before = ds.kc.clone()
+    ds.pos.fill_(128); ds.step.zero_()
+    ds.steps[step_kind()].run()
     torch.cuda.synchronize()
-    assert torch.equal(before, bb["kc"])
+    assert torch.equal(before, ds.kc)
 
 
 def test_history_dependent_processor_and_sampling(dev):

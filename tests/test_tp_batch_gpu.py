@@ -41,7 +41,7 @@ def test_tp_batched_code_path_single_rank_rccl(dev, B):
         a = USDMForCausalLM.from_state_dict(sd, CFG, dev, ctx_max=128).generate_batch(ps, max_new_tokens=14, bad_words_ids=BAD)
         m = USDMForCausalLM.from_state_dict(sd, CFG, dev, ctx_max=128, tp_segments=True, group=dist.group.WORLD)
         b = m.generate_batch(ps, max_new_tokens=14, bad_words_ids=BAD)
-        dec = m._batches[B]["steps"][step_kind()]
+        dec = m._batches[B].steps[step_kind()]
         print(f"B={B}: TP batched step graph captured: {dec.graph is not None} (fallback reason: {dec.failed})")
         for x, y in zip(a, b):
             assert torch.equal(x, y)

@@ -1,7 +1,7 @@
 """What enable_prefix_caching buys and costs on the random-init 7B, ONE process, option on and off alternated:
   batch    16 sequences through three chained generate_batch rounds with bench.py's pipeline_throughput lengths (560-token prompts
            + 32 text tokens, + 6 template tokens + 32 text tokens, + 1 token + `--units` unit tokens), bf16 cache: per round the
-           admission (prefill) time of the 16 prompts - every _admit call between two device synchronisations - the rows prefilled and
+           admission (prefill) time of the 16 prompts - every DecodeSlots.admit call between two device synchronisations - the rows prefilled and
            the usdm_kv_reorder copies (each sequence finds its prefix in its own slot: none are expected)
   single   one fp8-cache sequence through generate()'s three rounds of the same lengths, and score() of 8 candidates of 20 tokens
            behind one 500-token context: the prefill time (the plan's launches between two synchronisations) and the rows prefilled,
@@ -61,7 +61,7 @@ def batch_rounds(m, prompts, units, g, on):
     m.prefix_caching = on
     m.reset_prefix_cache()
     m.stats.clear()
-    watch, out = m._admit, []
+    watch, out = m.decode_slots(len(prompts)).admit, []
     for new, glue in ROUNDS + ((units, 0),):
         copies0 = m.stats.get("prefix_copies", 0)
         rows0 = m.stats.get("prefill_rows", 0)
@@ -128,8 +128,9 @@ def main():
     res = dict(repeats=a.repeats, units=a.units)
     if "batch" in parts:
         m = synth.make_llm(dev, ctx_max=2048, enable_prefix_caching=True)
-        m._admit = Stopwatch(m._admit)
         prompts = [torch.randint(0, 32000, (1, 560), generator=g).to(dev) for _ in range(16)]
+        ds = m.decode_slots(len(prompts))      # the 16 slots generate_batch runs these prompts on
+        ds.admit = Stopwatch(ds.admit)
         for on in (False, True):      # plans, graphs
             batch_rounds(m, prompts, a.units, torch.Generator().manual_seed(4), on)
         runs = {"off": [], "on": []}

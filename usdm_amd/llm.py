@@ -40,7 +40,10 @@ from . import ops
 from ._lib import ACT_SWIGLU
 from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
+from .prefix import reusable_past
 from .quant import Fp8Weight, Mxfp4Weight, check_kv_cache_dtype
+from .slots import (CHUNK, BeamSlots, DecodeSlots, TokenLogprobs, edit_buffers, logprob_buffers, penalty_buffers, read_logprobs,
+                    seed_edits, seed_penalties)
 
 MISTRAL_7B_USDM = dict(vocab_size=42003, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
                        num_attention_heads=32, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-5,
@@ -195,87 +198,6 @@ def step_kind(sampling=None, logprobs=None, penalties=False, edits=False):
     step into the sampling step (run with top_k = 1: the same ids)."""
     sampling = "hook" if sampling == "hook" else bool(sampling)
     return StepKind(sampling or logprobs is not None or bool(penalties) or bool(edits), logprobs, bool(penalties), bool(edits))
-
-
-def penalty_buffers(device, V, B=None):
-    """usdm_penalize's state for one sequence (B=None: plus its tokens-counted word) or B batch slots: the table of V words per
-    sequence (count of generated occurrences, bit 30 = in the prompt) and the device block of the knobs (zero-filled = neutral)."""
-    lead = () if B is None else (B,)
-    bufs = dict(table=torch.zeros(*lead, V, dtype=torch.int32, device=device), dev_params=ops.penalty_params_tensor(device, B or 1).view(*lead, -1))
-    if B is None:
-        bufs["count"] = torch.zeros(1, dtype=torch.int32, device=device)
-    return bufs
-
-
-def seed_penalties(bufs, prompt_ids, knobs):
-    """A new request for this sequence / slot: its knobs, an empty table with every prompt id flagged (prompt ids whose K/V were
-    reused from the cache included), nothing counted yet.  Plain torch calls, outside the captured graphs."""
-    ops.set_penalty_params(bufs["dev_params"], *(knobs or ops.PENALTY_NEUTRAL))
-    tbl = bufs["table"]
-    tbl.zero_()
-    tbl[prompt_ids.to(tbl.device, torch.long)] = ops.PENALTY_PROMPT_BIT
-    if "count" in bufs:
-        bufs["count"].zero_()
-
-
-def edit_buffers(device, ctx_max, B=None):
-    """usdm_logit_edit's state for one sequence (B=None) or B batch slots: the device block of the knobs (zero-filled = neutral), the
-    bias rows of ops.LOGIT_BIAS_MAX entries and the prompt row of ctx_max ids."""
-    lead = () if B is None else (B,)
-    return dict(dev_params=ops.edit_params_tensor(device, B or 1).view(*lead, -1),
-                bias_id=torch.zeros(*lead, ops.LOGIT_BIAS_MAX, dtype=torch.int32, device=device),
-                bias_val=torch.zeros(*lead, ops.LOGIT_BIAS_MAX, dtype=torch.float32, device=device),
-                prompt=torch.zeros(*lead, ctx_max, dtype=torch.int32, device=device))
-
-
-def seed_edits(bufs, prompt_ids, knobs):
-    """A new request for this sequence / slot: its bias list, n-gram size and prompt (ids whose K/V were reused from the cache
-    included); knobs = check_edits()'s (bias, n) or None: a request without, neutral.  Plain torch calls, outside the captured graphs."""
-    bias, n = knobs or ((), 0)
-    P = int(prompt_ids.shape[0]) if n else 0      # (the bias needs no history)
-    if P > bufs["prompt"].shape[-1]:
-        raise ValueError(f"the prompt of {P} ids does not fit the prompt row of {bufs['prompt'].shape[-1]}")
-    if bias:
-        bufs["bias_id"][:len(bias)] = torch.tensor([i for i, _ in bias], dtype=torch.int32)
-        bufs["bias_val"][:len(bias)] = torch.tensor([v for _, v in bias], dtype=torch.float32)
-    if P:
-        bufs["prompt"][:P] = prompt_ids.to(bufs["prompt"].device, torch.int32)
-    ops.set_edit_params(bufs["dev_params"], n, P, len(bias))
-
-
-class TokenLogprobs:
-    """Log-probabilities of one generated sequence of n tokens (host tensors): token_logprobs [n] f32 and ranks [n] i32 of the picked
-    tokens, top_ids [n][K] i32 / top_logprobs [n][K] f32 in descending log-probability (exact ties: lowest id first), cumulative = the
-    float64 sum of token_logprobs.  lp(i) = x_i - logsumexp(x) over the ban-masked logits row the token was picked from: the model's
-    distribution over the allowed ids, before temperature / top-k / top-p (usdm_logprobs)."""
-    __slots__ = ("token_logprobs", "ranks", "top_ids", "top_logprobs", "cumulative")
-
-    def __init__(self, token_logprobs, ranks, top_ids, top_logprobs):
-        self.token_logprobs, self.ranks, self.top_ids, self.top_logprobs = token_logprobs, ranks, top_ids, top_logprobs
-        self.cumulative = float(token_logprobs.double().sum())
-
-    def trimmed(self, n, k):
-        """The first n tokens with the k most likely ids each (a request served inside a group whose step carries a larger K)"""
-        return TokenLogprobs(self.token_logprobs[:n], self.ranks[:n], self.top_ids[:n, :k], self.top_logprobs[:n, :k])
-
-
-def logprob_buffers(device, max_out, B=None):
-    """The four output buffers of usdm_logprobs for one sequence (B=None: plus its rows-written count) or B batch slots, sized for
-    K = 20 so that K never re-allocates; the kernel addresses the top lists as [max_out][K]."""
-    lead = () if B is None else (B,)
-    z = lambda n, dt: torch.zeros(*lead, n, dtype=dt, device=device)
-    bufs = dict(tok_lp=z(max_out, torch.float32), tok_rank=z(max_out, torch.int32), top_id=z(max_out * ops.LOGPROBS_MAX_K, torch.int32),
-                top_lp=z(max_out * ops.LOGPROBS_MAX_K, torch.float32))
-    if B is None:
-        bufs["count"] = torch.zeros(1, dtype=torch.int32, device=device)
-    return bufs
-
-
-def read_logprobs(bufs, n, K, b=None):
-    """Rows 0 .. n-1 of a sequence's log-probability buffers (slot b of a batch's) as a TokenLogprobs on the host."""
-    row = (lambda t: t) if b is None else (lambda t: t[b])
-    top = lambda t: row(t)[:n * K].view(n, K).cpu()
-    return TokenLogprobs(row(bufs["tok_lp"])[:n].cpu(), row(bufs["tok_rank"])[:n].cpu(), top(bufs["top_id"]), top(bufs["top_lp"]))
 
 
 class _Segments:
@@ -451,7 +373,7 @@ class USDMForCausalLM:
         self._decode = None
         self._decodes = {}
         self._batches = {}
-        self._beams = {}          # beam search: the buffers, prefill plans and step of (num_beams, n_eos), built at first use (_beam_buffers)
+        self._beams = {}          # beam search: the slots.BeamSlots (buffers, prefill plans, step) of (num_beams, n_eos), built at first use
         self.last_beam_scores = None   # generate(num_beams > 1): HF's sequences_scores of the returned sequences (float32 tensor [n])
         self.last_beam_rows, self.last_beam_replay = None, None   # ... its recorded logits rows (tests: _beam_keep_rows) and its beam.BeamReplay
         self._ban_cache = LRU(8)
@@ -717,7 +639,7 @@ class USDMForCausalLM:
     def _lm_head_and_pick(self, rec, x, advance_pos, sampling=None, x_delta=None, slot=None, skip=None, batch_gemv=None, logprobs=None,
                           penalties=False, edits=False, beam=None):
         """lm_head GEMV + token choice, for the single sequence (slot=None), a batch slot's prefill, and the batched step
-        (slot = the batch's "all" view, batch_gemv = its projection launcher).  sampling=None: ban-masked arg-max (the reference's
+        (slot = the slots' "all" view, batch_gemv = its projection launcher).  sampling=None: ban-masked arg-max (the reference's
         top_k=1 path); sampling=True: usdm_sample_final over the ban-masked logits, knobs read from the device block sample_params
         (written per request by generate(): plans and graphs do not depend on temperature / top-k / top-p / seed).
         Under tensor parallelism the ranks' arg-max partials, or (sampled) their Vloc ban-masked logits, are gathered first - in the
@@ -732,16 +654,13 @@ class USDMForCausalLM:
         edits (sampled picks only): usdm_logit_edit directly in front of usdm_penalize (HF's and vLLM's order: bias, then penalties) -
         the logit bias and the n-gram ban of the sequence's / the slots' edit state (tensor parallel: on the gathered row, on every
         rank, with global ids).  Everything after it sees the edited row.
-        beam (the buffers of _beam_buffers; one GPU, no hook, no penalties, no edits, no log-probabilities): the pick is the beam
-        search's (_beam_pick) over ALL rows of those buffers - from the batched step (slot = their "all" view) with every row live,
+        beam (a slots.BeamSlots; one GPU, no hook, no penalties, no edits, no log-probabilities): the pick is the beam
+        search's (_beam_pick) over ALL rows of those slots - from the batched step (slot = their "all" view) with every row live,
         from the prompt's prefill into slot 0 (slot = that slot) with row 0 live."""
         c, H = self.cfg, self.cfg["hidden_size"]
-        if logprobs is not None and not sampling:
-            raise ValueError("log-probabilities need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
-        if penalties and not sampling:
-            raise ValueError("penalties need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
-        if edits and not sampling:
-            raise ValueError("logit edits need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
+        for what, asked in (("log-probabilities", logprobs is not None), ("penalties", penalties), ("logit edits", edits)):
+            if asked and not sampling:
+                raise ValueError(f"{what} need the sampling step (the arg-max path has no logits row); greedy runs it with top_k = 1")
         sl = slot or self   # where the picked token, the decode state and the next input row live (self = the single sequence)
         single = sl is self
         B = 0 if single else sl.batch
@@ -924,11 +843,11 @@ class USDMForCausalLM:
         self._layers(rec, gemm, attn, h, qkv, ao, act, "reduce" if self.tp_path else "fused", n=S * H, parts=(part, part))
         return rec, io, h, xn
 
-    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None, penalties=False, edits=False):
+    def _build_prefill(self, S, sampling=None, slot=None, past=0, logprobs=None, penalties=False, edits=False, beam=None):
         """Prefill of S new tokens at positions past .. past+S-1 (_prefill_rows), then the lm_head over the LAST row and the pick of the
-        first generated token."""
+        first generated token (beam: the prompt into slot 0 of those beam slots, logits row 0, the search's first pick)."""
         rec, io, h, _ = self._prefill_rows(S, slot=slot, past=past)
-        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs, penalties=penalties, edits=edits)
+        self._lm_head_and_pick(rec, h[S - 1], False, sampling, slot=slot, logprobs=logprobs, penalties=penalties, edits=edits, beam=beam)
         return rec.finish(), io
 
     def _score_head(self):
@@ -1071,6 +990,18 @@ class USDMForCausalLM:
                 plan.hold(*s.keep)
         return GraphedPlan(plan)
 
+    def _reused_past(self, input_ids, cap):
+        """Prefix reuse of the single sequence: (the prompt's ids as a list, or None with reuse off; past = how many of them, at most
+        cap, are not prefilled again because their K/V are already cached - the same ids at the same positions, prefix.reusable_past)."""
+        if not self.reuse_prefix:
+            return None, 0
+        ids_host = input_ids[0].tolist()
+        past = reusable_past(ids_host, self._kv_ids, cap, self._vt_upto, self.reuse_prefix == "exact")
+        if past > self._vt_upto and self.vtc is not None:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers (fp8 cache: the plan's usdm_kv_expand covers them)
+            a0 = self._vt_upto
+            self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
+        return ids_host, past
+
     @torch.no_grad()
     def score(self, input_ids, top_logprobs=0, start=1):
         """Log-probabilities of tokens that were GIVEN: TokenLogprobs whose row i describes token start + i of input_ids [1, L] given
@@ -1093,20 +1024,7 @@ class USDMForCausalLM:
             raise ValueError(f"score() needs 2 <= L <= ctx_max = {self.ctx_max} tokens, got {L}")
         if isinstance(start, bool) or not isinstance(start, int) or not 1 <= start <= L - 1:
             raise ValueError(f"start must be an integer 1 .. L - 1 = {L - 1}, got {start!r}")
-        past, ids_host = 0, None
-        if self.reuse_prefix:
-            ids_host = input_ids[0].tolist()
-            if self._kv_ids is not None:
-                n = min(start - 1, len(self._kv_ids))
-                while past < n and ids_host[past] == self._kv_ids[past]:
-                    past += 1
-                if self.reuse_prefix == "exact":
-                    past = min(past, self._vt_upto)      # rows beyond that were appended by decode steps
-                if past < 16:
-                    past = 0
-            if past > self._vt_upto and self.vtc is not None:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers (fp8 cache: the plan's usdm_kv_expand covers them)
-                a0 = self._vt_upto
-                self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
+        ids_host, past = self._reused_past(input_ids, start - 1)
         S, j0 = L - past, start - 1 - past
         key = (S, past, j0, K)
         hit = self._score_plans.get(key)
@@ -1123,98 +1041,42 @@ class USDMForCausalLM:
         top = lambda t: t[:S * K].view(S, K)[j0 + 1:].cpu()
         return TokenLogprobs(o["tok_lp"][j0 + 1:S].cpu(), o["tok_rank"][j0 + 1:S].cpu(), top(o["top_id"]), top(o["top_lp"]))
 
-    # ------------------------------------------------------------------ batched decode
-    class _Slot:
-        """Views of the batch buffers that stand in for the single-sequence attributes during a per-item prefill (batch = 0), or, as
-        the batch's "all" view, during the lm_head + pick of the batched step (batch = B).  No device-side end of sequence."""
-        batch, st_done, st_eos = 0, None, None
-
-    def _batch_buffers(self, B):
+    # ------------------------------------------------------------------ batched decode (the slots: usdm_amd/slots.py)
+    def decode_slots(self, B):
+        """The B slots that decode in lockstep (slots.DecodeSlots), built at first use and kept."""
         if B not in self._batches:
-            self._batches[B] = self._new_batch_buffers(B)
+            self._batches[B] = DecodeSlots(self, B)
         return self._batches[B]
 
-    def _new_batch_buffers(self, B):
-        """The buffers of B slots in lockstep (caches, decode state, logits rows) and their per-slot / whole-batch views; the caller
-        keeps them (generate_batch: self._batches[B]; beam search: its own, self._beams)."""
-        c, dev, bf = self.cfg, self.device, torch.bfloat16
-        L, d, H = c["num_hidden_layers"], c["head_dim"], c["hidden_size"]
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
-        cdt = torch.uint8 if self.kv8 else bf
-        bb = dict(kc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=cdt, device=dev),
-                  vc=torch.zeros(B, L, self.Hkv, self.ctx_max, d, dtype=cdt, device=dev),
-                  nxt=i32(B), step=i32(B), pos=i32(B), out=i32(B, self.max_out), h=torch.zeros(B, H, dtype=bf, device=dev),
-                  pv=torch.zeros(B, self.nparts, dtype=torch.float32, device=dev), pi=i32(B, self.nparts), prefill=LRU(16), steps={},
-                  logits=torch.zeros(B, self.Vloc, dtype=torch.float32, device=dev),
-                  sp=ops.sample_params_tensor(dev, B).view(B, -1))
-        if self.tp_path:
-            # tensor parallel: pv / pi hold THIS rank's partials; the decode step gathers them rank-major into pvg / pig
-            # [rank][sequence][nparts] (usdm_argmax_final_seg), a slot's prefill into its own row of pvs / pis [sequence][rank * nparts]
-            tp = self.tp_size
-            bb.update(pvg=torch.zeros(tp, B, self.nparts, dtype=torch.float32, device=dev), pig=i32(tp, B, self.nparts),
-                      pvs=torch.zeros(B, tp * self.nparts, dtype=torch.float32, device=dev), pis=i32(B, tp * self.nparts))
-            # sampled: the ranks' [B][Vloc] logits gathered rank-major into lg [rank][sequence][Vloc] (usdm_sample_final_seg); a
-            # slot's sampled prefill gathers its row into lrow [tp * Vloc] (prefills run one at a time)
-            bb.update(lg=torch.zeros(tp, B, self.Vloc, dtype=torch.float32, device=dev),
-                      lrow=torch.zeros(tp * self.Vloc, dtype=torch.float32, device=dev))
-        if self.kv8:
-            bb.update(ke=torch.zeros(B, L, self.Hkv, self.ctx_max, dtype=torch.int8, device=dev),
-                      ve=torch.zeros(B, L, self.Hkv, self.ctx_max, dtype=torch.int8, device=dev))
-        slots = []
-        for b in range(B):
-            sl = self._Slot()
-            sl.kcache, sl.vcache = bb["kc"][b], bb["vc"][b]
-            if self.kv8:
-                sl.kexp, sl.vexp = bb["ke"][b], bb["ve"][b]
-            sl.st_next, sl.st_step, sl.st_pos, sl.st_out = bb["nxt"][b:b + 1], bb["step"][b:b + 1], bb["pos"][b:b + 1], bb["out"][b]
-            sl.h_dec = bb["h"][b]
-            sl.part_val = sl.part_val_loc = bb["pv"][b]
-            sl.part_idx = sl.part_idx_loc = bb["pi"][b]
-            if self.tp_path:
-                sl.part_val, sl.part_idx = bb["pvs"][b], bb["pis"][b]
-            sl.logits, sl.sample_params = bb["logits"][b], bb["sp"][b]
-            sl.logits_row = bb.get("lrow")
-            slots.append(sl)
-        bb["slots"] = slots
-        al = bb["all"] = self._Slot()      # the whole batch, for the batched step's lm_head + pick
-        al.batch, al.st_next, al.st_step, al.st_pos, al.st_out, al.h_dec = B, bb["nxt"], bb["step"], bb["pos"], bb["out"], bb["h"]
-        al.part_val_loc, al.part_idx_loc = bb["pv"], bb["pi"]
-        al.part_val, al.part_idx = (bb["pvg"], bb["pig"]) if self.tp_path else (bb["pv"], bb["pi"])
-        al.logits, al.sample_params, al.logits_row = bb["logits"], bb["sp"], bb.get("lg")
-        return bb
+    def _batch_gemv(self, n, rec):
+        """(gemv, ks) of a step over n rows (B sequences; the T rows of a speculative step) into the open plan rec.  gemv: the projection
+        launcher, usdm_gemv's keywords over the n rows: x [n][K], outputs [n][N] (SwiGLU: half of that), residual [n][N].  ks: down_proj
+        on the matrix cores (K = 14336, n > 4): K split over workgroups, each holding its activation slice (usdm_gemv_batch ks_*); one
+        scratch for all layers - the launches of a step are serial and each leaves the counters zero.  fp8_matrix_cores: the FP8
+        projections of 5..16 rows on the matrix cores (usdm_gemv_fp8_mfma: the bf16 form's tiles, K split and epilogues, so the same ks
+        scratch); <= 4 keep the VALU FP8 form of gemv_batch."""
+        H, Z = self.cfg["hidden_size"], lambda n, dt: rec.plan.hold(torch.zeros(n, device=self.device, dtype=dt))
+        ksf = ops.gemv_batch_ks_floats(H, self.I) if n > 4 else 0
+        ks = (Z(ksf, torch.float32), Z(-(-H // 16), torch.int32)) if ksf else None
+        gemv_b = ops.gemv_fp8_mfma if (self.fp8_matrix_cores and n > 4) else ops.gemv_batch
 
-    def _batch_pick_state(self, B, kind):
-        """The B slots' buffers with what a step of this kind needs beyond the sampler's state (allocated at first use): bb["lp"], the
-        slots' log-probability buffers next to bb["out"], bb["pen"], their penalty state, and bb["edt"], their logit-edit state; every
-        slot views its own row as sl.lp / sl.pen / sl.edt.
-        No rows-written / tokens-counted word: batch slots have no device-side `done` word, every step writes its row and
-        counts the token of the step before, and the host ignores rows past a request's end."""
-        bb, new = self._batch_buffers(B), {}
-        if kind.logprobs is not None and "lp" not in bb:
-            new["lp"] = logprob_buffers(self.device, self.max_out, B)
-        if kind.penalties and "pen" not in bb:
-            new["pen"] = penalty_buffers(self.device, self.cfg["vocab_size"], B)
-        if kind.edits and "edt" not in bb:
-            new["edt"] = edit_buffers(self.device, self.ctx_max, B)
-        for name, bufs in new.items():
-            bb[name] = bufs
-            setattr(bb["all"], name, bufs)
-            for b, sl in enumerate(bb["slots"]):
-                setattr(sl, name, {k: v[b] for k, v in bufs.items()})
-        return bb
+        def gemv(W, x, *, N, K, act=0, residual=None, y_bs=None, **kw):
+            gemv_b(W, x, nb=n, N=N, K=K, x_bs=K, y_bs=(N // 2 if act else N) if y_bs is None else y_bs, res_bs=N if residual is not None else 0,
+                   act=act, residual=residual, plan=rec.plan, **kw)
+        return gemv, ks
 
     def _build_decode_batch(self, B, sampling=False, logprobs=None, penalties=False, edits=False, beam=None):
-        """One decode step of B sequences: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
-        sampling: the pick is usdm_sample_final's batched form - every slot draws with its OWN knobs (bb["sp"][b]: temperature,
-        top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1.
-        beam (the buffers of _beam_buffers): the step of a beam search over those buffers instead - the pick is usdm_beam_step over
+        """One decode step of the B decode slots: weights streamed once (usdm_gemv_batch), attention / token pick batched over items.
+        sampling: the pick is usdm_sample_final's batched form - every slot draws with its OWN knobs (row b of the slots' sp:
+        temperature, top-k, top-p, seed) and its own Philox counter; a greedy slot carries top_k = 1.
+        beam (a slots.BeamSlots): the step of a beam search over those slots instead - the pick is usdm_beam_step over
         the B rows, followed by usdm_kv_reorder; returned as its two segments (the pick's end is where an eager run can look)."""
         dev, bf = self.device, torch.bfloat16
         H, d, L, Hq, Hkv, I, nq = self._dims()
-        bb = self._batch_buffers(B) if beam is None else beam
+        ds = self.decode_slots(B) if beam is None else beam
         rec = _Segments()
         Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
-        h, qkv, ao, act = bb["h"], Z(B, nq), Z(B, Hq * d), Z(B, I)
+        h, qkv, ao, act = ds.h, Z(B, nq), Z(B, Hq * d), Z(B, I)
         NS = max(2, self.NS)
         if B > 4:
             # many sequences: B x Hkv x NS workgroups of ctx / NS keys each.  The batch-1 choice (32 splits of ~20 keys: latency-bound,
@@ -1224,10 +1086,7 @@ class USDMForCausalLM:
         pm, pl, po = Z(B * Hq * NS, dt=torch.float32), Z(B * Hq * NS, dt=torch.float32), Z(B * Hq * NS * d, dt=torch.float32)
         cnt = Z(B * Hkv, dt=torch.int32) if B > 4 and self.batch_fused_merge else None
         cache_bs = L * Hkv * self.ctx_max * d
-        # down_proj on the matrix cores (K = 14336): K split over workgroups, each holding its activation slice (usdm_gemv_batch ks_*);
-        # one scratch for all layers - the launches of a step are serial and each leaves the counters zero
-        ksf = ops.gemv_batch_ks_floats(H, I) if B > 4 else 0
-        ks = (Z(ksf, dt=torch.float32), Z(-(-H // 16), dt=torch.int32)) if ksf else None
+        gemv, ks = self._batch_gemv(B, rec)
         # Tensor parallel (SURVEY.md 8e x 8f-2; round 4, the collective form): the row-parallel projections leave f32 partial sums
         # [B][H], all-reduced through the job's process group (RCCL: one collective of B x 16 KB per projection instead of B of them),
         # then usdm_residual_add applies HF's rounding points; the plan is cut into segments at the collectives, as the
@@ -1235,22 +1094,14 @@ class USDMForCausalLM:
         # rank (usdm_sample_final_seg).
         tp = self.tp_path
         parts = (Z(B, H, dt=torch.float32), Z(B, H, dt=torch.float32)) if tp else None
-        # fp8_matrix_cores: the FP8 projections of 5..16 sequences on the matrix cores (usdm_gemv_fp8_mfma: the bf16 form's tiles, K
-        # split and epilogues, so the same ks scratch); <= 4 keep the VALU FP8 form of gemv_batch
-        gemv_b = ops.gemv_fp8_mfma if (self.fp8_matrix_cores and B > 4) else ops.gemv_batch
-
-        def gemv(W, x, *, N, K, act=0, residual=None, y_bs=None, **kw):
-            """usdm_gemv's keywords over the B rows: x [B][K], outputs [B][N] (SwiGLU: half of that), residual [B][N]"""
-            gemv_b(W, x, nb=B, N=N, K=K, x_bs=K, y_bs=(N // 2 if act else N) if y_bs is None else y_bs, res_bs=N if residual is not None else 0,
-                   act=act, residual=residual, plan=rec.plan, **kw)
 
         def attn(l):
-            ops.attn_decode(qkv, bb["pos"], self.cos, self.sin, bb["kc"][0, l], bb["vc"][0, l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
+            ops.attn_decode(qkv, ds.pos, self.cos, self.sin, ds.kc[0, l], ds.vc[0, l], pm, pl, po, ao, Hq=Hq, Hkv=Hkv,
                             ctx_max=self.ctx_max, NS=NS, scale=d ** -0.5, batch=B, qkv_bs=nq, out_bs=Hq * d, cache_bs=cache_bs, window=self.window,
-                            counters=cnt, kv8=(bb["ke"][0, l], bb["ve"][0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=rec.plan)
+                            counters=cnt, kv8=(ds.ke[0, l], ds.ve[0, l]) if self.kv8 else None, exp_bs=cache_bs // d, plan=rec.plan)
 
         self._layers(rec, gemv, attn, h, qkv, ao, act, "reduce" if tp else "fused", n=B * H, parts=parts, down_kw={} if tp else dict(ks=ks))
-        self._lm_head_and_pick(rec, h, True, sampling, slot=bb["all"], batch_gemv=gemv, logprobs=logprobs, penalties=penalties, edits=edits,
+        self._lm_head_and_pick(rec, h, True, sampling, slot=ds.all, batch_gemv=gemv, logprobs=logprobs, penalties=penalties, edits=edits,
                                beam=beam)
         segs = rec.finish()
         return segs if (tp or beam is not None) else segs[0]
@@ -1295,13 +1146,7 @@ class USDMForCausalLM:
         h, qkv, ao, act = r["h"], Z(T, nq), Z(T, Hq * d), Z(T, I)
         nsp = ops.attn_verify_splits(self.ctx_max, self.spec_split)
         pm, pl, po = Z(T * Hq * nsp, dt=torch.float32), Z(T * Hq * nsp, dt=torch.float32), Z(T * Hq * nsp * d, dt=torch.float32)
-        ksf = ops.gemv_batch_ks_floats(H, I) if T > 4 else 0
-        ks = (Z(ksf, dt=torch.float32), Z(-(-H // 16), dt=torch.int32)) if ksf else None
-        gemv_b = ops.gemv_fp8_mfma if (self.fp8_matrix_cores and T > 4) else ops.gemv_batch
-
-        def gemv(W, x, *, N, K, act=0, residual=None, y_bs=None, **kw):
-            gemv_b(W, x, nb=T, N=N, K=K, x_bs=K, y_bs=(N // 2 if act else N) if y_bs is None else y_bs, res_bs=N if residual is not None else 0,
-                   act=act, residual=residual, plan=rec.plan, **kw)
+        gemv, ks = self._batch_gemv(T, rec)
 
         def attn(l):
             ops.attn_verify(qkv, self.st_pos, self.cos, self.sin, self.kcache[l], self.vcache[l], pm, pl, po, ao, T=T, Hq=Hq, Hkv=Hkv,
@@ -1372,7 +1217,7 @@ class USDMForCausalLM:
         with usdm_logit_edit).  min_p is accepted and range-checked for symmetry with generate(): these picks are greedy (top_k = 1),
         where it changes nothing.
         On a model built with enable_prefix_caching=True every prompt reuses the rows of the longest prefix (>= 16 tokens) that a slot
-        of the group's buffers holds from an earlier prefill, and prefills the rest (_reuse_rows; self.stats counts prefix_hits,
+        of the group's buffers holds from an earlier prefill, and prefills the rest (DecodeSlots.admit; self.stats counts prefix_hits,
         prefix_rows_reused, prefix_copies, prefill_rows); bf16 cache: the same ids and log-probabilities, bit for bit."""
         lpk = check_logprobs(logprobs)
         n = len(input_ids_list)
@@ -1388,74 +1233,10 @@ class USDMForCausalLM:
                                          pens[g0:g0 + group], edits[g0:g0 + group])
         return outs
 
-    def _batch_step(self, B, kind):
-        """The replayable decode step of the B slots (built at first use), a plan / graph of its own per kind: greedy, sampled, the
-        sampled step followed by usdm_logprobs (per K), and each of the latter two with usdm_logit_edit and / or usdm_penalize in front
-        of the pick."""
-        bb = self._batch_pick_state(B, kind)
-        if kind not in bb["steps"]:
-            bb["steps"][kind] = self._graphed(self._build_decode_batch(B, *kind))
-        return bb["steps"][kind]
-
-    def _admit(self, B, b, ids, kind, knobs=None, edits=None):
-        """Admit a prompt (ids [L]) into slot b of the B slots, whose batch runs on the step `kind`: its step / position counters,
-        then the per-item prefill into the slot's cache, which also picks the first token as that step would (sampled; with row 0 of
-        the slot's log-probabilities).  On the penalised step the slot's table is reset and seeded from the prompt, with the request's
-        knobs (repetition, frequency, presence; None: a request without, neutral); on the step with logit edits the slot's edit state
-        is written from the prompt and the request's check_edits() value (None: neutral).
-        Returns (source slot, past): the rows [0, past) that were reused instead of prefilled and the slot they came from
-        (enable_prefix_caching, _reuse_rows); (None, 0) without the option or without a match."""
-        bb, L = self._batch_pick_state(B, kind), int(ids.shape[0])
-        bb["step"][b] = 0
-        bb["pos"][b] = L
-        if kind.penalties:
-            seed_penalties(bb["slots"][b].pen, ids, knobs)
-        if kind.edits:
-            seed_edits(bb["slots"][b].edt, ids, edits)
-        src, past = self._reuse_rows(bb, B, b, ids) if self.prefix_caching else (None, 0)
-        S = L - past
-        segs, io = bb["prefill"].get_or_build((S, past, b, *kind), lambda: self._build_prefill(S, kind.sampling or None, slot=bb["slots"][b], past=past,
-                                                                                               logprobs=kind.logprobs, penalties=kind.penalties,
-                                                                                               edits=kind.edits))
-        io["ids"].copy_(ids[past:])
-        self._run_segs(segs)
-        return src, past
-
-    def _prefix_index(self, bb, B):
-        """The slots' prefix index (usdm_amd/prefix.py) and the three device words of its usdm_kv_reorder copies, built at first use."""
-        if "prefix" not in bb:
-            from .prefix import PrefixIndex
-            from .serving import CHUNK
-            i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=self.device)
-            bb.update(prefix=PrefixIndex(B, self.ctx_max, CHUNK), px_parent=i32(B), px_lo=i32(1), px_pos=i32(1))
-        return bb["prefix"]
-
-    def _reuse_rows(self, bb, B, b, ids):
-        """enable_prefix_caching: the rows of the B slots that the prompt `ids`, about to be prefilled into slot b, can reuse ->
-        (source slot or None, past).  Rows [0, past) of another slot are copied into slot b (usdm_kv_reorder with parent[b] = source and
-        the identity elsewhere, lo = 0, pos = past: K, V and the fp8 cache's exponents in one launch); slot b's entry becomes the
-        prompt.  Counted in self.stats: prefix_hits, prefix_rows_reused, prefix_copies, prefill_rows."""
-        px, prompt = self._prefix_index(bb, B), ids.tolist()
-        src, past = px.match(prompt, b)
-        if src is not None and src != b:
-            parent = list(range(B))
-            parent[b] = src
-            bb["px_parent"].copy_(torch.tensor(parent, dtype=torch.int32))
-            bb["px_pos"].fill_(past)
-            arrays = [bb["kc"], bb["vc"]] + ([bb["ke"], bb["ve"]] if self.kv8 else [])
-            ops.kv_reorder(arrays, bb["px_parent"], bb["px_lo"], bb["px_pos"], B=B, nblk=self.cfg["num_hidden_layers"] * self.Hkv, ctx_max=self.ctx_max)
-        px.admit(b, prompt)
-        st = self.stats
-        for k, v in (("prefix_hits", int(past > 0)), ("prefix_rows_reused", past), ("prefix_copies", int(src is not None and src != b)),
-                     ("prefill_rows", len(prompt) - past)):
-            st[k] = st.get(k, 0) + v
-        return src, past
-
     def reset_prefix_cache(self):
         """vLLM's name: forget every reusable row, of the batch slots and of the single sequence (nothing on the device changes)."""
-        for bb in self._batches.values():
-            if "prefix" in bb:
-                bb["prefix"].reset()
+        for ds in self._batches.values():
+            ds.reset_prefix()
         self._kv_ids, self._vt_upto = None, 0
 
     def _generate_group(self, ids_list, max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, logprobs=None, pens=None, edits=None):
@@ -1466,30 +1247,27 @@ class USDMForCausalLM:
         for ids in ids_list:
             if ids.dim() != 2 or ids.shape[0] != 1:
                 raise ValueError("every prompt must be a LongTensor of shape [1, L]")
-        bb = self._batch_buffers(B)
-        self.ban.copy_(self._ban_mask(bad_words_ids))
+        ds = self.decode_slots(B)
+        self.load_ban(bad_words_ids)
         L0 = [int(ids.shape[1]) for ids in ids_list]
         max_new = min(max_new_tokens, self.ctx_max - max(L0), self.max_out)
         if max_new <= 0:
             if logprobs is not None:
                 self.last_logprobs += [None] * B
             return [ids.clone() for ids in ids_list]
-        for b, ids in enumerate(ids_list):
-            if kind.sampling:      # greedy on the sampling step: top_k = 1
-                ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
-            self._admit(B, b, ids[0], kind, knobs=pens[b] if kind.penalties else None, edits=edits[b] if kind.edits else None)
-        decode = self._batch_step(B, kind)
+        for b, ids in enumerate(ids_list):      # (greedy knobs: on the sampling step these picks run with top_k = 1)
+            ds.admit(b, ids[0], kind, knobs=pens[b] if kind.penalties else None, edits=edits[b] if kind.edits else None)
+        decode = ds.step_plan(kind)
         eos = stop_ids(eos_token_id)
-        produced, chunk = 1, 8
-        ends = [None] * B
+        produced, ends = 1, [None] * B
         while True:
-            toks = bb["out"][:, :produced].tolist()     # host sync point (EOS check)
+            toks = ds.tokens(produced)     # host sync point (EOS check)
             for b in range(B):
                 if ends[b] is None:
                     ends[b] = stop_index(toks[b], eos, min_new_tokens)
             if all(e is not None for e in ends) or produced >= max_new:
                 break
-            n = min(chunk, max_new - produced)
+            n = min(CHUNK, max_new - produced)
             for _ in range(n):
                 decode.run()
             produced += n
@@ -1498,39 +1276,22 @@ class USDMForCausalLM:
             n = ends[b] if ends[b] is not None else min(produced, max_new)
             res.append(torch.cat([ids[0], torch.tensor(toks[b][:n], dtype=torch.long, device=ids.device)]).unsqueeze(0))
             if logprobs is not None:
-                self.last_logprobs.append(read_logprobs(bb["lp"], n, logprobs, b))
+                self.last_logprobs.append(ds.logprobs(b, n, logprobs))
         return res
 
     # ------------------------------------------------------------------ beam search
-    def _beam_buffers(self, B, n_eos):
-        """The state of a search with B beams and n_eos EOS ids, in a cache of its own (generate_batch's slots and plans are not
-        touched): the B slots of _new_batch_buffers plus the running scores, the parents, the EOS ids, `lo` (first cache row the
-        reorder moves), usdm_beam_step's scratch and its step log [max_out][KC]; per prompt length one prefill plan, and the step."""
-        key = (B, n_eos)
-        if key not in self._beams:
-            dev, KC = self.device, ops.beam_candidates(B, n_eos)
-            bm = self._new_batch_buffers(B)
-            i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
-            f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-            bm.update(n_eos=n_eos, KC=KC, score=f32(B), parent=i32(B), eos=i32(ops.BEAM_MAX_EOS), lo=i32(1), cand_score=f32(B, KC),
-                      cand_index=i32(B, KC), log_score=f32(self.max_out, KC), log_token=i32(self.max_out, KC),
-                      log_parent=i32(self.max_out, KC), beam_graph=None, beam_eager=None)
-            self._beams[key] = bm
-        return self._beams[key]
-
     def _beam_pick(self, rec, bm, nlive, advance_pos):
-        """usdm_beam_step over the rows of the beam buffers, a segment boundary, usdm_kv_reorder of every cache array by the parents
+        """usdm_beam_step over the rows of the beam slots bm (slots.BeamSlots), a segment boundary, usdm_kv_reorder of every cache array by the parents
         the pick just wrote.  (The boundary costs nothing: a captured step joins its segments into one hipGraph.)"""
         H, d, L, Hq, Hkv, I, nq = self._dims()
-        al = bm["all"]
+        al = bm.all
         st = ops.decode_state(al.st_next, al.st_out, al.st_step, al.st_pos, advance_pos=advance_pos, batch=al.batch)
-        ops.beam_step(bm["logits"], st, V=self.v1 - self.v0, score=bm["score"], parent=bm["parent"], nlive=nlive, eos=bm["eos"],
-                      n_eos=bm["n_eos"], log_score=bm["log_score"], log_token=bm["log_token"], log_parent=bm["log_parent"],
-                      cand_score=bm["cand_score"], cand_index=bm["cand_index"], embed=self.W["embed"], h_out=bm["h"], Hd=H, plan=rec.plan)
+        ops.beam_step(bm.logits, st, V=self.v1 - self.v0, score=bm.score, parent=bm.parent, nlive=nlive, eos=bm.eos,
+                      n_eos=bm.n_eos, log_score=bm.log_score, log_token=bm.log_token, log_parent=bm.log_parent,
+                      cand_score=bm.cand_score, cand_index=bm.cand_index, embed=self.W["embed"], h_out=bm.h, Hd=H, plan=rec.plan)
         rec.plan.hold(st)
         rec.cut()
-        arrays = [bm["kc"], bm["vc"]] + ([bm["ke"], bm["ve"]] if self.kv8 else [])
-        ops.kv_reorder(arrays, bm["parent"], bm["lo"], bm["pos"], B=al.batch, nblk=L * Hkv, ctx_max=self.ctx_max, plan=rec.plan)
+        ops.kv_reorder(bm.cache_arrays(), bm.parent, bm.lo, bm.pos, B=al.batch, nblk=L * Hkv, ctx_max=self.ctx_max, plan=rec.plan)
 
     def _generate_beam(self, input_ids, max_new_tokens, B, n, length_penalty, early_stopping, eos_list, pad_token_id, bad_words_ids,
                        ban_mask, keep_rows=False, on_step=None):
@@ -1543,18 +1304,18 @@ class USDMForCausalLM:
         [B][V] logits rows to self.last_beam_rows; call on_step(phase, bm) with phase "pick" between the pick and the reorder and "step"
         after it.  self.last_beam_replay keeps the BeamReplay (the step log's tokens and parents as the host saw them)."""
         from .beam import BeamReplay
-        bm = self._beam_buffers(B, len(eos_list))
+        key = (B, len(eos_list))
+        if key not in self._beams:
+            self._beams[key] = BeamSlots(self, *key)
+        bm = self._beams[key]
         L0, V = int(input_ids.shape[1]), self.v1 - self.v0
-        if ban_mask is not None:
-            self.ban.copy_(ban_mask.to(torch.uint8)[self.v0:self.v1])
-        else:
-            self.ban.copy_(self._ban_mask(bad_words_ids))
-        bm["eos"].copy_(torch.tensor((eos_list + [0] * ops.BEAM_MAX_EOS)[:ops.BEAM_MAX_EOS], dtype=torch.int32))
-        bm["pos"].fill_(L0)
-        bm["step"].zero_()
-        bm["score"].zero_()
-        bm["lo"].zero_()
-        segs, io = bm["prefill"].get_or_build(L0, lambda: self._build_beam_prefill(L0, bm))
+        self.load_ban(bad_words_ids, ban_mask)
+        bm.eos.copy_(torch.tensor((eos_list + [0] * ops.BEAM_MAX_EOS)[:ops.BEAM_MAX_EOS], dtype=torch.int32))
+        bm.pos.fill_(L0)
+        bm.step.zero_()
+        bm.score.zero_()
+        bm.lo.zero_()
+        segs, io = bm.prefill.get_or_build(L0, lambda: self._build_prefill(L0, True, slot=bm.slots[0], beam=bm))
         io["ids"].copy_(input_ids[0])
         rows = [] if keep_rows else None
         hooked = keep_rows or on_step is not None
@@ -1565,7 +1326,7 @@ class USDMForCausalLM:
             *head, last = step_segs
             self._run_segs(head)
             if rows is not None:
-                rows.append(bm["logits"][:, :V].cpu().numpy().copy())
+                rows.append(bm.logits[:, :V].cpu().numpy().copy())
             if on_step is not None:
                 on_step("pick", bm)
             last.run()
@@ -1573,19 +1334,16 @@ class USDMForCausalLM:
                 on_step("step", bm)
 
         run(segs)      # prefill + first pick + the prompt's rows to every slot
-        bm["lo"].fill_(L0)
-        if hooked:
-            if bm["beam_eager"] is None:
-                bm["beam_eager"] = self._build_decode_batch(B, True, beam=bm)
-            step = bm["beam_eager"]
-        else:
-            if bm["beam_graph"] is None:
-                bm["beam_graph"] = self._graphed(self._build_decode_batch(B, True, beam=bm))
-            step = bm["beam_graph"]
+        bm.lo.fill_(L0)
+        if hooked and bm.beam_eager is None:
+            bm.beam_eager = self._build_decode_batch(B, True, beam=bm)
+        if not hooked and bm.beam_graph is None:
+            bm.beam_graph = self._graphed(self._build_decode_batch(B, True, beam=bm))
+        step = bm.beam_eager if hooked else bm.beam_graph
         rp = BeamReplay(B, eos_list, max_new_tokens, length_penalty, early_stopping)
-        produced, fed, chunk = 1, 0, 8
+        produced, fed = 1, 0
         while True:
-            log = [bm[k][fed:produced].cpu().numpy() for k in ("log_score", "log_token", "log_parent")]      # host sync point
+            log = [t[fed:produced].cpu().numpy() for t in (bm.log_score, bm.log_token, bm.log_parent)]      # host sync point
             over = False
             for r in range(produced - fed):
                 over = rp.feed(log[0][r], log[1][r], log[2][r])
@@ -1594,7 +1352,7 @@ class USDMForCausalLM:
             fed = produced
             if over or produced >= max_new_tokens:
                 break
-            for _ in range(min(chunk, max_new_tokens - produced)):
+            for _ in range(min(CHUNK, max_new_tokens - produced)):
                 run(step)
                 produced += 1
         seqs, scores = rp.results(n, pad_token_id)
@@ -1603,12 +1361,6 @@ class USDMForCausalLM:
         self.last_beam_replay = rp
         gen = torch.tensor(seqs, dtype=torch.long, device=input_ids.device).view(n, -1)
         return torch.cat([input_ids[0].expand(n, -1), gen], 1)
-
-    def _build_beam_prefill(self, L, bm):
-        """The prompt's prefill into slot 0 of the beam buffers, the lm_head over its last row into logits row 0, and the first pick."""
-        rec, io, h, _ = self._prefill_rows(L, slot=bm["slots"][0])
-        self._lm_head_and_pick(rec, h[L - 1], False, True, slot=bm["slots"][0], beam=bm)
-        return rec.finish(), io
 
     def _generate_spec(self, input_ids, ids_host, max_new, spec, script, dev_eos, eos, min_new):
         """The decode loop of generate(num_speculative_tokens=k) behind the prefill: the captured step is replayed in chunks and the
@@ -1627,7 +1379,7 @@ class USDMForCausalLM:
                 break
             if produced >= max_new or int(self.st_done.item()):
                 break
-            for _ in range(max(1, min(8, -(-(max_new - produced) // T)))):
+            for _ in range(max(1, min(CHUNK, -(-(max_new - produced) // T)))):
                 step.run()
         if self.reuse_prefix:   # committed rows only: the prompt and every emitted token that was fed back and accepted
             self._kv_ids = ids_host + (self.st_out[:produced - 1].tolist() if produced > 1 else [])
@@ -1652,6 +1404,18 @@ class USDMForCausalLM:
         t = m[self.v0:self.v1].to(self.device).contiguous()
         self._ban_cache.put(key, (bad_words_ids, t))
         return t
+
+    def load_ban(self, bad_words_ids=None, ban_mask=None):
+        """The live ban mask, read by every plan and graph: ban_mask (a ready-made [vocab] 0/1 mask: serving's static processors) or else bad_words_ids."""
+        self.ban.copy_(self._ban_mask(bad_words_ids) if ban_mask is None else ban_mask.to(torch.uint8)[self.v0:self.v1])
+
+    def _max_new(self, L0, max_new_tokens, max_length):
+        """generate()'s token budget: max_new_tokens, or else max_length - L0; at most what the context and the output row hold."""
+        if max_new_tokens is None:
+            if max_length is None:
+                raise ValueError("max_length or max_new_tokens is required")
+            max_new_tokens = max_length - L0
+        return min(max_new_tokens, self.ctx_max - L0, self.max_out)
 
     def _setup_call(self, input_ids, past, sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=None, logprobs=None,
                     penalties=None, edits=None):
@@ -1680,10 +1444,7 @@ class USDMForCausalLM:
             self._lp["count"].zero_()      # rows written so far (usdm_logprobs keys its write on it: the device-side EOS)
         io["ids"].copy_(input_ids[0, past:])
         self._kv_ids, self._vt_upto = None, L0      # (set again once this call's decode steps are known)
-        if ban_mask is not None:      # a ready-made [vocab] 0/1 mask (usdm_amd.serving: static logits processors)
-            self.ban.copy_(ban_mask.to(torch.uint8)[self.v0:self.v1])
-        else:
-            self.ban.copy_(self._ban_mask(bad_words_ids))
+        self.load_ban(bad_words_ids, ban_mask)
         self.st_pos.fill_(L0)
         self.st_step.zero_()
         eos_list = sorted(stop_ids(eos_token_id))
@@ -1765,12 +1526,7 @@ class USDMForCausalLM:
                 raise ValueError("temperature / top_p only apply with do_sample=True")
             if B > self.max_batch():
                 raise ValueError(f"num_beams={B}: a decode step of this model takes at most {self.max_batch()} sequences")
-            L0 = input_ids.shape[1]
-            if max_new_tokens is None:
-                if max_length is None:
-                    raise ValueError("max_length or max_new_tokens is required")
-                max_new_tokens = max_length - L0
-            max_new_tokens = min(max_new_tokens, self.ctx_max - L0, self.max_out)
+            max_new_tokens = self._max_new(input_ids.shape[1], max_new_tokens, max_length)
             if max_new_tokens <= 0:
                 return input_ids.expand(n, -1).clone()
             return self._generate_beam(input_ids, max_new_tokens, B, n, length_penalty, early_stopping, eos_list, pad_token_id,
@@ -1797,29 +1553,10 @@ class USDMForCausalLM:
         kind = step_kind(sampling, lpk, pen is not None, edt is not None)
         if kind.sampling and not sampling:      # greedy on the sampling step: top_k = 1
             ops.set_sample_params(self.sample_params, 1.0, 1, 1.0, 0)
-        L0 = input_ids.shape[1]
-        if max_new_tokens is None:
-            if max_length is None:
-                raise ValueError("max_length or max_new_tokens is required")
-            max_new_tokens = max_length - L0
-        max_new_tokens = min(max_new_tokens, self.ctx_max - L0, self.max_out)
+        max_new_tokens = self._max_new(input_ids.shape[1], max_new_tokens, max_length)
         if max_new_tokens <= 0:
             return input_ids.clone()
-        # prefix reuse: tokens whose K/V are already cached (same ids at the same positions) are not prefilled again
-        past, ids_host = 0, None
-        if self.reuse_prefix:
-            ids_host = input_ids[0].tolist()
-            if self._kv_ids is not None:
-                n = min(len(ids_host) - 1, len(self._kv_ids))
-                while past < n and ids_host[past] == self._kv_ids[past]:
-                    past += 1
-                if self.reuse_prefix == "exact":
-                    past = min(past, self._vt_upto)      # rows beyond that were appended by decode steps
-                if past < 16:
-                    past = 0
-            if past > self._vt_upto and self.vtc is not None:   # K/V appended by decode steps have no V^T yet: one transposed copy over all layers (fp8 cache: the plan's usdm_kv_expand covers them)
-                a0 = self._vt_upto
-                self.vtc[:, :, :, a0:past] = self.vcache[:, :, a0:past, :].transpose(2, 3)
+        ids_host, past = self._reused_past(input_ids, input_ids.shape[1] - 1)      # (the last token is always prefilled: its row yields the first pick)
         segs, dev_eos = self._setup_call(input_ids, past, kind.sampling, bad_words_ids, eos_token_id, min_new_tokens, ban_mask=ban_mask,
                                           logprobs=lpk, penalties=pen, edits=edt)
         self._run_segs(segs)  # prefill + first token
@@ -1829,7 +1566,7 @@ class USDMForCausalLM:
             self._decodes[kind] = self._graphed(self._build_decode(*kind), enabled=False if kind.sampling == "hook" else None)
         self._decode = self._decodes[kind]
         eos = stop_ids(eos_token_id)
-        produced, done, chunk = 1, False, 8
+        produced = 1
         toks = []
         while True:
             n_dev = int(self.st_step.item()) if dev_eos else produced   # steps past a device-side EOS did not run
@@ -1850,7 +1587,7 @@ class USDMForCausalLM:
             if produced >= max_new_tokens:
                 toks = toks[:max_new_tokens]
                 break
-            n = min(chunk, max_new_tokens - produced)
+            n = min(CHUNK, max_new_tokens - produced)
             for _ in range(n):
                 self._decode.run()
             produced += n

@@ -19,6 +19,19 @@ def common_prefix(a, b, limit):
     return i
 
 
+def reusable_past(ids, cached_ids, cap, written_upto, exact):
+    """The single sequence's rule (generate(), score()): how many leading tokens of the prompt `ids` are not prefilled again when the
+    cache holds the rows of `cached_ids` (None / empty: nothing cached) - their common prefix, at most `cap` (generate(): L - 1, the
+    last token's row yields the first pick; score(): start - 1); exact: at most the `written_upto` rows that prefill launches wrote
+    (rows beyond that were appended by decode steps).  Below MIN_MATCH tokens: 0."""
+    if not cached_ids:
+        return 0
+    past = common_prefix(ids, cached_ids, cap)
+    if exact:
+        past = min(past, written_upto)
+    return past if past >= MIN_MATCH else 0
+
+
 class PrefixIndex:
     """The index of one set of batch buffers: `nslots` slots of `ctx_max` rows whose idle slots are stepped `chunk` rows at a time."""
 

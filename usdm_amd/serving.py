@@ -43,13 +43,12 @@ from collections import deque
 
 import torch
 
-from . import ops
-from .llm import USDMForCausalLM, check_edits, check_logprobs, check_min_p, check_penalties, check_quantization, read_logprobs, step_kind, stop_index
+from .llm import USDMForCausalLM, check_edits, check_logprobs, check_min_p, check_penalties, check_quantization, step_kind, stop_index
 from .quant import check_kv_cache_dtype
+from .slots import CHUNK
 
 MAX_SLOTS = 16      # usdm_gemv_batch streams the weights once per step for up to 16 sequences (matrix-core form above 4)
 SMALL_SLOTS = 4     # groups of <= 4 requests use the 4-slot plan (VALU form: per slot bit-identical with the single-request path)
-CHUNK = 8           # decode steps between two scheduling points (host sync: stop checks, slot turnover)
 
 
 class SamplingParams:
@@ -488,7 +487,7 @@ class LLM:
     def _run_batched(self, grp):
         llm = self.llm
         nslots = min(self.max_slots, llm.max_batch(), SMALL_SLOTS if len(grp) <= SMALL_SLOTS else MAX_SLOTS)
-        bb = llm._batch_buffers(nslots)
+        ds = llm.decode_slots(nslots)
         # one request with log-probabilities -> the whole group runs on the log-probability step (the sampling step + usdm_logprobs),
         # with the group's largest K; every request's rows are trimmed to its own K on the host
         ks = [r["sp"].logprobs for r in grp if r["sp"].logprobs is not None]
@@ -498,17 +497,11 @@ class LLM:
         pen = any(r["sp"].penalties is not None for r in grp)
         edt = any(r["sp"].edits is not None for r in grp)      # likewise: the step with usdm_logit_edit
         kind = step_kind(any(not r["sp"].greedy for r in grp), lpk, pen, edt)       # one sampled request -> the whole group runs on the sampling graph
-        decode = llm._batch_step(nslots, kind)
-        if edt:
-            for b in range(nslots):
-                ops.set_edit_params(bb["edt"]["dev_params"][b])
-        if pen:
-            for b in range(nslots):
-                ops.set_penalty_params(bb["pen"]["dev_params"][b])
+        decode = ds.step_plan(kind)
         self.stats["sampled_in_batch"] = self.stats.get("sampled_in_batch", 0) + sum(not r["sp"].greedy for r in grp)
-        for b in range(nslots):                               # idle slots: harmless greedy knobs
-            ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
-        llm.ban.copy_(grp[0]["mask"][llm.v0:llm.v1])
+        for b in range(nslots):                               # idle slots: harmless greedy knobs, neutral penalties and edits
+            ds.reset_knobs(b)
+        llm.load_ban(ban_mask=grp[0]["mask"])
         queue, slots, results = deque(grp), [None] * nslots, []
         self.stats["batched_requests"] += len(grp)
         while queue or any(s is not None for s in slots):
@@ -516,11 +509,8 @@ class LLM:
                 if slots[b] is None and queue:
                     r = queue.popleft()
                     sp = r["sp"]
-                    if sp.greedy:
-                        ops.set_sample_params(bb["sp"][b], 1.0, 1, 1.0, 0)
-                    else:
-                        ops.set_sample_params(bb["sp"][b], sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"], min_p=sp.min_p)
-                    src, past = llm._admit(nslots, b, torch.tensor(r["ids"], dtype=torch.long), kind, knobs=sp.penalties, edits=sp.edits)      # (+ first token)
+                    knobs = None if sp.greedy else (sp.temperature, max(sp.top_k, 0), sp.top_p, r["seed"], sp.min_p)
+                    src, past = ds.admit(b, torch.tensor(r["ids"], dtype=torch.long), kind, knobs=sp.penalties, edits=sp.edits, sampling=knobs)      # (+ first token)
                     if self.prefix_caching:
                         st = self.stats
                         st["prefix_hits"] += past > 0
@@ -533,14 +523,11 @@ class LLM:
                     self.stats["admissions"] += 1
             active = [b for b in range(nslots) if slots[b] is not None]
             self.stats["max_active"] = max(self.stats["max_active"], len(active))
-            for b in range(nslots):                               # idle slots decode garbage into row 0 of their own cache
+            for b in range(nslots):                               # idle slots decode garbage where it destroys nothing (DecodeSlots.park)
                 if slots[b] is None:
-                    bb["step"][b] = 0
-                    # (enable_prefix_caching: behind the rows its index records, which the garbage would destroy - the idle slot's
-                    # attention then runs over those rows)
-                    bb["pos"][b] = llm._prefix_index(bb, nslots).park(b) if self.prefix_caching else 0
+                    ds.park(b)
             # tokens already known (the prefill's first token) are checked before any further step is spent
-            toks = bb["out"].tolist()                                # host sync = scheduling point
+            toks = ds.tokens()                                       # host sync = scheduling point
             need, freed = 0, False
             for b in active:
                 s, r = slots[b], slots[b]["r"]
@@ -551,13 +538,10 @@ class LLM:
                     # the slot's rows are read HERE, before a refill restarts its step at 0 and overwrites them; rows decoded past
                     # the stop, up to the end of the chunk, are dropped with their tokens
                     k = r["sp"].logprobs
-                    lp = read_logprobs(bb["lp"], len(seq[:n]), lpk, b).trimmed(len(seq[:n]), k) if k is not None else None
+                    lp = ds.logprobs(b, len(seq[:n]), lpk).trimmed(len(seq[:n]), k) if k is not None else None
                     results.append((r, seq[:n], "stop" if end is not None and end <= n else "length", lp))
                     slots[b] = None
-                    if pen:      # the idle slot keeps decoding garbage: with neutral knobs
-                        ops.set_penalty_params(bb["pen"]["dev_params"][b])
-                    if edt:
-                        ops.set_edit_params(bb["edt"]["dev_params"][b])
+                    ds.reset_knobs(b)      # the idle slot keeps decoding garbage: with neutral knobs
                     freed = True
                 else:
                     need = max(need, 1)
