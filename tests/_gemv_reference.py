@@ -1,0 +1,536 @@
+"""Plain CPU reference of the two bf16 decode-GEMV anchors, usdm_gemv and usdm_gemv_batch, and the inputs of
+tests/test_gemv_exact_gpu.py, checked themselves by tests/test_gemv_exact_cpu.py.  Written from the contract in include/usdm_hip.h
+(usdm_gemv_args, usdm_gemv_batch_args), not from the kernels:
+
+  x'      = bf16(x + bf16(x_delta))                                   (x_delta given; x_out receives x')
+  x'      = bf16(bf16(x' * rstd) * norm_w),  rstd = 1 / sqrt(mean(x'^2) + eps)      (norm_w given)
+  acc[n]  = sum_k W[n][k] * x'[k]
+  plain   : v = acc [-> bf16]; v += residual [-> bf16]                 ([-> bf16]: with round_bf16)
+  SwiGLU  : rows packed in blocks of 16 gate + 16 up rows; v = silu(g) * u, with round_bf16 bf16(bf16(silu(bf16(g))) * bf16(u))
+  lm_head : y32 = bf16(acc), -inf on banned rows; one (max, lowest-id arg-max + idx_offset) partial per block of rows, a block
+            without a candidate holds (-inf, 0x7fffffff)
+  batched : item b at + b * stride of x, y, residual and the partials; W, norm_w and ban are shared
+
+Conventions (those of tests/_gemm_reference.py)
+  * integer operands: x in {-1 ... 3} and W in +-{-1 ... 3} (one sign per row), both inside {-3 ... 3}, held as bf16.  With K <= 16384
+    every partial sum is an integer below 2^24, so an f32 accumulator holds the TRUE sum in any order (v_dot2 or MFMA), and one
+    fp64 matmul is the reference of every kernel bit for bit.  The means are +-1, so most sums are near +-K and round_bf16 does
+    something from K = 504 on.  Residuals are integers in {-8 ... 8}.
+  * every operand sits in a buffer whose gaps hold NaN: ldw = K + 8 and one row after the last of W, eight elements after x (per
+    item: x_bs = K + 8, and one more item row of NaN), norm_w, x_delta and the residual rows.  Bytes 1 follow the ban array.
+  * every output sits in a sentinel-filled buffer larger than what the kernel owns (y_bs > nout, part_bs > blocks, one more item
+    row; x_out likewise).  What the kernel owns must hold the reference, the rest the sentinel, bit for bit.
+  * SwiGLU: x = integers / 16 and W sparse in {-1, 0, 1}: the pre-activations are exact multiples of 1/16 within +-20.
+  * fused RMSNorm, family "exact": x = +-2, norm_w small integers (times 1/16 under SwiGLU) and eps = 1e-5 give
+    bf16(x * rstd) = +-1 for any rstd within 2^-11 of 1/2 (1 - 2^-9 is the tie below 1), so x' = +-norm_w exactly and the case is an integer case.
+    Family "probe": W rows are unit vectors, so y[n] = x'[k_n] with no arithmetic in between, x Gaussian with the last eight
+    elements x 16, norm_w = 1 + 0.1 Gaussian.  The reference x' is evaluated at rstd (1 - DELTA) and rstd (1 + DELTA); a GPU element
+    must equal one of the two.
+
+DELTA.  x is bf16, so every square is exact in f32 and only the additions of the sum of squares round.  All terms are positive: a
+sum whose longest chain has n additions is within n 2^-24 of the true sum, relatively.  The longest chain of any instantiation is
+the matrix-core kernel's at K = 4096: 128 sequential FMAs per lane (16 held fragments of 8 elements), 2 cross-lane additions and 8
+per-wave partials = 138.  (usdm_gemv at K = 16384 with 256 threads: 8 pieces per thread, each four times ss += lo lo + hi hi
+without contraction, i.e. 4 additions on the chain and one rounding of the pair sum beside it = 8 x 5 = 40, 6 for the wave, up to
+16 wave partials = 62.)  rstd = sum^(-1/2) halves the relative error: 69.  The division by K, the addition of eps
+and the device's rsqrt (one ulp) add at most 0.5 + 0.5 + 2, and the f32 rounding of x * rstd before its bf16 rounding acts like
+one more 2^-24 on rstd: 73 2^-24 < 128 2^-24 = 2^-17.
+"""
+import torch
+import torch.nn.functional as Fn
+
+from tests._glue_reference import BF, F32, F64, SENT32, bits, gen, is_sentinel, sentinel  # noqa: F401
+from tests._gemm_reference import (FLIP_CAP, GEMM_SWIGLU_TORCH_FP32_ERR, Exp, bf16_ulp, check_exact, check_guard, rbf64,  # noqa: F401
+                                   swiglu_rbf_ref)
+
+NAN, INF = float("nan"), float("inf")
+ACT_NONE, ACT_SWIGLU = 0, 3
+NO_IDX = 0x7fffffff
+EPS = 1e-5
+EPS32 = float(torch.tensor(EPS, dtype=F32))
+DELTA = 2.0 ** -17
+PROBE_CAP = 0.02            # share of a probe case's elements on which the two references may differ
+PAD = 8                     # elements of 16 bytes: the NaN gap after every operand row
+# SwiGLU without round_bf16: 4 x torch's own float32 error per max(|ref|, |u|), as the GEMM test.  The device evaluates e^-g as
+# exp2(-g log2 e): the product rounds once (2^-24 of |g| log2 e) and log2 e is held to 2^-25, so e^-g carries about
+# 1.5 |g| 2^-24 on top of the exp2's ulp.  silu'(e^-g) turns that into g^2 s (1 - s) 1.5 2^-24 with s = sigmoid(g); g^2 s (1 - s)
+# peaks at 0.44 (|g| = 2.4), i.e. 4e-8 per |u|, a sixteenth of the bound: no |g|-proportional term is needed at |g| <= 20.
+SWIGLU_TOL = 4.0 * GEMM_SWIGLU_TORCH_FP32_ERR
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+ALT16_BITS = 0x7e7e     # the second fill of a bf16 buffer (a finite bf16 again); f32 and int32 buffers: -SENT32 in their own dtype
+
+
+def alt_sentinel(shape, dtype, device=None):
+    """a buffer pre-filled with the dtype's second sentinel: an owned element that legitimately holds the first sentinel's bits is
+    read again over this fill (a written element holds the same bits again, an unwritten one this fill)"""
+    if dtype == BF:
+        return torch.full(shape, ALT16_BITS, dtype=torch.int16, device=device).view(BF)
+    return torch.full(shape, -int(SENT32) if dtype == torch.int32 else -SENT32, dtype=dtype, device=device)
+
+
+# ------------------------------------------------------------------------------------------------------------------ launch selection
+# (rows per wave, GLU, waves): output count at which usdm_gemv reaches each instantiation ("lm": lm_head mode, always 4 rows)
+VALU_INST = {(1, False, 4): 37, (2, False, 4): 4081, (3, False, 4): 8193, (4, False, 4): 16369, (1, False, 16): 4096,
+             (2, False, 12): 6144, (1, True, 4): 48, (2, True, 4): 5136, (2, True, 7): 7168}
+SMALL_INST = ((1, False, 4), (1, True, 4))
+LM_N = 1003
+BATCH_INST = ((1, False, 4), (1, False, 16), (1, True, 4))
+
+
+def inst_id(i):
+    return "lm_head" if i == "lm" else f"rw{i[0]}{'-glu' if i[1] else ''}-{i[2]}waves"
+
+
+def pick_rw(nout, glu):
+    """gemv_pick_rw: the largest rows-per-wave with >= 1024 workgroups at >= 90 % balance over 256 CUs, else the best score"""
+    cands = (2, 1) if glu else (4, 3, 2, 1)
+    best, best_score = cands[-1], -1.0
+    for rw in cands:
+        blocks = cdiv(nout, 4 * rw)
+        eff = (blocks / 256.0) / float((blocks + 255) // 256)
+        if blocks >= 1024 and eff >= 0.9:
+            return rw
+        score = eff * (1.0 if blocks >= 512 else 0.5 + blocks / 1024.0)
+        if score > best_score:
+            best_score, best = score, rw
+    return best
+
+
+def valu_select(N, *, glu=False, lm_head=False, batched=False):
+    """gemv_select for the plain single-GPU forms -> (rows per wave, GLU, waves per workgroup, grid)"""
+    nout = N // 2 if glu else N
+    rows_per_cu = nout // 256 if nout % 256 == 0 else 0
+    if not glu and not lm_head and rows_per_cu == 16:
+        return 1, False, 16, 256
+    if not glu and not lm_head and rows_per_cu == 24:
+        return 2, False, 12, 256
+    if not batched and glu and nout % 14 == 0 and (nout // 14) % 512 == 0:
+        return 2, True, 7, nout // 14
+    rw = 4 if lm_head else pick_rw(nout, glu)
+    return rw, glu, 4, cdiv(nout, 4 * rw)
+
+
+def ring_depth(rw, glu):
+    """gemv_ring_depth of the bf16 format: K iterations of 512 in flight per row"""
+    nr = 2 * rw if glu else rw
+    return 2 if nr >= 8 else 4 if nr >= 4 else 5 if nr == 3 else 8
+
+
+MW, CH, KS_K, KS_MAX, MTG_TRL = 8, 16, 2048, 8, 8
+MFMA_VARIANTS = ("hold", "hold16-recut", "hold16-frag", "stream", "stream56-recut", "stream56-frag", "ksplit")
+
+
+def ks_floats(N, K):
+    if K <= MW * CH * 32 or K % KS_K != 0 or K // KS_K > KS_MAX or N <= 0:
+        return 0
+    return cdiv(N, 16) * (K // KS_K) * 256
+
+
+def mfma_select(N, K, *, glu=False, lm_head=False, norm=False, form=1, ks=False):
+    """the matrix-core launcher's decisions -> dict(variant, rt (rows per tile), ksplit, ntiles, grid, kwg (workgroups that share the tiles))"""
+    cpw = cdiv(K // 32, MW)
+    hold = cpw <= CH
+    nout = N // 2 if glu else N
+    rt, ksplit = 16, 1
+    if ks_floats(N, K) and ks and not glu and not lm_head and not norm and form not in (3, 5):
+        ksplit = K // KS_K
+        if cdiv(cdiv(N, 16), min(256 // ksplit, cdiv(N, 16))) > MTG_TRL:
+            ksplit = 1
+    if glu:
+        ntiles = cdiv(nout, 8)
+    elif lm_head:
+        ntiles = cdiv(N, 16)
+    else:
+        best = 1 << 30
+        for r in (16, 12, 8):
+            nt = cdiv(N, r)
+            per = cdiv(nt, min(nt, 256)) * r
+            if per < best:
+                best, rt = per, r
+        ntiles = cdiv(N, rt)
+    grid = kwg = min(ntiles, 256)
+    if ksplit > 1:
+        rt, ntiles = 16, cdiv(N, 16)
+        kwg = min(256 // ksplit, ntiles)
+        grid = kwg * ksplit
+        variant = "ksplit"
+    else:
+        variant = "hold" if hold else "stream"
+        if cpw == (16 if hold else 56):      # K = 4096 / 14336: chunks per wave as a constant; row-contiguous loads re-cut through LDS unless form 3
+            variant += str(cpw) + ("-frag" if form == 3 else "-recut")
+    return dict(variant=variant, rt=rt, ksplit=ksplit, ntiles=ntiles, grid=grid, kwg=kwg)
+
+
+# ------------------------------------------------------------------------------------------------------------------ cases
+class Case:
+    """one projection.  nb = 0: usdm_gemv; nb >= 1: usdm_gemv_batch with `form`.  kind: "int" | "swiglu" | "probe"; norm: None |
+    "exact" | "probe"; ban: None | "none" | "workgroup" | "wave" | "scattered" | "last" (lm_head mode when not None)"""
+
+    def __init__(self, name, *, N, K, seed, nb=0, form=0, glu=False, kind="int", norm=None, res=False, inplace=False, ban=None, idx_offset=0,
+                 delta=False, skip=False, ks=False, inst=None, variant=None, rt=None):
+        self.name, self.N, self.K, self.seed, self.nb, self.form, self.glu = name, N, K, seed, nb, form, glu
+        self.kind, self.norm, self.res, self.inplace, self.ban, self.idx_offset = kind, norm, res, inplace, ban, idx_offset
+        self.delta, self.skip, self.ks, self.inst, self.variant, self.rt = delta, skip, ks, inst, variant, rt
+        self.B = max(nb, 1)
+        self.lm_head = ban is not None
+        self.mfma = nb >= 1 and (form in (1, 3, 5) or (form == 0 and nb > 4))
+        self.nout = N // 2 if glu else N
+        self.ldw = self.x_bs = K + PAD
+        self.y_bs = self.nout + 5
+        self.res_bs = self.y_bs if inplace else self.nout + 3
+        self.sel = mfma_select(N, K, glu=glu, lm_head=self.lm_head, norm=norm is not None, form=form, ks=ks) if self.mfma else None
+        self.nparts = (self.sel["grid"] if self.mfma else cdiv(N, 16)) if self.lm_head else 0
+        self.part_bs = self.nparts + 3 if self.lm_head else 0
+        assert not (glu and (res or self.lm_head)) and not (delta and nb) and K % 8 == 0
+
+    @property
+    def act(self):
+        return ACT_SWIGLU if self.glu else ACT_NONE
+
+    def selected(self):
+        """what the launch is expected to reach: the VALU tuple, or the matrix-core (variant, rows per tile)"""
+        if self.mfma:
+            return self.sel["variant"], self.sel["rt"]
+        return valu_select(self.N, glu=self.glu, lm_head=self.lm_head, batched=self.nb >= 1)[:3]
+
+    def threads(self):
+        return MW * 64 if self.mfma else 64 * self.selected()[2]
+
+    def __repr__(self):
+        return self.name
+
+
+class Data:
+    pass
+
+
+def _ints(shape, g, lo, hi, dtype=torch.int8):
+    return torch.randint(lo, hi + 1, tuple(shape), generator=g, dtype=dtype)
+
+
+def _guarded(vals, stride, rows=None, fill=NAN, dtype=BF):
+    """[rows + 1][stride] filled with `fill`, vals [rows][n] in its top left corner, flat"""
+    rows = vals.shape[0] if rows is None else rows
+    buf = torch.full((rows + 1, stride), fill, dtype=dtype)
+    buf[:vals.shape[0], :vals.shape[1]] = vals.to(dtype)
+    return buf.reshape(-1)
+
+
+def probe_positions(c):
+    """the K positions the probe's unit rows read: all of K where there are rows enough; else the last and first 16 elements and 16
+    either side of every multiple of 8 x threads, then evenly spread ones, as many as there are outputs"""
+    n, K = c.nout, c.K
+    if n >= K:
+        return torch.arange(n) % K
+    step = 8 * c.threads()
+    pos = list(range(K - 16, K)) + [p for m in range(step, K + 16, step) for p in range(m - 16, m + 16)] + list(range(16))
+    pos += [(i * K) // n for i in range(n)]
+    out = []
+    for p in pos:
+        if 0 <= p < K and p not in out:
+            out.append(p)
+    return torch.tensor(out[:n])
+
+
+def ban_pattern(c):
+    """uint8 [N] of the lm_head cases: rows the arg-max must ignore"""
+    N, ban = c.N, torch.zeros(c.N, dtype=torch.uint8)
+    g = gen(c.seed + 9)
+    if c.ban == "workgroup":            # blocks 1 and 2 of 16 rows entirely (a whole workgroup of either form), and the ragged last one
+        ban[16:48] = 1
+        ban[N - N % 16:] = 1
+    elif c.ban == "wave":               # rows 4 ... 7 of block 0 (a whole wave of usdm_gemv), rows 16 ... 30 (all but one of block 1)
+        ban[4:8] = 1
+        ban[16:31] = 1
+    elif c.ban == "scattered":
+        ban[torch.rand(N, generator=g) < 0.4] = 1
+    elif c.ban == "last":
+        ban[N - 1] = 1
+    return ban
+
+
+def build(c):
+    """the case's logical operands (fp64 / bf16) and its guarded flat buffers, all on the CPU"""
+    d, g = Data(), gen(c.seed)
+    N, K, B = c.N, c.K, c.B
+    d.kpos = None
+    # ---- x [B][K] (fp64, logical), norm_w [K], W [N][K] (bf16, logical)
+    if c.norm == "probe":
+        x = torch.randn(B, K, generator=g)
+        x[:, K - 8:] *= 16.0
+        d.xl = x.to(BF).double()
+        d.gl = (1.0 + 0.1 * torch.randn(K, generator=g)).float().double()
+    elif c.norm == "exact":
+        sgn = (_ints((B, K), g, 0, 1).double() * 2 - 1)
+        d.xl = 2.0 * sgn
+        if c.kind == "swiglu":
+            d.gl = _ints((K,), g, -3, 3).double() / 16
+        else:                            # positive x' for item 0 (the sign of norm_w follows item 0's x), so that the sums are near +-2 K
+            d.gl = sgn[0] * _ints((K,), g, 1, 3).double()
+    else:
+        d.gl = None
+        d.xl = _ints((B, K), g, -3, 3).double() / 16 if c.kind == "swiglu" else _ints((B, K), g, -1, 3).double()
+    if c.kind == "probe":
+        pos = probe_positions(c)
+        rows = torch.arange(c.nout)
+        d.kpos = torch.zeros(N, dtype=torch.int64)
+        if c.glu:                        # gate and up row of an output read the same element: y = silu(x'[k]) * x'[k]
+            gate = (rows // 16) * 32 + rows % 16
+            d.kpos[gate], d.kpos[gate + 16] = pos, pos
+        else:
+            d.kpos[rows] = pos
+        d.Wl = torch.zeros(N, K, dtype=BF)
+        d.Wl[torch.arange(N), d.kpos] = 1.0
+    elif c.kind == "swiglu":
+        keep = torch.rand(N, K, generator=g) < min(1.0, 800.0 / K)
+        d.Wl = (_ints((N, K), g, 0, 1) * 2 - 1).to(BF) * keep.to(BF)
+    else:
+        d.Wl = (_ints((N, K), g, -1, 3) * (_ints((N, 1), g, 0, 1) * 2 - 1)).to(BF)
+    d.W = _guarded(d.Wl, c.ldw)
+    d.x = _guarded(d.xl, c.x_bs)
+    d.norm_w = None if d.gl is None else _guarded(d.gl.view(1, -1), K + PAD, rows=0, dtype=F32)
+    # ---- x_delta: integer-valued f32 (with the exact norm family: zero but for a few elements whose x + delta is again +-2)
+    d.dl = d.x_delta = None
+    if c.delta:
+        if c.norm == "exact":
+            d.dl = torch.zeros(K, dtype=F64)
+            at = torch.randperm(K, generator=g)[:max(1, K // 5)]
+            d.dl[at] = -2.0 * d.xl[0, at]
+        else:
+            d.dl = _ints((K,), g, -2, 0).double()                 # x + delta stays inside {-3 ... 3}
+        d.x_delta = _guarded(d.dl.view(1, -1), K + PAD, rows=0, dtype=F32)
+    # ---- residual [B][nout], ban [N]
+    d.rl = _ints((B, c.nout), g, -8, 8).double() if c.res else None
+    d.res = None if d.rl is None else _guarded(d.rl, c.res_bs)
+    d.banl = ban_pattern(c) if c.lm_head else None
+    d.ban = None if (d.banl is None or c.ban == "none") else torch.cat([d.banl, torch.ones(16, dtype=torch.uint8)])
+    return d
+
+
+def x_prime(c, d, scale=1.0):
+    """(x' the projection multiplies, x' before the RMSNorm = what x_out receives), fp64 [B][K]; scale: applied to rstd"""
+    x = d.xl
+    if c.delta:
+        x = rbf64(x + rbf64(d.dl))
+    pre = x
+    if c.norm:
+        f32 = lambda t: t.float().double()
+        rstd = scale / torch.sqrt((x * x).mean(-1, keepdim=True) + EPS32)
+        x = rbf64(f32(rbf64(f32(x * rstd)) * d.gl))
+    return x, pre
+
+
+def ref_acc(d, xp):
+    """fp64 [B][N]; rows that are unit vectors: the element they select (a sum of it and exact zeros)"""
+    if d.kpos is not None:
+        return xp[:, d.kpos]
+    out = torch.empty(xp.shape[0], d.Wl.shape[0], dtype=F64)
+    for r0 in range(0, d.Wl.shape[0], 2048):
+        out[:, r0:r0 + 2048] = xp @ d.Wl[r0:r0 + 2048].double().T
+    return out
+
+
+def part_slot(c):
+    """[N]: the partial that row n's logit competes in (usdm_gemv and the VALU form: blocks of 16 rows; matrix cores: 16-row tiles
+    dealt round-robin to the workgroups)"""
+    blk = torch.arange(c.N) // 16
+    return blk % c.sel["kwg"] if c.mfma else blk
+
+
+def partials(c, logits):
+    """(val, idx) fp64 [B][written partials] of logits [B][N] (-inf where banned); the matrix-core form fills all of part_bs"""
+    nw = c.part_bs if c.mfma else c.nparts
+    val = torch.full((c.B, nw), -INF, dtype=F64)
+    idx = torch.full((c.B, nw), float(NO_IDX), dtype=F64)
+    slot, ids = part_slot(c), torch.arange(c.N)
+    for s in range(c.nparts):
+        m = slot == s
+        if not bool(m.any()):
+            continue
+        lg = logits[:, m]
+        best = lg.max(-1).values
+        first = (lg == best.view(-1, 1)).float().argmax(-1)           # the lowest id among the ties
+        val[:, s] = best
+        idx[:, s] = torch.where(best > -INF, (ids[m][first] + c.idx_offset).double(), torch.full((), float(NO_IDX), dtype=F64))
+    return val, idx
+
+
+def expected(c, d, *, rbf, scale=1.0):
+    """{"y": Exp, "part_val", "part_idx", "x_out"} of one launch with round_bf16 = rbf; d.acc_max for the CPU test"""
+    B, nout = c.B, c.nout
+    xp, xpre = x_prime(c, d, scale)
+    acc = ref_acc(d, xp)
+    d.acc_max = float(acc.abs().max())
+    e = {"y": Exp((B + 1) * c.y_bs)}
+    yi = torch.arange(B).view(-1, 1) * c.y_bs + torch.arange(nout).view(1, -1)
+    if c.lm_head:
+        logits = rbf64(acc)
+        logits[:, d.banl.bool()] = -INF
+        e["y"].put(yi, logits)
+        val, idx = partials(c, logits)
+        pi = torch.arange(B).view(-1, 1) * c.part_bs + torch.arange(val.shape[1]).view(1, -1)
+        e["part_val"], e["part_idx"] = Exp((B + 1) * c.part_bs), Exp((B + 1) * c.part_bs)
+        e["part_val"].put(pi, val)
+        e["part_idx"].put(pi, idx)
+    elif c.glu:
+        o = torch.arange(nout)
+        gate = (o // 16) * 32 + o % 16
+        gv, uv = acc[:, gate], acc[:, gate + 16]
+        e["y"].put(yi, swiglu_rbf_ref(gv, uv) if rbf else Fn.silu(gv) * uv, gv, uv)
+    else:
+        v = rbf64(acc) if rbf else acc
+        if c.res:
+            v = v + d.rl
+            v = rbf64(v) if rbf else v
+        e["y"].put(yi, v)
+    if c.delta:
+        e["x_out"] = Exp(c.K + PAD)
+        e["x_out"].put(torch.arange(c.K), xpre[0])
+    return e
+
+
+# ---- usdm_gemv: the K ladder of an instantiation (UNR: its ring depth, threads: its workgroup)
+def k_ladder(inst, small):
+    rw, glu, nwv = (4, False, 4) if inst == "lm" else inst
+    u, t = 512 * ring_depth(rw, glu), 8 * 64 * nwv
+    ks = (8, 504, 512, 520, u - 8, u, u + 8, t, t + 8, 16384) if small else (504, u + 8, t + 8)
+    return sorted(set(ks))
+
+
+def _shape(inst):
+    if inst == "lm":
+        return dict(N=LM_N, ban="none", inst=inst)
+    return dict(N=VALU_INST[inst] * (2 if inst[1] else 1), glu=inst[1], inst=inst)
+
+
+def is_small(inst):
+    return inst == "lm" or inst in SMALL_INST
+
+
+def _mk(name, inst, K, seed, nb=0, **kw):
+    a = dict(_shape(inst), **kw)
+    if a.get("glu") and a.get("kind", "int") == "int":
+        a["kind"] = "swiglu"
+    if nb:
+        a.update(nb=nb, form=-1)
+    return Case(f"{inst_id(inst)} {name} K{K}" + (f" nb{nb}" if nb else ""), K=K, seed=seed, **a)
+
+
+def _seed(inst, j):
+    return 1000 * (list(VALU_INST).index(inst) + 1 if inst != "lm" else 10) + j
+
+
+def valu_plain_cases(inst, nb=0):
+    """plain with a residual (GLU: SwiGLU; lm_head: no ban) over the K ladder"""
+    ks = k_ladder(inst, is_small(inst)) if not nb else (504, 8 * 64 * (4 if inst == "lm" else inst[2]) + 8)
+    return [_mk("plain", inst, K, _seed(inst, j) + 50 * nb, nb, res=inst != "lm" and not inst[1]) for j, K in enumerate(ks)]
+
+
+def valu_norm_exact_cases(inst, nb=0):
+    ks = k_ladder(inst, is_small(inst)) if not nb else (504, 8 * 64 * (4 if inst == "lm" else inst[2]) + 8)
+    return [_mk("norm-exact", inst, K, _seed(inst, j) + 100 + 50 * nb, nb, norm="exact", res=inst != "lm" and not inst[1]) for j, K in enumerate(ks)]
+
+
+def valu_probe_cases(inst, nb=0):
+    t = 64 * (4 if inst == "lm" else inst[2])
+    return [_mk("norm-probe", inst, K, _seed(inst, j) + 200 + 50 * nb, nb, kind="probe", norm="probe") for j, K in enumerate((504, 8 * t + 8))]
+
+
+BANS = ("none", "workgroup", "wave", "scattered", "last")           # "none": no ban array at all (a NULL pointer)
+
+
+def lm_head_cases(nb=0, mfma=False):
+    """every ban pattern, in every form: the banning ones at a one-iteration and a ragged multi-iteration K (matrix cores: multiples of
+    256), idx_offset != 0 on two; no ban array at K = 520 (matrix cores: K = 4096, the row-contiguous loads)"""
+    out = []
+    for j, ban in enumerate(BANS[1:]):
+        K = (256, 3840)[j % 2] if mfma else (504, 2056)[j % 2]
+        kw = dict(nb=nb, form=1, variant="hold", rt=16) if mfma else (dict(nb=nb, form=-1) if nb else {})
+        out.append(Case(f"lm_head {ban} K{K}" + (f" nb{nb}" if nb else ""), N=LM_N, K=K, seed=11000 + j + 10 * nb, ban=ban,
+                        idx_offset=(0, 70000)[j // 2], inst="lm", **kw))
+    K = 4096 if mfma else 520
+    kw = dict(nb=nb, form=1, variant="hold16-recut", rt=16) if mfma else (dict(nb=nb, form=-1) if nb else {})
+    out.append(Case(f"lm_head none K{K}" + (f" nb{nb}" if nb else ""), N=LM_N, K=K, seed=11005 + 10 * nb, ban="none", idx_offset=123, inst="lm", **kw))
+    return out
+
+
+def delta_cases(inst):
+    return [_mk("x_delta", inst, 2056, _seed(inst, 300), delta=True, res=True), _mk("x_delta+norm", inst, 2056, _seed(inst, 301), delta=True, norm="exact", res=True),
+            _mk("x_delta", inst, 504, _seed(inst, 302), delta=True, res=True), _mk("x_delta+norm", inst, 8200, _seed(inst, 303), delta=True, norm="exact")]
+
+
+def skip_cases(inst):
+    return [_mk("skip", inst, 520, _seed(inst, 310), skip=True, res=True, delta=True), _mk("skip+norm", inst, 520, _seed(inst, 311), skip=True, norm="exact")]
+
+
+DELTA_INST = ((1, False, 4), (1, False, 16))
+VALU_NB = (2, 3, 4)
+
+
+# ---- usdm_gemv_batch on the matrix cores
+MFMA_NB = (1, 5, 13, 16)
+# (K, form, ks): the variant each reaches is asserted by the CPU test
+MFMA_LADDER = ((256, 1, False), (3840, 1, False), (4096, 1, False), (4096, 3, False), (6144, 5, False), (16384, 5, False), (14336, 1, False),
+               (14336, 3, False), (14336, 5, False), (14336, 1, True), (6144, 1, True), (16384, 1, True))
+MFMA_LADDER_VARIANT = ("hold", "hold", "hold16-recut", "hold16-frag", "stream", "stream", "stream56-recut", "stream56-frag", "stream56-recut",
+                       "ksplit", "ksplit", "ksplit")
+N_SMALL = 37        # plain: five 8-row tiles (the launcher's loop takes the shortest workgroup); K split: three 16-row tiles, the last of 5 rows
+N_RAGGED16 = 4085   # 256 tiles of 16 rows, the last of 5 (12-row tiles would need two rounds, 8-row tiles are no shorter)
+N_ROWS12 = 6144
+# SwiGLU: 48 outputs = six tiles of 8 gate + 8 up rows.  The packed layout has whole blocks of 16 gate + 16 up rows only (N % 32 == 0;
+# N = 80, i.e. 40 outputs, would put the last up rows past W and is refused), so the output count is a multiple of 16 and no tile of
+# 8 outputs can be ragged: 48 is deliberate, there is no ragged SwiGLU tile to reach
+N_SWIGLU = 96
+
+
+def mfma_ladder_cases(nb):
+    """N = 37 with a residual, in place (y16 = residual) in the round_bf16 launch, over every variant"""
+    return [Case(f"mfma K{K} form{f}{' ks' if ks else ''} nb{nb}", N=N_SMALL, K=K, seed=20000 + 20 * j + nb, nb=nb, form=f, ks=ks, res=True, inplace=True,
+                 variant=MFMA_LADDER_VARIANT[j], rt=16 if ks else 8) for j, (K, f, ks) in enumerate(MFMA_LADDER)]
+
+
+def mfma_tile_cases(nb):
+    """12-row tiles (N = 6144), ragged 16-row tiles (N = 4085), at a generic held K and on both K = 4096 load patterns"""
+    out = []
+    for i, (N, rt) in enumerate(((N_ROWS12, 12), (N_RAGGED16, 16))):
+        for j, (K, f, v) in enumerate(((256, 1, "hold"), (4096, 1, "hold16-recut"), (4096, 3, "hold16-frag"))):
+            out.append(Case(f"mfma N{N} K{K} form{f} nb{nb}", N=N, K=K, seed=21000 + 10 * i + j + 100 * nb, nb=nb, form=f, res=True, inplace=True, variant=v, rt=rt))
+    return out
+
+
+def mfma_swiglu_cases(nb):
+    return [Case(f"mfma swiglu K{K} form{f} nb{nb}", N=N_SWIGLU, K=K, seed=22000 + j + 10 * nb, nb=nb, form=f, glu=True, kind="swiglu", variant=v, rt=16)
+            for j, (K, f, v) in enumerate(((256, 1, "hold"), (4096, 1, "hold16-recut"), (4096, 3, "hold16-frag"), (6144, 5, "stream")))]
+
+
+def mfma_norm_cases(nb):
+    """both RMSNorm families at K <= 4096 (the matrix-core form fuses the norm into the held activations only)"""
+    out = []
+    for j, (K, f, v) in enumerate(((256, 1, "hold"), (3840, 1, "hold"), (4096, 1, "hold16-recut"), (4096, 3, "hold16-frag"))):
+        out.append(Case(f"mfma norm-exact K{K} form{f} nb{nb}", N=N_SMALL, K=K, seed=23000 + j + 10 * nb, nb=nb, form=f, norm="exact", res=True, variant=v, rt=8))
+        out.append(Case(f"mfma norm-probe K{K} form{f} nb{nb}", N=4096, K=K, seed=23500 + j + 10 * nb, nb=nb, form=f, kind="probe", norm="probe", variant=v, rt=16))   # N >= K: all of K
+    out.append(Case(f"mfma swiglu norm-exact K4096 nb{nb}", N=N_SWIGLU, K=4096, seed=23900 + nb, nb=nb, form=1, glu=True, kind="swiglu", norm="exact",
+                    variant="hold16-recut", rt=16))
+    return out
+
+
+def all_cases():
+    """every case of the GPU test, for the CPU test's conditions"""
+    out = []
+    for inst in list(VALU_INST) + ["lm"]:
+        out += valu_plain_cases(inst) + valu_norm_exact_cases(inst) + valu_probe_cases(inst)
+    out += lm_head_cases()
+    for inst in DELTA_INST:
+        out += delta_cases(inst) + skip_cases(inst)
+    for nb in VALU_NB:
+        for inst in BATCH_INST + ("lm",):
+            out += valu_plain_cases(inst, nb) + valu_norm_exact_cases(inst, nb) + valu_probe_cases(inst, nb)
+        out += lm_head_cases(nb)
+    for nb in MFMA_NB:
+        out += mfma_ladder_cases(nb) + mfma_tile_cases(nb) + mfma_swiglu_cases(nb) + mfma_norm_cases(nb) + lm_head_cases(nb, mfma=True)
+    return out

@@ -1,0 +1,193 @@
+"""tests/_gemv_reference.py checked on the CPU: the reference against torch.nn.functional on float data, the conditions under which
+its cases are exact (2^24 headroom, the SwiGLU grid, the exact RMSNorm family, the 2 % cap of the probe), and that every case
+reaches the instantiation it is listed under and every instantiation is reached."""
+import pytest
+import torch
+import torch.nn.functional as Fn
+
+from tests import _gemv_reference as R
+from tests._gemv_reference import BF
+
+
+def test_launch_selection_mirror():
+    """the output counts of VALU_INST reach their instantiation; the odd ones leave the last workgroup ragged"""
+    for (rw, glu, nwv), nout in R.VALU_INST.items():
+        assert R.valu_select(nout * (2 if glu else 1), glu=glu)[:3] == (rw, glu, nwv), (rw, glu, nwv)
+    for nout in (37, 4081, 8193, 16369, 5136):
+        rw, _, nwv, _ = R.valu_select(nout * (2 if nout == 5136 else 1), glu=nout == 5136)
+        assert nout % (rw * nwv) != 0 or nout == 5136                                       # the last workgroup is ragged
+    assert R.valu_select(R.LM_N, lm_head=True)[:3] == (4, False, 4) and R.valu_select(4096, lm_head=True)[:3] == (4, False, 4)
+    assert R.valu_select(14336, glu=True, batched=True)[:3] != (2, True, 7)                 # batch-1 only
+    assert [R.ring_depth(*i[:2]) for i in R.VALU_INST] == [8, 8, 5, 4, 8, 8, 8, 4, 4]
+    # matrix cores: rows per tile, the K split
+    assert R.mfma_select(6144, 4096)["rt"] == 12 and R.mfma_select(R.N_RAGGED16, 4096)["rt"] == 16 and R.mfma_select(R.N_SMALL, 4096)["rt"] == 8
+    assert R.N_RAGGED16 % 16 != 0
+    assert [R.mfma_select(R.N_SMALL, K, ks=True)["ksplit"] for K in (6144, 14336, 16384, 4096, 5120)] == [3, 7, 8, 1, 1]
+    assert R.mfma_select(R.LM_N, 256, lm_head=True)["grid"] == 63 and R.mfma_select(R.N_SWIGLU, 256, glu=True)["ntiles"] == 6
+
+
+def test_every_case_reaches_its_instantiation_and_every_instantiation_is_reached():
+    cases = R.all_cases()
+    assert len({c.name for c in cases}) == len(cases)
+    valu, mfma, bans = set(), set(), set()
+    for c in cases:
+        if c.lm_head:
+            bans.add(("matrix cores" if c.mfma else "valu batch" if c.nb else "usdm_gemv", c.ban))
+        if c.mfma:
+            assert c.selected() == (c.variant, c.rt), c.name
+            mfma.add(c.variant)
+            continue
+        want = (4, False, 4) if c.inst == "lm" else c.inst
+        assert c.selected() == want, c.name
+        valu.add((c.inst, c.nb))
+    assert {i for i, nb in valu if nb == 0} == set(R.VALU_INST) | {"lm"}
+    assert {(i, nb) for i, nb in valu if nb} == {(i, nb) for i in R.BATCH_INST + ("lm",) for nb in R.VALU_NB}
+    assert mfma == set(R.MFMA_VARIANTS)
+    assert bans == {(f, b) for f in ("usdm_gemv", "valu batch", "matrix cores") for b in R.BANS} and len(R.BANS) == 5
+    for nb in R.MFMA_NB:                                        # ... in the matrix-core form for every batch size, "none" with a NULL array
+        assert {c.ban for c in R.lm_head_cases(nb, mfma=True)} == set(R.BANS)
+        assert all((R.build(c).ban is None) == (c.ban == "none") for c in R.lm_head_cases(nb, mfma=True))
+    rts = {(c.rt, c.glu, c.lm_head) for c in cases if c.mfma}
+    assert {(8, False, False), (12, False, False), (16, False, False), (16, True, False), (16, False, True)} <= rts
+
+
+def test_sentinels_of_every_output_dtype():
+    """the second fill differs from the first in every output dtype, int32 (part_idx) included, and neither is a NaN"""
+    for dt in (R.F32, BF, torch.int32):
+        a, b = R.sentinel((3,), dt), R.alt_sentinel((3,), dt)
+        assert a.dtype == dt and b.dtype == dt and bool(R.is_sentinel(a).all()) and not bool(R.is_sentinel(b).any())
+        assert not torch.equal(R.bits(a), R.bits(b)) and bool((a == a).all()) and bool((b == b).all())
+    assert R.alt_sentinel((1,), torch.int32).item() == -7 and R.sentinel((1,), torch.int32).item() == 7
+
+
+def test_k_ladders():
+    assert R.k_ladder((1, False, 4), True) == [8, 504, 512, 520, 2048, 2056, 4088, 4096, 4104, 16384]
+    assert R.k_ladder("lm", True) == [8, 504, 512, 520, 2040, 2048, 2056, 16384]
+    assert R.k_ladder((1, False, 16), False) == [504, 4104, 8200] and R.k_ladder((2, False, 12), False) == [504, 4104, 6152]
+    assert R.k_ladder((3, False, 4), False) == [504, 2056, 2568] and R.k_ladder((2, True, 7), False) == [504, 2056, 3592]
+
+
+def _float_case(**kw):
+    """a small case whose operands are replaced by float data"""
+    c = R.Case("float", N=96, K=520, seed=5, **kw)
+    d = R.build(c)
+    g = R.gen(77)
+    d.Wl = (torch.randn(c.N, c.K, generator=g) * c.K ** -0.5).to(BF)
+    d.xl = torch.randn(c.B, c.K, generator=g).to(BF).double()
+    return c, d
+
+
+def test_reference_against_torch_functional():
+    # plain + residual, both rounding modes
+    c, d = _float_case(res=True, nb=3, form=-1)
+    lin = Fn.linear(d.xl, d.Wl.double())
+    e = R.expected(c, d, rbf=False)["y"]
+    assert torch.equal(e.vals[e.owned].view(3, -1), lin + d.rl)
+    e = R.expected(c, d, rbf=True)["y"]
+    assert torch.equal(e.vals[e.owned].view(3, -1), (lin.to(BF).double() + d.rl).to(BF).double())
+    assert int(e.owned.sum()) == 3 * 96 and not bool(e.owned.view(4, -1)[3].any()) and not bool(e.owned.view(4, -1)[:, 96:].any())
+    # RMSNorm with HF's rounding points, then the projection
+    c, d = _float_case(norm="probe", kind="int")
+    xn = (d.xl * torch.rsqrt(d.xl.pow(2).mean(-1, keepdim=True) + R.EPS32)).float().to(BF).double()
+    xn = (xn * d.gl).float().to(BF).double()
+    e = R.expected(c, d, rbf=False)["y"]
+    assert torch.equal(e.vals[e.owned].view(1, -1), Fn.linear(xn, d.Wl.double()))
+    # SwiGLU on packed rows
+    c, d = _float_case(glu=True, kind="swiglu")
+    lin = Fn.linear(d.xl, d.Wl.double()).view(1, 3, 2, 16)
+    gate, up = lin[:, :, 0].reshape(1, -1), lin[:, :, 1].reshape(1, -1)
+    e = R.expected(c, d, rbf=False)["y"]
+    assert torch.equal(e.vals[e.owned].view(1, -1), Fn.silu(gate) * up)
+    e = R.expected(c, d, rbf=True)["y"]
+    ref = (Fn.silu(gate.to(BF).double()).to(BF).double() * up.to(BF).double()).to(BF).double()
+    assert torch.equal(e.vals[e.owned].view(1, -1), ref)
+    # x_delta
+    c, d = _float_case(delta=True)
+    d.dl = torch.randn(c.K, generator=R.gen(3)).float().double()
+    xp = (d.xl + d.dl.to(BF).double()).to(BF).double()
+    e = R.expected(c, d, rbf=False)
+    assert torch.equal(e["x_out"].vals[:c.K], xp[0]) and torch.equal(e["y"].vals[e["y"].owned].view(1, -1), Fn.linear(xp, d.Wl.double()))
+
+
+@pytest.mark.parametrize("mfma", [False, True])
+def test_lm_head_reference(mfma):
+    """logits, ban mask and partials: the best partial is the lowest-id arg-max of the masked logits; fully banned blocks say so"""
+    for c in R.lm_head_cases(nb=3, mfma=mfma):
+        d = R.build(c)
+        e = R.expected(c, d, rbf=True)
+        lg = Fn.linear(R.x_prime(c, d)[0], d.Wl.double()).to(BF).double()
+        lg[:, d.banl.bool()] = -R.INF
+        y = e["y"].vals.view(c.B + 1, -1)[:c.B, :c.N]
+        assert torch.equal(y, lg)
+        pv, pi = e["part_val"].vals.view(c.B + 1, -1)[:c.B], e["part_idx"].vals.view(c.B + 1, -1)[:c.B]
+        for b in range(c.B):
+            best = pv[b].max()
+            assert best == lg[b].max() and int(pi[b][pv[b] == best].min()) - c.idx_offset == int((lg[b] == best).nonzero()[0])
+        if c.ban == "workgroup":
+            assert bool((pv[:, 1:3] == -R.INF).all()) and bool((pi[:, 1:3] == R.NO_IDX).all()) and pv[0, 62] == -R.INF
+        if c.ban == "wave":
+            assert bool((pi[:, 1] == 31 + c.idx_offset).all())
+        if mfma:
+            assert bool((pv[:, c.nparts:] == -R.INF).all()) and bool((pi[:, c.nparts:] == R.NO_IDX).all()) and pv.shape[1] == c.part_bs
+        ties = sum(int(((lg[b] == lg[b].max()).sum() > 1)) for b in range(c.B))
+        print(f"[gemv] {c.name}: {ties} of {c.B} items have tied maxima")
+
+
+def test_probe_positions():
+    for c in R.valu_probe_cases((1, False, 4)) + R.valu_probe_cases((1, False, 16)) + R.valu_probe_cases((1, True, 4)):
+        pos = R.probe_positions(c)
+        assert pos.numel() == c.nout and int(pos.min()) >= 0 and int(pos.max()) < c.K
+        if c.nout >= c.K:
+            assert set(pos.tolist()) == set(range(c.K))
+            continue
+        assert pos.unique().numel() == pos.numel() and set(range(c.K - 16, c.K)) <= set(pos.tolist())
+        step = 8 * c.threads()
+        if step < c.K:
+            assert {step - 1, step, step + 7} <= set(pos.tolist())
+
+
+def _groups():
+    out = [("valu-" + R.inst_id(i), (lambda i=i: R.valu_plain_cases(i) + R.valu_norm_exact_cases(i) + R.valu_probe_cases(i))) for i in list(R.VALU_INST) + ["lm"]]
+    out.append(("valu-rest", lambda: R.lm_head_cases() + [c for i in R.DELTA_INST for c in R.delta_cases(i) + R.skip_cases(i)]))
+    for nb in R.VALU_NB:
+        out.append((f"valu-nb{nb}", lambda nb=nb: [c for i in R.BATCH_INST + ("lm",) for c in R.valu_plain_cases(i, nb) + R.valu_norm_exact_cases(i, nb) + R.valu_probe_cases(i, nb)]
+                    + R.lm_head_cases(nb)))
+    for nb in R.MFMA_NB:
+        out.append((f"mfma-nb{nb}", lambda nb=nb: R.mfma_ladder_cases(nb) + R.mfma_tile_cases(nb) + R.mfma_swiglu_cases(nb) + R.mfma_norm_cases(nb) + R.lm_head_cases(nb, mfma=True)))
+    return out
+
+
+@pytest.mark.parametrize("group", _groups(), ids=lambda g: g[0])
+def test_exactness_conditions(group):
+    """per case: max |acc| + max |res| < 2^24; SwiGLU pre-activations are multiples of 1/16 within +-20; the exact RMSNorm family gives
+    x' = +-norm_w for any rstd within 2^-11 of 1/2; the probe's two references differ on at most 2 % of the elements"""
+    worst = 0.0
+    for c in group[1]():
+        d = R.build(c)
+        e = R.expected(c, d, rbf=False)
+        Wb, xb = d.W.view(c.N + 1, c.ldw), d.x.view(c.B + 1, c.x_bs)
+        assert bool(torch.isnan(Wb[:, c.K:]).all()) and bool(torch.isnan(Wb[c.N]).all()) and bool(torch.isnan(xb[:, c.K:]).all()) and bool(torch.isnan(xb[c.B]).all())
+        if c.kind == "probe":
+            lo, hi = R.expected(c, d, rbf=False, scale=1 - R.DELTA)["y"], R.expected(c, d, rbf=False, scale=1 + R.DELTA)["y"]
+            share = float((lo.vals != hi.vals)[lo.owned].double().mean())
+            worst = max(worst, share)
+            assert share <= R.PROBE_CAP, (c.name, share)
+            mid = e["y"].vals
+            assert bool(((mid == lo.vals) | (mid == hi.vals)).all())
+            continue
+        res_max = float(d.rl.abs().max()) if d.rl is not None else 0.0
+        if c.kind == "swiglu":
+            y = e["y"]
+            for v in (y.pre[y.owned], y.up[y.owned]):
+                assert bool((v * 16 == torch.round(v * 16)).all()) and float(v.abs().max()) <= 20.0, (c.name, float(v.abs().max()))
+        else:
+            assert d.acc_max + res_max < 2.0 ** 24, c.name
+            assert bool((d.Wl.abs() <= 3).all()) and bool((d.Wl == d.Wl.round()).all())
+            if c.K >= 504 and not c.norm and not c.lm_head and not c.delta:          # most sums exceed 256: round_bf16 does something
+                y = e["y"]
+                assert float((y.vals[y.owned].abs() > 256).double().mean()) > 0.5, c.name
+        if c.norm == "exact":
+            a, b = R.x_prime(c, d, 1 - 2.0 ** -10)[0], R.x_prime(c, d, 1 + 2.0 ** -10)[0]    # rstd ~ 1/2: 2^-11 absolute either side
+            assert torch.equal(a, b) and torch.equal(a.abs(), d.gl.abs().expand_as(a)), c.name
+    if worst:
+        print(f"[gemv] {group[0]}: the probe's references differ on at most {100 * worst:.2f} % of a case's elements (cap 2 %)")

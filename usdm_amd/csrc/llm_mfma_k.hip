@@ -897,6 +897,7 @@ int mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st, const char* who,
   const bool hold = d.cpw <= CH;
   USDM_CHECK_ARG(!a.norm_w || (hold && a.K <= GAM_FLOATS && a.K % 4 == 0), "%s (matrix-core form): the fused RMSNorm needs K <= 4096", who);
   USDM_CHECK_ARG(!lmh || (a.part_idx && !glu), "%s: lm_head partial buffers", who);
+  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "%s (matrix-core form): swiglu needs N %% 32 == 0 (packed gate/up rows)", who);   // (else the last up rows lie past W)
   d.nout = glu ? a.N / 2 : a.N;
   d.rt = 16;
   d.ksplit = 1;
