@@ -731,6 +731,23 @@ typedef struct usdm_attn_verify_args {
 int usdm_attn_verify(const usdm_attn_verify_args* args, usdm_stream_t stream);
 int usdm_sizeof_attn_verify_args(void);
 
+/* The same for B slots x T rows in one launch (batched speculative decoding).  v describes slot 0 and the arrays:
+ * row b * T + i of qkv [B * T][qkv_ld] is the token at position pos[b] + i of slot b, slot b's caches start cache_bs ELEMENTS behind
+ * slot b - 1's (usdm_attn_decode's cache_bs), out is [B * T][out_ld], the partials [B][T][Hq][NSP] (po: x 128), pos and skip are [B]:
+ * skip[b] != 0 -> slot b writes nothing.  T is the same for every slot.  Grid (Hkv, NSP, B), the merge (Hq, T, B); workgroup
+ * (kh, s, b) runs usdm_attn_verify's workgroup (kh, s) on slot b's arrays - the same device function - so slot b's out rows and
+ * cache equal, bit for bit, usdm_attn_verify on that slot alone, and every point of the position-invariance contract holds per slot.
+ * Rows at positions >= ctx_max are neither appended nor computed: slot b's rows never reach slot b + 1's.
+ * Refused (error, no fall-back): B < 1, B * T > 16, cache_bs < Hkv * ctx_max * 128 or no multiple of 8, and everything
+ * usdm_attn_verify refuses. */
+typedef struct usdm_attn_verify_batch_args {
+  usdm_attn_verify_args v;
+  int32_t B;
+  int64_t cache_bs;
+} usdm_attn_verify_batch_args;
+int usdm_attn_verify_batch(const usdm_attn_verify_batch_args* args, usdm_stream_t stream);
+int usdm_sizeof_attn_verify_batch_args(void);
+
 /* The end of a speculative step, in place of usdm_argmax_final: pick, accept, commit, propose, embed - one launch, one workgroup.
  * Picks g_0 .. g_{T-1}: the arg-max of row i's partials part_val / part_idx [T][nparts] (ties to the lowest id, the reduction of
  * usdm_argmax_final; no candidate -> id 0), token = id + st->id_offset.  drafts[i], i = 1 .. T-1, are the tokens that were fed as
@@ -762,6 +779,22 @@ typedef struct usdm_spec_args {
 int usdm_spec_commit(const usdm_spec_args* args, const usdm_decode_state* st, const void* embed_table_bf16, int32_t Hd,
                      void* h_out_bf16, usdm_stream_t stream);
 int usdm_sizeof_spec_args(void);
+
+/* The same for the slots [slot_lo, slot_lo + n) of a batched state, one workgroup per slot.  st->batch = B is the
+ * number of slots the arrays hold (B * T <= 16): next_token / step / pos / done [B] (done is required), out_tokens [B][max_out],
+ * eos [B][8] (a stop block per slot, or NULL).  s describes slot 0 and the arrays: part_val / part_idx [B * T][nparts], drafts [B][8],
+ * limit [B], prompt [B][prompt_max], prompt_len [B], script [B][st->max_out] or NULL, counters [B][3]; params [4] is shared.  h_out is
+ * [B * T][Hd].  Workgroup b runs usdm_spec_commit's workgroup - the same device function - on slot b's rows b * T .. b * T + T - 1
+ * and words, so every buffer equals usdm_spec_commit applied slot by slot.  done[b] != 0 on entry: slot b changes nothing (idle
+ * slots are kept that way).  propose_only over a range of one slot gives an admitted request its first drafts and input rows.
+ * Refused: what usdm_spec_commit refuses, B < 1 or B * T > 16, a slot range outside [0, B), done == NULL. */
+typedef struct usdm_spec_batch_args {
+  usdm_spec_args s;
+  int32_t slot_lo, n;
+} usdm_spec_batch_args;
+int usdm_spec_commit_batch(const usdm_spec_batch_args* args, const usdm_decode_state* st, const void* embed_table_bf16, int32_t Hd,
+                           void* h_out_bf16, usdm_stream_t stream);
+int usdm_sizeof_spec_batch_args(void);
 
 /* ------------------------------------------------------------------------------------------------
  * One-shot peer-to-peer all-reduce for the tensor-parallel decode step (replaces the single-GPU

@@ -40,6 +40,8 @@ lib.usdm_kv_reorder.restype = C.c_int
 lib.usdm_kv_expand.restype = C.c_int         # (the prefix-cache entry point: likewise)
 lib.usdm_attn_verify.restype = C.c_int       # (the speculative-decoding entry points: likewise)
 lib.usdm_spec_commit.restype = C.c_int
+lib.usdm_attn_verify_batch.restype = C.c_int
+lib.usdm_spec_commit_batch.restype = C.c_int
 _exp = None
 
 
@@ -313,6 +315,14 @@ class SpecArgs(C.Structure):
     ]
 
 
+class AttnVerifyBatchArgs(C.Structure):
+    _fields_ = [("v", AttnVerifyArgs), ("B", C.c_int32), ("cache_bs", C.c_int64)]
+
+
+class SpecBatchArgs(C.Structure):
+    _fields_ = [("s", SpecArgs), ("slot_lo", C.c_int32), ("n", C.c_int32)]
+
+
 def check(rc, what=""):
     if rc != 0:
         raise UsdmError(f"{what} failed (rc={rc}): {lib.usdm_last_error().decode()}")
@@ -329,7 +339,8 @@ def _selfcheck():
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
                       ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs), ("beam", BeamArgs),
-                      ("kv_reorder", KvReorderArgs), ("kv_expand", KvExpandArgs), ("attn_verify", AttnVerifyArgs), ("spec", SpecArgs)):
+                      ("kv_reorder", KvReorderArgs), ("kv_expand", KvExpandArgs), ("attn_verify", AttnVerifyArgs), ("spec", SpecArgs),
+                      ("attn_verify_batch", AttnVerifyBatchArgs), ("spec_batch", SpecBatchArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

@@ -833,185 +833,34 @@ __device__ __forceinline__ int av_lo(int p, int window) { return (window > 0 && 
 
 template <int G, int MB>
 __global__ __launch_bounds__(256) void attn_verify_kernel(const usdm_attn_verify_args a) {
-  constexpr int M = MB * 16;
-  // scores [M][AV_SLD] f32; after the softmax the same bytes hold the V tile [AV_KT][AV_VLD] bf16
-  __shared__ __attribute__((aligned(16))) char raw[M * AV_SLD * 4 > AV_KT * AV_VLD * 2 ? M * AV_SLD * 4 : AV_KT * AV_VLD * 2];
-  __shared__ __attribute__((aligned(16))) bf16_t qb[M][AV_VLD];
-  __shared__ __attribute__((aligned(16))) bf16_t kn[AV_TMAX][128], vn[AV_TMAX][128];
-  __shared__ __attribute__((aligned(16))) bf16_t pb[M][AV_PLD];
-  static_assert(AV_KT * AV_VLD * 2 <= (int)sizeof(raw), "the V tile fits the score bytes");
-  float (*sc)[AV_SLD] = (float (*)[AV_SLD])raw;
-  bf16_t (*vs)[AV_VLD] = (bf16_t (*)[AV_VLD])raw;
-  if (a.skip && *a.skip) return;
-  const int kh = blockIdx.x, sp = blockIdx.y, NSP = gridDim.y;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, lc = lane >> 4;
-  const int pos = *a.pos;
-  if ((unsigned)pos >= (unsigned)a.ctx_max) return;
-  const int Tl = min(a.T, a.ctx_max - pos);      // rows at positions < ctx_max
-  const int last = pos + Tl - 1;
-  const int kbeg = sp * a.C;
-  if (kbeg > last) return;                       // past the live context
-  const int kend = min(kbeg + a.C, last + 1);    // keys [kbeg, kend)
-  const int tb0 = max(kbeg, av_lo(pos, a.window) & ~(AV_KT - 1));   // first tile any row sees a key of
-  const bf16_t* qkv = (const bf16_t*)a.qkv;
-  const bf16_t* Kc = (const bf16_t*)a.kcache + (int64_t)kh * a.ctx_max * 128;
-  const bf16_t* Vc = (const bf16_t*)a.vcache + (int64_t)kh * a.ctx_max * 128;
-  // ---- rope of the Tl x G q rows and the Tl k rows, the v rows as they are; dead q rows are zero
-  for (int it = tid; it < Tl * (G + 1) * 64; it += 256) {
-    const int i = it / ((G + 1) * 64), rem = it - i * ((G + 1) * 64);
-    const int hsel = rem >> 6, d = rem & 63;
-    const int p = pos + i;
-    const float c = bf2f(a.cos[(int64_t)p * 64 + d]), sn = bf2f(a.sin[(int64_t)p * 64 + d]);
-    const bf16_t* row = qkv + (int64_t)i * a.qkv_ld;
-    const bf16_t* src = hsel < G ? row + (kh * G + hsel) * 128 : row + (a.Hq + kh) * 128;
-    float o1, o2;
-    rope_pair(bf2f(src[d]), bf2f(src[d + 64]), c, sn, o1, o2);
-    if (hsel < G) { qb[i * G + hsel][d] = f2bf(o1); qb[i * G + hsel][d + 64] = f2bf(o2); }
-    else { kn[i][d] = f2bf(o1); kn[i][d + 64] = f2bf(o2); }
-  }
-  for (int it = tid; it < Tl * 128; it += 256) vn[it >> 7][it & 127] = qkv[(int64_t)(it >> 7) * a.qkv_ld + (a.Hq + a.Hkv + kh) * 128 + (it & 127)];
-  for (int it = tid; it < (M - Tl * G) * 128; it += 256) qb[Tl * G + (it >> 7)][it & 127] = 0;
-  __syncthreads();
-  if (sp == 0) {   // designated writer of the new cache rows (positions pos .. last < ctx_max)
-    bf16_t* kc = (bf16_t*)a.kcache + ((int64_t)kh * a.ctx_max + pos) * 128;
-    bf16_t* vc = (bf16_t*)a.vcache + ((int64_t)kh * a.ctx_max + pos) * 128;
-    for (int it = tid; it < Tl * 64; it += 256) {
-      ((unsigned*)kc)[it] = ((const unsigned*)&kn[0][0])[it];
-      ((unsigned*)vc)[it] = ((const unsigned*)&vn[0][0])[it];
-    }
-  }
-  // ---- scores
-  {
-    bf16x8 qf[MB][4];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) qf[mb][s] = __builtin_bit_cast(bf16x8, *(const u32x4*)&qb[mb * 16 + lr][32 * s + 8 * lc]);
-    for (int tb = tb0; tb < kend; tb += AV_KT) {
-      const int key = tb + 16 * wave + lr;
-      const bool own = key >= pos && key <= last;
-      const bf16_t* kp = Kc + (int64_t)min(key, a.ctx_max - 1) * 128 + 8 * lc;     // (in bounds whatever the key; unused when masked)
-      const bf16_t* op = &kn[own ? key - pos : 0][8 * lc];
-      f32x4 acc[MB];
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) acc[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-      u32x4 kg[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) kg[s] = *(const u32x4*)(kp + 32 * s);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const u32x4 ko = *(const u32x4*)(op + 32 * s);
-        u32x4 kv = own ? ko : kg[s];
-        if (key > last) kv = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[mb][s], __builtin_bit_cast(bf16x8, kv), acc[mb], 0, 0, 0);
-      }
-      const int kk = tb - kbeg + 16 * wave + lr;
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[mb * 16 + 4 * lc + r][kk] = acc[mb][r] * a.scale;
-    }
-  }
-  __syncthreads();
-  // ---- softmax: a wave per row, lanes over the split's keys in index order; P as bf16 (0 for a key the row does not see)
-  const int kk0 = tb0 - kbeg;
-  const int kkp = min(a.C, (kend - kbeg + AV_KT - 1) & ~(AV_KT - 1));      // whole tiles
-  for (int r = wave; r < M; r += 4) {
-    const bool live = r < Tl * G;
-    const int i = r / G, p = pos + i;
-    const int lo = av_lo(p, a.window);
-    float m = -1e30f;
-    for (int kk = kk0 + lane; kk < kkp; kk += 64) {
-      const int key = kbeg + kk;
-      if (live && key >= lo && key <= p) m = fmaxf(m, sc[r][kk]);
-    }
-    m = wave_max(m);
-    float l = 0.f;
-    for (int kk = kk0 + lane; kk < kkp; kk += 64) {
-      const int key = kbeg + kk;
-      float pe = 0.f;
-      if (live && key >= lo && key <= p) pe = __expf(sc[r][kk] - m);
-      l += pe;
-      pb[r][kk] = f2bf(pe);
-    }
-    l = wave_sum(l);
-    if (live && lane == 0) {
-      const int64_t o = ((int64_t)i * a.Hq + kh * G + (r - i * G)) * NSP + sp;
-      a.pm[o] = m;
-      a.pl[o] = l;
-    }
-  }
-  __syncthreads();
-  // ---- PV: the V tile through LDS (own rows from vn, keys past `last` zero), a wave per 32 d, tiles in ascending order
-  {
-    f32x4 acc[MB][2];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto ldv = [&](int tb, u32x4 (&v)[4]) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int q = tid + 256 * u, row = q >> 4, c = q & 15;
-        const int key = tb + row;
-        const bool own = key >= pos && key <= last;
-        const u32x4 g = *(const u32x4*)(Vc + (int64_t)min(key, a.ctx_max - 1) * 128 + c * 8);
-        const u32x4 o = *(const u32x4*)&vn[own ? key - pos : 0][c * 8];
-        v[u] = own ? o : g;
-        if (key > last) v[u] = u32x4{0u, 0u, 0u, 0u};
-      }
-    };
-    u32x4 cur[4], nxt[4];
-    if (tb0 < kend) ldv(tb0, cur);
-    for (int tb = tb0; tb < kend; tb += AV_KT) {
-      const bool more = tb + AV_KT < kend;
-      if (more) ldv(tb + AV_KT, nxt);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int q = tid + 256 * u;
-        *(u32x4*)&vs[q >> 4][(q & 15) * 8] = cur[u];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 pf[MB];
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) pf[mb] = __builtin_bit_cast(bf16x8, *(const u32x4*)&pb[mb * 16 + lr][tb - kbeg + 32 * ks + 8 * lc]);
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-          const int d = (2 * wave + nb) * 16 + lr;
-          u32x4 vv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            vv[e] = (unsigned)vs[32 * ks + 8 * lc + 2 * e][d] | ((unsigned)vs[32 * ks + 8 * lc + 2 * e + 1][d] << 16);
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[mb], __builtin_bit_cast(bf16x8, vv), acc[mb][nb], 0, 0, 0);
-        }
-      }
-      __syncthreads();
-      if (more) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
-      }
-    }
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = mb * 16 + 4 * lc + r;
-        if (row >= Tl * G) continue;
-        const int i = row / G;
-        float* po = a.po + (((int64_t)i * a.Hq + kh * G + (row - i * G)) * NSP + sp) * 128;
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) po[(2 * wave + nb) * 16 + lr] = acc[mb][nb][r];
-      }
-  }
+#include "attn_verify_body.h"
+}
+
+// slot b's view of a batched launch: the arrays of ba.v moved on by b slots (NSP splits per row and head in the partials)
+__device__ __forceinline__ usdm_attn_verify_args attn_verify_slot(const usdm_attn_verify_batch_args& ba, int b, int NSP) {
+  usdm_attn_verify_args a = ba.v;
+  const int64_t r0 = (int64_t)b * a.T, p0 = r0 * a.Hq * NSP;
+  a.qkv = (const bf16_t*)a.qkv + r0 * a.qkv_ld;
+  a.out = (bf16_t*)a.out + r0 * a.out_ld;
+  a.pos += b;
+  if (a.skip) a.skip += b;
+  a.kcache = (bf16_t*)a.kcache + b * ba.cache_bs;
+  a.vcache = (bf16_t*)a.vcache + b * ba.cache_bs;
+  a.pm += p0;
+  a.pl += p0;
+  a.po += p0 * 128;
+  return a;
+}
+
+// usdm_attn_verify_batch: grid (Hkv, NSP, B), workgroup (kh, sp, b) is usdm_attn_verify's workgroup (kh, sp) on slot b
+template <int G, int MB>
+__global__ __launch_bounds__(256) void attn_verify_batch_kernel(const usdm_attn_verify_batch_args ba) {
+  const usdm_attn_verify_args a = attn_verify_slot(ba, blockIdx.z, gridDim.y);
+#include "attn_verify_body.h"
 }
 
 // the merge of row i's partials over splits 0 .. p / C, p = *pos + i, in split order: attn_combine_kernel's arithmetic
-__global__ __launch_bounds__(128) void attn_verify_merge_kernel(const usdm_attn_verify_args a, int NSP) {
+__device__ __forceinline__ void attn_verify_merge_body(const usdm_attn_verify_args& a, int NSP) {
   if (a.skip && *a.skip) return;
   __shared__ float w[64];
   __shared__ float linv;
@@ -1030,25 +879,41 @@ __global__ __launch_bounds__(128) void attn_verify_merge_kernel(const usdm_attn_
   const float o = attn_merge_sum<4>(ns, w, [&](int s) { return po[s * 128]; });
   ((bf16_t*)a.out)[(int64_t)i * a.out_ld + hq * 128 + d] = f2bf(o * linv);
 }
+
+__global__ __launch_bounds__(128) void attn_verify_merge_kernel(const usdm_attn_verify_args a, int NSP) { attn_verify_merge_body(a, NSP); }
+
+// grid (Hq, T, B)
+__global__ __launch_bounds__(128) void attn_verify_merge_batch_kernel(const usdm_attn_verify_batch_args ba, int NSP) {
+  const usdm_attn_verify_args a = attn_verify_slot(ba, blockIdx.z, NSP);
+  attn_verify_merge_body(a, NSP);
+}
+
+// what both launchers refuse; name: the entry point, for the message
+int attn_verify_check(const char* name, const usdm_attn_verify_args* pa) {
+  USDM_CHECK_ARG(pa && pa->qkv && pa->pos && pa->cos && pa->sin && pa->kcache && pa->vcache && pa->pm && pa->pl && pa->po && pa->out,
+                 "%s: null args", name);
+  const usdm_attn_verify_args& a = *pa;
+  USDM_CHECK_ARG(a.T >= 1 && a.T <= AV_TMAX, "%s: T = %d outside 1 .. %d", name, a.T, AV_TMAX);
+  USDM_CHECK_ARG(a.Hkv > 0 && a.Hq > 0 && a.Hq % a.Hkv == 0 && a.ctx_max > 0 && a.window >= 0, "%s: heads, ctx_max > 0, window >= 0", name);
+  USDM_CHECK_ARG(a.C >= AV_KT && a.C <= AV_CMAX && a.C % AV_KT == 0, "%s: C = %d must be a multiple of the key tile %d in %d .. %d", name,
+                 a.C, AV_KT, AV_KT, AV_CMAX);
+  const int NSP = cdiv(a.ctx_max, a.C);
+  USDM_CHECK_ARG(NSP <= 64, "%s: ctx_max / C = %d splits exceed 64", name, NSP);
+  USDM_CHECK_ARG(((uintptr_t)a.kcache & 15) == 0 && ((uintptr_t)a.vcache & 15) == 0, "%s: the caches must be 16-byte aligned", name);
+  USDM_CHECK_ARG(((uintptr_t)a.qkv & 3) == 0 && ((uintptr_t)a.out & 3) == 0 && ((uintptr_t)a.pos & 3) == 0 && ((uintptr_t)a.pm & 3) == 0 &&
+                 ((uintptr_t)a.pl & 3) == 0 && ((uintptr_t)a.po & 3) == 0 && (!a.skip || ((uintptr_t)a.skip & 3) == 0),
+                 "%s: qkv, out, pos, skip and the partials must be 4-byte aligned", name);
+  USDM_CHECK_ARG(a.qkv_ld >= (int64_t)(a.Hq + 2 * a.Hkv) * 128 && a.qkv_ld % 2 == 0 && a.out_ld >= (int64_t)a.Hq * 128,
+                 "%s: qkv_ld even and >= (Hq + 2 Hkv) * 128, out_ld >= Hq * 128", name);
+  return 0;
+}
 }  // namespace
 
 extern "C" int usdm_sizeof_attn_verify_args(void) { return (int)sizeof(usdm_attn_verify_args); }
 extern "C" int usdm_attn_verify(const usdm_attn_verify_args* pa, usdm_stream_t stream) {
-  USDM_CHECK_ARG(pa && pa->qkv && pa->pos && pa->cos && pa->sin && pa->kcache && pa->vcache && pa->pm && pa->pl && pa->po && pa->out,
-                 "usdm_attn_verify: null args");
+  if (int rc = attn_verify_check("usdm_attn_verify", pa)) return rc;
   const usdm_attn_verify_args& a = *pa;
-  USDM_CHECK_ARG(a.T >= 1 && a.T <= AV_TMAX, "usdm_attn_verify: T = %d outside 1 .. %d", a.T, AV_TMAX);
-  USDM_CHECK_ARG(a.Hkv > 0 && a.Hq > 0 && a.Hq % a.Hkv == 0 && a.ctx_max > 0 && a.window >= 0, "usdm_attn_verify: heads, ctx_max > 0, window >= 0");
-  USDM_CHECK_ARG(a.C >= AV_KT && a.C <= AV_CMAX && a.C % AV_KT == 0, "usdm_attn_verify: C = %d must be a multiple of the key tile %d in %d .. %d",
-                 a.C, AV_KT, AV_KT, AV_CMAX);
   const int NSP = cdiv(a.ctx_max, a.C);
-  USDM_CHECK_ARG(NSP <= 64, "usdm_attn_verify: ctx_max / C = %d splits exceed 64", NSP);
-  USDM_CHECK_ARG(((uintptr_t)a.kcache & 15) == 0 && ((uintptr_t)a.vcache & 15) == 0, "usdm_attn_verify: the caches must be 16-byte aligned");
-  USDM_CHECK_ARG(((uintptr_t)a.qkv & 3) == 0 && ((uintptr_t)a.out & 3) == 0 && ((uintptr_t)a.pos & 3) == 0 && ((uintptr_t)a.pm & 3) == 0 &&
-                 ((uintptr_t)a.pl & 3) == 0 && ((uintptr_t)a.po & 3) == 0 && (!a.skip || ((uintptr_t)a.skip & 3) == 0),
-                 "usdm_attn_verify: qkv, out, pos, skip and the partials must be 4-byte aligned");
-  USDM_CHECK_ARG(a.qkv_ld >= (int64_t)(a.Hq + 2 * a.Hkv) * 128 && a.qkv_ld % 2 == 0 && a.out_ld >= (int64_t)a.Hq * 128,
-                 "usdm_attn_verify: qkv_ld even and >= (Hq + 2 Hkv) * 128, out_ld >= Hq * 128");
   const int G = a.Hq / a.Hkv;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a.Hkv, NSP);
@@ -1060,6 +925,32 @@ extern "C" int usdm_attn_verify(const usdm_attn_verify_args* pa, usdm_stream_t s
     return rc;
   USDM_LAUNCH_CHECK();
   hipLaunchKernelGGL(attn_verify_merge_kernel, dim3(a.Hq, a.T), dim3(128), 0, st, a, NSP);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int usdm_sizeof_attn_verify_batch_args(void) { return (int)sizeof(usdm_attn_verify_batch_args); }
+extern "C" int usdm_attn_verify_batch(const usdm_attn_verify_batch_args* pb, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pb, "usdm_attn_verify_batch: null args");
+  if (int rc = attn_verify_check("usdm_attn_verify_batch", &pb->v)) return rc;
+  const usdm_attn_verify_args& a = pb->v;
+  USDM_CHECK_ARG(pb->B >= 1 && pb->B * a.T <= 16, "usdm_attn_verify_batch: B = %d slots of T = %d rows: B >= 1 and B * T <= 16", pb->B, a.T);
+  USDM_CHECK_ARG(pb->cache_bs >=(int64_t)a.Hkv * a.ctx_max * 128,
+                 "usdm_attn_verify_batch: cache_bs = %lld is smaller than one slot's cache of Hkv * ctx_max * 128 = %lld elements",
+                 (long long)pb->cache_bs, (long long)a.Hkv * a.ctx_max * 128);
+  USDM_CHECK_ARG(pb->cache_bs % 8 == 0, "usdm_attn_verify_batch: cache_bs must keep every slot's cache 16-byte aligned");
+  const int NSP = cdiv(a.ctx_max, a.C);
+  const int G = a.Hq / a.Hkv;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(a.Hkv, NSP, pb->B);
+  if (int rc = da_dispatch_g("usdm_attn_verify_batch", G, [&](auto GC) {
+        constexpr int g = decltype(GC)::value;
+        if (a.T * g <= 16) hipLaunchKernelGGL((attn_verify_batch_kernel<g, 1>), grid, dim3(256), 0, st, *pb);
+        else hipLaunchKernelGGL((attn_verify_batch_kernel<g, 2>), grid, dim3(256), 0, st, *pb);
+      }))
+    return rc;
+  USDM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attn_verify_merge_batch_kernel, dim3(a.Hq, a.T, pb->B), dim3(128), 0, st, *pb, NSP);
   USDM_LAUNCH_CHECK();
   return 0;
 }

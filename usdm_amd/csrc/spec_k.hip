@@ -15,131 +15,70 @@ __device__ __forceinline__ int spec_hist(const usdm_spec_args& a, const usdm_dec
 
 __global__ __launch_bounds__(256) void spec_commit_kernel(const usdm_spec_args a, const usdm_decode_state st, const bf16_t* E, int Hd,
                                                           bf16_t* h_out) {
-  __shared__ float sv[256];
-  __shared__ int si[256];
-  __shared__ int s_g[SP_TMAX], s_d[SP_TMAX];
-  __shared__ int s_step, s_next, s_stop;
-  const int tid = threadIdx.x, T = a.T;
-  if (st.done && st.done[0]) return;
-  if (!a.propose_only) {
-    // ---- picks: row i's arg-max over its partials, usdm_argmax_final's reduction
-    for (int i = 0; i < T; ++i) {
-      const float* pv = a.part_val + (int64_t)i * a.nparts;
-      const int* pi = a.part_idx + (int64_t)i * a.nparts;
-      float bv = -INFINITY;
-      int bi = PICK_NO_ID;
-      for (int k = tid; k < a.nparts; k += 256) {
-        const float v = pv[k];
-        const int id = pi[k];
-        if (pick_better(v, id, bv, bi)) { bv = v; bi = id; }
-      }
-      pick_block_best<256>(sv, si, bv, bi);
-      if (tid == 0) s_g[i] = (si[0] == PICK_NO_ID ? 0 : si[0]) + st.id_offset;
-      __syncthreads();
-    }
-    // ---- accept and commit (one thread: at most 8 tokens)
-    if (tid == 0) {
-      const int s0 = st.step[0];
-      const int lim = min(*a.limit, st.max_out);
-      int stop = 0;
-      if (s0 >= lim) {
-        if (st.done) st.done[0] = 1;
-        stop = 1;
-      } else {
-        int n = 0, drafted = 0;
-        while (n < T - 1 && a.drafts[n + 1] == s_g[n]) ++n;
-        for (int i = 1; i < T; ++i) drafted += a.drafts[i] >= 0;
-        const int neos = st.eos ? min(st.eos[0], 6) : 0, mn = st.eos ? st.eos[1] : 0;
-        int m = 0, done = 0;
-        for (int i = 0; i <= n && s0 + m < lim; ++i) {
-          const int tok = s_g[i];
-          st.out_tokens[s0 + m] = tok;
-          ++m;
-          bool hit = false;
-          for (int e = 0; e < neos; ++e) hit |= (st.eos[2 + e] == tok);
-          if (hit && s0 + m >= mn) { done = 1; break; }
-        }
-        if (s0 + m >= lim) done = 1;
-        st.step[0] = s0 + m;
-        st.pos[0] = st.pos[0] + m;
-        st.next_token[0] = st.out_tokens[s0 + m - 1];
-        if (done && st.done) st.done[0] = 1;
-        a.counters[0] += 1;
-        a.counters[1] += drafted;
-        a.counters[2] += m - 1;
-      }
-      s_stop = stop;
-    }
-    __syncthreads();
-    if (s_stop) return;
-  }
-  if (tid == 0) { s_step = st.step[0]; s_next = st.next_token[0]; }
-  if (tid < SP_TMAX) s_d[tid] = -1;
-  __syncthreads();
-  // ---- propose the next step's drafts
-  const int step = min(max(s_step, 0), st.max_out);
-  const int P = min(max(*a.prompt_len, 0), a.prompt_max);
-  const int Lh = P + step;
-  if (a.script && a.params[2]) {
-    if (tid >= 1 && tid < T) {
-      const int j = step + tid - 1;
-      s_d[tid] = j < st.max_out ? a.script[j] : -1;
-    }
-  } else {
-    const int nmax = min(a.params[0], SP_NMAX), nmin = max(a.params[1], 1);
-    for (int n = nmax; n >= nmin; --n) {
-      if (Lh < n + 1) continue;
-      int best = -1;
-      for (int j = tid; j <= Lh - n - 1; j += 256) {      // ascending: the thread's last match is its most recent
-        bool eq = true;
-        for (int e = 0; e < n && eq; ++e) eq = spec_hist(a, st, P, j + e) == spec_hist(a, st, P, Lh - n + e);
-        if (eq) best = j;
-      }
-      si[tid] = best;
-      __syncthreads();
-      for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) si[tid] = max(si[tid], si[tid + s]);
-        __syncthreads();
-      }
-      const int jb = si[0];
-      __syncthreads();
-      if (jb < 0) continue;
-      if (tid >= 1 && tid < T) {
-        const int j = jb + n + tid - 1;
-        s_d[tid] = j < Lh ? spec_hist(a, st, P, j) : -1;
-      }
-      break;
-    }
-  }
-  __syncthreads();
-  if (tid >= 1 && tid < T) {
-    int d = s_d[tid];
-    if (d - st.id_offset < 0 || d - st.id_offset >= a.V) d = -1;
-    s_d[tid] = d;
-    a.drafts[tid] = d;
-  }
-  __syncthreads();
-  // ---- the next step's input rows: the token to continue from, then the drafts (no draft: the row of id 0, its pick is ignored)
-  for (int i = 0; i < T; ++i) {
-    const int tok = i == 0 ? s_next : (s_d[i] >= 0 ? s_d[i] : st.id_offset);
-    pick_embed_row<256>(E, tok, Hd, h_out + (int64_t)i * Hd);
-  }
+#include "spec_commit_body.h"
+}
+
+// usdm_spec_commit_batch: workgroup i is usdm_spec_commit's on slot b = slot_lo + i - the arrays of ba.s and st moved on by b slots
+__global__ __launch_bounds__(256) void spec_commit_batch_kernel(const usdm_spec_batch_args ba, const usdm_decode_state bst, const bf16_t* E,
+                                                                int Hd, bf16_t* h_out) {
+  const int b = ba.slot_lo + blockIdx.x;
+  usdm_spec_args a = ba.s;
+  usdm_decode_state st = bst;
+  const int64_t r0 = (int64_t)b * a.T;
+  if (a.part_val) { a.part_val += r0 * a.nparts; a.part_idx += r0 * a.nparts; }
+  a.drafts += b * SP_TMAX;
+  a.limit += b;
+  if (a.prompt) a.prompt += (int64_t)b * a.prompt_max;
+  a.prompt_len += b;
+  if (a.script) a.script += (int64_t)b * st.max_out;
+  a.counters += b * 3;
+  st.next_token += b;
+  st.out_tokens += (int64_t)b * st.max_out;
+  st.step += b;
+  st.pos += b;
+  st.done += b;
+  if (st.eos) st.eos += b * 8;
+  h_out += r0 * Hd;
+#include "spec_commit_body.h"
+}
+
+// what both launchers refuse; name: the entry point, for the message
+int spec_commit_check(const char* name, const usdm_spec_args* pa, const usdm_decode_state* st, const void* embed_table, int Hd, const void* h_out) {
+  USDM_CHECK_ARG(pa && st && embed_table && h_out, "%s: null args", name);
+  const usdm_spec_args& a = *pa;
+  USDM_CHECK_ARG(a.T >= 1 && a.T <= SP_TMAX, "%s: T = %d outside 1 .. %d", name, a.T, SP_TMAX);
+  USDM_CHECK_ARG(st->next_token && st->out_tokens && st->step && st->pos && st->max_out > 0, "%s: decode state incomplete", name);
+  USDM_CHECK_ARG(a.drafts && a.limit && a.prompt_len && a.params && a.counters && (a.prompt || a.prompt_max == 0) && a.prompt_max >= 0,
+                 "%s: drafts, limit, prompt, prompt_len, params and counters are required", name);
+  USDM_CHECK_ARG(a.propose_only || (a.part_val && a.part_idx && a.nparts > 0), "%s: arg-max partials missing", name);
+  USDM_CHECK_ARG(a.V > 0 && Hd > 0 && Hd % 8 == 0, "%s: V > 0, Hd a positive multiple of 8", name);
+  return 0;
 }
 }  // namespace
 
 extern "C" int usdm_sizeof_spec_args(void) { return (int)sizeof(usdm_spec_args); }
 extern "C" int usdm_spec_commit(const usdm_spec_args* pa, const usdm_decode_state* st, const void* embed_table, int32_t Hd, void* h_out,
                                 usdm_stream_t stream) {
-  USDM_CHECK_ARG(pa && st && embed_table && h_out, "usdm_spec_commit: null args");
+  if (int rc = spec_commit_check("usdm_spec_commit", pa, st, embed_table, Hd, h_out)) return rc;
   const usdm_spec_args& a = *pa;
-  USDM_CHECK_ARG(a.T >= 1 && a.T <= SP_TMAX, "usdm_spec_commit: T = %d outside 1 .. %d", a.T, SP_TMAX);
   USDM_CHECK_ARG(st->batch <= 1, "usdm_spec_commit: one sequence only (batch = %d)", st->batch);
-  USDM_CHECK_ARG(st->next_token && st->out_tokens && st->step && st->pos && st->max_out > 0, "usdm_spec_commit: decode state incomplete");
-  USDM_CHECK_ARG(a.drafts && a.limit && a.prompt_len && a.params && a.counters && (a.prompt || a.prompt_max == 0) && a.prompt_max >= 0,
-                 "usdm_spec_commit: drafts, limit, prompt, prompt_len, params and counters are required");
-  USDM_CHECK_ARG(a.propose_only || (a.part_val && a.part_idx && a.nparts > 0), "usdm_spec_commit: arg-max partials missing");
-  USDM_CHECK_ARG(a.V > 0 && Hd > 0 && Hd % 8 == 0, "usdm_spec_commit: V > 0, Hd a positive multiple of 8");
   hipLaunchKernelGGL(spec_commit_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, *st, (const bf16_t*)embed_table, Hd, (bf16_t*)h_out);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int usdm_sizeof_spec_batch_args(void) { return (int)sizeof(usdm_spec_batch_args); }
+extern "C" int usdm_spec_commit_batch(const usdm_spec_batch_args* pb, const usdm_decode_state* st, const void* embed_table, int32_t Hd,
+                                      void* h_out, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pb, "usdm_spec_commit_batch: null args");
+  if (int rc = spec_commit_check("usdm_spec_commit_batch", &pb->s, st, embed_table, Hd, h_out)) return rc;
+  USDM_CHECK_ARG(st->batch >= 1 && st->batch * pb->s.T <= SP_NMAX, "usdm_spec_commit_batch: a state of %d slots with T = %d rows each: 1 .. 16 rows",
+                 st->batch, pb->s.T);
+  USDM_CHECK_ARG(pb->slot_lo >= 0 && pb->n >= 1 && pb->slot_lo + pb->n <= st->batch, "usdm_spec_commit_batch: slots [%d, %d) outside the state's %d",
+                 pb->slot_lo, pb->slot_lo + pb->n, st->batch);
+  USDM_CHECK_ARG(st->done, "usdm_spec_commit_batch: the per-slot done words are required");
+  hipLaunchKernelGGL(spec_commit_batch_kernel, dim3(pb->n), dim3(256), 0, (hipStream_t)stream, *pb, *st, (const bf16_t*)embed_table, Hd,
+                     (bf16_t*)h_out);
   USDM_LAUNCH_CHECK();
   return 0;
 }

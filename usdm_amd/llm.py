@@ -42,8 +42,8 @@ from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
 from .prefix import reusable_past
 from .quant import Fp8Weight, Mxfp4Weight, check_kv_cache_dtype
-from .slots import (CHUNK, BeamSlots, DecodeSlots, TokenLogprobs, edit_buffers, logprob_buffers, penalty_buffers, read_logprobs,
-                    seed_edits, seed_penalties)
+from .slots import (CHUNK, NO_CANDIDATE_IDX, BeamSlots, DecodeSlots, SpecSlots, TokenLogprobs, edit_buffers, logprob_buffers, penalty_buffers,
+                    read_logprobs, seed_edits, seed_penalties, stop_index)
 
 MISTRAL_7B_USDM = dict(vocab_size=42003, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
                        num_attention_heads=32, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-5,
@@ -65,9 +65,6 @@ def vocab_shard(V, rank, tp):
     v0 = min(V, rank * Vloc)
     v1 = min(V, v0 + Vloc)
     return Vloc, v0, v1, ops.gemv_nblocks(Vloc)
-
-
-NO_CANDIDATE_IDX = 0x7fffffff
 
 
 def agree_seed(seed, group, rank, device=None):
@@ -110,11 +107,6 @@ def stop_ids(eos_token_id):
     if eos_token_id is None:
         return set()
     return set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])
-
-
-def stop_index(toks, stops, min_new):
-    """How many of `toks` a sequence keeps when it ends at its first stop id that is at least its min_new-th token; None: no stop."""
-    return next((i + 1 for i, t in enumerate(toks) if t in stops and i + 1 >= min_new), None)
 
 
 def check_logprobs(logprobs):
@@ -388,6 +380,7 @@ class USDMForCausalLM:
         # speculative greedy decoding: the device words of usdm_spec_commit, the rows, plan and graph per T, all built at
         # first use (_spec_state); generate(num_speculative_tokens=None / 0) touches none of it
         self._spec = None
+        self._spec_batches = {}        # B -> slots.SpecSlots: generate_batch(num_speculative_tokens=k), serving
         self.last_spec_stats = None    # generate(num_speculative_tokens=k): dict(steps=, drafted=, accepted=) of the last call
         # usdm_attn_verify's keys per split: a plan constant (fixed absolute key ranges).  Reasoned, not measured: 128 keys x 2 x 256 B
         # = 64 KB per workgroup, 5 .. 28 splits x 8 kv heads over the 600 .. 3 500 rows of an utterance, at most one per CU; 256 where
@@ -1183,6 +1176,68 @@ class USDMForCausalLM:
             sp["steps"][T] = self._graphed(self._build_decode_spec(T))
         return sp["steps"][T]
 
+    # ------------------------------------------------------------------ batched speculative decoding
+    def spec_slots(self, B):
+        """The B slots of batched speculative decoding (slots.SpecSlots), built at first use and kept."""
+        if B not in self._spec_batches:
+            self._spec_batches[B] = SpecSlots(self, B, step_kind())
+        return self._spec_batches[B]
+
+    def _check_spec_shape(self, k):
+        """ValueError where this model's step or context cannot take k drafts"""
+        if k + 1 > self.max_batch():
+            raise ValueError(f"num_speculative_tokens={k}: a decode step of this model takes at most {self.max_batch()} rows")
+        if -(-self.ctx_max // self.spec_split) > 64 or self.spec_split % ops.ATTN_VERIFY_TILE or not 0 < self.spec_split <= ops.ATTN_VERIFY_CMAX:
+            raise ValueError(f"speculative decoding: ctx_max = {self.ctx_max} with {self.spec_split} keys per split (a multiple of "
+                             f"{ops.ATTN_VERIFY_TILE} up to {ops.ATTN_VERIFY_CMAX}, at most 64 splits) is not supported")
+
+    def spec_group(self, k):
+        """Sequences per speculative step with k drafts each: the rows of a step shared out in slots of k + 1"""
+        return self.max_batch() // (k + 1)
+
+    def _build_decode_spec_batch(self, B, T):
+        """One speculative step of the B speculative slots (spec_slots(B)) x T rows each (row b * T + i: slot b's token at position pos[b] + i):
+        _layers with the batched projections over B * T rows (weights streamed once; <= 4 rows on the VALU form, 5 .. 16 on the matrix
+        cores), usdm_attn_verify_batch on the slots' caches, the lm_head in batched arg-max mode, usdm_spec_commit_batch.  Slots with
+        done != 0 are skipped by the attention and the commit.  One plan, one graph per (B, T)."""
+        dev, bf = self.device, torch.bfloat16
+        H, d, L, Hq, Hkv, I, nq = self._dims()
+        ss, n = self.spec_slots(B), B * T
+        if n > self.max_batch():
+            raise ValueError(f"{B} slots of {T} rows: a decode step of this model takes at most {self.max_batch()} rows")
+        r = ss.spec_rows(T)
+        rec = _Segments()
+        Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
+        h, qkv, ao, act = r["h"], Z(n, nq), Z(n, Hq * d), Z(n, I)
+        nsp = ops.attn_verify_splits(self.ctx_max, self.spec_split)
+        pm, pl, po = Z(n * Hq * nsp, dt=torch.float32), Z(n * Hq * nsp, dt=torch.float32), Z(n * Hq * nsp * d, dt=torch.float32)
+        gemv, ks = self._batch_gemv(n, rec)
+
+        def attn(l):
+            ops.attn_verify_batch(qkv, ss.pos, self.cos, self.sin, ss.kc[0, l], ss.vc[0, l], pm, pl, po, ao, B=B, T=T, Hq=Hq, Hkv=Hkv,
+                                  ctx_max=self.ctx_max, C=self.spec_split, scale=d ** -0.5, cache_bs=L * Hkv * self.ctx_max * d,
+                                  window=self.window, skip=ss.done, plan=rec.plan)
+
+        self._layers(rec, gemv, attn, h, qkv, ao, act, "fused", n=n * H, down_kw=dict(ks=ks))
+        gemv(self.W["lm_head"], h, N=self.v1 - self.v0, K=H, norm_w=self.W["norm"], eps=self.cfg["rms_norm_eps"], ban=self.ban,
+             part_val=r["pv"], part_idx=r["pi"], idx_offset=self.v0, part_bs=self.nparts, y_bs=0)
+        ss.commit(T, rec.plan)
+        return rec.finish()[0]
+
+    def _generate_spec_group(self, ids_list, limits, spec, scripts, bad_words_ids, eos_token_id, min_new_tokens):
+        """A group of 2 .. max_batch() // (k + 1) sequences on the speculative slots: per-slot prefill, then the step of B x (k + 1)
+        rows replayed in chunks (SpecSlots.serve).  -> (the sequences, their dict(steps=, drafted=, accepted=))"""
+        k, lookup_max, lookup_min = spec
+        ss = self.spec_slots(len(ids_list))
+        self.load_ban(bad_words_ids)
+        ss.set_lookup(lookup_max, lookup_min, scripts is not None)
+        stops = stop_ids(eos_token_id)
+        reqs = [dict(ids=ids[0], limit=lim, stops=stops, min_new=min_new_tokens, script=None if scripts is None else scripts[b])
+                for b, (ids, lim) in enumerate(zip(ids_list, limits))]
+        res, _ = ss.serve(reqs, k + 1)
+        outs = [torch.cat([ids[0], torch.tensor(toks, dtype=torch.long, device=ids.device)]).unsqueeze(0) for ids, (toks, _) in zip(ids_list, res)]
+        return outs, [st for _, st in res]
+
     MAX_BATCH = 16      # sequences per decode step (usdm_gemv_batch: VALU form up to 4, matrix-core form up to 16)
 
     def max_batch(self):
@@ -1204,7 +1259,7 @@ class USDMForCausalLM:
     @torch.no_grad()
     def generate_batch(self, input_ids_list, max_new_tokens, bad_words_ids=None, eos_token_id=None, min_new_tokens=0, group=None,
                        logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None,
-                       no_repeat_ngram_size=0):
+                       no_repeat_ngram_size=0, num_speculative_tokens=None, prompt_lookup_max=3, prompt_lookup_min=1, _spec_script=None):
         """Greedy generation of several utterances in lockstep (the serving-side batching of inference_vllm.py:109-125): up to
         `group` (default 16) sequences per step, longer lists run in groups.  Each prompt is prefilled on its own; every decode
         step then streams the weights once for the whole group.  Groups of <= 4 run on the VALU kernel and equal generate() per
@@ -1218,7 +1273,18 @@ class USDMForCausalLM:
         where it changes nothing.
         On a model built with enable_prefix_caching=True every prompt reuses the rows of the longest prefix (>= 16 tokens) that a slot
         of the group's buffers holds from an earlier prefill, and prefills the rest (DecodeSlots.admit; self.stats counts prefix_hits,
-        prefix_rows_reused, prefix_copies, prefill_rows); bf16 cache: the same ids and log-probabilities, bit for bit."""
+        prefix_rows_reused, prefix_copies, prefill_rows); bf16 cache: the same ids and log-probabilities, bit for bit.
+        num_speculative_tokens=k in 1 .. 7 (None / 0: this call is what it is without the argument, nothing is built): batched
+        speculative greedy decoding (DESIGN.md 8k-2; see generate()).  The list runs in groups of max_batch() // (k + 1) sequences
+        (`group`, if given, caps that too); every step verifies k drafts of EVERY sequence of the group in one pass over the weights:
+        B x (k + 1) rows.  A group of one - a list of one, the last of an odd list, a model whose step has no room for two (mxfp4 / VALU
+        fp8 weights with k > 1) - runs generate()'s single-sequence path.  The ids do not depend on the drafts; at B * (k + 1) <= 4 rows
+        they equal generate(num_speculative_tokens=k) bit for bit, above they are equal up to near-ties (the matrix cores).
+        max_new_tokens may then be a list with one value per sequence.  self.last_spec_stats = [dict(steps=, drafted=, accepted=)] per
+        sequence.  _spec_script (tests, tools/spec_batch_rate.py): one script per sequence.  Refused as in generate()
+        (spec.check_spec_call), and (NotImplementedError) groups of two or more on a model built with enable_prefix_caching=True."""
+        from .spec import check_spec_args, check_spec_call
+        spec = check_spec_args(num_speculative_tokens, prompt_lookup_max, prompt_lookup_min)
         lpk = check_logprobs(logprobs)
         n = len(input_ids_list)
         pens = [check_penalties(*k) for k in zip(*(_per_sequence(k, n) for k in (repetition_penalty, presence_penalty, frequency_penalty)))]
@@ -1226,11 +1292,47 @@ class USDMForCausalLM:
             check_min_p(v)
         V = self.cfg["vocab_size"]
         edits = [check_edits(lb, ng, V) for lb, ng in zip(_per_sequence(logit_bias, n), _per_sequence(no_repeat_ngram_size, n))]
+        if spec is not None:
+            check_spec_call(False, lpk, next((p for p in pens if p is not None), None), next((e for e in edits if e is not None), None),
+                            any(_per_sequence(min_p, n)), tensor_parallel=self.tp_path, kv_cache_fp8=self.kv8)
+            return self._generate_batch_spec(input_ids_list, max_new_tokens, spec, _spec_script, bad_words_ids, eos_token_id, min_new_tokens, group)
         group = self.max_batch() if group is None else max(1, min(int(group), self.max_batch()))
         outs, self.last_logprobs = [], (None if lpk is None else [])
         for g0 in range(0, n, group):
             outs += self._generate_group(input_ids_list[g0:g0 + group], max_new_tokens, bad_words_ids, eos_token_id, min_new_tokens, lpk,
                                          pens[g0:g0 + group], edits[g0:g0 + group])
+        return outs
+
+    def _generate_batch_spec(self, ids_list, max_new_tokens, spec, scripts, bad_words_ids, eos_token_id, min_new_tokens, group=None):
+        """generate_batch(num_speculative_tokens=k): the groups of spec_group(k) sequences; a group of one is generate()'s call"""
+        k, lookup_max, lookup_min = spec
+        n = len(ids_list)
+        self._check_spec_shape(k)
+        if scripts is not None and len(scripts) != n:
+            raise ValueError("_spec_script: one script per sequence")
+        for ids in ids_list:
+            if ids.dim() != 2 or ids.shape[0] != 1:
+                raise ValueError("every prompt must be a LongTensor of shape [1, L]")
+        per = _per_sequence(max_new_tokens, n)
+        size = max(1, self.spec_group(k) if group is None else min(int(group), self.spec_group(k)))
+        outs, stats = [], []
+        for g0 in range(0, n, size):
+            grp = ids_list[g0:g0 + size]
+            room = self.ctx_max - max(int(ids.shape[1]) for ids in grp)      # (the group's common bound, as _generate_group's)
+            limits = [min(mx, room, self.max_out) for mx in per[g0:g0 + size]]
+            sc = None if scripts is None else scripts[g0:g0 + size]
+            if max(limits) <= 0:
+                outs += [ids.clone() for ids in grp]
+                stats += [dict(steps=0, drafted=0, accepted=0) for _ in grp]
+            elif len(grp) == 1:
+                outs.append(self.generate(grp[0], max_new_tokens=limits[0], bad_words_ids=bad_words_ids, eos_token_id=eos_token_id,
+                                          min_new_tokens=min_new_tokens, num_speculative_tokens=k, prompt_lookup_max=lookup_max,
+                                          prompt_lookup_min=lookup_min, _spec_script=None if sc is None else sc[0]))
+                stats.append(self.last_spec_stats)
+            else:
+                res, st = self._generate_spec_group(grp, limits, spec, sc, bad_words_ids, eos_token_id, min_new_tokens)
+                outs, stats = outs + res, stats + st
+        self.last_spec_stats = stats
         return outs
 
     def reset_prefix_cache(self):
@@ -1510,11 +1612,7 @@ class USDMForCausalLM:
             raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1, as the reference calls it)")
         if spec is not None:
             check_spec_call(bool(do_sample) and top_k != 1, lpk, pen, edt, min_p, _logits_hook, num_beams, self.tp_path, self.kv8)
-            if spec[0] + 1 > self.max_batch():
-                raise ValueError(f"num_speculative_tokens={spec[0]}: a decode step of this model takes at most {self.max_batch()} rows")
-            if -(-self.ctx_max // self.spec_split) > 64 or self.spec_split % ops.ATTN_VERIFY_TILE or not 0 < self.spec_split <= ops.ATTN_VERIFY_CMAX:
-                raise ValueError(f"speculative decoding: ctx_max = {self.ctx_max} with {self.spec_split} keys per split (a multiple of "
-                                 f"{ops.ATTN_VERIFY_TILE} up to {ops.ATTN_VERIFY_CMAX}, at most 64 splits) is not supported")
+            self._check_spec_shape(spec[0])
         if num_beams is not None and num_beams != 1:
             from .beam import check_beam_args, check_beam_call
             eos_list = list(dict.fromkeys(int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else

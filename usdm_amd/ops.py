@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnVerifyArgs, SpecArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnVerifyArgs, AttnVerifyBatchArgs, SpecArgs, SpecBatchArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 
@@ -818,16 +818,36 @@ def attn_verify_splits(ctx_max, C):
     return -(-ctx_max // C)
 
 
-def attn_verify(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, T, Hq, Hkv, ctx_max, C, scale, window=0, skip=None, qkv_ld=None,
-                out_ld=None, plan=None):
-    """usdm_attn_verify: decode attention for T new tokens of one sequence (qkv [T][qkv_ld], out [T][out_ld], bf16 caches)."""
+def _attn_verify_args(a, qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, T, Hq, Hkv, ctx_max, C, scale, window, skip, qkv_ld, out_ld):
     _need_cuda(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, skip)
-    a = AttnVerifyArgs()
     a.qkv, a.qkv_ld, a.pos = _ptr(qkv), (Hq + 2 * Hkv) * 128 if qkv_ld is None else qkv_ld, _ptr(pos)
     a.T, a.Hq, a.Hkv, a.ctx_max, a.C, a.window, a.scale = T, Hq, Hkv, ctx_max, C, int(window), scale
     a.cos, a.sin, a.kcache, a.vcache = _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache)
     a.pm, a.pl, a.po, a.out, a.out_ld, a.skip = _ptr(pm), _ptr(pl), _ptr(po), _ptr(out), Hq * 128 if out_ld is None else out_ld, _ptr(skip)
+
+
+def attn_verify(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, T, Hq, Hkv, ctx_max, C, scale, window=0, skip=None, qkv_ld=None,
+                out_ld=None, plan=None):
+    """usdm_attn_verify: decode attention for T new tokens of one sequence (qkv [T][qkv_ld], out [T][out_ld], bf16 caches)."""
+    a = AttnVerifyArgs()
+    _attn_verify_args(a, qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, T, Hq, Hkv, ctx_max, C, scale, window, skip, qkv_ld, out_ld)
     _go(plan, "usdm_attn_verify", lib.usdm_attn_verify, C_.byref(a))
+
+
+def attn_verify_batch(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, B, T, Hq, Hkv, ctx_max, C, scale, cache_bs, window=0, skip=None,
+                      qkv_ld=None, out_ld=None, plan=None):
+    """usdm_attn_verify_batch: the same for B slots x T rows (qkv [B*T][qkv_ld], out [B*T][out_ld], pos / skip [B], partials
+    [B][T][Hq][splits]); kcache / vcache are slot 0's, slot b's lie b * cache_bs elements behind."""
+    a = AttnVerifyBatchArgs()
+    _attn_verify_args(a.v, qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, T, Hq, Hkv, ctx_max, C, scale, window, skip, qkv_ld, out_ld)
+    a.B, a.cache_bs = B, cache_bs
+    _go(plan, "usdm_attn_verify_batch", lib.usdm_attn_verify_batch, C_.byref(a))
+
+
+def _spec_args(a, part_val, part_idx, nparts, T, drafts, limit, prompt, prompt_len, prompt_max, params, counters, V, script, propose_only):
+    a.part_val, a.part_idx, a.nparts, a.T = _ptr(part_val), _ptr(part_idx), nparts, T
+    a.drafts, a.limit, a.prompt, a.prompt_len, a.prompt_max = _ptr(drafts), _ptr(limit), _ptr(prompt), _ptr(prompt_len), prompt_max
+    a.script, a.params, a.V, a.counters, a.propose_only = _ptr(script), _ptr(params), V, _ptr(counters), int(propose_only)
 
 
 def spec_commit(part_val, part_idx, nparts, st, *, T, drafts, limit, prompt, prompt_len, params, counters, V, script=None, embed, h_out, Hd,
@@ -835,10 +855,20 @@ def spec_commit(part_val, part_idx, nparts, st, *, T, drafts, limit, prompt, pro
     """usdm_spec_commit: pick, accept, commit, propose and embed at the end of a speculative step (propose_only: after the prefill)."""
     _need_cuda(part_val, part_idx, drafts, limit, prompt, prompt_len, params, counters, script, embed, h_out)
     a = SpecArgs()
-    a.part_val, a.part_idx, a.nparts, a.T = _ptr(part_val), _ptr(part_idx), nparts, T
-    a.drafts, a.limit, a.prompt, a.prompt_len, a.prompt_max = _ptr(drafts), _ptr(limit), _ptr(prompt), _ptr(prompt_len), prompt.numel()
-    a.script, a.params, a.V, a.counters, a.propose_only = _ptr(script), _ptr(params), V, _ptr(counters), int(propose_only)
+    _spec_args(a, part_val, part_idx, nparts, T, drafts, limit, prompt, prompt_len, prompt.numel(), params, counters, V, script, propose_only)
     _go(plan, "usdm_spec_commit", lib.usdm_spec_commit, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
+
+
+def spec_commit_batch(part_val, part_idx, nparts, st, *, T, drafts, limit, prompt, prompt_len, params, counters, V, script=None, embed, h_out, Hd,
+                      slot_lo=0, n=None, propose_only=False, plan=None):
+    """usdm_spec_commit_batch: usdm_spec_commit on the slots [slot_lo, slot_lo + n) (default: all) of the batched state st (st.batch = B
+    slots): part_val / part_idx [B*T][nparts], drafts [B][8], limit / prompt_len [B], prompt [B][prompt_max], script [B][max_out] or
+    None, counters [B][3], params [4] shared, h_out [B*T][Hd]."""
+    _need_cuda(part_val, part_idx, drafts, limit, prompt, prompt_len, params, counters, script, embed, h_out)
+    a = SpecBatchArgs()
+    _spec_args(a.s, part_val, part_idx, nparts, T, drafts, limit, prompt, prompt_len, prompt.shape[-1], params, counters, V, script, propose_only)
+    a.slot_lo, a.n = slot_lo, st.batch - slot_lo if n is None else n
+    _go(plan, "usdm_spec_commit_batch", lib.usdm_spec_commit_batch, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
 
 
 def residual_add(h, delta, n, plan=None):

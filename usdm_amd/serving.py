@@ -274,15 +274,19 @@ class LLM:
             self.stats.update(prefix_hits=0, prefix_rows_reused=0, prefill_rows=0, prefix_copies=0, prefix_hits_live=0)
             self.admission_log = deque(maxlen=256)
         # speculative_config (vLLM's name and shape): {"method": "ngram", "num_speculative_tokens": k, "prompt_lookup_max": ..,
-        # "prompt_lookup_min": ..} - a greedy request with a static mask that is served alone runs on the speculative step
-        # (USDMForCausalLM.generate(num_speculative_tokens=k)); everything else runs as without the option
+        # "prompt_lookup_min": ..} - greedy requests with a static mask run on the speculative step: two or more of a group share the
+        # speculative slots (slots.SpecSlots), one that is alone runs generate(num_speculative_tokens=k);
+        # everything else runs as without the option
         from .spec import check_spec_call, check_speculative_config
         self.spec = check_speculative_config(speculative_config)
         if self.spec is not None:
             check_spec_call(tensor_parallel=self.llm.tp_path, kv_cache_fp8=self.llm.kv8)
             if self.spec[0] + 1 > self.llm.max_batch():
                 raise ValueError(f"num_speculative_tokens={self.spec[0]}: a decode step of this model takes at most {self.llm.max_batch()} rows")
-            self.stats.update(spec_requests=0, spec_steps=0, spec_drafted=0, spec_accepted=0)
+            # spec_requests: served alone on the single-sequence speculative step; spec_batched_requests: served through the speculative
+            # slots (counted in batched_requests too), spec_max_active: the most of them decoding in one step;
+            # spec_steps / spec_drafted / spec_accepted: per-sequence steps, drafts fed and drafts accepted of both
+            self.stats.update(spec_requests=0, spec_steps=0, spec_drafted=0, spec_accepted=0, spec_batched_requests=0, spec_max_active=0)
         self._next_id = 0
 
     def get_tokenizer(self):
@@ -356,7 +360,8 @@ class LLM:
                 groups.setdefault(bytes(r["mask"].cpu().numpy().tobytes()), []).append(r)
         for grp in groups.values():
             if len(grp) >= 2:
-                for r, toks, why, lp in self._run_batched(grp):
+                fast, grp = self._spec_split(grp)
+                for r, toks, why, lp in (self._run_spec_batched(fast) if fast else []) + (self._run_batched(grp) if grp else []):
                     done[r["i"]] = (toks, why, lp)
         for r in reqs:
             if r["i"] not in done:
@@ -453,9 +458,7 @@ class LLM:
         sampled = not sp.greedy
         if sampled:
             kw.update(do_sample=True, temperature=sp.temperature, top_p=sp.top_p, top_k=(sp.top_k if sp.top_k > 0 else None), seed=r["seed"])
-        spec = (self.spec is not None and r["mask"] is not None and not sampled and sp.logprobs is None and not sp.min_p
-                and sp.penalties is None and sp.edits is None)
-        if spec:        # a plain greedy request served alone: the speculative step
+        if self._spec_eligible(r):        # a plain greedy request served alone: the speculative step
             k, lmax, lmin = self.spec
             out = llm.generate(ban_mask=r["mask"], num_speculative_tokens=k, prompt_lookup_max=lmax, prompt_lookup_min=lmin, **kw)
             st = llm.last_spec_stats
@@ -482,6 +485,49 @@ class LLM:
         toks = out[0, len(r["ids"]):].tolist()
         why = "stop" if (toks and toks[-1] in r["stops"] and len(toks) >= sp.min_tokens) else "length"
         return toks, why, llm.last_logprobs
+
+    # ------------------------------------------------------------------ speculative decoding: who, and the slots
+    def _spec_eligible(self, r):
+        """speculative_config is on and the request is plain greedy with a static mask: no logprobs, min_p, penalties or edits"""
+        sp = r["sp"]
+        return (self.spec is not None and r["mask"] is not None and sp.greedy and sp.logprobs is None and not sp.min_p
+                and sp.penalties is None and sp.edits is None)
+
+    def _spec_slot_count(self):
+        """Slots of the batched speculative step: the rows of a step shared out in slots of k + 1, at most max_num_seqs; 0 = off (no
+        speculative_config, or a model with enable_prefix_caching, whose index the speculative slots do not keep)"""
+        if self.spec is None or self.prefix_caching:
+            return 0
+        return min(self.max_slots, self.llm.spec_group(self.spec[0]))
+
+    def _spec_split(self, grp):
+        """A group of requests with one mask -> (those served through the speculative slots, the rest).  Fewer than two eligible
+        requests or fewer than two slots: nobody - a lone eligible request keeps the single path, the others go where they went."""
+        fast = [r for r in grp if self._spec_eligible(r)]
+        if len(fast) < 2 or self._spec_slot_count() < 2:
+            return [], grp
+        return fast, [r for r in grp if not self._spec_eligible(r)]
+
+    def _run_spec_batched(self, grp):
+        """Eligible requests of one mask through the speculative slots, with turnover as in _run_batched (SpecSlots.serve); per-request
+        stop ids and max_tokens go into the slot's stop block and limit."""
+        llm, (k, lmax, lmin) = self.llm, self.spec
+        ss = llm.spec_slots(self._spec_slot_count())
+        llm.load_ban(ban_mask=grp[0]["mask"])
+        ss.set_lookup(lmax, lmin, False)
+        reqs = [dict(ids=torch.tensor(r["ids"], dtype=torch.long), limit=r["max_new"], stops=r["stops"], min_new=r["sp"].min_tokens) for r in grp]
+        res, max_active = ss.serve(reqs, k + 1)
+        st = self.stats
+        st["batched_requests"] += len(grp)
+        st["spec_batched_requests"] += len(grp)
+        st["spec_max_active"] = max(st["spec_max_active"], max_active)
+        out = []
+        for r, (toks, c) in zip(grp, res):
+            for name in ("steps", "drafted", "accepted"):
+                st["spec_" + name] += c[name]
+            why = "stop" if (toks and toks[-1] in r["stops"] and len(toks) >= r["sp"].min_tokens) else "length"
+            out.append((r, toks, why, None))
+        return out
 
     # ------------------------------------------------------------------ continuous batching over the decode slots
     def _run_batched(self, grp):

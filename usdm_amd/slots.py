@@ -2,6 +2,8 @@
 buffers and the host protocol around them: which knob block is written when, where an idle slot is parked, which arrays make up "the
 cache".  The model (usdm_amd/llm.py) states the launches; the schedulers talk to the methods here.  What a step kind adds (log-probability
 rows, penalty tables, logit-edit state) is built here for the single sequence too (B=None)."""
+from collections import deque
+
 import torch
 
 from . import ops
@@ -9,7 +11,13 @@ from .plancache import LRU
 from .prefix import PrefixIndex
 
 CHUNK = 8           # decode steps between two scheduling points (host sync: stop checks, slot turnover)
+NO_CANDIDATE_IDX = 0x7fffffff      # the id of an arg-max partial that saw no allowed row
 GREEDY_KNOBS = (1.0, 1, 1.0, 0)      # temperature, top_k, top_p, seed: greedy on the sampling step (top_k = 1); harmless on an idle slot
+
+
+def stop_index(toks, stops, min_new):
+    """How many of `toks` a sequence keeps when it ends at its first stop id that is at least its min_new-th token; None: no stop."""
+    return next((i + 1 for i, t in enumerate(toks) if t in stops and i + 1 >= min_new), None)
 
 
 def penalty_buffers(device, V, B=None):
@@ -264,3 +272,116 @@ class BeamSlots(DecodeSlots):
         self.cand_score, self.cand_index = f32(B, KC), i32(B, KC)
         self.log_score, self.log_token, self.log_parent = f32(T, KC), i32(T, KC), i32(T, KC)
         self.beam_graph = self.beam_eager = None
+
+
+class SpecSlots(DecodeSlots):
+    """B slots of batched speculative greedy decoding, in a cache of their own (generate_batch's slots and plans are not
+    touched): the B slots plus, per slot, the words of usdm_spec_commit_batch - done, limit, a stop block {n, min_new, ids}, drafts [8],
+    the prompt row, a script row, the three counters - and the shared lookup params; per T = k + 1 the B * T rows the step runs on
+    (h, the arg-max partials), the captured step and the slots' one-slot propose_only launches; one prefill plan cache (DecodeSlots').
+    A slot without a request has done = 1: the verify attention skips it and the commit changes nothing, so it never decodes garbage
+    and needs no parking.  Not on a model with enable_prefix_caching (whose index protocol assumes parked, decoding idle slots)."""
+
+    def __init__(self, model, B, kind):
+        if model.prefix_caching:
+            raise NotImplementedError("batched speculative decoding on a model built with enable_prefix_caching=True: the prefix index "
+                                      "assumes idle slots are parked and decoding; the single-sequence speculative path works there")
+        super().__init__(model, B)
+        i32 = lambda *s, v=0: torch.full(s, v, dtype=torch.int32, device=model.device)
+        self.kind = kind      # llm.step_kind(): the ban-masked arg-max pick of the slots' prefills
+        self.done, self.limit, self.eos, self.drafts = i32(B, v=1), i32(B), i32(B, 8), i32(B, ops.SPEC_MAX_T, v=-1)
+        self.prompt, self.prompt_len, self.script = i32(B, model.ctx_max), i32(B), i32(B, model.max_out, v=-1)
+        self.counters, self.params = i32(B, 3), i32(4)
+        self.rows, self.spec_steps, self.inits = {}, {}, {}
+
+    def spec_rows(self, T):
+        """h [B*T][H] and the arg-max partials [B*T][nparts] of the step with T rows per slot"""
+        if T not in self.rows:
+            m, n = self.model, self.B * T
+            self.rows[T] = dict(h=torch.zeros(n, m.cfg["hidden_size"], dtype=torch.bfloat16, device=m.device),
+                                pv=torch.full((n, m.nparts), float("-inf"), dtype=torch.float32, device=m.device),
+                                pi=torch.full((n, m.nparts), NO_CANDIDATE_IDX, dtype=torch.int32, device=m.device))
+        return self.rows[T]
+
+    def commit(self, T, plan, slot_lo=0, n=None, propose_only=False):
+        """usdm_spec_commit_batch over the slots [slot_lo, slot_lo + n) (default: all): the end of the step, or (propose_only) an
+        admitted slot's first drafts and input rows"""
+        m, r = self.model, self.spec_rows(T)
+        st = ops.decode_state(self.nxt, self.out, self.step, self.pos, advance_pos=True, batch=self.B, done=self.done, eos=self.eos)
+        st.max_out = m.max_out
+        ops.spec_commit_batch(r["pv"], r["pi"], m.nparts, st, T=T, drafts=self.drafts, limit=self.limit, prompt=self.prompt,
+                              prompt_len=self.prompt_len, params=self.params, counters=self.counters, V=m.cfg["vocab_size"], script=self.script,
+                              embed=m.W["embed"], h_out=r["h"], Hd=m.cfg["hidden_size"], slot_lo=slot_lo, n=n, propose_only=propose_only, plan=plan)
+        plan.hold(st)
+
+    def spec_step(self, T):
+        """The replayable speculative step of the B slots x T rows (built and captured at first use)"""
+        if T not in self.spec_steps:
+            self.spec_steps[T] = self.model._graphed(self.model._build_decode_spec_batch(self.B, T))
+        return self.spec_steps[T]
+
+    def set_lookup(self, lookup_max, lookup_min, use_script):
+        self.params.copy_(torch.tensor([lookup_max, lookup_min, int(bool(use_script)), 0], dtype=torch.int32))
+
+    def admit_spec(self, b, ids, T, limit, stops=(), min_new=0, script=None):
+        """Admit a prompt (ids [L]) into slot b: DecodeSlots.admit's per-slot prefill, whose pick is committed as step 1, then the
+        slot's speculative words - limit, the stop block (at most 6 ids on the device; the host checks every id anyway), the prompt
+        row, the script, zeroed counters, done = 0 - and a one-slot propose_only launch for its first drafts and input rows."""
+        m, L = self.model, int(ids.shape[0])
+        self.admit(b, ids, self.kind)
+        dev_eos = sorted(stops) if len(stops) <= 6 else []
+        self.eos[b] = torch.tensor(([len(dev_eos), int(min_new)] + dev_eos + [0] * 6)[:8], dtype=torch.int32)
+        self.limit[b] = int(limit)
+        self.prompt[b, :L] = ids.to(m.device, torch.int32)
+        self.prompt_len[b] = L
+        self.counters[b] = 0
+        self.drafts[b] = -1
+        self.script[b] = -1
+        if script is not None:
+            sc = torch.as_tensor(script).to(torch.int32).reshape(-1)[:m.max_out]
+            self.script[b, :sc.numel()] = sc.to(m.device)
+        self.done[b] = 0
+        if (T, b) not in self.inits:
+            plan = ops.Plan()
+            self.commit(T, plan, slot_lo=b, n=1, propose_only=True)
+            self.inits[T, b] = plan
+        self.inits[T, b].run()
+
+    def release(self, b):
+        """Slot b has no request: every launch of the step leaves it alone"""
+        self.done[b] = 1
+
+    def serve(self, requests, T, stops_of=None):
+        """Run `requests` - dicts with ids [L] (a tensor), limit (tokens to emit, <= ctx_max - L and max_out), stops (a set), min_new
+        and optionally script - through the slots with turnover: a finished slot is refilled from the queue at the next scheduling
+        point.  The captured step is replayed in chunks; the host reads step / done / out at each scheduling point and never
+        runs more replays than the slot with the most tokens left needs at one token per step.  Replays past a slot's device-side
+        stop change nothing of that slot.  -> ([(tokens, dict(steps=, drafted=, accepted=)) per request], most slots active at once)"""
+        step = self.spec_step(T)
+        queue, slots, results, max_active = deque(enumerate(requests)), [None] * self.B, [None] * len(requests), 0
+        while queue or any(s is not None for s in slots):
+            for b in range(self.B):
+                if slots[b] is None and queue:
+                    i, r = queue.popleft()
+                    self.admit_spec(b, r["ids"], T, r["limit"], r["stops"], r["min_new"], r.get("script"))
+                    slots[b] = (i, r)
+            active = [b for b in range(self.B) if slots[b] is not None]
+            max_active = max(max_active, len(active))
+            steps, done, toks = self.step.tolist(), self.done.tolist(), self.tokens()      # host sync = scheduling point
+            left, freed = 0, False
+            for b in active:
+                i, r = slots[b]
+                seq = toks[b][:min(steps[b], r["limit"])]
+                end = stop_index(seq, r["stops"], r["min_new"])
+                if end is not None or done[b] or len(seq) >= r["limit"]:
+                    c = self.counters[b].tolist()
+                    results[i] = (seq[:end], dict(steps=c[0], drafted=c[1], accepted=c[2]))
+                    self.release(b)
+                    slots[b], freed = None, True
+                else:
+                    left = max(left, r["limit"] - len(seq))
+            if not left or (freed and queue):
+                continue                                             # refill the freed slot(s) before spending more steps
+            for _ in range(min(CHUNK, left)):
+                step.run()
+        return results, max_active
