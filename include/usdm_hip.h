@@ -292,6 +292,16 @@ typedef struct usdm_gemv_args {
    * while the others poll, which holds exactly because the whole grid is resident at once; a launch for which it did not hold
    * would cost one timeout per layer (and raise through *cmb_err), not hang. */
   unsigned long long* cmb_gran; int32_t* cmb_err; int32_t cmb_timeout_ms;
+  /* Form of the SwiGLU launch (benchmarking / test override, as usdm_gemm_args.tile_sel; it occupies what was the struct's tail
+   * padding, so sizeof and every other offset are unchanged and a zero-filled struct means what it always did).
+   *   0  the launcher's choice: gate/up of the 7B (14-output tiles of 7 waves) runs RESIDENT on bf16 weights - the grid is the number
+   *      of workgroups the device holds at once, workgroup b streams tiles b, b + grid, ... behind ONE prologue, and the weight ring
+   *      of a tile is refilled from the next tile's rows - every other shape as before;
+   *   -1 one tile per workgroup;
+   *   >0 resident on at most this many workgroups.
+   * A non-zero value also selects the 14-output tile at EVERY SwiGLU shape (so that both forms partition the RMSNorm sums alike at
+   * the small shapes of the tests).  Both forms give identical bits; FP8 / MXFP4 weights and x_delta have the one-tile form only. */
+  int32_t resident;
 } usdm_gemv_args;
 int usdm_gemv(const usdm_gemv_args* args, usdm_stream_t stream);
 int usdm_gemv_nblocks(int32_t N, int32_t act); /* number of partials the lm_head mode writes */

@@ -155,6 +155,7 @@ class GemvArgs(C.Structure):
         ("p2p", C.c_void_p), ("p2p_site", C.c_int32), ("p2p_mode", C.c_int32),
         ("mrg_pm", C.c_void_p), ("mrg_pl", C.c_void_p), ("mrg_po", C.c_void_p), ("mrg_ns", C.c_int32),
         ("cmb_gran", C.c_void_p), ("cmb_err", C.c_void_p), ("cmb_timeout_ms", C.c_int32),
+        ("resident", C.c_int32),
     ]
 
 

@@ -6,7 +6,10 @@
 namespace {
 // ---- launch selection: the instantiation (rows per wave, waves per workgroup, GLU) and the grid that run a shape.  The launchers,
 // usdm_gemv_threads and through it usdm_gemv_engine (which reproduces the RMSNorm partition) all read this one table.
-struct gemv_sel { int rw, nwv; bool glu; int grid; };
+// res: 0 = one tile per workgroup (grid = tiles); > 0 = the batch-1 bf16 launcher may run the tiles RESIDENT (gemv_resident_kernel)
+// on at most that many workgroups - how many the device holds at once is its question, asked at the launch, not here (this table
+// is also read where there is no device).
+struct gemv_sel { int rw, nwv; bool glu; int grid; int res; };
 
 // Rows per wave: HBM streaming wants >= ~4 workgroups (16 waves) per CU in flight AND a grid that is a whole
 // number of workgroups per CU (256 CUs); take the largest RW that gives both, else the best balanced one.
@@ -41,7 +44,10 @@ static gemv_sel gemv_select(const usdm_gemv_args& a, bool batched) {
   // gate/up of the 7B (14336 outputs), batch-1 only: 7-wave workgroups of 14 outputs = 1024 workgroups = exactly two rounds of two
   // workgroups per CU, instead of 1792 four-wave workgroups = 1.75 rounds of four
   // (a 14-wave GLU variant with one workgroup per CU was measured 15 % slower than 7 four-wave workgroups per CU)
-  if (!batched && glu && nout % 14 == 0 && (nout / 14) % 512 == 0) return gemv_sel{2, 7, true, nout / 14};
+  // usdm_gemv_args.resident: 0 = resident where this row applies; -1 = one tile per workgroup; > 0 = resident on at most that many
+  // workgroups; non-zero: this row at every SwiGLU shape (the last tile may be ragged)
+  if (!batched && glu && (a.resident != 0 || (nout % 14 == 0 && (nout / 14) % 512 == 0)))
+    return gemv_sel{2, 7, true, cdiv(nout, 14), a.resident < 0 ? 0 : a.resident > 0 ? a.resident : 0x7fffffff};
   const int rw = a.part_val ? 4 : gemv_pick_rw(nout, glu);   // lm_head: 4 rows
   return gemv_sel{rw, 4, glu, cdiv(nout, 4 * rw)};
 }

@@ -10,6 +10,7 @@
 // product and residual add is rounded to bf16; logits are bf16 values compared in fp32.
 #include "common.h"
 #include <stdlib.h>
+#include <utility>
 #include "../../include/usdm_hip.h"
 #include "gemv_launch.h"
 #include "attn_merge.h"
@@ -504,6 +505,229 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   }
 }
 
+template <class F, int... I>
+__device__ __forceinline__ void gemv_for_seq(F&& f, std::integer_sequence<int, I...>) { (f(gemv_ic<I>{}), ...); }
+// f(gemv_ic<0>{}) ... f(gemv_ic<N - 1>{}): a loop whose counter is a constant expression (asm immediates)
+template <int N, class F>
+__device__ __forceinline__ void gemv_for(F&& f) { gemv_for_seq(f, std::make_integer_sequence<int, N>{}); }
+
+// ---------------------------------------------------------------------------------------------
+// Resident multi-tile form of gemv_kernel<RW, true, NWV> for bf16 weights (gate/up of the decode step).
+// The grid is the number of workgroups the device holds at once, not the number of tiles: workgroup b takes the tiles b,
+// b + grid, ... (a tile = the NWV * RW outputs of one gemv_kernel workgroup).  The prologue - skip word, hand-counted early loads,
+// first ring, the one counted wait, x staged and RMS-normalised into LDS - runs ONCE per workgroup, as gemv_kernel's.  The ring
+// never drains between tiles: in the last UNR iterations of a tile every freed slot is refilled from the rows of the next tile
+// (slot u = its iteration u, what the first ring holds), so the wave reduction, SwiGLU and store of a tile run with the next
+// tile's ring in flight.  The last tile keeps gemv_kernel's tail.
+// Per output the arithmetic is gemv_kernel's, statement for statement: the lane-to-K assignment, the iteration order, dot8,
+// wave_sum, gemv_swiglu_value, the RMSNorm partition over NWV waves and its rounding points - identical bits.
+// TPW > 0, NIT > 0: every workgroup has exactly TPW tiles and K = NIT * 512, both compile-time, so that the tile seam is
+// straight-line code (the wait-count pass drains the ring at control-flow joins around loads: profiles/r04_decode_ablation.txt
+// items 1 and 13).  TPW = 0, NIT = 0: any tile count per workgroup (also uneven), any K, ragged last tile; correct, seams not tuned.
+// No x_delta (the launcher keeps the one-tile form for it).
+// ---------------------------------------------------------------------------------------------
+template <int RW, int NWV, int TPW, int NIT>
+__global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) void gemv_resident_kernel(const usdm_gemv_args a) {
+  static_assert((TPW > 0) == (NIT > 0), "straight-line seams need both counts");
+  constexpr int NTH = NWV * 64;
+  constexpr int NR = 2 * RW;
+  constexpr int UNR = gemv_ring_depth(NR, false, false);
+  constexpr int TILE = NWV * RW;   // outputs per tile
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* xs = (bf16_t*)smem;  // [Kpad] bf16, zero padded
+  __shared__ float red[NWV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int skipv = a.skip ? *a.skip : 0;
+  GTR(0);
+  const int K = a.K;
+  const int Kpad = (K + 511) & ~511;
+  const int nit = NIT ? NIT : Kpad >> 9;
+  const bool tail_ok = NIT ? true : ((nit - 1) << 9) + lane * 8 < K;
+  // row j of this wave in tile t (packed layout: blocks of 32 rows = 16 gate + 16 up; rows past N re-read the last row, never stored)
+  const int uwave = __builtin_amdgcn_readfirstlane(wave);   // the row bases are wave-uniform: scalar registers, one lane offset
+  auto row_ptr = [&](int t, int j) -> const char* {
+    const int o = (blockIdx.x + t * gridDim.x) * TILE + uwave * RW + (j % RW);
+    int r = (o >> 4) * 32 + (o & 15) + (j >= RW ? 16 : 0);
+    r = r < a.N ? r : a.N - 1;
+    return (const char*)((const bf16_t*)a.W + (int64_t)r * a.ldw);
+  };
+  const unsigned voff = lane * 16;   // this lane's 16 bytes of a K iteration (512 elements = 1024 bytes)
+  // Generic form: compiler-issued loads, the last iteration past K redirected to the row start (x is zero there in LDS).
+  auto wload = [&](const char* p, int it) -> u32x4 {
+    return __builtin_nontemporal_load((const u32x4*)(p + ((it == nit - 1 && !tail_ok) ? 0u : voff + it * 1024u)));
+  };
+  // Straight-line form: HAND-COUNTED ring loads (scalar row base + lane offset + immediate), invisible to the wait-count pass like
+  // the early loads below, each consumed behind an asm wait that names how many younger loads stay in flight.  Left to the
+  // compiler, the straight-line ring was clustered into bursts with vmcnt(0) between them and spilled.
+  auto aload = [&](u32x4& dst, const char* p, auto IT) {
+    constexpr int it = decltype(IT)::value;
+    const unsigned vo = voff + (it >> 2) * 4096u;
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(dst) : "v"(vo), "s"(p), "n"((it & 3) * 1024) : "memory");
+  };
+  const char* wp[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) wp[j] = row_ptr(0, j);
+  // ---- prologue, once per workgroup (gemv_kernel's EARLY form)
+  const int i0 = tid * 8;
+  u32x4 x0 = {0u, 0u, 0u, 0u}, ge0v = x0, ge1v = x0;
+  {
+    const int ic = min(i0, K - 8);
+    const float* gp0 = a.norm_w ? a.norm_w + ic : (const float*)a.x;
+    const float* gp1 = a.norm_w ? gp0 + 4 : gp0;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x0) : "v"((const bf16_t*)a.x + ic) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ge0v) : "v"(gp0) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ge1v) : "v"(gp1) : "memory");
+  }
+  u32x4 ring[NR][UNR];   // always NR x UNR loads: the wait below names an exact count
+  if constexpr (TPW > 0) {
+    static_assert(NIT == 0 || (NIT >= UNR && NIT % UNR == 0), "slot u = iteration u of every tile");
+    gemv_for<UNR>([&](auto U) { gemv_for<NR>([&](auto J) { aload(ring[J.value][U.value], wp[J.value], U); }); });
+  } else {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int j = 0; j < NR; ++j) ring[j][u] = u < nit ? wload(wp[j], u) : __builtin_nontemporal_load((const u32x4*)wp[j]);
+  }
+  GTR(1);
+  asm volatile("s_waitcnt vmcnt(%3)" : "+v"(x0), "+v"(ge0v), "+v"(ge1v) : "n"(UNR * NR));
+  if (skipv) return;
+  const float4 ge0 = __builtin_bit_cast(float4, ge0v), ge1 = __builtin_bit_cast(float4, ge1v);
+  const bf16_t* xg = (const bf16_t*)a.x;
+  const int iloop = i0 + NTH * 8;
+  if (a.norm_w) {
+    float ss = 0.f;
+    if (i0 < K) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float lo = bf2f(x0[e] & 0xffff), hi = bf2f(x0[e] >> 16);
+        ss += lo * lo + hi * hi;
+      }
+    }
+    for (int i = iloop; i < K; i += NTH * 8) {
+      const u32x4 v = *(const u32x4*)(xg + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
+        ss += lo * lo + hi * hi;
+      }
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) red[wave] = ss;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < NWV; ++w) tot += red[w];
+    const float rstd = rsqrtf(tot / (float)K + a.eps);
+    auto normed = [&](u32x4 v, float4 g0, float4 g1) -> u32x4 {
+      const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+      u32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
+        o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
+      }
+      return o;
+    };
+    if (i0 < Kpad) *(u32x4*)(xs + i0) = i0 < K ? normed(x0, ge0, ge1) : u32x4{0, 0, 0, 0};
+    for (int i = iloop; i < Kpad; i += NTH * 8) {
+      u32x4 o = {0, 0, 0, 0};
+      if (i < K) o = normed(*(const u32x4*)(xg + i), *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
+      *(u32x4*)(xs + i) = o;
+    }
+  } else {
+    if (i0 < Kpad) *(u32x4*)(xs + i0) = i0 < K ? x0 : u32x4{0, 0, 0, 0};
+    for (int i = iloop; i < Kpad; i += NTH * 8) {
+      u32x4 v = {0, 0, 0, 0};
+      if (i < K) v = *(const u32x4*)(xg + i);
+      *(u32x4*)(xs + i) = v;
+    }
+  }
+  __syncthreads();
+  GTR(2);
+
+  // ---- the tiles: consume a ring slot, refill it UNR iterations ahead - in this tile's rows, else in the next tile's
+  float acc[NR];
+  const char* wn[NR];
+  // the epilogue of tile t (gemv_kernel's), run with the next tile's ring in flight; then the next tile's rows become current
+  auto finish = [&](int t) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) acc[j] = wave_sum(acc[j]);
+    if (t < 4) GTR(3 + t);
+    if (lane == 0) {
+      const int ob = (blockIdx.x + t * gridDim.x) * TILE + wave * RW;
+#pragma unroll
+      for (int j = 0; j < RW; ++j) {
+        const int o = ob + j;
+        if (2 * o >= a.N) continue;
+        const float r = gemv_swiglu_value(acc[j], acc[j + RW], a.round_bf16);
+        if (a.y16) ((bf16_t*)a.y16)[o] = f2bf(r);
+        if (a.y32) a.y32[o] = r;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j) wp[j] = wn[j];
+  };
+  if constexpr (TPW > 0) {
+    // Loads complete in order and every consumed slot is refilled at once, so NR * UNR loads are in flight in front of every
+    // consume and its load is the oldest: the wait leaves the NR * UNR - 1 younger ones.  In the last UNR iterations of the last
+    // tile nothing is refilled and the count falls by one per consume.  (The epilogue's stores move the same counter; a store
+    // younger than the load waited for only makes the wait take one more of the oldest loads with it.)  The lane's piece of x is
+    // read from LDS one iteration ahead: the asm statements are compiler barriers, the read would otherwise sit in front of its use.
+    u32x4 xv = *(const u32x4*)(xs + lane * 8);
+    gemv_for<TPW>([&](auto T) {
+      constexpr int t = decltype(T)::value;
+      constexpr bool has_next = t + 1 < TPW;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        acc[j] = 0.f;
+        wn[j] = has_next ? row_ptr(t + 1, j) : wp[j];
+      }
+      gemv_for<NIT>([&](auto IT) {
+        constexpr int it = decltype(IT)::value, u = it % UNR;
+        constexpr bool refill = it + UNR < NIT || has_next;
+        const u32x4 xn = *(const u32x4*)(xs + (((it + 1) % NIT) * 64 + lane) * 8);
+        gemv_for<NR>([&](auto J) {
+          constexpr int j = decltype(J)::value;
+          constexpr int younger = refill ? NR * UNR - 1 : NR * UNR - 1 - ((it - (NIT - UNR)) * NR + j);
+          asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ring[j][u]) : "n"(younger) : "memory");
+          acc[j] = dot8(ring[j][u], xv, acc[j]);
+          if constexpr (it + UNR < NIT) aload(ring[j][u], wp[j], gemv_ic<it + UNR>{});
+          else if constexpr (has_next) aload(ring[j][u], wn[j], gemv_ic<u>{});
+        });
+        xv = xn;
+      });
+      finish(t);
+    });
+  } else {
+    const int ntiles = (a.N / 2 + TILE - 1) / TILE;
+    const int ntl = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;   // >= 1: the grid is <= ntiles
+    for (int t = 0; t < ntl; ++t) {
+      const bool has_next = t + 1 < ntl;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        acc[j] = 0.f;
+        wn[j] = has_next ? row_ptr(t + 1, j) : wp[j];
+      }
+      for (int it0 = 0; it0 < nit; it0 += UNR) {
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+          const int it = it0 + u;
+          if (it < nit) {
+            const u32x4 xv = *(const u32x4*)(xs + (it * 64 + lane) * 8);
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+              acc[j] = dot8(ring[j][u], xv, acc[j]);
+              const bool own = it + UNR < nit;   // else the next tile's iteration u (u = it % UNR < nit)
+              if (own || has_next) ring[j][u] = wload(own ? wp[j] : wn[j], own ? it + UNR : u);
+            }
+          }
+        }
+      }
+      finish(t);
+    }
+  }
+}
+
 // final arg-max over the per-block partials; advances the device-side decode state
 // (nseg segments of nparts partials per sequence, seg_stride apart: the tensor-parallel batched step gathers [rank][sequence][nparts])
 __global__ void argmax_final_kernel(const float* pv, const int* pi, int nparts, int nseg, int64_t seg_stride, usdm_decode_state st,
@@ -554,10 +778,62 @@ __global__ void residual_add_kernel(bf16_t* h, const float* delta, int n) {
 // Launches the instantiation gemv_select names.  One selection for every weight format, so an FP8 or MXFP4 launch partitions K and
 // the RMSNorm sums exactly as the bf16 launch of the same shape.  FORM: GEMV_PLAIN (no merged input, no peer-to-peer epilogue:
 // the only form of the FP8 / MXFP4 weights), GEMV_MRG or GEMV_CMB, with the kernel's MRG / P2P / CMB flags.
+// Workgroups of `kern` the current device holds at once (the occupancy query x its CUs), remembered for the last kernel, device
+// and LDS size asked about
+static int gemv_resident_count(const void* kern, int nth, size_t lds, int* out) {
+  static thread_local const void* c_kern = nullptr;
+  static thread_local int c_dev = -1, c_n = 0;
+  static thread_local size_t c_lds = 0;
+  int dev = 0;
+  USDM_HIP(hipGetDevice(&dev));
+  if (kern != c_kern || dev != c_dev || lds != c_lds) {
+    int ncu = 0, per = 0;
+    USDM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    USDM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, nth, lds));
+    USDM_CHECK_ARG(ncu > 0 && per > 0, "usdm_gemv: the resident form does not fit a CU (%zu bytes of LDS)", lds);
+    c_kern = kern; c_dev = dev; c_lds = lds; c_n = ncu * per;
+  }
+  *out = c_n;
+  return 0;
+}
+
+// The resident form of the selection's (2, GLU, 7) row: *launched = false where one tile per workgroup is all there is to run
+// (every tile already resident, or x_delta) and the one-tile kernel takes the launch.
+static int gemv_launch_resident(const usdm_gemv_args& a, const gemv_sel& s, size_t lds, hipStream_t st, bool* launched) {
+  *launched = false;
+  if (a.x_delta) return 0;
+  constexpr int RW = 2, NWV = 7;
+  auto straight = gemv_resident_kernel<RW, NWV, 2, 8>;   // gate/up of the 7B: two tiles per workgroup, K = 4096
+  auto generic = gemv_resident_kernel<RW, NWV, 0, 0>;
+  const int ntiles = s.grid;
+  int n = 0;
+  if (int rc = gemv_resident_count((const void*)straight, NWV * 64, lds, &n)) return rc;
+  int grid = min(min(n, s.res), ntiles);
+  if (grid == ntiles) return 0;
+  if (a.K == 8 * 512 && ntiles == 2 * grid) {
+    hipLaunchKernelGGL(straight, dim3(grid), dim3(NWV * 64), lds, st, a);
+  } else {
+    if (int rc = gemv_resident_count((const void*)generic, NWV * 64, lds, &n)) return rc;
+    grid = min(min(n, s.res), ntiles);
+    if (grid == ntiles) return 0;
+    hipLaunchKernelGGL(generic, dim3(grid), dim3(NWV * 64), lds, st, a);
+  }
+  *launched = true;
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+
 template <int FORM, bool MRG, bool P2P, bool CMB, bool FP8, class... FMT>
 static int gemv_launch(const usdm_gemv_args& a, hipStream_t st, FMT... fmt) {
   const size_t lds = (size_t)((a.K + 511) & ~511) * 2;
   const gemv_sel s = gemv_select(a, false);
+  if constexpr (FORM == GEMV_PLAIN && !FP8 && sizeof...(FMT) == 0) {
+    if (s.res > 0) {
+      bool launched = false;
+      if (int rc = gemv_launch_resident(a, s, lds, st, &launched)) return rc;
+      if (launched) return 0;
+    }
+  }
   const bool found = gemv_dispatch<FORM>(s, [&](auto RW, auto GLU, auto NWV) {
     constexpr int nwv = decltype(NWV)::value;
     hipLaunchKernelGGL((gemv_kernel<decltype(RW)::value, decltype(GLU)::value != 0, nwv, MRG, P2P, CMB, FP8, FMT...>), dim3(s.grid),

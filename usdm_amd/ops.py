@@ -249,9 +249,11 @@ def _fill_gemv(a, W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_b
 
 
 def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p_mode=0, merge=None, cmb=None, plan=None,
-         only_args=False, **common):
+         only_args=False, resident=None, **common):
     """usdm_gemv: batch-1 weight-streaming GEMV (see include/usdm_hip.h; **common: the keywords of _fill_gemv).
     p2p: a usdm_amd.p2p.P2PComm (fused all-reduce).
+    resident: usdm_gemv_args.resident (SwiGLU: 0 the launcher's choice, -1 one tile per workgroup, n > 0 resident on at most n
+    workgroups); None: USDM_GEMV_RESIDENT, else 0.
     only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
     W a quant.Fp8Weight / quant.Mxfp4Weight: usdm_gemv_fp8 / usdm_gemv_mxfp4 (the plain single-GPU forms only; the library refuses
     the others)."""
@@ -261,7 +263,10 @@ def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p
     a = GemvArgs()
     _fill_gemv(a, W, x, **common)
     a.x_delta, a.x_out, a.skip = _ptr(x_delta), _ptr(x_out), _ptr(skip)
-    if merge is not None:       # (pm, pl, po, NS): x is merged from the decode-attention partials in the prologue
+    if resident is None:        # benchmarks / form-equivalence tests: the library itself reads no environment
+        resident = int(os.environ.get("USDM_GEMV_RESIDENT", "0"))
+    a.resident = resident
+    if merge is not None:      # (pm, pl, po, NS): x is merged from the decode-attention partials in the prologue
         pm, pl, po, ns = merge
         _need_cuda(pm, pl, po)
         a.mrg_pm, a.mrg_pl, a.mrg_po, a.mrg_ns = _ptr(pm), _ptr(pl), _ptr(po), ns
