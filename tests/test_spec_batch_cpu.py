@@ -78,6 +78,19 @@ def test_generate_batch_argument_checks():
     assert all(torch.equal(a, b) for a, b in zip(out, full)) and m.last_spec_stats == [dict(steps=0, drafted=0, accepted=0)] * 2
 
 
+def test_stop_block():
+    """slots.stop_block: {n, min_new, ids...} in 8 int32 words - the ids sorted and zero-padded; more than 6 ids: n = 0, no ids, and
+    nothing for the device to check (the host checks every id anyway)"""
+    from usdm_amd.slots import stop_block
+    for stops, min_new, words, dev in ((set(), 0, [0, 0, 0, 0, 0, 0, 0, 0], []),
+                                       ({9}, 3, [1, 3, 9, 0, 0, 0, 0, 0], [9]),
+                                       ({40, 7, 300, 2, 11, 5}, 2, [6, 2, 2, 5, 7, 11, 40, 300], [2, 5, 7, 11, 40, 300]),
+                                       ({40, 7, 300, 2, 11, 5, 1}, 4, [0, 4, 0, 0, 0, 0, 0, 0], []),
+                                       ([8, 3], 1, [2, 1, 3, 8, 0, 0, 0, 0], [3, 8])):
+        block, ids = stop_block(stops, min_new)
+        assert block.dtype == torch.int32 and block.tolist() == words and ids == dev
+
+
 def _req(i, **kw):
     from usdm_amd.serving import SamplingParams
     mask = kw.pop("mask", torch.zeros(8, dtype=torch.uint8))

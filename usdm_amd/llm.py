@@ -42,8 +42,8 @@ from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
 from .prefix import reusable_past
 from .quant import Fp8Weight, Mxfp4Weight, check_kv_cache_dtype
-from .slots import (CHUNK, NO_CANDIDATE_IDX, BeamSlots, DecodeSlots, SpecSlots, TokenLogprobs, edit_buffers, logprob_buffers, penalty_buffers,
-                    read_logprobs, seed_edits, seed_penalties, stop_index)
+from .slots import (CHUNK, NO_CANDIDATE_IDX, BeamSlots, DecodeSlots, SpecSequence, SpecSlots, TokenLogprobs, edit_buffers, logprob_buffers,
+                    penalty_buffers, read_logprobs, seed_edits, seed_penalties, stop_block, stop_index)
 
 MISTRAL_7B_USDM = dict(vocab_size=42003, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
                        num_attention_heads=32, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-5,
@@ -377,8 +377,8 @@ class USDMForCausalLM:
         self.last_logprobs = None  # generate(logprobs=K): TokenLogprobs of the last call (generate_batch: a list); None when not asked
         self._pen = None          # penalty state of the single sequence (penalty_buffers; allocated at first use)
         self._edt = None          # logit-edit state of the single sequence (edit_buffers; allocated at first use)
-        # speculative greedy decoding: the device words of usdm_spec_commit, the rows, plan and graph per T, all built at
-        # first use (_spec_state); generate(num_speculative_tokens=None / 0) touches none of it
+        # speculative greedy decoding: the single sequence's slots.SpecSequence - the device words of usdm_spec_commit,
+        # the rows, plan and graph per T - built at first use; generate(num_speculative_tokens=None / 0) touches none of it
         self._spec = None
         self._spec_batches = {}        # B -> slots.SpecSlots: generate_batch(num_speculative_tokens=k), serving
         self.last_spec_stats = None    # generate(num_speculative_tokens=k): dict(steps=, drafted=, accepted=) of the last call
@@ -1099,84 +1099,38 @@ class USDMForCausalLM:
         segs = rec.finish()
         return segs if (tp or beam is not None) else segs[0]
 
-    # ------------------------------------------------------------------ speculative greedy decoding
-    def _spec_state(self, T=None):
-        """The device words of usdm_spec_commit for the single sequence (drafts, limit, prompt row, script, {lookup_max, lookup_min,
-        use_script}, the three counters) and, per T, the rows the step runs on: h [T][H] and the arg-max partials [T][nparts]."""
-        dev = self.device
-        if self._spec is None:
-            i32 = lambda n, v=0: torch.full((n,), v, dtype=torch.int32, device=dev)
-            self._spec = dict(drafts=i32(ops.SPEC_MAX_T, -1), limit=i32(1), prompt=i32(self.ctx_max), prompt_len=i32(1), script=i32(self.max_out, -1),
-                              params=i32(4), counters=i32(3), rows={}, steps={}, inits={})
-        sp = self._spec
-        if T is not None and T not in sp["rows"]:
-            sp["rows"][T] = dict(h=torch.zeros(T, self.cfg["hidden_size"], dtype=torch.bfloat16, device=dev),
-                                 pv=torch.full((T, self.nparts), float("-inf"), dtype=torch.float32, device=dev),
-                                 pi=torch.full((T, self.nparts), NO_CANDIDATE_IDX, dtype=torch.int32, device=dev))
-        return sp
-
-    def _spec_commit(self, T, plan, propose_only=False):
-        """usdm_spec_commit over the T rows of _spec_state: the end of the step, or (propose_only, after the prefill, whose pick is
-        already committed) the first drafts and the first T input rows."""
-        sp = self._spec_state(T)
-        r = sp["rows"][T]
-        st = ops.decode_state(self.st_next, self.st_out, self.st_step, self.st_pos, advance_pos=True, done=self.st_done, eos=self.st_eos)
-        ops.spec_commit(r["pv"], r["pi"], self.nparts, st, T=T, drafts=sp["drafts"], limit=sp["limit"], prompt=sp["prompt"],
-                        prompt_len=sp["prompt_len"], params=sp["params"], counters=sp["counters"], V=self.cfg["vocab_size"], script=sp["script"],
-                        embed=self.W["embed"], h_out=r["h"], Hd=self.cfg["hidden_size"], propose_only=propose_only, plan=plan)
-        plan.hold(st)
-
-    def _build_decode_spec(self, T):
-        """One speculative step of the single sequence: T rows (the token to continue from and T - 1 drafts of the SAME sequence) through
-        _layers with the batched projections of _build_decode_batch (weights streamed once; <= 4 rows on the VALU form, bit-identical
-        per row with the single step, 5 .. 8 on the matrix cores), usdm_attn_verify on the single sequence's caches (every cached row
-        read once for all rows), the lm_head in batched arg-max mode, usdm_spec_commit.  One plan, one graph per T."""
+    # ------------------------------------------------------------------ speculative greedy decoding (the states: usdm_amd/slots.py)
+    def _build_spec_step(self, state, T):
+        """One speculative step of a slots.SpecState: its n sequences x T rows each (row b * T + i: sequence b's token at position
+        pos[b] + i - the token to continue from and T - 1 drafts) through _layers with the batched projections of _build_decode_batch
+        over n * T rows (weights streamed once; <= 4 rows on the VALU form, bit-identical per row with the single step, 5 .. 16 on the
+        matrix cores), the state's verify attention on its caches (SpecSequence: usdm_attn_verify, every cached row read once for all
+        rows; SpecSlots: usdm_attn_verify_batch), the lm_head in batched arg-max mode, the state's commit (usdm_spec_commit /
+        usdm_spec_commit_batch).  Sequences with done != 0 are skipped by the attention and the commit.  One plan, one graph per
+        state and T."""
         dev, bf = self.device, torch.bfloat16
         H, d, L, Hq, Hkv, I, nq = self._dims()
-        r = self._spec_state(T)["rows"][T]
+        n = state.n * T
+        if n > self.max_batch():
+            raise ValueError(f"{state.n} slots of {T} rows: a decode step of this model takes at most {self.max_batch()} rows")
+        r = state.spec_rows(T)
         rec = _Segments()
         Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
-        h, qkv, ao, act = r["h"], Z(T, nq), Z(T, Hq * d), Z(T, I)
+        h, qkv, ao, act = r["h"], Z(n, nq), Z(n, Hq * d), Z(n, I)
         nsp = ops.attn_verify_splits(self.ctx_max, self.spec_split)
-        pm, pl, po = Z(T * Hq * nsp, dt=torch.float32), Z(T * Hq * nsp, dt=torch.float32), Z(T * Hq * nsp * d, dt=torch.float32)
-        gemv, ks = self._batch_gemv(T, rec)
+        pm, pl, po = Z(n * Hq * nsp, dt=torch.float32), Z(n * Hq * nsp, dt=torch.float32), Z(n * Hq * nsp * d, dt=torch.float32)
+        gemv, ks = self._batch_gemv(n, rec)
 
         def attn(l):
-            ops.attn_verify(qkv, self.st_pos, self.cos, self.sin, self.kcache[l], self.vcache[l], pm, pl, po, ao, T=T, Hq=Hq, Hkv=Hkv,
-                            ctx_max=self.ctx_max, C=self.spec_split, scale=d ** -0.5, window=self.window, skip=self.st_done, plan=rec.plan)
+            state.attn(l, qkv, pm, pl, po, ao, T=T, Hq=Hq, Hkv=Hkv, ctx_max=self.ctx_max, C=self.spec_split, scale=d ** -0.5,
+                       window=self.window, plan=rec.plan)
 
-        self._layers(rec, gemv, attn, h, qkv, ao, act, "fused", n=T * H, down_kw=dict(ks=ks))
+        self._layers(rec, gemv, attn, h, qkv, ao, act, "fused", n=n * H, down_kw=dict(ks=ks))
         gemv(self.W["lm_head"], h, N=self.v1 - self.v0, K=H, norm_w=self.W["norm"], eps=self.cfg["rms_norm_eps"], ban=self.ban,
              part_val=r["pv"], part_idx=r["pi"], idx_offset=self.v0, part_bs=self.nparts, y_bs=0)
-        self._spec_commit(T, rec.plan)
+        state.commit(T, rec.plan)
         return rec.finish()[0]
 
-    def _spec_begin(self, T, input_ids, max_new, lookup_max, lookup_min, script):
-        """Per-call state of a speculative generate() behind its prefill (whose pick is committed: step = 1): limit, lookup
-        bounds, the prompt row, the script, zeroed counters; then the first drafts and input rows (usdm_spec_commit, propose_only).
-        Returns the replayable step."""
-        sp = self._spec_state(T)
-        L0 = int(input_ids.shape[1])
-        sp["limit"].fill_(int(max_new))
-        sp["prompt"][:L0] = input_ids[0].to(self.device, torch.int32)
-        sp["prompt_len"].fill_(L0)
-        sp["counters"].zero_()
-        sp["drafts"].fill_(-1)
-        if script is not None:
-            sc = torch.as_tensor(script).to(torch.int32).reshape(-1)[:self.max_out]
-            sp["script"].fill_(-1)
-            sp["script"][:sc.numel()] = sc.to(self.device)
-        sp["params"].copy_(torch.tensor([lookup_max, lookup_min, int(script is not None), 0], dtype=torch.int32))
-        if T not in sp["inits"]:
-            plan = ops.Plan()
-            self._spec_commit(T, plan, propose_only=True)
-            sp["inits"][T] = plan
-        sp["inits"][T].run()
-        if T not in sp["steps"]:
-            sp["steps"][T] = self._graphed(self._build_decode_spec(T))
-        return sp["steps"][T]
-
-    # ------------------------------------------------------------------ batched speculative decoding (DESIGN.md 8k-2)
     def spec_slots(self, B):
         """The B slots of batched speculative decoding (slots.SpecSlots), built at first use and kept."""
         if B not in self._spec_batches:
@@ -1194,35 +1148,6 @@ class USDMForCausalLM:
     def spec_group(self, k):
         """Sequences per speculative step with k drafts each: the rows of a step shared out in slots of k + 1"""
         return self.max_batch() // (k + 1)
-
-    def _build_decode_spec_batch(self, B, T):
-        """One speculative step of the B speculative slots (spec_slots(B)) x T rows each (row b * T + i: slot b's token at position pos[b] + i):
-        _layers with the batched projections over B * T rows (weights streamed once; <= 4 rows on the VALU form, 5 .. 16 on the matrix
-        cores), usdm_attn_verify_batch on the slots' caches, the lm_head in batched arg-max mode, usdm_spec_commit_batch.  Slots with
-        done != 0 are skipped by the attention and the commit.  One plan, one graph per (B, T)."""
-        dev, bf = self.device, torch.bfloat16
-        H, d, L, Hq, Hkv, I, nq = self._dims()
-        ss, n = self.spec_slots(B), B * T
-        if n > self.max_batch():
-            raise ValueError(f"{B} slots of {T} rows: a decode step of this model takes at most {self.max_batch()} rows")
-        r = ss.spec_rows(T)
-        rec = _Segments()
-        Z = lambda *s, dt=bf: rec.plan.hold(torch.zeros(*s, device=dev, dtype=dt))
-        h, qkv, ao, act = r["h"], Z(n, nq), Z(n, Hq * d), Z(n, I)
-        nsp = ops.attn_verify_splits(self.ctx_max, self.spec_split)
-        pm, pl, po = Z(n * Hq * nsp, dt=torch.float32), Z(n * Hq * nsp, dt=torch.float32), Z(n * Hq * nsp * d, dt=torch.float32)
-        gemv, ks = self._batch_gemv(n, rec)
-
-        def attn(l):
-            ops.attn_verify_batch(qkv, ss.pos, self.cos, self.sin, ss.kc[0, l], ss.vc[0, l], pm, pl, po, ao, B=B, T=T, Hq=Hq, Hkv=Hkv,
-                                  ctx_max=self.ctx_max, C=self.spec_split, scale=d ** -0.5, cache_bs=L * Hkv * self.ctx_max * d,
-                                  window=self.window, skip=ss.done, plan=rec.plan)
-
-        self._layers(rec, gemv, attn, h, qkv, ao, act, "fused", n=n * H, down_kw=dict(ks=ks))
-        gemv(self.W["lm_head"], h, N=self.v1 - self.v0, K=H, norm_w=self.W["norm"], eps=self.cfg["rms_norm_eps"], ban=self.ban,
-             part_val=r["pv"], part_idx=r["pi"], idx_offset=self.v0, part_bs=self.nparts, y_bs=0)
-        ss.commit(T, rec.plan)
-        return rec.finish()[0]
 
     def _generate_spec_group(self, ids_list, limits, spec, scripts, bad_words_ids, eos_token_id, min_new_tokens):
         """A group of 2 .. max_batch() // (k + 1) sequences on the speculative slots: per-slot prefill, then the step of B x (k + 1)
@@ -1471,7 +1396,13 @@ class USDMForCausalLM:
         device-side stop change nothing."""
         k, lookup_max, lookup_min = spec
         T = k + 1
-        step = self._spec_begin(T, input_ids, max_new, lookup_max, lookup_min, script)
+        if self._spec is None:
+            self._spec = SpecSequence(self)
+        sp = self._spec      # behind the prefill, whose pick is committed (step = 1): the call's words, then the first drafts and input rows
+        sp.seed(0, input_ids[0], max_new, script)
+        sp.set_lookup(lookup_max, lookup_min, script is not None)
+        sp.propose(T, 0)
+        step = sp.spec_step(T)
         while True:
             produced = min(int(self.st_step.item()), max_new)      # host sync point
             toks = self.st_out[:produced].tolist()
@@ -1485,8 +1416,7 @@ class USDMForCausalLM:
                 step.run()
         if self.reuse_prefix:   # committed rows only: the prompt and every emitted token that was fed back and accepted
             self._kv_ids = ids_host + (self.st_out[:produced - 1].tolist() if produced > 1 else [])
-        c = self._spec["counters"].tolist()
-        self.last_spec_stats = dict(steps=c[0], drafted=c[1], accepted=c[2])
+        self.last_spec_stats = sp.stats(0)
         out = torch.cat([input_ids[0], torch.tensor(toks, dtype=torch.long, device=input_ids.device)])
         return out.unsqueeze(0)
 
@@ -1549,9 +1479,8 @@ class USDMForCausalLM:
         self.load_ban(bad_words_ids, ban_mask)
         self.st_pos.fill_(L0)
         self.st_step.zero_()
-        eos_list = sorted(stop_ids(eos_token_id))
-        dev_eos = eos_list if len(eos_list) <= 6 else []      # more ids than the device list holds: host-side check only
-        self.st_eos.copy_(torch.tensor(([len(dev_eos), int(min_new_tokens)] + dev_eos + [0] * 6)[:8], dtype=torch.int32))
+        block, dev_eos = stop_block(stop_ids(eos_token_id), min_new_tokens)      # more ids than the block holds: host-side check only
+        self.st_eos.copy_(block)
         self.st_done.zero_()
         return segs, dev_eos
 

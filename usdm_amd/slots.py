@@ -20,6 +20,13 @@ def stop_index(toks, stops, min_new):
     return next((i + 1 for i, t in enumerate(toks) if t in stops and i + 1 >= min_new), None)
 
 
+def stop_block(stops, min_new):
+    """The device stop block {n, min_new, ids...} of a sequence that ends at one of `stops` -> (its 8 int32 words, the ids the device
+    checks: sorted; none where there are more than the block's 6, which leaves the check to the host)."""
+    dev = sorted(stops) if len(stops) <= 6 else []
+    return torch.tensor(([len(dev), int(min_new)] + dev + [0] * 6)[:8], dtype=torch.int32), dev
+
+
 def penalty_buffers(device, V, B=None):
     """usdm_penalize's state for one sequence (B=None: plus its tokens-counted word) or B batch slots: the table of V words per
     sequence (count of generated occurrences, bit 30 = in the prompt) and the device block of the knobs (zero-filled = neutral)."""
@@ -274,63 +281,50 @@ class BeamSlots(DecodeSlots):
         self.beam_graph = self.beam_eager = None
 
 
-class SpecSlots(DecodeSlots):
-    """B slots of batched speculative greedy decoding (DESIGN.md 8k-2), in a cache of their own (generate_batch's slots and plans are not
-    touched): the B slots plus, per slot, the words of usdm_spec_commit_batch - done, limit, a stop block {n, min_new, ids}, drafts [8],
-    the prompt row, a script row, the three counters - and the shared lookup params; per T = k + 1 the B * T rows the step runs on
-    (h, the arg-max partials), the captured step and the slots' one-slot propose_only launches; one prefill plan cache (DecodeSlots').
-    A slot without a request has done = 1: the verify attention skips it and the commit changes nothing, so it never decodes garbage
-    and needs no parking.  Not on a model with enable_prefix_caching (whose index protocol assumes parked, decoding idle slots)."""
+class SpecState:
+    """The host side of speculative greedy decoding for n sequences on `model`: per sequence the words of
+    usdm_spec_commit - drafts [8], limit, the prompt row, a script row, the three counters - and the shared lookup params; per
+    T = k + 1 the n * T rows the step runs on (h, the arg-max partials), the captured step (model._build_spec_step) and the
+    one-sequence propose_only launches.  A holder adds where its sequences live, as the step's two launches that differ:
+    attn(l, qkv, pm, pl, po, ao, **shape), the verify attention of layer l on its caches, and commit(T, plan, b, propose_only), the
+    commit over all its sequences (b = None) or sequence b alone, on its decode state."""
 
-    def __init__(self, model, B, kind):
-        if model.prefix_caching:
-            raise NotImplementedError("batched speculative decoding on a model built with enable_prefix_caching=True: the prefix index "
-                                      "assumes idle slots are parked and decoding; the single-sequence speculative path works there")
-        super().__init__(model, B)
+    def __init__(self, model, n=1):
         i32 = lambda *s, v=0: torch.full(s, v, dtype=torch.int32, device=model.device)
-        self.kind = kind      # llm.step_kind(): the ban-masked arg-max pick of the slots' prefills
-        self.done, self.limit, self.eos, self.drafts = i32(B, v=1), i32(B), i32(B, 8), i32(B, ops.SPEC_MAX_T, v=-1)
-        self.prompt, self.prompt_len, self.script = i32(B, model.ctx_max), i32(B), i32(B, model.max_out, v=-1)
-        self.counters, self.params = i32(B, 3), i32(4)
+        self.model, self.n = model, n
+        self.drafts, self.limit, self.counters, self.params = i32(n, ops.SPEC_MAX_T, v=-1), i32(n), i32(n, 3), i32(4)
+        self.prompt, self.prompt_len, self.script = i32(n, model.ctx_max), i32(n), i32(n, model.max_out, v=-1)
         self.rows, self.spec_steps, self.inits = {}, {}, {}
 
     def spec_rows(self, T):
-        """h [B*T][H] and the arg-max partials [B*T][nparts] of the step with T rows per slot"""
+        """h [n*T][H] and the arg-max partials [n*T][nparts] of the step with T rows per sequence"""
         if T not in self.rows:
-            m, n = self.model, self.B * T
-            self.rows[T] = dict(h=torch.zeros(n, m.cfg["hidden_size"], dtype=torch.bfloat16, device=m.device),
-                                pv=torch.full((n, m.nparts), float("-inf"), dtype=torch.float32, device=m.device),
-                                pi=torch.full((n, m.nparts), NO_CANDIDATE_IDX, dtype=torch.int32, device=m.device))
+            m, rows = self.model, self.n * T
+            self.rows[T] = dict(h=torch.zeros(rows, m.cfg["hidden_size"], dtype=torch.bfloat16, device=m.device),
+                                pv=torch.full((rows, m.nparts), float("-inf"), dtype=torch.float32, device=m.device),
+                                pi=torch.full((rows, m.nparts), NO_CANDIDATE_IDX, dtype=torch.int32, device=m.device))
         return self.rows[T]
 
-    def commit(self, T, plan, slot_lo=0, n=None, propose_only=False):
-        """usdm_spec_commit_batch over the slots [slot_lo, slot_lo + n) (default: all): the end of the step, or (propose_only) an
-        admitted slot's first drafts and input rows"""
+    def commit_words(self, T):
+        """What both commit launches take besides their decode state: the rows' partials and the words above"""
         m, r = self.model, self.spec_rows(T)
-        st = ops.decode_state(self.nxt, self.out, self.step, self.pos, advance_pos=True, batch=self.B, done=self.done, eos=self.eos)
-        st.max_out = m.max_out
-        ops.spec_commit_batch(r["pv"], r["pi"], m.nparts, st, T=T, drafts=self.drafts, limit=self.limit, prompt=self.prompt,
-                              prompt_len=self.prompt_len, params=self.params, counters=self.counters, V=m.cfg["vocab_size"], script=self.script,
-                              embed=m.W["embed"], h_out=r["h"], Hd=m.cfg["hidden_size"], slot_lo=slot_lo, n=n, propose_only=propose_only, plan=plan)
-        plan.hold(st)
+        return (r["pv"], r["pi"], m.nparts), dict(T=T, drafts=self.drafts, limit=self.limit, prompt=self.prompt, prompt_len=self.prompt_len,
+                                                  params=self.params, counters=self.counters, V=m.cfg["vocab_size"], script=self.script,
+                                                  embed=m.W["embed"], h_out=r["h"], Hd=m.cfg["hidden_size"])
 
     def spec_step(self, T):
-        """The replayable speculative step of the B slots x T rows (built and captured at first use)"""
+        """The replayable speculative step of the n sequences x T rows (built and captured at first use)"""
         if T not in self.spec_steps:
-            self.spec_steps[T] = self.model._graphed(self.model._build_decode_spec_batch(self.B, T))
+            self.spec_steps[T] = self.model._graphed(self.model._build_spec_step(self, T))
         return self.spec_steps[T]
 
     def set_lookup(self, lookup_max, lookup_min, use_script):
         self.params.copy_(torch.tensor([lookup_max, lookup_min, int(bool(use_script)), 0], dtype=torch.int32))
 
-    def admit_spec(self, b, ids, T, limit, stops=(), min_new=0, script=None):
-        """Admit a prompt (ids [L]) into slot b: DecodeSlots.admit's per-slot prefill, whose pick is committed as step 1, then the
-        slot's speculative words - limit, the stop block (at most 6 ids on the device; the host checks every id anyway), the prompt
-        row, the script, zeroed counters, done = 0 - and a one-slot propose_only launch for its first drafts and input rows."""
+    def seed(self, b, ids, limit, script=None):
+        """A new request for sequence b behind its prefill: limit, the prompt row (ids [L]), zeroed counters, no drafts, the script
+        (cut at max_out; None: none)."""
         m, L = self.model, int(ids.shape[0])
-        self.admit(b, ids, self.kind)
-        dev_eos = sorted(stops) if len(stops) <= 6 else []
-        self.eos[b] = torch.tensor(([len(dev_eos), int(min_new)] + dev_eos + [0] * 6)[:8], dtype=torch.int32)
         self.limit[b] = int(limit)
         self.prompt[b, :L] = ids.to(m.device, torch.int32)
         self.prompt_len[b] = L
@@ -340,12 +334,77 @@ class SpecSlots(DecodeSlots):
         if script is not None:
             sc = torch.as_tensor(script).to(torch.int32).reshape(-1)[:m.max_out]
             self.script[b, :sc.numel()] = sc.to(m.device)
-        self.done[b] = 0
+
+    def propose(self, T, b):
+        """Sequence b's first drafts and input rows behind its prefill, whose pick is already committed: a propose_only commit of
+        that sequence alone (one plan per (T, b), built at first use)"""
         if (T, b) not in self.inits:
-            plan = ops.Plan()
-            self.commit(T, plan, slot_lo=b, n=1, propose_only=True)
-            self.inits[T, b] = plan
+            self.inits[T, b] = ops.Plan()
+            self.commit(T, self.inits[T, b], b, propose_only=True)
         self.inits[T, b].run()
+
+    def stats(self, b):
+        """Sequence b's counters: the speculative steps, the drafts fed (ids, not the -1 of "no draft") and the drafts accepted"""
+        c = self.counters[b].tolist()
+        return dict(steps=c[0], drafted=c[1], accepted=c[2])
+
+
+class SpecSequence(SpecState):
+    """The single sequence's speculative state (n = 1): the model's own caches, decode state and prefix bookkeeping."""
+
+    def attn(self, l, qkv, *bufs, **kw):
+        m = self.model
+        ops.attn_verify(qkv, m.st_pos, m.cos, m.sin, m.kcache[l], m.vcache[l], *bufs, skip=m.st_done, **kw)
+
+    def commit(self, T, plan, b=None, propose_only=False):
+        """usdm_spec_commit over the T rows: the end of the step, or (propose_only) the first drafts and the first T input rows"""
+        m, (parts, words) = self.model, self.commit_words(T)
+        st = ops.decode_state(m.st_next, m.st_out, m.st_step, m.st_pos, advance_pos=True, done=m.st_done, eos=m.st_eos)
+        ops.spec_commit(*parts, st, **words, propose_only=propose_only, plan=plan)
+        plan.hold(st)
+
+
+class SpecSlots(DecodeSlots, SpecState):
+    """B slots of batched speculative greedy decoding (DESIGN.md 8k-2), in a cache of their own (generate_batch's slots and plans are not
+    touched): the B slots plus SpecState's words with n = B and, per slot, done and a stop block {n, min_new, ids}; one prefill plan
+    cache (DecodeSlots').  A slot without a request has done = 1: the verify attention skips it and the commit changes nothing, so it
+    never decodes garbage and needs no parking.  Not on a model with enable_prefix_caching (whose index protocol assumes parked,
+    decoding idle slots)."""
+
+    def __init__(self, model, B, kind):
+        if model.prefix_caching:
+            raise NotImplementedError("batched speculative decoding on a model built with enable_prefix_caching=True: the prefix index "
+                                      "assumes idle slots are parked and decoding; the single-sequence speculative path works there")
+        DecodeSlots.__init__(self, model, B)
+        SpecState.__init__(self, model, B)
+        self.kind = kind      # llm.step_kind(): the ban-masked arg-max pick of the slots' prefills
+        self.done = torch.ones(B, dtype=torch.int32, device=model.device)
+        self.eos = torch.zeros(B, 8, dtype=torch.int32, device=model.device)
+
+    def attn(self, l, qkv, *bufs, **kw):
+        m = self.model
+        ops.attn_verify_batch(qkv, self.pos, m.cos, m.sin, self.kc[0, l], self.vc[0, l], *bufs, B=self.B, cache_bs=self.kc.stride(0),
+                              skip=self.done, **kw)
+
+    def commit(self, T, plan, b=None, propose_only=False):
+        """usdm_spec_commit_batch over all slots or (b) slot b alone: the end of the step, or (propose_only) an admitted slot's first
+        drafts and input rows"""
+        parts, words = self.commit_words(T)
+        st = ops.decode_state(self.nxt, self.out, self.step, self.pos, advance_pos=True, batch=self.B, done=self.done, eos=self.eos)
+        st.max_out = self.model.max_out
+        lo, n = (0, None) if b is None else (b, 1)
+        ops.spec_commit_batch(*parts, st, **words, slot_lo=lo, n=n, propose_only=propose_only, plan=plan)
+        plan.hold(st)
+
+    def admit_spec(self, b, ids, T, limit, stops=(), min_new=0, script=None):
+        """Admit a prompt (ids [L]) into slot b: DecodeSlots.admit's per-slot prefill, whose pick is committed as step 1, then the
+        slot's stop block (the host checks every id anyway), its speculative words (seed), done = 0, and its first drafts and input
+        rows (propose)."""
+        self.admit(b, ids, self.kind)
+        self.eos[b] = stop_block(stops, min_new)[0]
+        self.seed(b, ids, limit, script)
+        self.done[b] = 0
+        self.propose(T, b)
 
     def release(self, b):
         """Slot b has no request: every launch of the step leaves it alone"""
@@ -374,8 +433,7 @@ class SpecSlots(DecodeSlots):
                 seq = toks[b][:min(steps[b], r["limit"])]
                 end = stop_index(seq, r["stops"], r["min_new"])
                 if end is not None or done[b] or len(seq) >= r["limit"]:
-                    c = self.counters[b].tolist()
-                    results[i] = (seq[:end], dict(steps=c[0], drafted=c[1], accepted=c[2]))
+                    results[i] = (seq[:end], self.stats(b))
                     self.release(b)
                     slots[b], freed = None, True
                 else:

@@ -1,6 +1,7 @@
 """Speculative greedy decoding with n-gram (prompt-lookup) drafts: argument checks shared by generate(), usdm_amd.serving and the CLI
-(DESIGN.md 8k).  The kernels are usdm_attn_verify and usdm_spec_commit; the step is USDMForCausalLM._build_decode_spec.  Batches
-(DESIGN.md 8k-2): usdm_attn_verify_batch and usdm_spec_commit_batch, slots.SpecSlots, USDMForCausalLM._build_decode_spec_batch."""
+(DESIGN.md 8k).  The kernels are usdm_attn_verify and usdm_spec_commit; the host state is slots.SpecState (the single sequence:
+slots.SpecSequence), the step USDMForCausalLM._build_spec_step.  Batches: usdm_attn_verify_batch and
+usdm_spec_commit_batch, slots.SpecSlots, the same state and step."""
 from . import ops
 
 MAX_SPECULATIVE_TOKENS = ops.SPEC_MAX_T - 1      # k drafts + the token to continue from = T <= 8 rows
