@@ -300,13 +300,18 @@ typedef struct usdm_gemv_args {
    *   -1 one tile per workgroup;
    *   >0 resident on at most this many workgroups.
    * A non-zero value also selects the 14-output tile at EVERY SwiGLU shape (so that both forms partition the RMSNorm sums alike at
-   * the small shapes of the tests).  Both forms give identical bits; FP8 / MXFP4 weights and x_delta have the one-tile form only. */
+   * the small shapes of the tests).  Both forms give identical bits; FP8 / MXFP4 weights and x_delta have the one-tile form only.
+   * A plain bf16 projection with K = 14336 (no SwiGLU, norm_w, x_delta, lm_head mode, merged input or fused all-reduce; down_proj
+   * of the 7B) has a straight-line form of the 16-wave one-row kernel, whose weight ring stays in flight through the K loop:
+   *   0  that form where the launcher picks 16-wave workgroups anyway (N = 16 * 256);  -1 never;
+   *   >0 that form at every N, one workgroup per 16 rows (the value itself means nothing more).  Identical bits again. */
   int32_t resident;
 } usdm_gemv_args;
 int usdm_gemv(const usdm_gemv_args* args, usdm_stream_t stream);
 int usdm_gemv_nblocks(int32_t N, int32_t act); /* number of partials the lm_head mode writes */
 
 int usdm_gemv_threads(const usdm_gemv_args* args);   /* threads per workgroup usdm_gemv would launch this projection with */
+int usdm_gemv_streams(const usdm_gemv_args* args);   /* 1 where usdm_gemv runs it (bf16 weights) in the straight-line K = 14336 form */
 
 /* Batched decode (the serving path's request lists, src/inference_vllm.py:109-125): the same projection over nb
  * input vectors, weights streamed ONCE per step.  g holds item 0's pointers; item b is at + b * stride.  Two forms:

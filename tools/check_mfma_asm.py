@@ -26,13 +26,15 @@ def trim(fifo, n):
     return fifo[-n:] if n else []
 
 
-def kernels(lines, pat):
-    """(name, first line, s_endpgm line) of every function whose label matches pat"""
+def kernels(lines, pat, whole=False):
+    """(name, first line, s_endpgm line) of every function whose label matches pat; whole: up to the function's end label instead
+    (a kernel with an early exit has its first s_endpgm in the prologue: gemv_stream_kernel's skip return)"""
     out = []
     for i, l in enumerate(lines):
         m = re.match(r"(_Z\S*" + pat + r"\S*):", l)
         if m:
-            i1 = next(j for j in range(i, len(lines)) if "s_endpgm" in lines[j])
+            end = ".Lfunc_end" if whole else "s_endpgm"
+            i1 = next(j for j in range(i, len(lines)) if end in lines[j])
             out.append((m.group(1), i, i1))
     return out
 

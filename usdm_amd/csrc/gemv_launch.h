@@ -9,7 +9,9 @@ namespace {
 // res: 0 = one tile per workgroup (grid = tiles); > 0 = the batch-1 bf16 launcher may run the tiles RESIDENT (gemv_resident_kernel)
 // on at most that many workgroups - how many the device holds at once is its question, asked at the launch, not here (this table
 // is also read where there is no device).
-struct gemv_sel { int rw, nwv; bool glu; int grid; int res; };
+// stream: the batch-1 bf16 launcher runs the row's straight-line form (gemv_stream_kernel) - the same workgroups, rows and threads
+// as gemv_kernel<1, false, 16>, which every other launcher of the row runs.
+struct gemv_sel { int rw, nwv; bool glu; int grid; int res; bool stream; };
 
 // Rows per wave: HBM streaming wants >= ~4 workgroups (16 waves) per CU in flight AND a grid that is a whole
 // number of workgroups per CU (256 CUs); take the largest RW that gives both, else the best balanced one.
@@ -39,7 +41,12 @@ static gemv_sel gemv_select(const usdm_gemv_args& a, bool batched) {
   // batch-1 only: the merged-attention input (also its cmb_gran hand-off form) and / or the peer-to-peer all-reduce epilogue have
   // the 4096-output shape of the 7B or the general one-row form
   if (!batched && (a.mrg_po || a.p2p_mode)) return rows_per_cu == 16 ? wide16 : gemv_sel{1, 4, false, cdiv(nout, 4)};
-  if (!glu && !a.part_val && rows_per_cu == 16) return wide16;
+  // down_proj of the 7B (K = 14336: 28 K iterations per row, 20 ring refills per lane), batch-1 only: the wide16 row in its
+  // straight-line form, whose weight ring stays in flight through the K loop (llm_k.hip gemv_stream_kernel)
+  // usdm_gemv_args.resident at this K and form: 0 = where wide16 applies; -1 = gemv_kernel; > 0 = at every N, one workgroup per 16 rows
+  const bool stream = !batched && !glu && !a.part_val && a.K == 14336 && !a.norm_w && !a.x_delta && a.resident >= 0;
+  if (stream && a.resident > 0) return gemv_sel{1, 16, false, cdiv(nout, 16), 0, true};
+  if (!glu && !a.part_val && rows_per_cu == 16) return gemv_sel{1, 16, false, 256, 0, stream};
   if (!glu && !a.part_val && rows_per_cu == 24) return wide12;
   // gate/up of the 7B (14336 outputs), batch-1 only: 7-wave workgroups of 14 outputs = 1024 workgroups = exactly two rounds of two
   // workgroups per CU, instead of 1792 four-wave workgroups = 1.75 rounds of four

@@ -23,6 +23,9 @@
 #ifndef USDM_GEMV_RES_PREFETCH
 #define USDM_GEMV_RES_PREFETCH 1   // 0: the residual is read in the epilogue (A/B builds)
 #endif
+#ifndef USDM_GEMV_DOWN_UNR
+#define USDM_GEMV_DOWN_UNR 8   // ring depth of gemv_stream_kernel (12 for A/B builds: 48 of its 128 VGPRs)
+#endif
 namespace {
 // ---------------------------------------------------------------------------------------------
 // GEMV: y = W x, W bf16 [N][ldw] row-major (the nn.Linear layout).
@@ -728,6 +731,85 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) v
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Straight-line form of gemv_kernel<1, false, 16> for bf16 weights and a long K (down_proj of the decode step, K = 14336; DESIGN.md
+// section 5): one row per wave, 16 waves per workgroup, K = NIT * 512 a compile-time count, no RMSNorm, no x_delta, no lm_head mode.
+// gemv_kernel's K loop refills a slot under a run-time test, and for that source the compiler lands every refill in a temporary
+// and waits for it - vmcnt(0) - before the next consume: the ring drains in every iteration.  Here the NIT iterations are
+// straight-line code and the ring is HAND-COUNTED, as gemv_resident_kernel's: every consume sits behind a wait that names the
+// UNR - 1 younger loads, and the freed slot is refilled at once, so UNR loads per lane stay in flight until the last UNR iterations.
+// Both of the thread's pieces of x are requested BEFORE the ring (gemv_kernel requests the second behind it: loads return in order,
+// so its LDS write, the barrier and the first consume waited for the whole first ring).
+// Per output the arithmetic is gemv_kernel's, statement for statement: the lane-to-K assignment, the iteration order, dot8,
+// wave_sum, the roundings around the residual add - identical bits.  A workgroup depends on nothing another workgroup does.
+// ---------------------------------------------------------------------------------------------
+template <int NIT, int UNR>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void gemv_stream_kernel(const usdm_gemv_args a) {
+  constexpr int NWV = 16, NTH = NWV * 64, K = NIT * 512;
+  static_assert(NIT >= UNR && UNR >= 1 && K <= 2 * NTH * 8, "a full first ring; a thread stages at most two pieces of x");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* xs = (bf16_t*)smem;  // [K] bf16
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int skipv = a.skip ? *a.skip : 0;   // requested now, tested once the first ring is in flight
+  GTR(0);
+  const int ob = blockIdx.x * NWV + wave;   // this wave's output (rows past N re-read the last row, never stored)
+  const int urow = min((int)blockIdx.x * NWV + __builtin_amdgcn_readfirstlane(wave), a.N - 1);   // wave-uniform: a scalar row base
+  const char* wp = (const char*)((const bf16_t*)a.W + (int64_t)urow * a.ldw);
+  const unsigned voff = lane * 16;          // this lane's 16 bytes of a K iteration (512 elements = 1024 bytes)
+  auto aload = [&](u32x4& dst, const char* p, auto IT) {
+    constexpr int it = decltype(IT)::value;
+    const unsigned vo = voff + (it >> 2) * 4096u;
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(dst) : "v"(vo), "s"(p), "n"((it & 3) * 1024) : "memory");
+  };
+  // ---- prologue.  The residual value as gemv_kernel requests it: unconditional, the weight row as a dummy address without one.
+  const bf16_t* rbase = a.residual ? (const bf16_t*)a.residual : (const bf16_t*)a.W;
+  const unsigned short resraw = rbase[min(ob, a.N - 1)];
+  // Both pieces of x, hand-counted and unconditional (the second with a clamped index; written to LDS only where inside K)
+  const int i0 = tid * 8, i1 = i0 + NTH * 8;
+  u32x4 x0, x1;
+  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x0) : "v"((const bf16_t*)a.x + min(i0, K - 8)) : "memory");
+  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x1) : "v"((const bf16_t*)a.x + min(i1, K - 8)) : "memory");
+  u32x4 ring[UNR];   // always UNR loads: the wait below names an exact count
+  gemv_for<UNR>([&](auto U) { aload(ring[U.value], wp, U); });
+  GTR(1);
+  // in-order completion: x has landed, the ring stays in flight.  (The skip word is an operand so that its test, and with it the
+  // wait for its scalar load, stays behind the ring's issue.)
+  asm volatile("s_waitcnt vmcnt(%3)" : "+v"(x0), "+v"(x1), "+s"(skipv) : "n"(UNR));
+  if (skipv) return;
+  if (i0 < K) *(u32x4*)(xs + i0) = x0;
+  if (i1 < K) *(u32x4*)(xs + i1) = x1;
+  __syncthreads();
+  GTR(2);
+
+  // ---- stream: NIT iterations, straight-line.  The consumed slot's load is the oldest of the UNR in flight: the wait leaves the
+  // UNR - 1 younger ones; in the last UNR iterations nothing is refilled and the count falls by one per consume.  The lane's piece
+  // of x is read from LDS one iteration ahead (the asm statements are compiler barriers: the read would sit in front of its use).
+  float acc = 0.f;
+  u32x4 xv = *(const u32x4*)(xs + lane * 8);
+  gemv_for<NIT>([&](auto IT) {
+    constexpr int it = decltype(IT)::value, u = it % UNR;
+    constexpr int younger = it + UNR < NIT ? UNR - 1 : NIT - 1 - it;
+    const u32x4 xn = *(const u32x4*)(xs + (((it + 1) % NIT) * 64 + lane) * 8);
+    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ring[u]) : "n"(younger) : "memory");
+    acc = dot8(ring[u], xv, acc);
+    if constexpr (it + UNR < NIT) aload(ring[u], wp, gemv_ic<it + UNR>{});
+    xv = xn;
+  });
+  acc = wave_sum(acc);
+  GTR(3);
+
+  // ---- epilogue (gemv_kernel's plain form)
+  if (lane != 0 || ob >= a.N) return;
+  float v = acc;
+  if (a.round_bf16) v = round_bf(v);
+  if (a.residual) {
+    v += bf2f(resraw);
+    if (a.round_bf16) v = round_bf(v);
+  }
+  if (a.y16) ((bf16_t*)a.y16)[ob] = f2bf(v);
+  if (a.y32) a.y32[ob] = v;
+}
+
 // final arg-max over the per-block partials; advances the device-side decode state
 // (nseg segments of nparts partials per sequence, seg_stride apart: the tensor-parallel batched step gathers [rank][sequence][nparts])
 __global__ void argmax_final_kernel(const float* pv, const int* pi, int nparts, int nseg, int64_t seg_stride, usdm_decode_state st,
@@ -828,6 +910,11 @@ static int gemv_launch(const usdm_gemv_args& a, hipStream_t st, FMT... fmt) {
   const size_t lds = (size_t)((a.K + 511) & ~511) * 2;
   const gemv_sel s = gemv_select(a, false);
   if constexpr (FORM == GEMV_PLAIN && !FP8 && sizeof...(FMT) == 0) {
+    if (s.stream) {   // K = 14336 = 28 iterations (gemv_select)
+      hipLaunchKernelGGL((gemv_stream_kernel<28, USDM_GEMV_DOWN_UNR>), dim3(s.grid), dim3(1024), lds, st, a);
+      USDM_LAUNCH_CHECK();
+      return 0;
+    }
     if (s.res > 0) {
       bool launched = false;
       if (int rc = gemv_launch_resident(a, s, lds, st, &launched)) return rc;
@@ -990,6 +1077,8 @@ extern "C" int usdm_gemv_nblocks(int32_t N, int32_t act) { return cdiv(N, 16); }
 // threads per workgroup of the variant usdm_gemv launches for this projection: gemv_select's, the launcher's own choice (the
 // fused RMSNorm's partial sums follow that partition; usdm_gemv_engine reproduces it to stay bit-identical)
 extern "C" int usdm_gemv_threads(const usdm_gemv_args* pa) { return 64 * gemv_select(*pa, false).nwv; }
+// 1 where usdm_gemv runs this (bf16) projection in the straight-line form (gemv_stream_kernel)
+extern "C" int usdm_gemv_streams(const usdm_gemv_args* pa) { return gemv_select(*pa, false).stream ? 1 : 0; }
 
 extern "C" int usdm_argmax_final_seg(const float* part_val, const int32_t* part_idx, int32_t nparts, int32_t nseg, int64_t seg_stride,
                                      const usdm_decode_state* st, const void* embed_table, int32_t Hd, void* h_out,

@@ -253,7 +253,8 @@ def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p
     """usdm_gemv: batch-1 weight-streaming GEMV (see include/usdm_hip.h; **common: the keywords of _fill_gemv).
     p2p: a usdm_amd.p2p.P2PComm (fused all-reduce).
     resident: usdm_gemv_args.resident (SwiGLU: 0 the launcher's choice, -1 one tile per workgroup, n > 0 resident on at most n
-    workgroups); None: USDM_GEMV_RESIDENT, else 0.
+    workgroups; a plain K = 14336 projection: 0 the launcher's choice, -1 gemv_kernel, n > 0 the straight-line form at any N);
+    None: USDM_GEMV_RESIDENT, else 0.
     only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
     W a quant.Fp8Weight / quant.Mxfp4Weight: usdm_gemv_fp8 / usdm_gemv_mxfp4 (the plain single-GPU forms only; the library refuses
     the others)."""
