@@ -27,6 +27,13 @@ Conventions (those of tests/_gemm_reference.py)
     elements x 16, norm_w = 1 + 0.1 Gaussian.  The reference x' is evaluated at rstd (1 - DELTA) and rstd (1 + DELTA); a GPU element
     must equal one of the two.
 
+Quantized weight formats (Case.fmt = "fp8" | "mxfp4": usdm_gemv_fp8, usdm_gemv_mxfp4, their VALU batch forms, usdm_gemv_fp8_mfma; the
+cases of tests/test_gemv_quant_exact_gpu.py).  The logical weights are the same small integers times a power of two per row (FP8)
+or per block of 32 (MXFP4) that differs between neighbours (weight_exponents), so that dequantize(quantize(W)) = W bit for bit and
+the fp64 reference above is the exact reference of these kernels too; device_weight builds what the entry points take (FP8: NaN
+bytes in the gap after every row and in one more row).  Probe rows are not scaled.  The K ladders follow the format's own ring
+(fmt_ring_depth, k_ladder).
+
 DELTA.  x is bf16, so every square is exact in f32 and only the additions of the sum of squares round.  All terms are positive: a
 sum whose longest chain has n additions is within n 2^-24 of the true sum, relatively.  The longest chain of any instantiation is
 the matrix-core kernel's at K = 4096: 128 sequential FMAs per lane (16 held fragments of 8 elements), 2 cross-lane additions and 8
@@ -121,6 +128,16 @@ def ring_depth(rw, glu):
     return 2 if nr >= 8 else 4 if nr >= 4 else 5 if nr == 3 else 8
 
 
+FMTS = ("fp8", "mxfp4")     # the quantized weight formats; "bf16" is the default of every case
+
+
+def fmt_ring_depth(rw, glu, fmt="bf16"):
+    """gemv_ring_depth(NR, FP8, MX4): FP8 twice the bf16 depth (8-byte loads); MXFP4: slots of one group = four K iterations"""
+    if fmt == "mxfp4":
+        return 2 if (2 * rw if glu else rw) >= 3 else 4
+    return ring_depth(rw, glu) * (2 if fmt == "fp8" else 1)
+
+
 MW, CH, KS_K, KS_MAX, MTG_TRL = 8, 16, 2048, 8, 8
 MFMA_VARIANTS = ("hold", "hold16-recut", "hold16-frag", "stream", "stream56-recut", "stream56-frag", "ksplit")
 
@@ -172,21 +189,27 @@ class Case:
     "exact" | "probe"; ban: None | "none" | "workgroup" | "wave" | "scattered" | "last" (lm_head mode when not None)"""
 
     def __init__(self, name, *, N, K, seed, nb=0, form=0, glu=False, kind="int", norm=None, res=False, inplace=False, ban=None, idx_offset=0,
-                 delta=False, skip=False, ks=False, inst=None, variant=None, rt=None):
+                 delta=False, skip=False, ks=False, inst=None, variant=None, rt=None, fmt="bf16", mfma=None):
         self.name, self.N, self.K, self.seed, self.nb, self.form, self.glu = name, N, K, seed, nb, form, glu
         self.kind, self.norm, self.res, self.inplace, self.ban, self.idx_offset = kind, norm, res, inplace, ban, idx_offset
         self.delta, self.skip, self.ks, self.inst, self.variant, self.rt = delta, skip, ks, inst, variant, rt
+        self.fmt = fmt
         self.B = max(nb, 1)
         self.lm_head = ban is not None
-        self.mfma = nb >= 1 and (form in (1, 3, 5) or (form == 0 and nb > 4))
+        # (mfma=True: usdm_gemv_fp8_mfma, which runs the matrix cores at every nb and takes form 0 where usdm_gemv_batch takes 1)
+        self.mfma = (nb >= 1 and (form in (1, 3, 5) or (form == 0 and nb > 4))) if mfma is None else mfma
         self.nout = N // 2 if glu else N
         self.ldw = self.x_bs = K + PAD
+        if fmt == "fp8" and self.mfma:       # usdm_gemv_fp8_mfma wants 16-byte rows of bytes: a gap of 16
+            self.ldw = K + 2 * PAD
         self.y_bs = self.nout + 5
         self.res_bs = self.y_bs if inplace else self.nout + 3
         self.sel = mfma_select(N, K, glu=glu, lm_head=self.lm_head, norm=norm is not None, form=form, ks=ks) if self.mfma else None
         self.nparts = (self.sel["grid"] if self.mfma else cdiv(N, 16)) if self.lm_head else 0
         self.part_bs = self.nparts + 3 if self.lm_head else 0
         assert not (glu and (res or self.lm_head)) and not (delta and nb) and K % 8 == 0
+        assert fmt == "bf16" or (fmt in FMTS and not delta and form != 3), "the quantized formats refuse x_delta and have no fragment-shaped form"
+        assert fmt != "mxfp4" or (K % 32 == 0 and not self.lm_head and not self.mfma), "MXFP4: whole blocks of 32, no lm_head mode, no matrix cores"
 
     @property
     def act(self):
@@ -254,6 +277,47 @@ def ban_pattern(c):
     return ban
 
 
+def weight_exponents(c):
+    """int32 [N][1] (FP8: per row) or [N][K / 32] (MXFP4: per block): the power of two each logical weight of an integer or SwiGLU
+    case is multiplied by, so that neighbouring rows and blocks have different scales.  Integer cases: -3 ... 3 per row, 0 ... 3 per
+    block.  SwiGLU cases shrink only (|g| <= 20 stays true): -3 ... 0, four values, because the sparse +-1 weights have one magnitude
+    per scale and the CPU test asks for four distinct exponents (scale bytes) per case.
+    The row term is (5 n) mod 7 throughout: its period is odd, so rows 1, 4 or 16 apart (the next row, wave, gate / up partner) differ.
+    MXFP4: ((5 n) mod 7 + 3 b + 3 (b div 64)) mod 4 for block b of row n.  With (n + 3 b) mod 4 alone, rows 4 apart and blocks 64
+    apart (the same place in the next group, i.e. in the next ring slot) would share their scales, and a kernel that took the scale
+    dword of the wrong slot or row would still pass.  The factor 3 keeps blocks 1, 64 and 128 apart different (4 groups apart
+    coincide: there are four values)."""
+    n = (5 * torch.arange(c.N, dtype=torch.int32).view(-1, 1)) % 7
+    if c.fmt == "fp8":
+        return -(n % 4) if c.kind == "swiglu" else n - 3
+    b = torch.arange(c.K // 32, dtype=torch.int32).view(1, -1)
+    e = (n + 3 * b + 3 * (b // 64)) % 4
+    return -e if c.kind == "swiglu" else e
+
+
+FP8_NAN = 0x7f      # e4m3fn NaN: the fill of the gaps of an FP8 weight buffer
+
+
+def device_weight(c, d, dev="cpu", fmt=None):
+    """(W, ldw) as ops.gemv / gemv_batch / gemv_fp8_mfma take it, on dev.  fmt (default: the case's): "bf16" gives the guarded bf16
+    buffer of d.Wl (of a quantized case: the operand of the bf16 entry point it is compared with).  "fp8": quantize_rows(d.Wl) with
+    q widened to [N + 1][ldw], NaN bytes in the gap and in the extra row (whose exponent is 0).  "mxfp4": Mxfp4Weight.from_matrix;
+    its padding to whole groups (zero codes, scale bytes 127) belongs to the format.  Quantization runs on dev (it is deterministic:
+    comparisons, frexp and ldexp only), once per case."""
+    from usdm_amd import quant
+    fmt = c.fmt if fmt is None else fmt
+    if fmt == "bf16":
+        W = _guarded(d.Wl, c.K + PAD) if d.W is None else d.W
+        return W.to(dev), c.K + PAD
+    Wl = d.Wl.to(dev)
+    if fmt == "mxfp4":
+        return quant.Mxfp4Weight.from_matrix(Wl), None
+    q, e = quant.quantize_rows(Wl)
+    buf = torch.full((c.N + 1, c.ldw), FP8_NAN, dtype=torch.uint8, device=dev)
+    buf[:c.N, :c.K] = q
+    return quant.Fp8Weight(buf, torch.cat([e, torch.zeros(1, dtype=torch.int8, device=dev)])), c.ldw
+
+
 def build(c):
     """the case's logical operands (fp64 / bf16) and its guarded flat buffers, all on the CPU"""
     d, g = Data(), gen(c.seed)
@@ -291,7 +355,12 @@ def build(c):
         d.Wl = (_ints((N, K), g, 0, 1) * 2 - 1).to(BF) * keep.to(BF)
     else:
         d.Wl = (_ints((N, K), g, -1, 3) * (_ints((N, 1), g, 0, 1) * 2 - 1)).to(BF)
-    d.W = _guarded(d.Wl, c.ldw)
+    d.wexp = None
+    if c.fmt != "bf16" and c.kind != "probe":
+        d.wexp = weight_exponents(c)
+        # exact: small integers x 2^e; + 0.0: the sparse SwiGLU weights hold -0.0, which the MXFP4 codes do not have
+        d.Wl = (torch.ldexp(d.Wl.float().view(N, d.wexp.shape[1], -1), d.wexp.float()[:, :, None]).view(N, K) + 0.0).to(BF)
+    d.W = _guarded(d.Wl, c.ldw) if c.fmt == "bf16" else None      # (the quantized formats: device_weight)
     d.x = _guarded(d.xl, c.x_bs)
     d.norm_w = None if d.gl is None else _guarded(d.gl.view(1, -1), K + PAD, rows=0, dtype=F32)
     # ---- x_delta: integer-valued f32 (with the exact norm family: zero but for a few elements whose x + delta is again +-2)
@@ -395,11 +464,32 @@ def expected(c, d, *, rbf, scale=1.0):
 
 
 # ---- usdm_gemv: the K ladder of an instantiation (UNR: its ring depth, threads: its workgroup)
-def k_ladder(inst, small):
+def k_ladder(inst, small, fmt="bf16"):
+    """u: the elements of one ring; t: the workgroup's first pass over x.  MXFP4 (K % 32 == 0): 2048 is the group boundary"""
     rw, glu, nwv = (4, False, 4) if inst == "lm" else inst
-    u, t = 512 * ring_depth(rw, glu), 8 * 64 * nwv
-    ks = (8, 504, 512, 520, u - 8, u, u + 8, t, t + 8, 16384) if small else (504, u + 8, t + 8)
+    t = 8 * 64 * nwv
+    if fmt == "mxfp4":
+        u = 2048 * fmt_ring_depth(rw, glu, fmt)
+        ks = (32, 480, 512, 544, 2016, 2048, 2080, u - 32, u, u + 32, t, t + 32, 16384) if small else (480, 2080, u + 32, t + 32)
+    else:
+        u = 512 * fmt_ring_depth(rw, glu, fmt)
+        ks = (8, 504, 512, 520, u - 8, u, u + 8, t, t + 8, 16384) if small else (504, u + 8, t + 8)
     return sorted(set(ks))
+
+
+def ragged_k(fmt):
+    """the first K with a ragged (FP8: redirected) last iteration; one iteration of 512"""
+    return 480 if fmt == "mxfp4" else 504
+
+
+def k_step(fmt):
+    return 32 if fmt == "mxfp4" else 8
+
+
+FMT_SEED = {"bf16": 0, "fp8": 100000, "mxfp4": 200000}
+# The probe's cap (2 % of a case's elements may differ between its two references) is less than one element of the 37- and
+# 48-output cases, so their seeds are ones at which no element sits on a rounding boundary of the reference (the CPU test checks it)
+PROBE_SEED = {"bf16": 0, "fp8": 2, "mxfp4": 5}
 
 
 def _shape(inst):
@@ -412,51 +502,68 @@ def is_small(inst):
     return inst == "lm" or inst in SMALL_INST
 
 
-def _mk(name, inst, K, seed, nb=0, **kw):
+def _mk(name, inst, K, seed, nb=0, fmt="bf16", **kw):
     a = dict(_shape(inst), **kw)
     if a.get("glu") and a.get("kind", "int") == "int":
         a["kind"] = "swiglu"
     if nb:
         a.update(nb=nb, form=-1)
-    return Case(f"{inst_id(inst)} {name} K{K}" + (f" nb{nb}" if nb else ""), K=K, seed=seed, **a)
+    return Case(_pre(fmt) + f"{inst_id(inst)} {name} K{K}" + (f" nb{nb}" if nb else ""), K=K, seed=seed + FMT_SEED[fmt], fmt=fmt, **a)
+
+
+def _pre(fmt):
+    return "" if fmt == "bf16" else fmt + " "
+
+
+def _ks(inst, nb, fmt):
+    """the K of a family: the instantiation's ladder; batched: the first ragged K and one step past the first pass over x"""
+    if not nb:
+        return k_ladder(inst, is_small(inst), fmt)
+    return (ragged_k(fmt), 8 * 64 * (4 if inst == "lm" else inst[2]) + k_step(fmt))
 
 
 def _seed(inst, j):
     return 1000 * (list(VALU_INST).index(inst) + 1 if inst != "lm" else 10) + j
 
 
-def valu_plain_cases(inst, nb=0):
+def valu_plain_cases(inst, nb=0, fmt="bf16"):
     """plain with a residual (GLU: SwiGLU; lm_head: no ban) over the K ladder"""
-    ks = k_ladder(inst, is_small(inst)) if not nb else (504, 8 * 64 * (4 if inst == "lm" else inst[2]) + 8)
-    return [_mk("plain", inst, K, _seed(inst, j) + 50 * nb, nb, res=inst != "lm" and not inst[1]) for j, K in enumerate(ks)]
+    return [_mk("plain", inst, K, _seed(inst, j) + 50 * nb, nb, fmt, res=inst != "lm" and not inst[1]) for j, K in enumerate(_ks(inst, nb, fmt))]
 
 
-def valu_norm_exact_cases(inst, nb=0):
-    ks = k_ladder(inst, is_small(inst)) if not nb else (504, 8 * 64 * (4 if inst == "lm" else inst[2]) + 8)
-    return [_mk("norm-exact", inst, K, _seed(inst, j) + 100 + 50 * nb, nb, norm="exact", res=inst != "lm" and not inst[1]) for j, K in enumerate(ks)]
+def valu_norm_exact_cases(inst, nb=0, fmt="bf16"):
+    return [_mk("norm-exact", inst, K, _seed(inst, j) + 100 + 50 * nb, nb, fmt, norm="exact", res=inst != "lm" and not inst[1])
+            for j, K in enumerate(_ks(inst, nb, fmt))]
 
 
-def valu_probe_cases(inst, nb=0):
+def valu_probe_cases(inst, nb=0, fmt="bf16"):
     t = 64 * (4 if inst == "lm" else inst[2])
-    return [_mk("norm-probe", inst, K, _seed(inst, j) + 200 + 50 * nb, nb, kind="probe", norm="probe") for j, K in enumerate((504, 8 * t + 8))]
+    return [_mk("norm-probe", inst, K, _seed(inst, j) + 200 + 50 * nb + PROBE_SEED[fmt], nb, fmt, kind="probe", norm="probe")
+            for j, K in enumerate((ragged_k(fmt), 8 * t + k_step(fmt)))]
 
 
 BANS = ("none", "workgroup", "wave", "scattered", "last")           # "none": no ban array at all (a NULL pointer)
 
 
-def lm_head_cases(nb=0, mfma=False):
+def lm_head_cases(nb=0, mfma=False, fmt="bf16"):
     """every ban pattern, in every form: the banning ones at a one-iteration and a ragged multi-iteration K (matrix cores: multiples of
     256), idx_offset != 0 on two; no ban array at K = 520 (matrix cores: K = 4096, the row-contiguous loads)"""
     out = []
     for j, ban in enumerate(BANS[1:]):
         K = (256, 3840)[j % 2] if mfma else (504, 2056)[j % 2]
-        kw = dict(nb=nb, form=1, variant="hold", rt=16) if mfma else (dict(nb=nb, form=-1) if nb else {})
-        out.append(Case(f"lm_head {ban} K{K}" + (f" nb{nb}" if nb else ""), N=LM_N, K=K, seed=11000 + j + 10 * nb, ban=ban,
-                        idx_offset=(0, 70000)[j // 2], inst="lm", **kw))
+        kw = dict(nb=nb, variant="hold", rt=16, **_mfma_form(1, fmt)) if mfma else (dict(nb=nb, form=-1) if nb else {})
+        out.append(Case(_pre(fmt) + f"lm_head {ban} K{K}" + (f" nb{nb}" if nb else ""), N=LM_N, K=K, seed=11000 + j + 10 * nb + FMT_SEED[fmt], ban=ban,
+                        idx_offset=(0, 70000)[j // 2], inst="lm", fmt=fmt, **kw))
     K = 4096 if mfma else 520
-    kw = dict(nb=nb, form=1, variant="hold16-recut", rt=16) if mfma else (dict(nb=nb, form=-1) if nb else {})
-    out.append(Case(f"lm_head none K{K}" + (f" nb{nb}" if nb else ""), N=LM_N, K=K, seed=11005 + 10 * nb, ban="none", idx_offset=123, inst="lm", **kw))
+    kw = dict(nb=nb, variant="hold16-recut", rt=16, **_mfma_form(1, fmt)) if mfma else (dict(nb=nb, form=-1) if nb else {})
+    out.append(Case(_pre(fmt) + f"lm_head none K{K}" + (f" nb{nb}" if nb else ""), N=LM_N, K=K, seed=11005 + 10 * nb + FMT_SEED[fmt], ban="none", idx_offset=123,
+                    inst="lm", fmt=fmt, **kw))
     return out
+
+
+def _mfma_form(form, fmt):
+    """the matrix-core form of a case: usdm_gemv_fp8_mfma takes 0 where usdm_gemv_batch takes 1, and 5 as it is"""
+    return dict(form=form) if fmt == "bf16" else dict(form=0 if form == 1 else form, mfma=True)
 
 
 def delta_cases(inst):
@@ -464,8 +571,10 @@ def delta_cases(inst):
             _mk("x_delta", inst, 504, _seed(inst, 302), delta=True, res=True), _mk("x_delta+norm", inst, 8200, _seed(inst, 303), delta=True, norm="exact")]
 
 
-def skip_cases(inst):
-    return [_mk("skip", inst, 520, _seed(inst, 310), skip=True, res=True, delta=True), _mk("skip+norm", inst, 520, _seed(inst, 311), skip=True, norm="exact")]
+def skip_cases(inst, fmt="bf16"):
+    K = 544 if fmt == "mxfp4" else 520
+    return [_mk("skip", inst, K, _seed(inst, 310), fmt=fmt, skip=True, res=True, delta=fmt == "bf16"),
+            _mk("skip+norm", inst, K, _seed(inst, 311), fmt=fmt, skip=True, norm="exact")]
 
 
 DELTA_INST = ((1, False, 4), (1, False, 16))
@@ -488,34 +597,76 @@ N_ROWS12 = 6144
 N_SWIGLU = 96
 
 
-def mfma_ladder_cases(nb):
-    """N = 37 with a residual, in place (y16 = residual) in the round_bf16 launch, over every variant"""
-    return [Case(f"mfma K{K} form{f}{' ks' if ks else ''} nb{nb}", N=N_SMALL, K=K, seed=20000 + 20 * j + nb, nb=nb, form=f, ks=ks, res=True, inplace=True,
-                 variant=MFMA_LADDER_VARIANT[j], rt=16 if ks else 8) for j, (K, f, ks) in enumerate(MFMA_LADDER)]
+def mfma_ladder_cases(nb, fmt="bf16"):
+    """N = 37 with a residual, in place (y16 = residual) in the round_bf16 launch, over every variant (FP8: all but the
+    fragment-shaped form 3, which usdm_gemv_fp8_mfma does not have)"""
+    return [Case(_pre(fmt) + f"mfma K{K} form{f}{' ks' if ks else ''} nb{nb}", N=N_SMALL, K=K, seed=20000 + 20 * j + nb + FMT_SEED[fmt], nb=nb, ks=ks, res=True,
+                 inplace=True, variant=MFMA_LADDER_VARIANT[j], rt=16 if ks else 8, fmt=fmt, **_mfma_form(f, fmt))
+            for j, (K, f, ks) in enumerate(MFMA_LADDER) if fmt == "bf16" or f != 3]
 
 
-def mfma_tile_cases(nb):
-    """12-row tiles (N = 6144), ragged 16-row tiles (N = 4085), at a generic held K and on both K = 4096 load patterns"""
+def mfma_tile_cases(nb, fmt="bf16"):
+    """12-row tiles (N = 6144), ragged 16-row tiles (N = 4085), at a generic held K and on both K = 4096 load patterns (FP8: K = 4096
+    on its forms 0 and 5, both with the re-cut loads)"""
     out = []
+    third = (4096, 3, "hold16-frag") if fmt == "bf16" else (4096, 5, "hold16-recut")
     for i, (N, rt) in enumerate(((N_ROWS12, 12), (N_RAGGED16, 16))):
-        for j, (K, f, v) in enumerate(((256, 1, "hold"), (4096, 1, "hold16-recut"), (4096, 3, "hold16-frag"))):
-            out.append(Case(f"mfma N{N} K{K} form{f} nb{nb}", N=N, K=K, seed=21000 + 10 * i + j + 100 * nb, nb=nb, form=f, res=True, inplace=True, variant=v, rt=rt))
+        for j, (K, f, v) in enumerate(((256, 1, "hold"), (4096, 1, "hold16-recut"), third)):
+            out.append(Case(_pre(fmt) + f"mfma N{N} K{K} form{f} nb{nb}", N=N, K=K, seed=21000 + 10 * i + j + 100 * nb + FMT_SEED[fmt], nb=nb, res=True, inplace=True,
+                            variant=v, rt=rt, fmt=fmt, **_mfma_form(f, fmt)))
     return out
 
 
-def mfma_swiglu_cases(nb):
-    return [Case(f"mfma swiglu K{K} form{f} nb{nb}", N=N_SWIGLU, K=K, seed=22000 + j + 10 * nb, nb=nb, form=f, glu=True, kind="swiglu", variant=v, rt=16)
-            for j, (K, f, v) in enumerate(((256, 1, "hold"), (4096, 1, "hold16-recut"), (4096, 3, "hold16-frag"), (6144, 5, "stream")))]
+def mfma_swiglu_cases(nb, fmt="bf16"):
+    return [Case(_pre(fmt) + f"mfma swiglu K{K} form{f} nb{nb}", N=N_SWIGLU, K=K, seed=22000 + j + 10 * nb + FMT_SEED[fmt], nb=nb, glu=True, kind="swiglu", variant=v,
+                 rt=16, fmt=fmt, **_mfma_form(f, fmt))
+            for j, (K, f, v) in enumerate(((256, 1, "hold"), (4096, 1, "hold16-recut"), (4096, 3, "hold16-frag"), (6144, 5, "stream"))) if fmt == "bf16" or f != 3]
 
 
-def mfma_norm_cases(nb):
+def mfma_norm_cases(nb, fmt="bf16"):
     """both RMSNorm families at K <= 4096 (the matrix-core form fuses the norm into the held activations only)"""
-    out = []
+    out, s = [], FMT_SEED[fmt]
     for j, (K, f, v) in enumerate(((256, 1, "hold"), (3840, 1, "hold"), (4096, 1, "hold16-recut"), (4096, 3, "hold16-frag"))):
-        out.append(Case(f"mfma norm-exact K{K} form{f} nb{nb}", N=N_SMALL, K=K, seed=23000 + j + 10 * nb, nb=nb, form=f, norm="exact", res=True, variant=v, rt=8))
-        out.append(Case(f"mfma norm-probe K{K} form{f} nb{nb}", N=4096, K=K, seed=23500 + j + 10 * nb, nb=nb, form=f, kind="probe", norm="probe", variant=v, rt=16))   # N >= K: all of K
-    out.append(Case(f"mfma swiglu norm-exact K4096 nb{nb}", N=N_SWIGLU, K=4096, seed=23900 + nb, nb=nb, form=1, glu=True, kind="swiglu", norm="exact",
-                    variant="hold16-recut", rt=16))
+        if fmt != "bf16" and f == 3:
+            continue
+        out.append(Case(_pre(fmt) + f"mfma norm-exact K{K} form{f} nb{nb}", N=N_SMALL, K=K, seed=23000 + j + 10 * nb + s, nb=nb, norm="exact", res=True, variant=v,
+                        rt=8, fmt=fmt, **_mfma_form(f, fmt)))
+        out.append(Case(_pre(fmt) + f"mfma norm-probe K{K} form{f} nb{nb}", N=4096, K=K, seed=23500 + j + 10 * nb + s, nb=nb, kind="probe", norm="probe", variant=v,
+                        rt=16, fmt=fmt, **_mfma_form(f, fmt)))   # N >= K: all of K
+    out.append(Case(_pre(fmt) + f"mfma swiglu norm-exact K4096 nb{nb}", N=N_SWIGLU, K=4096, seed=23900 + nb + s, nb=nb, glu=True, kind="swiglu", norm="exact",
+                    variant="hold16-recut", rt=16, fmt=fmt, **_mfma_form(1, fmt)))
+    return out
+
+
+FP8_MFMA_VARIANTS = ("hold", "hold16-recut", "stream", "stream56-recut", "ksplit")
+
+
+def quant_insts(fmt):
+    """the instantiations a format reaches: MXFP4 has no lm_head mode"""
+    return list(VALU_INST) + (["lm"] if fmt == "fp8" else [])
+
+
+def quant_batch_insts(fmt):
+    return BATCH_INST + (("lm",) if fmt == "fp8" else ())
+
+
+def quant_cases():
+    """every case of tests/test_gemv_quant_exact_gpu.py"""
+    out = []
+    for fmt in FMTS:
+        for inst in quant_insts(fmt):
+            out += valu_plain_cases(inst, fmt=fmt) + valu_norm_exact_cases(inst, fmt=fmt) + valu_probe_cases(inst, fmt=fmt)
+        for inst in DELTA_INST:
+            out += skip_cases(inst, fmt)
+        for nb in VALU_NB:
+            for inst in quant_batch_insts(fmt):
+                out += valu_plain_cases(inst, nb, fmt) + valu_norm_exact_cases(inst, nb, fmt) + valu_probe_cases(inst, nb, fmt)
+    out += lm_head_cases(fmt="fp8")
+    for nb in VALU_NB:
+        out += lm_head_cases(nb, fmt="fp8")
+    for nb in MFMA_NB:
+        out += (mfma_ladder_cases(nb, "fp8") + mfma_tile_cases(nb, "fp8") + mfma_swiglu_cases(nb, "fp8") + mfma_norm_cases(nb, "fp8")
+                + lm_head_cases(nb, mfma=True, fmt="fp8"))
     return out
 
 
@@ -533,4 +684,4 @@ def all_cases():
         out += lm_head_cases(nb)
     for nb in MFMA_NB:
         out += mfma_ladder_cases(nb) + mfma_tile_cases(nb) + mfma_swiglu_cases(nb) + mfma_norm_cases(nb) + lm_head_cases(nb, mfma=True)
-    return out
+    return out + quant_cases()

@@ -67,6 +67,165 @@ def test_k_ladders():
     assert R.k_ladder((3, False, 4), False) == [504, 2056, 2568] and R.k_ladder((2, True, 7), False) == [504, 2056, 3592]
 
 
+def test_quant_ring_mirror_and_k_ladders():
+    """the FP8 ring is twice the bf16 one, an MXFP4 slot is a group of four iterations; every ladder has a K above one ring whose last
+    iteration is ragged (FP8: the refill meets the redirect to the row start) or whose last group is partial (MXFP4)"""
+    assert [R.fmt_ring_depth(*i[:2], "fp8") for i in R.VALU_INST] == [16, 16, 10, 8, 16, 16, 16, 8, 8]
+    assert [R.fmt_ring_depth(*i[:2], "mxfp4") for i in R.VALU_INST] == [4, 4, 2, 2, 4, 4, 4, 2, 2]
+    assert [R.fmt_ring_depth(*i[:2]) for i in R.VALU_INST] == [R.ring_depth(*i[:2]) for i in R.VALU_INST]
+    assert R.k_ladder((1, False, 4), True, "fp8") == [8, 504, 512, 520, 2048, 2056, 8184, 8192, 8200, 16384]
+    assert R.k_ladder((3, False, 4), False, "fp8") == [504, 2056, 5128]
+    assert R.k_ladder("lm", True, "fp8") == [8, 504, 512, 520, 2048, 2056, 4088, 4096, 4104, 16384]
+    assert R.k_ladder((4, False, 4), False, "fp8") == [504, 2056, 4104] and R.k_ladder((2, True, 7), False, "fp8") == [504, 3592, 4104]
+    assert R.k_ladder((1, False, 16), False, "fp8") == [504, 8200] and R.k_ladder((2, False, 12), False, "fp8") == [504, 6152, 8200]
+    assert R.k_ladder((1, False, 4), True, "mxfp4") == [32, 480, 512, 544, 2016, 2048, 2080, 8160, 8192, 8224, 16384]
+    assert R.k_ladder((1, True, 4), True, "mxfp4") == R.k_ladder((1, False, 4), True, "mxfp4")
+    assert R.k_ladder((3, False, 4), False, "mxfp4") == [480, 2080, 4128] and R.k_ladder((2, True, 7), False, "mxfp4") == [480, 2080, 3616, 4128]
+    assert R.k_ladder((1, False, 16), False, "mxfp4") == [480, 2080, 8224] and R.k_ladder((2, False, 12), False, "mxfp4") == [480, 2080, 6176, 8224]
+    assert R.k_ladder((1, False, 4), True) == R.k_ladder((1, False, 4), True, "bf16")
+    for fmt in R.FMTS:
+        for inst in R.quant_insts(fmt):
+            rw, glu, _ = (4, False, 4) if inst == "lm" else inst
+            ring = (2048 if fmt == "mxfp4" else 512) * R.fmt_ring_depth(rw, glu, fmt)
+            ks = R.k_ladder(inst, R.is_small(inst), fmt)
+            assert any(K > ring and K % (2048 if fmt == "mxfp4" else 512) != 0 for K in ks), (fmt, inst)
+            assert all(K % R.k_step(fmt) == 0 and K <= 16384 for K in ks)
+            assert {c.K for c in R.valu_plain_cases(inst, fmt=fmt)} == set(ks) == {c.K for c in R.valu_norm_exact_cases(inst, fmt=fmt)}
+
+
+def test_quant_cases_reach_every_format_instantiation_and_variant():
+    """every (format, instantiation), every (format, batch size) and every FP8 matrix-core variant has its cases, each in the families
+    the issue lists; the quantized cases are new names next to the bf16 ones, which keep theirs"""
+    cases = R.quant_cases()
+    assert all(c.fmt in R.FMTS and c.name.startswith(c.fmt + " ") and not c.delta for c in cases)
+    assert not [c for c in R.all_cases() if c.fmt == "bf16" and c.name.split()[0] in R.FMTS]
+    fams = {}
+    for c in cases:
+        if c.mfma:
+            assert c.fmt == "fp8" and c.form in (0, 5) and c.selected() == (c.variant, c.rt) and c.ldw % 16 == 0, c.name
+            continue
+        assert c.selected() == ((4, False, 4) if c.inst == "lm" else c.inst) and c.form in (0, -1), c.name
+        fam = "skip" if c.skip else "probe" if c.kind == "probe" else "norm-exact" if c.norm else "bans" if (c.lm_head and c.ban != "none") else "plain"
+        fams.setdefault((c.fmt, c.inst, c.nb), set()).add(fam)
+    for fmt in R.FMTS:
+        for inst in R.quant_insts(fmt):
+            assert {"plain", "norm-exact", "probe"} <= fams[(fmt, inst, 0)], (fmt, inst)
+        for nb in R.VALU_NB:
+            for inst in R.quant_batch_insts(fmt):
+                assert {"plain", "norm-exact", "probe"} <= fams[(fmt, inst, nb)], (fmt, inst, nb)
+        assert all("skip" in fams[(fmt, inst, 0)] for inst in R.DELTA_INST)
+    assert all("bans" in fams[("fp8", "lm", nb)] for nb in (0,) + R.VALU_NB) and not [k for k in fams if k[0] == "mxfp4" and k[1] == "lm"]
+    for nb in (0,) + R.VALU_NB:
+        assert {c.ban for c in R.lm_head_cases(nb, fmt="fp8")} == set(R.BANS) and any(c.idx_offset for c in R.lm_head_cases(nb, fmt="fp8"))
+    mf = [c for c in cases if c.mfma]
+    assert {c.variant for c in mf} == set(R.FP8_MFMA_VARIANTS) and {c.nb for c in mf} == set(R.MFMA_NB)
+    for nb in R.MFMA_NB:
+        of = [c for c in mf if c.nb == nb]
+        assert {c.variant for c in of} == set(R.FP8_MFMA_VARIANTS) and {c.ban for c in of if c.lm_head} == set(R.BANS)
+        assert {(c.rt, c.glu, c.lm_head) for c in of} >= {(8, False, False), (12, False, False), (16, False, False), (16, True, False), (16, False, True)}
+        assert {(c.N, c.form) for c in of if c.N in (R.N_ROWS12, R.N_RAGGED16)} == {(N, f) for N in (R.N_ROWS12, R.N_RAGGED16) for f in (0, 5)}
+        assert {c.kind for c in of if c.norm} == {"int", "swiglu", "probe"} and max(c.K for c in of if c.norm) == 4096
+        # the rows of the bf16 ladder that usdm_gemv_fp8_mfma accepts, form 1 as its form 0
+        assert [(c.K, c.form, c.ks) for c in R.mfma_ladder_cases(nb, "fp8")] == [(K, 0 if f == 1 else f, ks) for K, f, ks in R.MFMA_LADDER if f != 3]
+
+
+def _quant_groups():
+    out = []
+    for fmt in R.FMTS:
+        for i in R.quant_insts(fmt):
+            out.append((f"{fmt}-{R.inst_id(i)}", lambda i=i, fmt=fmt: R.valu_plain_cases(i, fmt=fmt) + R.valu_norm_exact_cases(i, fmt=fmt) + R.valu_probe_cases(i, fmt=fmt)))
+        out.append((f"{fmt}-rest", lambda fmt=fmt: [c for i in R.DELTA_INST for c in R.skip_cases(i, fmt)] + (R.lm_head_cases(fmt="fp8") if fmt == "fp8" else [])))
+        for nb in R.VALU_NB:
+            out.append((f"{fmt}-nb{nb}", lambda nb=nb, fmt=fmt: [c for i in R.quant_batch_insts(fmt) for c in R.valu_plain_cases(i, nb, fmt) + R.valu_norm_exact_cases(i, nb, fmt)
+                                                                + R.valu_probe_cases(i, nb, fmt)] + (R.lm_head_cases(nb, fmt="fp8") if fmt == "fp8" else [])))
+    for nb in R.MFMA_NB:
+        out.append((f"fp8-mfma-nb{nb}", lambda nb=nb: R.mfma_ladder_cases(nb, "fp8") + R.mfma_tile_cases(nb, "fp8") + R.mfma_swiglu_cases(nb, "fp8") + R.mfma_norm_cases(nb, "fp8")
+                    + R.lm_head_cases(nb, mfma=True, fmt="fp8")))
+    return out
+
+
+def test_quant_groups_are_all_the_quantized_cases():
+    assert sorted(c.name for g in _quant_groups() for c in g[1]()) == sorted(c.name for c in R.quant_cases())
+
+
+@pytest.mark.parametrize("group", _quant_groups(), ids=lambda g: g[0])
+def test_quant_exactness_conditions(group):
+    """per quantized case: dequantize(quantize(W)) is W bit for bit (no MXFP4 code a negative zero), so the fp64 reference of the bf16
+    kernels is the exact reference of the quantized ones; rows / blocks carry different scales; sum |W| |x'| + |residual| in units of
+    the smallest weight step stays below 2^24 (every partial sum is exact in f32 in any order, and so is the sum with the residual);
+    SwiGLU pre-activations stay within +-20; the exact RMSNorm family, the probe's 2 % cap and the SwiGLU rounding cap hold for the
+    reference alone"""
+    from usdm_amd import quant
+    worst, nsw, dsw = 0.0, 0, 0
+    for c in group[1]():
+        d = R.build(c)
+        xb = d.x.view(c.B + 1, c.x_bs)
+        assert bool(torch.isnan(xb[:, c.K:]).all()) and bool(torch.isnan(xb[c.B]).all()) and d.W is None
+        # ---- lossless, and the buffers as the kernels get them
+        W, ldw = R.device_weight(c, d)
+        if c.fmt == "fp8":
+            assert ldw == c.ldw and W.q.shape == (c.N + 1, ldw) and W.e.shape == (c.N + 1,) and ldw >= c.K + 8
+            assert bool((W.q[:, c.K:] == R.FP8_NAN).all()) and bool((W.q[c.N] == R.FP8_NAN).all())
+            assert bool(torch.isnan(W.q[c.N:, c.K:].view(torch.float8_e4m3fn).float()).all())
+            back, scales = quant.dequantize_rows(W.q[:c.N, :c.K], W.e[:c.N]), W.e[:c.N]
+            per_row = 1
+        else:
+            codes, scales = W.unpack()
+            assert ldw is None and W.K == c.K and W.N == c.N and not bool((codes == 8).any()), c.name
+            back = quant.dequantize_mxfp4(codes, scales)
+            per_row = max(int(r.unique().numel()) for r in scales[:8])
+        assert torch.equal(R.bits(back), R.bits(d.Wl)), f"{c.name}: quantization is not lossless"
+        wb, _ = R.device_weight(c, d, fmt="bf16")                            # (what the bf16 entry point is given for the comparison)
+        wb = wb.view(c.N + 1, c.K + R.PAD)
+        assert torch.equal(R.bits(wb[:c.N, :c.K]), R.bits(d.Wl)) and bool(torch.isnan(wb[:, c.K:]).all()) and bool(torch.isnan(wb[c.N]).all())
+        # ---- scales that differ between neighbouring rows and blocks
+        if c.kind != "probe" and c.N >= 8:
+            assert int(scales.unique().numel()) >= 4 and (c.fmt == "fp8" or per_row >= 2 or c.K == 32), (c.name, scales.unique().tolist())   # (K = 32: one block per row)
+            # the next row's and the next wave's scale is another one, and most gate / up partners' (16 rows on); MXFP4: and the next block's and the next group's (ring slot's)
+            x_ = d.wexp
+            assert bool((x_[1:] != x_[:-1]).all()) and bool((x_[4:] != x_[:-4]).all()) and float((x_[16:] != x_[:-16]).float().mean()) > 0.5, c.name
+            assert c.fmt == "mxfp4" or bool((scales[1:8] != scales[0:7]).all()), c.name
+            if c.fmt == "mxfp4" and c.kind == "int":
+                assert bool((x_[:, 1:] != x_[:, :-1]).all()) and bool((x_[:, 64:] != x_[:, :-64]).all()) and bool((x_[:, 128:] != x_[:, :-128]).all()), c.name
+                if c.K >= 4096:     # ... in the scale bytes themselves, wherever both blocks hold a 3 (nearly everywhere)
+                    assert float((scales[:, 64:] != scales[:, :-64]).float().mean()) > 0.9, c.name
+        e = R.expected(c, d, rbf=False)
+        if c.kind == "probe":
+            assert d.wexp is None and bool(((d.Wl == 0) | (d.Wl == 1)).all())
+            lo, hi = R.expected(c, d, rbf=False, scale=1 - R.DELTA)["y"], R.expected(c, d, rbf=False, scale=1 + R.DELTA)["y"]
+            share = float((lo.vals != hi.vals)[lo.owned].double().mean())
+            worst = max(worst, share)
+            assert share <= R.PROBE_CAP, (c.name, share)
+            assert bool(((e["y"].vals == lo.vals) | (e["y"].vals == hi.vals)).all())
+            continue
+        # ---- 2^24 headroom in units of the smallest step: W is a multiple of 2^emin, x' of xu, the residual an integer
+        emin = int(d.wexp.min())
+        assert (-3 <= emin <= int(d.wexp.max()) <= 0) if c.kind == "swiglu" else (emin == (-3 if c.fmt == "fp8" else 0) and int(d.wexp.max()) == 3)
+        xp = R.x_prime(c, d)[0]
+        xu = 1.0 / 16 if c.kind == "swiglu" else 1.0
+        step = 2.0 ** min(emin, 0) * xu
+        Wd = d.Wl.double()
+        assert bool((Wd / 2.0 ** emin == (Wd / 2.0 ** emin).round()).all()) and bool((xp / xu == (xp / xu).round()).all()), c.name
+        absum = max(float((xp.abs() @ Wd[r0:r0 + 2048].abs().T).max()) for r0 in range(0, c.N, 2048))
+        res_max = float(d.rl.abs().max()) if d.rl is not None else 0.0
+        assert (absum + res_max) / step < 2.0 ** 24 and d.acc_max <= absum, (c.name, absum, step)
+        if c.kind == "swiglu":
+            y = e["y"]
+            assert float(y.pre[y.owned].abs().max()) <= 20.0 and float(y.up[y.owned].abs().max()) <= 20.0, c.name
+            g, u, ref = y.pre[y.owned], y.up[y.owned], R.expected(c, d, rbf=True)["y"].vals[y.owned]
+            t32 = R.swiglu_rbf_ref(g, u, dtype=R.F32)
+            assert bool(((t32 - ref).abs() <= R.bf16_ulp(ref)).all()) and torch.equal(ref.float().to(BF).double(), ref), c.name
+            nsw, dsw = nsw + ref.numel(), dsw + int((t32 != ref).sum())
+        if c.norm == "exact":
+            a, b = R.x_prime(c, d, 1 - 2.0 ** -10)[0], R.x_prime(c, d, 1 + 2.0 ** -10)[0]    # rstd ~ 1/2: 2^-11 absolute either side
+            assert torch.equal(a, b) and torch.equal(a.abs(), d.gl.abs().expand_as(a)), c.name
+    if worst:
+        print(f"[gemv] {group[0]}: the probe's references differ on at most {100 * worst:.2f} % of a case's elements (cap 2 %)")
+    if nsw:
+        print(f"[gemv] {group[0]}: torch float32 differs from the fp64 SwiGLU reference with round_bf16 on {dsw} of {nsw} outputs")
+        assert dsw <= R.FLIP_CAP * nsw, (group[0], dsw, nsw)
+
+
 def _float_case(**kw):
     """a small case whose operands are replaced by float data"""
     c = R.Case("float", N=96, K=520, seed=5, **kw)

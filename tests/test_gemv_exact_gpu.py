@@ -23,11 +23,14 @@ EXP_OF = {"y32": "y", "y16": "y", "part_val": "part_val", "part_idx": "part_idx"
 class Run:
     """a case on the device: its operands uploaded once, launches into fresh sentinel-filled outputs"""
 
-    def __init__(self, c, dev):
-        self.c, self.dev, self.d = c, dev, R.build(c)
+    def __init__(self, c, dev, d=None, fmt=None):
+        """d, fmt="bf16": the bf16 entry point on the logical weights of a quantized case that is already built (its twin)"""
+        self.c, self.dev, self.d = c, dev, R.build(c) if d is None else d
+        self.fmt = c.fmt if fmt is None else fmt
         up = lambda t: None if t is None else t.to(dev)
         d = self.d
-        self.W, self.x, self.norm_w, self.res, self.ban, self.x_delta = up(d.W), up(d.x), up(d.norm_w), up(d.res), up(d.ban), up(d.x_delta)
+        self.W, self.ldw = R.device_weight(c, d, dev, self.fmt)       # (a quantized format: quantized here, once per case, on the device)
+        self.x, self.norm_w, self.res, self.ban, self.x_delta = up(d.x), up(d.norm_w), up(d.res), up(d.ban), up(d.x_delta)
         self.skip = torch.ones(1, dtype=torch.int32, device=dev) if c.skip else None
         self.ks = None
         if c.ks:
@@ -50,10 +53,14 @@ class Run:
             view = out["y16"].view(c.B + 1, c.y_bs)
             view[:c.B, :c.nout] = self.d.rl.to(BF).to(dev)
             res = out["y16"]
-        kw = dict(N=c.N, K=c.K, ldw=c.ldw, norm_w=self.norm_w, eps=R.EPS, act=c.act, round_bf16=rbf, residual=res, y16=out.get("y16"), y32=out.get("y32"),
+        kw = dict(N=c.N, K=c.K, ldw=self.ldw, norm_w=self.norm_w, eps=R.EPS, act=c.act, round_bf16=rbf, residual=res, y16=out.get("y16"), y32=out.get("y32"),
                   ban=self.ban, part_val=out.get("part_val"), part_idx=out.get("part_idx"), idx_offset=c.idx_offset)
         if c.nb:
-            ops.gemv_batch(self.W, self.x, nb=c.nb, x_bs=c.x_bs, y_bs=c.y_bs, res_bs=c.res_bs, part_bs=c.part_bs, form=c.form, ks=self.ks, **kw)
+            bkw = dict(nb=c.nb, x_bs=c.x_bs, y_bs=c.y_bs, res_bs=c.res_bs, part_bs=c.part_bs, ks=self.ks, **kw)
+            if c.fmt == "fp8" and c.mfma and self.fmt == "fp8":
+                ops.gemv_fp8_mfma(self.W, self.x, form=c.form, **bkw)
+            else:               # (the twin of an usdm_gemv_fp8_mfma case: form 1 is what its form 0 must equal)
+                ops.gemv_batch(self.W, self.x, form=1 if (c.fmt == "fp8" and c.mfma and c.form == 0) else c.form, **bkw)
         else:
             ops.gemv(self.W, self.x, x_delta=self.x_delta, x_out=out.get("x_out"), skip=self.skip, **kw)
         torch.cuda.synchronize()
@@ -67,11 +74,14 @@ class Run:
         from usdm_amd import _lib, ops
         c = self.c
         pv = torch.empty(1, device=self.dev) if c.lm_head else None
-        a = ops.gemv(self.W, self.x, only_args=True, N=c.N, K=c.K, ldw=c.ldw, act=c.act, part_val=pv, part_idx=pv)
+        W = self.W if self.fmt == "bf16" else self.W.q        # (the launch selection does not depend on the format: the bf16 arguments)
+        a = ops.gemv(W, self.x, only_args=True, N=c.N, K=c.K, ldw=c.ldw, act=c.act, part_val=pv, part_idx=pv)
         return _lib.lib.usdm_gemv_threads(ctypes.byref(a))
 
 
 def _names(c, rbf):
+    if c.fmt == "mxfp4":                                            # (usdm_gemv_mxfp4 has no y32 and no lm_head mode)
+        return ["y16"]
     n = ["y32"] + (["y16"] if rbf and not c.lm_head else [])       # (lm_head mode has f32 logits only)
     if c.lm_head:
         n += ["part_val", "part_idx"]
@@ -93,10 +103,21 @@ def _exact(r, rbf, e, inplace=False):
         if bool(amb.any()):
             again = r.launch(rbf, names, alt=True, inplace=inplace) if again is None else again
             assert torch.equal(R.bits(again[n])[amb], R.bits(got[n])[amb]), f"{c.name} {n}: owned elements never written"
-    if "y16" in got:
+    if "y16" in got and "y32" in got:
         own = e["y"].owned
         assert torch.equal(R.bits(got["y16"])[own], R.bits(got["y32"].to(BF))[own]), f"{c.name}: y16 is not y32 rounded to bf16"
     return got
+
+
+def _twin(r):
+    """a quantized case's logical weights are bf16 values that quantize losslessly (tests/test_gemv_exact_cpu.py), so the bf16 entry
+    point on them must give the same bits; None for a bf16 case"""
+    return None if r.fmt == "bf16" else Run(r.c, r.dev, d=r.d, fmt="bf16")
+
+
+def _equals_twin(r, got, tw):
+    for n in got:
+        assert torch.equal(R.bits(got[n]), R.bits(tw[n])), f"{r.c.name} {n}: differs from the bf16 entry point on the same weights"
 
 
 def _partials_follow_logits(c, got):
@@ -111,8 +132,16 @@ def _swiglu(r):
     """round_bf16 off: within SWIGLU_TOL of fp64 silu(g) u; on: within one bf16 ulp of the reference with HF's rounding points, at most
     FLIP_CAP of the outputs differing at all"""
     c = r.c
+    t = _twin(r)
     e = R.expected(c, r.d, rbf=False)["y"]
-    got = r.launch(False, ["y32"])["y32"]
+    if t is None:
+        got = r.launch(False, ["y32"])["y32"]
+    else:           # the bound on y32 (MXFP4 has none: on the twin's, whose y16 = bf16(y32) it must equal), and the twin's bits
+        q, tw = r.launch(False, _names(c, True)), t.launch(False, ["y32", "y16"])
+        got = q["y32"] if "y32" in q else tw["y32"]
+        _equals_twin(r, q, tw)
+        R.check_guard(f"{c.name} y16", q["y16"], e, R.bf16_ulp(e.vals))
+        assert torch.equal(R.bits(tw["y16"])[e.owned], R.bits(tw["y32"].to(BF))[e.owned]), f"{c.name}: y16 is not y32 rounded to bf16"
     own = e.owned
     tol = R.SWIGLU_TOL * torch.where(own, torch.maximum(e.vals.abs(), e.up.abs()), torch.zeros((), dtype=F64))
     R.check_guard(f"{c.name} y32", got, e, tol)
@@ -121,14 +150,17 @@ def _swiglu(r):
     print(f"[gemv] {c.name}: SwiGLU worst error / bound {ratio:.3f}")
     assert bool((err <= tol).all()), f"{c.name}: {ratio:.3f} x the SwiGLU bound"
     e = R.expected(c, r.d, rbf=True)["y"]
-    got = r.launch(True, ["y32", "y16"])
+    got = r.launch(True, _names(c, True))
+    if t is not None:
+        _equals_twin(r, got, t.launch(True, list(got)))
     for n, g in got.items():
         R.check_guard(f"{c.name} {n}", g, e, R.bf16_ulp(e.vals))
         dd = (g.double() - e.vals).abs()[own]
         nd = int((dd != 0).sum())
         print(f"[gemv] {c.name} {n}: {nd} of {dd.numel()} differ with round_bf16")
         assert bool((dd <= R.bf16_ulp(e.vals[own])).all()) and nd <= R.FLIP_CAP * dd.numel(), (c.name, n)
-    assert torch.equal(R.bits(got["y16"])[own], R.bits(got["y32"].to(BF))[own]), f"{c.name}: y16 is not y32 rounded to bf16"
+    if "y32" in got:
+        assert torch.equal(R.bits(got["y16"])[own], R.bits(got["y32"].to(BF))[own]), f"{c.name}: y16 is not y32 rounded to bf16"
     return ratio
 
 
@@ -137,18 +169,28 @@ def _probe(r):
     c = r.c
     lo, hi = (R.expected(c, r.d, rbf=not c.glu, scale=s) for s in (1 - R.DELTA, 1 + R.DELTA))
     own = lo["y"].owned
+    t = _twin(r)
     if c.glu:       # y = silu(x') x': within the SwiGLU bound of either reference (a bf16 step of x' is 2^-8, the bound 7e-7)
-        got = r.launch(False, ["y32"])
+        if t is None:
+            got = r.launch(False, ["y32"])
+        else:       # (MXFP4 has no y32: the bound on the twin's, whose y16 = bf16(y32) it must equal)
+            q, got = r.launch(False, _names(c, True)), t.launch(False, ["y32", "y16"])
+            _equals_twin(r, q, got)
+            R.check_guard(f"{c.name} y16", q["y16"], lo["y"], 1e-5)
+            assert torch.equal(R.bits(got["y16"])[own], R.bits(got["y32"].to(BF))[own]), f"{c.name}: y16 is not y32 rounded to bf16"
         g = got["y32"].double()
         R.check_guard(f"{c.name} y32", got["y32"], lo["y"], 1e-5)
         ok = [(g - e["y"].vals).abs() <= R.SWIGLU_TOL * torch.maximum(e["y"].vals.abs(), e["y"].up.abs()) for e in (lo, hi)]
     else:           # round_bf16 rounds bf16 values: y32 = y16 = x'[k_n]
         got = r.launch(True, _names(c, True))
-        R.check_guard(f"{c.name} y32", got["y32"], lo["y"], 0.0)
-        if "y16" in got:
+        if t is not None:
+            _equals_twin(r, got, t.launch(True, list(got)))
+        main = "y32" if "y32" in got else "y16"
+        R.check_guard(f"{c.name} {main}", got[main], lo["y"], 0.0)
+        if "y16" in got and main == "y32":
             R.check_guard(f"{c.name} y16", got["y16"], lo["y"], 0.0)
             assert torch.equal(R.bits(got["y16"])[own], R.bits(got["y32"].to(BF))[own]), f"{c.name}: y16 is not y32 rounded to bf16"
-        ok = [R.bits(got["y32"]) == R.bits(e["y"].vals.float()) for e in (lo, hi)]
+        ok = [R.bits(got[main]) == R.bits(e["y"].vals.to(got[main].dtype)) for e in (lo, hi)]
         if c.lm_head:
             _partials_follow_logits(c, got)
             for n in ("part_val", "part_idx"):
