@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compares the gfx950 device code of .hip files between two source trees, function by function (CPU only: hipcc, no GPU).
 
-    python tools/isa_diff.py TREE_A TREE_B llm_k.hip llm_batch_k.hip [--rename 9gemvb_mx4=8gemv_mx4] [--keep DIR]
+    python tools/isa_diff.py TREE_A TREE_B llm_k.hip llm_batch_k.hip [--rename 9gemvb_mx4=8gemv_mx4] [--keep DIR] [--classify]
 
 TREE_A / TREE_B are checkouts of this repository (each file is compiled from TREE/usdm_amd/csrc with usdm_amd.build.FLAGS plus
 build.EXTRA, --cuda-device-only -S) or directories that already hold NAME.s for every NAME.hip listed.  The assembly is split into
@@ -11,6 +11,12 @@ difference even where the instructions agree.
 
 --rename OLD=NEW replaces OLD by NEW in the mangled names of A before matching (a type that changed its name, as the MXFP4 argument
 struct did when the two GEMV files began to share it).  Exit status 1 if any function differs or exists on one side only.
+
+--classify sorts every matched function into one of three classes instead (exit status 1 only for functions on one side only):
+  A  identical after the normalisation above;
+  B  same schedule: the .amdhsa_ lines, the multiset of mnemonics and the ordered sequence of memory instructions and s_waitcnt
+     (mnemonic, wait counts / cache-policy words) are equal - only register numbers and commutative operand order differ;
+  C  anything else; the changed descriptor lines, the waves per SIMD the register counts allow and the mnemonic-count delta follow.
 """
 import argparse
 import os
@@ -64,6 +70,71 @@ def functions(text):
     return out
 
 
+MEMORY = ("global", "flat", "buffer", "tbuffer", "scratch", "ds")   # first word of a vector-memory / LDS mnemonic
+POLICY = {"nt", "sc0", "sc1", "glc", "slc", "dlc", "lds"}
+
+
+def _split(body):
+    """(descriptor lines, instruction lines) of a normalised body"""
+    desc = [ln for ln in body if ln.startswith(".amdhsa_")]
+    return desc, [ln for ln in body if not ln.startswith(".") and not ln.endswith(":")]
+
+
+def _mnemonics(ins):
+    out = {}
+    for ln in ins:
+        m = ln.split(" ", 1)[0]
+        out[m] = out.get(m, 0) + 1
+    return out
+
+
+def _memory_sequence(ins):
+    """ordered (mnemonic, wait counts or cache-policy words) of the memory instructions and waits"""
+    seq = []
+    for ln in ins:
+        m, _, rest = ln.partition(" ")
+        if m == "s_waitcnt":
+            seq.append((m, rest.strip()))
+        elif m.split("_", 1)[0] in MEMORY or m.startswith(("s_load", "s_buffer_load")):
+            seq.append((m, " ".join(w for w in rest.replace(",", " ").split() if w in POLICY)))
+    return seq
+
+
+def _waves_per_simd(desc):
+    """occupancy step of a gfx950 kernel: 512 unified registers per lane, allocated in blocks of 8, at most 8 waves"""
+    for ln in desc:
+        if ln.startswith(".amdhsa_next_free_vgpr "):
+            n = max(1, int(ln.split()[1]))
+            return min(8, 512 // (-(-n // 8) * 8))
+    return None
+
+
+def classify(a, b):
+    """("A" | "B" | "C", report lines) of two normalised bodies"""
+    if a == b:
+        return "A", []
+    (da, ia), (db, ib) = _split(a), _split(b)
+    ma, mb = _mnemonics(ia), _mnemonics(ib)
+    if da == db and ma == mb and _memory_sequence(ia) == _memory_sequence(ib):
+        return "B", []
+    rep = [f"{x}  ->  {y}" for x, y in zip(da, db) if x != y]
+    if len(da) != len(db):
+        rep.append(f"{len(da)} -> {len(db)} descriptor lines")
+    rep.append(f"waves per SIMD {_waves_per_simd(da)} -> {_waves_per_simd(db)}")
+    delta = {m: mb.get(m, 0) - ma.get(m, 0) for m in sorted(set(ma) | set(mb)) if ma.get(m, 0) != mb.get(m, 0)}
+    rep.append("mnemonics: " + (", ".join(f"{m} {d:+d}" for m, d in delta.items()) or "same counts")
+               + ("; memory / wait sequence differs" if _memory_sequence(ia) != _memory_sequence(ib) else "; memory / wait sequence equal"))
+    return "C", rep
+
+
+def classify_file(sa, sb, renames):
+    """({name: (class, report)}, only in A, only in B) of one file's two assemblies"""
+    fa, fb = functions(sa), functions(sb)
+    out = {n: classify(body, fb[_apply(n, renames)]) for n, body in fa.items() if _apply(n, renames) in fb}
+    matched = {_apply(n, renames) for n in fa}
+    return out, [n for n in fa if n not in out], [n for n in fb if n not in matched]
+
+
 def _apply(name, renames):
     for old, repl in renames:
         name = name.replace(old, repl)
@@ -94,6 +165,7 @@ def main():
     ap.add_argument("files", nargs="+", help=".hip file names under usdm_amd/csrc")
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     ap.add_argument("--keep", metavar="DIR", help="keep the compiled assembly under DIR/a and DIR/b")
+    ap.add_argument("--classify", action="store_true", help="print class A / B / C per function (see above)")
     args = ap.parse_args()
     renames = [tuple(r.split("=", 1)) for r in args.rename]
     with tempfile.TemporaryDirectory() as tmp:
@@ -105,6 +177,19 @@ def main():
         bad = 0
         for f in args.files:
             sa, sb = (open(os.path.join(d, f[:-4] + ".s")).read() for d in dirs)
+            if args.classify:
+                cls, only_a, only_b = classify_file(sa, sb, renames)
+                count = {c: sum(1 for k, _ in cls.values() if k == c) for c in "ABC"}
+                print(f"{f}: {count['A']} class A, {count['B']} class B, {count['C']} class C, {len(only_a)} only in A, {len(only_b)} only in B")
+                for n, (k, rep) in cls.items():
+                    print(f"  {k} {n}")
+                    for ln in rep:
+                        print(f"      {ln}")
+                for tag, ns in (("ONLY IN A", only_a), ("ONLY IN B", only_b)):
+                    for n in ns:
+                        print(f"  {tag} {n}")
+                bad += len(only_a) + len(only_b)
+                continue
             same, renamed, differ, only_a, only_b = diff_file(sa, sb, renames)
             print(f"{f}: {len(same) + len(renamed)} device functions identical ({len(renamed)} of them renamed), "
                   f"{len(differ)} different, {len(only_a)} only in A, {len(only_b)} only in B")

@@ -1,7 +1,16 @@
-// What the weight-streaming decode GEMVs share: gemv_kernel (llm_k.hip), gemv_batch_kernel (llm_batch_k.hip) and, for the row
-// exponents only, gemv_mfma_kernel (llm_mfma_k.hip); the experimental kernels take dot8.
+// What the weight-streaming decode GEMVs share: gemv_kernel, gemv_resident_kernel, gemv_stream_kernel (llm_k.hip),
+// gemv_batch_kernel (llm_batch_k.hip), gemv_mfma_kernel (llm_mfma_k.hip: the row exponents only) and the experimental chain and
+// engine kernels (llm_chain_k.hip, llm_engine_k.hip).
 //   * the weight-format trait (bf16 / FP8 / MXFP4): load width, the MXFP4 argument, the ring depth;
-//   * the per-item arithmetic the two VALU kernels must share bit for bit.
+//   * the per-item arithmetic they must share bit for bit, one text each:
+//       dot8               every VALU kernel
+//       gemv_sumsq8        gemv_kernel, gemv_resident_kernel, chain, engine (gemv_batch_kernel keeps the text, see there;
+//                          gemv_mfma_kernel's statistic is another expression on purpose)
+//       gemv_rmsnorm8      gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain, engine (gemv_mfma_kernel keeps the text)
+//       gemv_glu_row       gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain
+//       gemv_swiglu_value  gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain, engine
+//       gemv_plain_value   gemv_kernel, gemv_stream_kernel, chain, engine (gemv_batch_kernel keeps the text)
+// The structural pieces of the bf16 batch-1 kernels (hand-counted loads, the RMSNorm reduction): gemv_pieces.h.
 // The launch selection and the argument checks of the launchers: gemv_launch.h.
 // A new weight format plugs in here: DESIGN.md section 8f.
 #pragma once
@@ -46,7 +55,29 @@ constexpr int gemv_ring_depth(int NR, bool FP8, bool MX4) {
   return MX4 ? (NR >= 3 ? 2 : 4) : FP8 ? 2 * bf16_depth : bf16_depth;
 }
 
-// ---- per-item arithmetic that gemv_kernel and gemv_batch_kernel must share bit for bit (a batched step = independent steps)
+// ---- per-item arithmetic that every kernel above must share bit for bit (a batched step = independent steps)
+// sum of squares of 8 bf16 onto ss, element pairs in order (the RMSNorm statistic)
+__device__ __forceinline__ float gemv_sumsq8(u32x4 v, float ss) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
+    ss += lo * lo + hi * hi;
+  }
+  return ss;
+}
+// RMSNorm of 8 bf16 with their 8 f32 weights, HF rounding: bf16(bf16(x * rstd) * weight)
+__device__ __forceinline__ u32x4 gemv_rmsnorm8(u32x4 v, float rstd, float4 g0, float4 g1) {
+  const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+  u32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
+    o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
+  }
+  return o;
+}
+// weight row of SwiGLU output o in the packed gate/up layout: blocks of 32 rows = 16 gate + 16 up
+__device__ __forceinline__ int gemv_glu_row(int o, bool up) { return (o >> 4) * 32 + (o & 15) + (up ? 16 : 0); }
 // SwiGLU output of a gate / up pair of f32 sums; round_bf16: HF's rounding points (the projections' bf16 outputs, silu, the product)
 __device__ __forceinline__ float gemv_swiglu_value(float g, float u, bool round_bf16) {
   if (round_bf16) {
@@ -54,5 +85,17 @@ __device__ __forceinline__ float gemv_swiglu_value(float g, float u, bool round_
     return round_bf(round_bf(gt / (1.0f + __expf(-gt))) * up);
   }
   return (g / (1.0f + __expf(-g))) * u;
+}
+// output of a plain projection from its f32 sum: HF rounds the Linear output and the residual add.  res(): the residual value,
+// asked for only where there is one (its pointer may be null otherwise)
+template <class RES>
+__device__ __forceinline__ float gemv_plain_value(float acc, bool round_bf16, bool has_res, RES&& res) {
+  float v = acc;
+  if (round_bf16) v = round_bf(v);
+  if (has_res) {
+    v += res();
+    if (round_bf16) v = round_bf(v);
+  }
+  return v;
 }
 }  // namespace

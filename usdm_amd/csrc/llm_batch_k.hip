@@ -38,13 +38,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
   const unsigned* wsp[MX4 ? NR : 1];   // MX4: the rows' scale dwords of this lane's quad
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
-    int r;
-    if (GLU) {
-      const int o = ob + (j % RW);
-      r = (o >> 4) * 32 + (o & 15) + (j >= RW ? 16 : 0);
-    } else {
-      r = ob + j;
-    }
+    int r = GLU ? gemv_glu_row(ob + (j % RW), j >= RW) : ob + j;
     r = r < a.N ? r : a.N - 1;
     if constexpr (FP8) {
       wp[j] = (const wvec*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
@@ -109,7 +103,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
       ss[b] = 0.f;
       const bf16_t* xg = (const bf16_t*)a.x + (int64_t)b * ba.x_bs;
       for (int i = tid * 8; i < K; i += NTH * 8) {
-        const u32x4 v = *(const u32x4*)(xg + i);
+        const u32x4 v = *(const u32x4*)(xg + i);   // (gemv_sumsq8's text: as the function the NWV = 12 / 16 forms compiled to other branches)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
@@ -129,16 +123,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
       const bf16_t* xg = (const bf16_t*)a.x + (int64_t)b * ba.x_bs;
       for (int i = tid * 8; i < Kpad; i += NTH * 8) {
         u32x4 o = {0, 0, 0, 0};
-        if (i < K) {
-          const u32x4 v = *(const u32x4*)(xg + i);
-          const float4 g0 = *(const float4*)(a.norm_w + i), g1 = *(const float4*)(a.norm_w + i + 4);
-          const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
-            o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
-          }
-        }
+        if (i < K) o = gemv_rmsnorm8(*(const u32x4*)(xg + i), rstd, *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
         *(u32x4*)(xs + (int64_t)b * Kpad + i) = o;
       }
     }
@@ -267,7 +252,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_batch_kernel(const usdm_gemv_ba
       for (int j = 0; j < NR; ++j) {
         const int n = ob + j;
         if (n >= a.N) continue;
-        float v = acc[j][b];
+        float v = acc[j][b];   // (gemv_plain_value's text: as the function these loops compiled to other device code)
         if (a.round_bf16) v = round_bf(v);
         if (a.residual) {
           v += bf2f(((const bf16_t*)a.residual)[(int64_t)b * ba.res_bs + n]);

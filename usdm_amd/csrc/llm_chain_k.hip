@@ -12,7 +12,7 @@
 // (sc1) stores, every storing wave drains them, ONE lane adds to the arrival counter; consumers poll the counter (bounded) and read
 // the handed-off vectors only with agent-scope loads.
 #include "common.h"
-#include "gemv_common.h"
+#include "gemv_pieces.h"
 #include "../../include/usdm_hip_experimental.h"
 
 namespace {
@@ -46,13 +46,7 @@ __device__ __forceinline__ void row_ptrs(const usdm_gemv_args& a, int tile, int 
   const int ob = tile * TILE + wave * 2;
 #pragma unroll
   for (int j = 0; j < Shape<GLU>::NR; ++j) {
-    int r;
-    if (GLU) {   // packed layout: blocks of 32 rows = 16 gate + 16 up
-      const int o = ob + (j & 1);
-      r = (o >> 4) * 32 + (o & 15) + (j >= 2 ? 16 : 0);
-    } else {
-      r = ob + j;
-    }
+    int r = GLU ? gemv_glu_row(ob + (j & 1), j >= 2) : ob + j;
     r = r < a.N ? r : a.N - 1;
     wp[j] = (unsigned)(((int64_t)r * a.ldw + lane * 8) * 2);
   }
@@ -103,22 +97,13 @@ __device__ __forceinline__ void run_tile(const usdm_gemv_args& a, int tile, cons
       float r = 0.f;
       if (o < nout) {
         if (GLU) {
-          const float g = acc[j], u = acc[j + 2];
-          if (a.round_bf16) {
-            const float gt = round_bf(g), up = round_bf(u);
-            r = round_bf(round_bf(gt / (1.0f + __expf(-gt))) * up);
-          } else {
-            r = (g / (1.0f + __expf(-g))) * u;
-          }
+          r = gemv_swiglu_value(acc[j], acc[j + 2], a.round_bf16);
         } else {
-          r = acc[j];
-          if (a.round_bf16) r = round_bf(r);
-          if (a.residual) {
+          r = gemv_plain_value(acc[j], a.round_bf16, a.residual != nullptr, [&] {
             // the residual stream may have been written by another workgroup earlier in this launch: agent-scope load
             const unsigned w = __hip_atomic_load((const unsigned*)((const bf16_t*)a.residual + (o & ~1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            r += bf2f((o & 1) ? (bf16_t)(w >> 16) : (bf16_t)(w & 0xffff));
-            if (a.round_bf16) r = round_bf(r);
-          }
+            return bf2f((o & 1) ? (bf16_t)(w >> 16) : (bf16_t)(w & 0xffff));
+          });
         }
       }
       outs[wave * 2 + j] = r;
@@ -142,33 +127,11 @@ __device__ __forceinline__ void stage_x(const usdm_gemv_args& a, bf16_t* xs, flo
   if (a.norm_w) {
     float ss = 0.f;
 #pragma unroll 1
-    for (int i = tid * 8; i < K; i += CTH * 8) {
-      const u32x4 v = ld_shared8(xg + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
-        ss += lo * lo + hi * hi;
-      }
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < CW; ++w) tot += red[w];
-    const float rstd = rsqrtf(tot / (float)K + a.eps);
+    for (int i = tid * 8; i < K; i += CTH * 8) ss = gemv_sumsq8(ld_shared8(xg + i), ss);
+    const float rstd = gemv_rms_rstd<CW>(ss, red, K, a.eps);
 #pragma unroll 1
     for (int i = tid * 8; i < K; i += CTH * 8) {
-      const u32x4 v = ld_shared8(xg + i);
-      const float4 g0 = *(const float4*)(a.norm_w + i), g1 = *(const float4*)(a.norm_w + i + 4);
-      const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-      u32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
-        o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
-      }
-      *(u32x4*)(xs + i) = o;
+      *(u32x4*)(xs + i) = gemv_rmsnorm8(ld_shared8(xg + i), rstd, *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
     }
   } else {
 #pragma unroll 2

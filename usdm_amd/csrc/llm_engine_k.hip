@@ -229,27 +229,14 @@ __device__ __forceinline__ void gather(const usdm_gemv_chain_args& c, int p, int
     for (int v = 0; v < nv; ++v) {
       float ss = 0.f;
       for (int i = (v * 64 + lane) * 8; i < K; i += nth * 8) {
-        const u32x4 q = *(const u32x4*)(xs + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float lo = bf2f(q[e] & 0xffff), hi = bf2f(q[e] >> 16);
-          ss += lo * lo + hi * hi;
-        }
+        ss = gemv_sumsq8(*(const u32x4*)(xs + i), ss);
       }
       tot += wave_sum(ss);
     }
     const float rstd = rsqrtf(tot / (float)K + a.eps);
     for (int i = lane * 8; i < K; i += 512) {
       const u32x4 q = *(const u32x4*)(xs + i);
-      const float4 g0 = *(const float4*)(a.norm_w + i), g1 = *(const float4*)(a.norm_w + i + 4);
-      const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-      u32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf2f(q[e] & 0xffff), hi = bf2f(q[e] >> 16);
-        o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
-      }
-      *(u32x4*)(xs + i) = o;
+      *(u32x4*)(xs + i) = gemv_rmsnorm8(q, rstd, *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
@@ -315,12 +302,7 @@ __device__ __forceinline__ void consumer(const usdm_gemv_chain_args& c, char* sm
           a0 = wave_sum(a0); a1 = wave_sum(a1);
           ETR_ADD(32 + cw * 4 + 1);     // consumer: reads + dots + reduction of one slot
           if (ph.glu) {
-            if (a.round_bf16) {
-              const float gt = round_bf(a0), up = round_bf(a1);
-              r[h] = round_bf(round_bf(gt / (1.0f + __expf(-gt))) * up);
-            } else {
-              r[h] = (a0 / (1.0f + __expf(-a0))) * a1;
-            }
+            r[h] = gemv_swiglu_value(a0, a1, a.round_bf16);
           } else {
             r[0] = a0; r[1] = a1;
           }
@@ -352,14 +334,8 @@ __device__ __forceinline__ void consumer(const usdm_gemv_chain_args& c, char* sm
         // plain projection epilogue: bf16 rounding, residual add (HF rounding points)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          float v = r[h];
-          if (a.round_bf16) v = round_bf(v);
-          if (a.residual) {
-            const float res = rsrc >= 0 ? hloc[2 * job + h] : bf2f(((const bf16_t*)a.residual)[u0 + h]);
-            v += res;
-            if (a.round_bf16) v = round_bf(v);
-          }
-          r[h] = v;
+          r[h] = gemv_plain_value(r[h], a.round_bf16, a.residual != nullptr,
+                                  [&] { return rsrc >= 0 ? hloc[2 * job + h] : bf2f(((const bf16_t*)a.residual)[u0 + h]); });
         }
       }
       if (lane == 0) {

@@ -13,16 +13,11 @@
 #include <utility>
 #include "../../include/usdm_hip.h"
 #include "gemv_launch.h"
+#include "gemv_pieces.h"
 #include "attn_merge.h"
 #include "p2p.h"
 #include "pick_commit.h"
 
-#ifndef USDM_GEMV_X_FIRST
-#define USDM_GEMV_X_FIRST 1   // 0: the input vector is requested behind the first weight ring and read twice by the RMSNorm prologue (A/B builds)
-#endif
-#ifndef USDM_GEMV_RES_PREFETCH
-#define USDM_GEMV_RES_PREFETCH 1   // 0: the residual is read in the epilogue (A/B builds)
-#endif
 #ifndef USDM_GEMV_DOWN_UNR
 #define USDM_GEMV_DOWN_UNR 8   // ring depth of gemv_stream_kernel (12 for A/B builds: 48 of its 128 VGPRs)
 #endif
@@ -94,13 +89,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   const unsigned* wsp[MX4 ? NR : 1];   // MX4: the rows' scale dwords of this lane's quad
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
-    int r;
-    if (GLU) {  // packed layout: blocks of 32 rows = 16 gate + 16 up
-      const int o = ob + (j % RW);
-      r = (o >> 4) * 32 + (o & 15) + (j >= RW ? 16 : 0);
-    } else {
-      r = ob + j;
-    }
+    int r = GLU ? gemv_glu_row(ob + (j % RW), j >= RW) : ob + j;
     r = r < a.N ? r : a.N - 1;
     if constexpr (FP8) {
       wp[j] = (const wvec*)((const uint8_t*)a.W + (int64_t)r * a.ldw) + lane;
@@ -144,7 +133,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   // load was a full memory latency at the very end of every o_proj / down_proj launch, with nothing left to hide it.  Unconditional
   // (a predicated load is waited for at the join of its predicate): without a residual the address is the weight row, never used.
   unsigned short resraw[GLU ? 1 : NR];
-  if constexpr (!GLU && USDM_GEMV_RES_PREFETCH) {
+  if constexpr (!GLU) {
     const bf16_t* rbase = a.residual ? (const bf16_t*)a.residual : (const bf16_t*)a.W;
 #pragma unroll
     for (int j = 0; j < NR; ++j) resraw[j] = rbase[min(ob + j, a.N - 1)];
@@ -155,21 +144,13 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   // in flight.  Now the prologue runs under the ring's latency and reads nothing twice.  Unconditional loads (clamped index; a
   // dummy address without RMSNorm): a predicated load would be waited for at the join of its predicate, i.e. before the ring is
   // issued.  Not in the merged-input variants (their x is not in memory).
-  constexpr bool EARLY = USDM_GEMV_X_FIRST && !CMB && !MRG;
+  constexpr bool EARLY = !CMB && !MRG;
   const int i0 = tid * 8;
   // The three loads are HAND-COUNTED (asm, invisible to the compiler; cdna_hip_programming.md 5.7): the ring below is issued under
   // run-time tests (u < nit), so the wait-count pass cannot know how many loads are younger than x0 and would wait for all but the
   // few it is sure of - the whole ring again.  The wait further down names the exact count for the full-ring case.
   u32x4 x0 = {0u, 0u, 0u, 0u}, ge0v = x0, ge1v = x0;
-  if constexpr (EARLY) {
-    const int ic = min(i0, K - 8);
-    // (without RMSNorm the two weight loads re-read the first 16 bytes of x - always there, K >= 8 - and are not used)
-    const float* gp0 = a.norm_w ? a.norm_w + ic : (const float*)a.x;
-    const float* gp1 = a.norm_w ? gp0 + 4 : gp0;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x0) : "v"((const bf16_t*)a.x + ic) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ge0v) : "v"(gp0) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ge1v) : "v"(gp1) : "memory");
-  }
+  if constexpr (EARLY) gemv_early_loads(a, i0, K, x0, ge0v, ge1v);
   // The first ring is ALWAYS NR x UNR loads (slots past the row's K, or of a wave whose rows are all banned, re-read the row start
   // and are never multiplied / their results never used): the wait for the early loads below can then name an exact count.
   wvec ring[NR][UNR];
@@ -214,61 +195,31 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
   };
   auto ldx = [&](int i, bool publish) -> u32x4 { return with_delta(*(const u32x4*)(xg + i), i, publish); };
   const int iloop = EARLY ? i0 + NTH * 8 : i0;               // EARLY: the first piece is x0, the loops below take the rest
+  // (this staging and gemv_resident_kernel's stay two texts: as one function the x_delta tests compile to other branches here)
   if (a.norm_w) {
     float ss = 0.f;
     u32x4 v0 = x0;
     if constexpr (EARLY) {
       if (i0 < K) {
         v0 = with_delta(x0, i0, false);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float lo = bf2f(v0[e] & 0xffff), hi = bf2f(v0[e] >> 16);
-          ss += lo * lo + hi * hi;
-        }
+        ss = gemv_sumsq8(v0, ss);
       }
     }
-    for (int i = iloop; i < K; i += NTH * 8) {
-      const u32x4 v = ldx(i, false);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
-        ss += lo * lo + hi * hi;
-      }
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) tot += red[w];
-    const float rstd = rsqrtf(tot / (float)K + a.eps);
+    for (int i = iloop; i < K; i += NTH * 8) ss = gemv_sumsq8(ldx(i, false), ss);
+    const float rstd = gemv_rms_rstd<NWV>(ss, red, K, a.eps);
     if constexpr (EARLY) {
       if (i0 < Kpad) {
         u32x4 o = {0, 0, 0, 0};
         if (i0 < K) {
           if (a.x_delta && a.x_out && blockIdx.x == 0) *(u32x4*)((bf16_t*)a.x_out + i0) = v0;
-          const float gw[8] = {ge0.x, ge0.y, ge0.z, ge0.w, ge1.x, ge1.y, ge1.z, ge1.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float lo = bf2f(v0[e] & 0xffff), hi = bf2f(v0[e] >> 16);
-            o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
-          }
+          o = gemv_rmsnorm8(v0, rstd, ge0, ge1);
         }
         *(u32x4*)(xs + i0) = o;
       }
     }
     for (int i = iloop; i < Kpad; i += NTH * 8) {
       u32x4 o = {0, 0, 0, 0};
-      if (i < K) {
-        const u32x4 v = ldx(i, true);
-        const float4 g0 = *(const float4*)(a.norm_w + i), g1 = *(const float4*)(a.norm_w + i + 4);
-        const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
-          o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
-        }
-      }
+      if (i < K) o = gemv_rmsnorm8(ldx(i, true), rstd, *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
       *(u32x4*)(xs + i) = o;
     }
   } else if constexpr (CMB) {
@@ -496,12 +447,7 @@ __global__ __launch_bounds__(NWV * 64) void gemv_kernel(const usdm_gemv_args a, 
     for (int j = 0; j < NR; ++j) {
       const int n = ob + j;
       if (n >= a.N) continue;
-      float v = acc[j];
-      if (a.round_bf16) v = round_bf(v);
-      if (a.residual) {
-        v += USDM_GEMV_RES_PREFETCH ? bf2f(resraw[j]) : bf2f(((const bf16_t*)a.residual)[n]);
-        if (a.round_bf16) v = round_bf(v);
-      }
+      const float v = gemv_plain_value(acc[j], a.round_bf16, a.residual != nullptr, [&] { return bf2f(resraw[j]); });
       if (a.y16) ((bf16_t*)a.y16)[n] = f2bf(v);
       if (a.y32) a.y32[n] = v;
     }
@@ -550,7 +496,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) v
   const int uwave = __builtin_amdgcn_readfirstlane(wave);   // the row bases are wave-uniform: scalar registers, one lane offset
   auto row_ptr = [&](int t, int j) -> const char* {
     const int o = (blockIdx.x + t * gridDim.x) * TILE + uwave * RW + (j % RW);
-    int r = (o >> 4) * 32 + (o & 15) + (j >= RW ? 16 : 0);
+    int r = gemv_glu_row(o, j >= RW);
     r = r < a.N ? r : a.N - 1;
     return (const char*)((const bf16_t*)a.W + (int64_t)r * a.ldw);
   };
@@ -559,32 +505,20 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) v
   auto wload = [&](const char* p, int it) -> u32x4 {
     return __builtin_nontemporal_load((const u32x4*)(p + ((it == nit - 1 && !tail_ok) ? 0u : voff + it * 1024u)));
   };
-  // Straight-line form: HAND-COUNTED ring loads (scalar row base + lane offset + immediate), invisible to the wait-count pass like
-  // the early loads below, each consumed behind an asm wait that names how many younger loads stay in flight.  Left to the
-  // compiler, the straight-line ring was clustered into bursts with vmcnt(0) between them and spilled.
-  auto aload = [&](u32x4& dst, const char* p, auto IT) {
-    constexpr int it = decltype(IT)::value;
-    const unsigned vo = voff + (it >> 2) * 4096u;
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(dst) : "v"(vo), "s"(p), "n"((it & 3) * 1024) : "memory");
-  };
+  // Straight-line form: HAND-COUNTED ring loads (gemv_ring_load), invisible to the wait-count pass like the early loads below, each
+  // consumed behind an asm wait that names how many younger loads stay in flight.  Left to the compiler, the straight-line ring
+  // was clustered into bursts with vmcnt(0) between them and spilled.
   const char* wp[NR];
 #pragma unroll
   for (int j = 0; j < NR; ++j) wp[j] = row_ptr(0, j);
   // ---- prologue, once per workgroup (gemv_kernel's EARLY form)
   const int i0 = tid * 8;
   u32x4 x0 = {0u, 0u, 0u, 0u}, ge0v = x0, ge1v = x0;
-  {
-    const int ic = min(i0, K - 8);
-    const float* gp0 = a.norm_w ? a.norm_w + ic : (const float*)a.x;
-    const float* gp1 = a.norm_w ? gp0 + 4 : gp0;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x0) : "v"((const bf16_t*)a.x + ic) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ge0v) : "v"(gp0) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ge1v) : "v"(gp1) : "memory");
-  }
+  gemv_early_loads(a, i0, K, x0, ge0v, ge1v);
   u32x4 ring[NR][UNR];   // always NR x UNR loads: the wait below names an exact count
   if constexpr (TPW > 0) {
     static_assert(NIT == 0 || (NIT >= UNR && NIT % UNR == 0), "slot u = iteration u of every tile");
-    gemv_for<UNR>([&](auto U) { gemv_for<NR>([&](auto J) { aload(ring[J.value][U.value], wp[J.value], U); }); });
+    gemv_for<UNR>([&](auto U) { gemv_for<NR>([&](auto J) { gemv_ring_load<U.value>(ring[J.value][U.value], wp[J.value], voff); }); });
   } else {
 #pragma unroll
     for (int u = 0; u < UNR; ++u)
@@ -599,42 +533,13 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) v
   const int iloop = i0 + NTH * 8;
   if (a.norm_w) {
     float ss = 0.f;
-    if (i0 < K) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf2f(x0[e] & 0xffff), hi = bf2f(x0[e] >> 16);
-        ss += lo * lo + hi * hi;
-      }
-    }
-    for (int i = iloop; i < K; i += NTH * 8) {
-      const u32x4 v = *(const u32x4*)(xg + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
-        ss += lo * lo + hi * hi;
-      }
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) tot += red[w];
-    const float rstd = rsqrtf(tot / (float)K + a.eps);
-    auto normed = [&](u32x4 v, float4 g0, float4 g1) -> u32x4 {
-      const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-      u32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = bf2f(v[e] & 0xffff), hi = bf2f(v[e] >> 16);
-        o[e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
-      }
-      return o;
-    };
-    if (i0 < Kpad) *(u32x4*)(xs + i0) = i0 < K ? normed(x0, ge0, ge1) : u32x4{0, 0, 0, 0};
+    if (i0 < K) ss = gemv_sumsq8(x0, ss);
+    for (int i = iloop; i < K; i += NTH * 8) ss = gemv_sumsq8(*(const u32x4*)(xg + i), ss);
+    const float rstd = gemv_rms_rstd<NWV>(ss, red, K, a.eps);
+    if (i0 < Kpad) *(u32x4*)(xs + i0) = i0 < K ? gemv_rmsnorm8(x0, rstd, ge0, ge1) : u32x4{0, 0, 0, 0};
     for (int i = iloop; i < Kpad; i += NTH * 8) {
       u32x4 o = {0, 0, 0, 0};
-      if (i < K) o = normed(*(const u32x4*)(xg + i), *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
+      if (i < K) o = gemv_rmsnorm8(*(const u32x4*)(xg + i), rstd, *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
       *(u32x4*)(xs + i) = o;
     }
   } else {
@@ -694,8 +599,8 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) v
           constexpr int younger = refill ? NR * UNR - 1 : NR * UNR - 1 - ((it - (NIT - UNR)) * NR + j);
           asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ring[j][u]) : "n"(younger) : "memory");
           acc[j] = dot8(ring[j][u], xv, acc[j]);
-          if constexpr (it + UNR < NIT) aload(ring[j][u], wp[j], gemv_ic<it + UNR>{});
-          else if constexpr (has_next) aload(ring[j][u], wn[j], gemv_ic<u>{});
+          if constexpr (it + UNR < NIT) gemv_ring_load<it + UNR>(ring[j][u], wp[j], voff);
+          else if constexpr (has_next) gemv_ring_load<u>(ring[j][u], wn[j], voff);
         });
         xv = xn;
       });
@@ -756,21 +661,16 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
   const int urow = min((int)blockIdx.x * NWV + __builtin_amdgcn_readfirstlane(wave), a.N - 1);   // wave-uniform: a scalar row base
   const char* wp = (const char*)((const bf16_t*)a.W + (int64_t)urow * a.ldw);
   const unsigned voff = lane * 16;          // this lane's 16 bytes of a K iteration (512 elements = 1024 bytes)
-  auto aload = [&](u32x4& dst, const char* p, auto IT) {
-    constexpr int it = decltype(IT)::value;
-    const unsigned vo = voff + (it >> 2) * 4096u;
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(dst) : "v"(vo), "s"(p), "n"((it & 3) * 1024) : "memory");
-  };
   // ---- prologue.  The residual value as gemv_kernel requests it: unconditional, the weight row as a dummy address without one.
   const bf16_t* rbase = a.residual ? (const bf16_t*)a.residual : (const bf16_t*)a.W;
   const unsigned short resraw = rbase[min(ob, a.N - 1)];
   // Both pieces of x, hand-counted and unconditional (the second with a clamped index; written to LDS only where inside K)
   const int i0 = tid * 8, i1 = i0 + NTH * 8;
   u32x4 x0, x1;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x0) : "v"((const bf16_t*)a.x + min(i0, K - 8)) : "memory");
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x1) : "v"((const bf16_t*)a.x + min(i1, K - 8)) : "memory");
+  gemv_load16(x0, (const bf16_t*)a.x + min(i0, K - 8));
+  gemv_load16(x1, (const bf16_t*)a.x + min(i1, K - 8));
   u32x4 ring[UNR];   // always UNR loads: the wait below names an exact count
-  gemv_for<UNR>([&](auto U) { aload(ring[U.value], wp, U); });
+  gemv_for<UNR>([&](auto U) { gemv_ring_load<U.value>(ring[U.value], wp, voff); });
   GTR(1);
   // in-order completion: x has landed, the ring stays in flight.  (The skip word is an operand so that its test, and with it the
   // wait for its scalar load, stays behind the ring's issue.)
@@ -792,7 +692,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
     const u32x4 xn = *(const u32x4*)(xs + (((it + 1) % NIT) * 64 + lane) * 8);
     asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ring[u]) : "n"(younger) : "memory");
     acc = dot8(ring[u], xv, acc);
-    if constexpr (it + UNR < NIT) aload(ring[u], wp, gemv_ic<it + UNR>{});
+    if constexpr (it + UNR < NIT) gemv_ring_load<it + UNR>(ring[u], wp, voff);
     xv = xn;
   });
   acc = wave_sum(acc);
@@ -800,12 +700,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
 
   // ---- epilogue (gemv_kernel's plain form)
   if (lane != 0 || ob >= a.N) return;
-  float v = acc;
-  if (a.round_bf16) v = round_bf(v);
-  if (a.residual) {
-    v += bf2f(resraw);
-    if (a.round_bf16) v = round_bf(v);
-  }
+  const float v = gemv_plain_value(acc, a.round_bf16, a.residual != nullptr, [&] { return bf2f(resraw); });
   if (a.y16) ((bf16_t*)a.y16)[ob] = f2bf(v);
   if (a.y32) a.y32[ob] = v;
 }
@@ -857,9 +752,6 @@ __global__ void residual_add_kernel(bf16_t* h, const float* delta, int n) {
 }
 }  // namespace
 
-// Launches the instantiation gemv_select names.  One selection for every weight format, so an FP8 or MXFP4 launch partitions K and
-// the RMSNorm sums exactly as the bf16 launch of the same shape.  FORM: GEMV_PLAIN (no merged input, no peer-to-peer epilogue:
-// the only form of the FP8 / MXFP4 weights), GEMV_MRG or GEMV_CMB, with the kernel's MRG / P2P / CMB flags.
 // Workgroups of `kern` the current device holds at once (the occupancy query x its CUs), remembered for the last kernel, device
 // and LDS size asked about
 static int gemv_resident_count(const void* kern, int nth, size_t lds, int* out) {
@@ -905,6 +797,9 @@ static int gemv_launch_resident(const usdm_gemv_args& a, const gemv_sel& s, size
   return 0;
 }
 
+// Launches the instantiation gemv_select names.  One selection for every weight format, so an FP8 or MXFP4 launch partitions K and
+// the RMSNorm sums exactly as the bf16 launch of the same shape.  FORM: GEMV_PLAIN (no merged input, no peer-to-peer epilogue:
+// the only form of the FP8 / MXFP4 weights), GEMV_MRG or GEMV_CMB, with the kernel's MRG / P2P / CMB flags.
 template <int FORM, bool MRG, bool P2P, bool CMB, bool FP8, class... FMT>
 static int gemv_launch(const usdm_gemv_args& a, hipStream_t st, FMT... fmt) {
   const size_t lds = (size_t)((a.K + 511) & ~511) * 2;

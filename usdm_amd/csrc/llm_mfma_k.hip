@@ -370,6 +370,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
           for (int e = 0; e < 4; ++e) {
             const float lo = bf2f(xf[c][e] & 0xffff), hi = bf2f(xf[c][e] >> 16);
             ss = fmaf(hi, hi, fmaf(lo, lo, ss));      // (explicit: the build contracts nothing; this prologue is ~700 vector instructions per wave)
+            // (not gemv_sumsq8: this kernel's statistic is deliberately this fmaf chain with a 16-lane reduction)
           }
         }
       if (r16 >= nb) ss = 0.f;
@@ -390,7 +391,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
           const float4 g0 = *(const float4*)(gam + (kc0 + c) * 32 + 8 * g), g1 = *(const float4*)(gam + (kc0 + c) * 32 + 8 * g + 4);
           const float gw[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
+          for (int e = 0; e < 4; ++e) {   // (gemv_rmsnorm8's text: as the function the 16-chunk forms gained 32 instructions)
             const float lo = bf2f(xf[c][e] & 0xffff), hi = bf2f(xf[c][e] >> 16);
             xf[c][e] = pack_bf2(round_bf(round_bf(lo * rstd) * gw[2 * e]), round_bf(round_bf(hi * rstd) * gw[2 * e + 1]));
           }
