@@ -442,7 +442,8 @@ typedef struct usdm_sample_args {
    * captured decode graph serves every request (the host rewrites 24 bytes instead of re-capturing per seed). */
   const usdm_sample_params* dev_params;
   /* batched decode (usdm_decode_state.batch > 1): sequence b reads logits + b * logits_bs, dev_params[b] (required), the state
-   * words [b] and writes h_out + b * Hd; its Philox counter is ITS step, so its tokens equal those of the single-sequence call
+   * words [b] and writes h_out + b * Hd and probs_out + b * V (contiguous [batch][V], also where logits_bs > V); its Philox
+   * counter is ITS step, so its tokens equal those of the single-sequence call
    * (per-slot sampling inside a continuous batch: src/inference_vllm.py:109-123 passes one SamplingParams per request). */
   int64_t logits_bs;
   float min_p;   /* [0, 1], 0 = off (dev_params: the block's) */

@@ -255,7 +255,7 @@ extern "C" int usdm_sample_final(const usdm_sample_args* pa, const usdm_decode_s
   const int nb = logits_rows(st->batch);
   USDM_CHECK_ARG(nb == 1 || (pa->logits_bs >= pa->V && pa->dev_params), "usdm_sample_final: the batched form needs logits_bs >= V and dev_params[batch]");
   hipLaunchKernelGGL(sample_final_kernel<false>, dim3(nb), dim3(NT), 0, (hipStream_t)stream, *pa, *st, (const bf16_t*)embed_table, Hd,
-                     (bf16_t*)h_out, (int64_t)0, 0, 0u, pa->logits_bs);
+                     (bf16_t*)h_out, (int64_t)0, 0, 0u, (int64_t)pa->V);   // probs_out is [batch][V], whatever the rows' stride
   USDM_LAUNCH_CHECK();
   return 0;
 }
