@@ -42,6 +42,35 @@ without contraction, i.e. 4 additions on the chain and one rounding of the pair 
 16 wave partials = 62.)  rstd = sum^(-1/2) halves the relative error: 69.  The division by K, the addition of eps
 and the device's rsqrt (one ulp) add at most 0.5 + 0.5 + 2, and the f32 rounding of x * rstd before its bf16 rounding acts like
 one more 2^-24 on rstd: 73 2^-24 < 128 2^-24 = 2^-17.
+
+Merged-attention input (Case.merge = "mrg" | "cmb": usdm_gemv with mrg_pm / mrg_pl / mrg_po / mrg_ns, and its hand-off form
+cmb_gran; the cases of tests/test_gemv_merge_exact_gpu.py).  From usdm_gemv_args and the header of csrc/attn_merge.h: K = heads x 128,
+  x[h 128 + d] = bf16(sum_s po[h][s][d] e_s / sum_s pl[h][s] e_s),  e_s = exp(pm[h][s] - max_s pm[h][s])        (merge_ref)
+and x is what the projection multiplies; the x pointer is not read (a buffer of NaN).  NaN follows pm, pl (PAD elements) and po
+(one more row of 128).  e_s is a float32 number: below the smallest float32 denormal it is 0.
+  * family "exact": per head 1 <= L <= NS live splits at places of their own share ONE pm, so their e_s is 1 in any arithmetic;
+    their pl are positive integers that sum to 2^j (j differs between heads), their po integers that sum to x 2^j with x the
+    integer x of the integer cases, every sum of magnitudes far below 2^24.  The merged x then IS that integer x in float32 in
+    any order of summation (fma or not), and everything downstream is the integer case above, bit for bit.  The other splits are
+    dead: the kernels' own marker (pm = -1e30, pl = 0), or pm = max - 200 with pl = 3 (e^-200 = 0 in float32).  A dead split's po
+    is +-2^100: any weight but an exact 0 shows.
+  * family "probe": real softmax weights.  pm Gaussian (sigma 1, 3, 6 by head) clipped to max - 16, one dead split (the marker)
+    per head, pl in (0.5, 1.5), po Gaussian; W rows are unit vectors and round_bf16 is off, so y32[n] = x[k_n].  A GPU element must
+    be a bf16 value with |got - ref64| <= half a bf16 ulp of ref64 + B,
+      B = MERGE_K 2^-24 S / D,  S = sum_s |po_s| e_s,  D = sum_s pl_s e_s.
+
+MERGE_K, in units of u = 2^-24 (one float32 rounding, relative).  e_s: the argument pm_s - max rounds once, and where exp is
+exp2(a log2 e) so do the constant and the product: three roundings of an argument of magnitude |a| <= 16 move e^a by 3 |a| u <= 48 u,
+and the device's exp2 is good to one ulp = 2 u: 50 u per weight (the maximum's own weight is exactly 1).  Numerator: one rounding per
+product (none with fma) and at most 64 additions, each relative to a partial sum of magnitude <= S, and the weights' 50 u: (1 + 64
++ 50) u S = 115 u S absolute.  Denominator, all terms positive: 115 u relative.  One reciprocal (one ulp: 2 u) and one product
+(u).  With |ref| = |num| / D <= S / D:  |v - ref| <= (115 + 115 + 2 + 1) u S / D = 233 u S / D < 256 u S / D: MERGE_K = 256.
+The bf16 rounding of v: got is the bf16 value nearest to v; if it is not the one nearest to ref, a midpoint m lies between ref and
+v, got is half a spacing from m and |m - ref| <= |v - ref|: half an ulp + B.  (The spacing is the one at ref unless v crossed a
+power of two upwards by more than half the wider spacing, which takes B above one ulp of ref: the few elements that cancel that
+much.  The test keeps half an ulp OF REF there too, the stricter reading.)
+S / |num| is the cancellation of an element; B is below half an ulp while it is below 128 (tests/test_gemv_exact_cpu.py: for
+>= 98 % of each case's elements, a condition on the seeds).
 """
 import torch
 import torch.nn.functional as Fn
@@ -108,10 +137,13 @@ def pick_rw(nout, glu):
     return best
 
 
-def valu_select(N, *, glu=False, lm_head=False, batched=False):
-    """gemv_select for the plain single-GPU forms -> (rows per wave, GLU, waves per workgroup, grid)"""
+def valu_select(N, *, glu=False, lm_head=False, batched=False, merge=None):
+    """gemv_select for the single-GPU forms -> (rows per wave, GLU, waves per workgroup, grid).  merge: "mrg" (mrg_po given: the
+    16-wave row at 16 rows per CU, else one row per wave whatever the balance rule says) | "cmb" (refused unless N = 4096)"""
     nout = N // 2 if glu else N
     rows_per_cu = nout // 256 if nout % 256 == 0 else 0
+    if merge and not batched:
+        return (1, False, 16, 256) if (rows_per_cu == 16 or merge == "cmb") else (1, False, 4, cdiv(nout, 4))
     if not glu and not lm_head and rows_per_cu == 16:
         return 1, False, 16, 256
     if not glu and not lm_head and rows_per_cu == 24:
@@ -186,11 +218,15 @@ def mfma_select(N, K, *, glu=False, lm_head=False, norm=False, form=1, ks=False)
 # ------------------------------------------------------------------------------------------------------------------ cases
 class Case:
     """one projection.  nb = 0: usdm_gemv; nb >= 1: usdm_gemv_batch with `form`.  kind: "int" | "swiglu" | "probe"; norm: None |
-    "exact" | "probe"; ban: None | "none" | "workgroup" | "wave" | "scattered" | "last" (lm_head mode when not None)"""
+    "exact" | "probe"; ban: None | "none" | "workgroup" | "wave" | "scattered" | "last" (lm_head mode when not None); merge: None |
+    "mrg" | "cmb" (x merged from NS attention partials per head; mfam: "exact" with kind "int", "probe" with kind "probe")"""
 
     def __init__(self, name, *, N, K, seed, nb=0, form=0, glu=False, kind="int", norm=None, res=False, inplace=False, ban=None, idx_offset=0,
-                 delta=False, skip=False, ks=False, inst=None, variant=None, rt=None, fmt="bf16", mfma=None):
+                 delta=False, skip=False, ks=False, inst=None, variant=None, rt=None, fmt="bf16", mfma=None, merge=None, NS=0, mfam="exact"):
         self.name, self.N, self.K, self.seed, self.nb, self.form, self.glu = name, N, K, seed, nb, form, glu
+        self.merge, self.NS, self.mfam = merge, NS, mfam
+        assert merge is None or (merge in ("mrg", "cmb") and 1 <= NS <= 64 and K % 128 == 0 and kind == ("int" if mfam == "exact" else "probe")
+                                 and not (nb or glu or norm or delta or ban) and fmt == "bf16"), "the merged input: a plain batch-1 bf16 projection"
         self.kind, self.norm, self.res, self.inplace, self.ban, self.idx_offset = kind, norm, res, inplace, ban, idx_offset
         self.delta, self.skip, self.ks, self.inst, self.variant, self.rt = delta, skip, ks, inst, variant, rt
         self.fmt = fmt
@@ -219,7 +255,7 @@ class Case:
         """what the launch is expected to reach: the VALU tuple, or the matrix-core (variant, rows per tile)"""
         if self.mfma:
             return self.sel["variant"], self.sel["rt"]
-        return valu_select(self.N, glu=self.glu, lm_head=self.lm_head, batched=self.nb >= 1)[:3]
+        return valu_select(self.N, glu=self.glu, lm_head=self.lm_head, batched=self.nb >= 1, merge=self.merge)[:3]
 
     def threads(self):
         return MW * 64 if self.mfma else 64 * self.selected()[2]
@@ -246,12 +282,19 @@ def _guarded(vals, stride, rows=None, fill=NAN, dtype=BF):
 
 def probe_positions(c):
     """the K positions the probe's unit rows read: all of K where there are rows enough; else the last and first 16 elements and 16
-    either side of every multiple of 8 x threads, then evenly spread ones, as many as there are outputs"""
+    either side of every multiple of 8 x threads, then evenly spread ones, as many as there are outputs.
+    Merged input (37 outputs must do): a thread stages four elements (the hand-off form: one granule of two) and a head is 128: the
+    last and first four elements (whole threads and granules, the last element of the last head), four either side of every pass
+    of the workgroup, the last and first element of a head (127, 128) and the first two of the last head, then evenly spread ones"""
     n, K = c.nout, c.K
     if n >= K:
         return torch.arange(n) % K
-    step = 8 * c.threads()
-    pos = list(range(K - 16, K)) + [p for m in range(step, K + 16, step) for p in range(m - 16, m + 16)] + list(range(16))
+    if c.merge:
+        step = (2 if c.merge == "cmb" else 4) * c.threads()
+        pos = list(range(K - 4, K)) + list(range(4)) + [p for m in range(step, K + 4, step) for p in range(m - 4, m + 4)] + [127, 128, K - 128, K - 127]
+    else:
+        step = 8 * c.threads()
+        pos = list(range(K - 16, K)) + [p for m in range(step, K + 16, step) for p in range(m - 16, m + 16)] + list(range(16))
     pos += [(i * K) // n for i in range(n)]
     out = []
     for p in pos:
@@ -378,11 +421,86 @@ def build(c):
     d.res = None if d.rl is None else _guarded(d.rl, c.res_bs)
     d.banl = ban_pattern(c) if c.lm_head else None
     d.ban = None if (d.banl is None or c.ban == "none") else torch.cat([d.banl, torch.ones(16, dtype=torch.uint8)])
+    if c.merge:
+        _build_merge(c, d, g)
     return d
+
+
+MRG_DEAD_PM = -1e30         # the marker usdm_attn_decode leaves in an empty split (with pl = 0)
+MRG_DEAD_PO = 2.0 ** 100
+
+
+def _build_merge(c, d, g):
+    """d.pm, d.pl [H][NS], d.po [H][NS][128] (float32, logical), their guarded flat buffers d.pm_buf, d.pl_buf, d.po_buf, d.live
+    (bool [H][NS]), and d.x = K elements of NaN (the x pointer is not read).  The exact family merges to d.xl (module docstring)"""
+    H, NS, K = c.K // 128, c.NS, c.K
+    dead_po = MRG_DEAD_PO * (_ints((H, NS, 128), g, 0, 1).float() * 2 - 1)
+    if c.mfam == "probe":
+        sigma = torch.tensor([1.0, 3.0, 6.0])[torch.arange(H) % 3].view(H, 1)
+        pm = (sigma * torch.randn(H, NS, generator=g)).float()
+        live = torch.ones(H, NS, dtype=torch.bool)
+        live[torch.arange(H), _ints((H,), g, 0, NS - 1, torch.int64)] = False
+        mx = torch.where(live, pm, torch.full((), -INF)).max(-1, keepdim=True).values
+        pm = torch.maximum(pm, (mx.double() - 16.0).float())
+        pm = torch.where(mx.double() - pm.double() > 16.0, torch.nextafter(pm, mx), pm)      # (the float32 of max - 16 may lie below it)
+        pl = (0.5 + torch.rand(H, NS, generator=g)).float()
+        po = torch.randn(H, NS, 128, generator=g).float()
+        pm, pl = torch.where(live, pm, torch.full((), MRG_DEAD_PM)), torch.where(live, pl, torch.zeros(()))
+    else:
+        x = d.xl[0].view(H, 128)
+        pm, pl, live = torch.empty(H, NS), torch.empty(H, NS), torch.zeros(H, NS, dtype=torch.bool)
+        po = torch.zeros(H, NS, 128)
+        for h in range(H):
+            L = NS if h % 4 == 1 else 1 if h % 4 == 2 else int(_ints((1,), g, 1, NS, torch.int64))
+            at = torch.randperm(NS, generator=g)[:L]
+            live[h, at] = True
+            j = (L - 1).bit_length() + h % 4                              # 2^j >= L; j <= 9
+            w = torch.rand(L, generator=g).double()
+            a = 1 + torch.floor((2 ** j - L) * w / w.sum())              # positive integers ...
+            a[0] += 2 ** j - a.sum()                                      # ... that sum to 2^j
+            o = _ints((L, 128), g, -2 ** (j + 1), 2 ** (j + 1), torch.int64).double()
+            o[L - 1] = x[h] * 2 ** j - o[:L - 1].sum(0)
+            pmh = float(3.0 * torch.randn(1, generator=g))
+            s = torch.arange(NS)
+            pm[h] = torch.where((s + h) % 2 == 0, torch.full((), MRG_DEAD_PM), torch.full((), pmh - 200.0))
+            pl[h] = torch.where((s + h) % 2 == 0, torch.zeros(()), torch.full((), 3.0))
+            pm[h, at], pl[h, at], po[h, at] = pmh, a.float(), o.float()
+    d.live = live
+    d.pm, d.pl, d.po = pm.float(), pl.float(), torch.where(live.view(H, NS, 1), po.float(), dead_po)
+    nan = lambda n: torch.full((n,), NAN, dtype=F32)
+    d.pm_buf, d.pl_buf = torch.cat([d.pm.reshape(-1), nan(PAD)]), torch.cat([d.pl.reshape(-1), nan(PAD)])
+    d.po_buf = torch.cat([d.po.reshape(-1), nan(128)])
+    d.x = torch.full((K,), NAN, dtype=BF)
+
+
+MERGE_K = 256.0
+
+
+def merge_ref(c, d, dtype=F64):
+    """the merge of the contract in dtype -> (x [K] before its bf16 rounding, B [K]: the probe family's bound, module docstring)"""
+    pm, pl, po = d.pm.to(dtype), d.pl.to(dtype), d.po.to(dtype)
+    e = torch.exp(pm - pm.max(-1, keepdim=True).values)
+    e = torch.where(e < 2.0 ** -149, torch.zeros((), dtype=dtype), e)      # a float32 number: e^-200 is 0
+    den = (pl * e).sum(-1, keepdim=True)
+    x = (po * e.unsqueeze(-1)).sum(1) / den
+    B = MERGE_K * 2.0 ** -24 * (po.abs() * e.unsqueeze(-1)).sum(1) / den
+    return x.reshape(-1), B.reshape(-1)
+
+
+GRAN_TAIL = (2 << 32) | 0x7e7e7f7f      # the fill of the 16 granules after cmb_gran[K / 2]: not zero, its tag not 1
+
+
+def granules(x):
+    """int64 [K / 2]: the granules {tag 1, bf16 x[2 i], x[2 i + 1]} of the hand-off form for the merged x (fp64, bf16 values)"""
+    b = bits(x.to(BF)).to(torch.int64) & 0xffff
+    return (1 << 32) | b[0::2] | (b[1::2] << 16)
 
 
 def x_prime(c, d, scale=1.0):
     """(x' the projection multiplies, x' before the RMSNorm = what x_out receives), fp64 [B][K]; scale: applied to rstd"""
+    if c.merge:
+        x = rbf64(merge_ref(c, d)[0]).view(1, c.K)
+        return x, x
     x = d.xl
     if c.delta:
         x = rbf64(x + rbf64(d.dl))
@@ -639,6 +757,53 @@ def mfma_norm_cases(nb, fmt="bf16"):
 
 
 FP8_MFMA_VARIANTS = ("hold", "hold16-recut", "stream", "stream56-recut", "ksplit")
+
+
+# ---- usdm_gemv with the merged-attention input: GEMV_MRG on (1, false, 16) and (1, false, 4), GEMV_CMB on (1, false, 16)
+MERGE_FORMS = ("mrg16", "mrg4", "cmb")
+MERGE_INST = {"mrg16": (1, False, 16), "mrg4": (1, False, 4), "cmb": (1, False, 16)}
+# (N, K).  mrg16: 1024 threads x 4 elements = 4096 per pass: one head (most threads idle, zero fill to Kpad), exactly one pass, a
+# second pass of 32 threads, two passes.  mrg4: 1024 per pass, the last workgroup ragged (37 = 9 x 4 + 1, 4081 = 1020 x 4 + 1); 16384 is
+# the K limit (128 heads).  cmb: the gather takes 1024 granules = 2048 elements per pass; K = 128: workgroup 0 alone combines
+MERGE_SHAPES = {"mrg16": ((4096, 128), (4096, 4096), (4096, 4224), (4096, 8192)),
+                "mrg4": ((37, 128), (37, 1024), (37, 1152), (37, 16384), (4081, 1024)),
+                "cmb": ((4096, 128), (4096, 2048), (4096, 4096), (4096, 4224), (4096, 8192))}
+# mrg: chunks of 8 splits with clamped loads; cmb: groups of four and a scalar tail, 64 lanes of weights
+MERGE_NS = {"mrg16": (1, 7, 8, 9, 64), "mrg4": (1, 7, 8, 9, 64), "cmb": (1, 3, 4, 5, 21, 64)}
+MERGE_NS_PAIR = {"mrg16": (7, 9), "mrg4": (7, 9), "cmb": (3, 5)}       # below and above a chunk / a group: at every shape
+MERGE_NS_AT = {"mrg16": (4096, 4224), "mrg4": (37, 1152), "cmb": (4096, 4224)}      # the shape that runs the whole NS ladder
+MERGE_VARIANTS = (dict(res=True), dict(res=True, inplace=True), dict())     # in place: y16 = residual in the round_bf16 launch
+MERGE_PROBE = {"mrg16": ((4096, 4096, 9), (4096, 4096, 64)), "mrg4": ((37, 1152, 9), (37, 1152, 64), (4081, 1152, 9)),
+               "cmb": ((4096, 4096, 5), (4096, 4096, 21), (4096, 4096, 64))}
+
+
+def _merge_case(form, tag, N, K, NS, seed, **kw):
+    return Case(f"{form} {tag} N{N} K{K} NS{NS}", N=N, K=K, seed=seed, merge="cmb" if form == "cmb" else "mrg", NS=NS, inst=MERGE_INST[form], **kw)
+
+
+def merge_exact_cases(form, shape):
+    """the exact family at one (N, K): the two NS either side of a chunk / group, the whole NS ladder at MERGE_NS_AT; plain, with a
+    residual and with the residual in place by turns"""
+    f, i = MERGE_FORMS.index(form), MERGE_SHAPES[form].index(shape)
+    ns = MERGE_NS[form] if shape == MERGE_NS_AT[form] else MERGE_NS_PAIR[form]
+    return [_merge_case(form, "exact", *shape, NS, 30000 + 1000 * f + 100 * i + NS, **MERGE_VARIANTS[(i + j) % 3]) for j, NS in enumerate(ns)]
+
+
+def merge_skip_cases(form):
+    N, K = MERGE_SHAPES[form][1]
+    return [_merge_case(form, "skip", N, K, MERGE_NS_PAIR[form][1], 33000 + MERGE_FORMS.index(form), skip=True, res=True)]
+
+
+def merge_probe_cases(form):
+    """(the seeds: ones at which B is below half an ulp on >= 98 % of a case's elements, i.e. on all 37 of the small cases; the CPU
+    test checks it)"""
+    return [_merge_case(form, "probe", N, K, NS, 34000 + 1000 * MERGE_FORMS.index(form) + 100 * j, kind="probe", mfam="probe")
+            for j, (N, K, NS) in enumerate(MERGE_PROBE[form])]
+
+
+def merge_cases():
+    """every case of tests/test_gemv_merge_exact_gpu.py"""
+    return [c for form in MERGE_FORMS for c in [x for s in MERGE_SHAPES[form] for x in merge_exact_cases(form, s)] + merge_skip_cases(form) + merge_probe_cases(form)]
 
 
 def quant_insts(fmt):

@@ -1,6 +1,8 @@
 """tests/_gemv_reference.py checked on the CPU: the reference against torch.nn.functional on float data, the conditions under which
 its cases are exact (2^24 headroom, the SwiGLU grid, the exact RMSNorm family, the 2 % cap of the probe), and that every case
-reaches the instantiation it is listed under and every instantiation is reached."""
+reaches the instantiation it is listed under and every instantiation is reached.  The merged-attention input: its two families'
+conditions (the exact merge in two float32 orders, the probe's bound against half an ulp), its launch selection and what usdm_gemv
+refuses before a launch."""
 import pytest
 import torch
 import torch.nn.functional as Fn
@@ -350,3 +352,141 @@ def test_exactness_conditions(group):
             assert torch.equal(a, b) and torch.equal(a.abs(), d.gl.abs().expand_as(a)), c.name
     if worst:
         print(f"[gemv] {group[0]}: the probe's references differ on at most {100 * worst:.2f} % of a case's elements (cap 2 %)")
+
+
+# ------------------------------------------------------------------------------------------------------------------ merged-attention input
+def _gemv_threads(c):
+    """usdm_gemv_threads on the arguments that make the selection (dummy addresses: nothing is read)"""
+    import ctypes
+    from usdm_amd import _lib
+    kw = dict(mrg_pm=8, mrg_pl=8, mrg_po=8, mrg_ns=c.NS, **(dict(cmb_gran=8, cmb_err=8) if c.merge == "cmb" else {})) if c.merge else {}
+    a = _lib.GemvArgs(W=8, x=8, N=c.N, K=c.K, ldw=c.ldw, act=c.act, y32=8, **kw)
+    return _lib.lib.usdm_gemv_threads(ctypes.byref(a))
+
+
+def test_merge_selection_mirror_and_coverage():
+    """valu_select's merge row agrees with usdm_gemv_threads, as Run.threads asks of every GPU case; the three instantiations, every
+    shape, the NS ladders and the variants of the issue are all there"""
+    cases = R.merge_cases()
+    assert len({c.name for c in cases}) == len(cases)
+    for c in cases:
+        assert c.selected() == c.inst and _gemv_threads(c) == c.threads() == 64 * c.inst[2], c.name
+    assert R.valu_select(4096, merge="mrg") == (1, False, 16, 256) == R.valu_select(4096, merge="cmb") and R.valu_select(37, merge="mrg") == (1, False, 4, 10)
+    assert R.valu_select(6144, merge="mrg") == (1, False, 4, 1536) and R.valu_select(16369, merge="mrg")[:3] == (1, False, 4)     # (plain: 2 x 12 waves, 4 rows per wave)
+    for N in (37, 4081, 6144, 16369, 4096):
+        assert _gemv_threads(R.Case("t", N=N, K=128, seed=0, merge="mrg", NS=2)) == 64 * R.valu_select(N, merge="mrg")[2], N
+    for form in R.MERGE_FORMS:
+        ex = [c for s in R.MERGE_SHAPES[form] for c in R.merge_exact_cases(form, s)]
+        assert {(c.N, c.K) for c in ex} == set(R.MERGE_SHAPES[form]) and all(c.merge == ("cmb" if form == "cmb" else "mrg") for c in ex)
+        assert {c.NS for c in ex if (c.N, c.K) == R.MERGE_NS_AT[form]} == set(R.MERGE_NS[form])
+        for s in R.MERGE_SHAPES[form]:
+            assert set(R.MERGE_NS_PAIR[form]) <= {c.NS for c in ex if (c.N, c.K) == s}
+        assert {(c.res, c.inplace) for c in ex} == {(False, False), (True, False), (True, True)}
+        assert [c.skip for c in R.merge_skip_cases(form)] == [True] and {(c.N, c.K, c.NS) for c in R.merge_probe_cases(form)} == set(R.MERGE_PROBE[form])
+    assert all(N % 4 == 1 for N, _ in R.MERGE_SHAPES["mrg4"]) and max(K for _, K in R.MERGE_SHAPES["mrg4"]) == 16384
+    assert max(c.N * c.ldw for c in cases) == 4096 * 8200
+
+
+def _merge32(d, order):
+    """the merge in float32, by hand: "split": one split after the other; "four": groups of four ((a0 w0 + a1 w1) + (a2 w2 + a3 w3))
+    and a tail -> (x [K] float32, the weights e [H][NS])"""
+    pm, pl, po = d.pm, d.pl, d.po
+    NS = pm.shape[1]
+    e = torch.exp(pm - pm.max(-1, keepdim=True).values)
+    assert e.dtype == R.F32
+    o, l = torch.zeros(po.shape[0], 128), torch.zeros(po.shape[0])
+    t = lambda s: po[:, s] * e[:, s, None]
+    s = 0
+    while order == "four" and s + 4 <= NS:
+        o, l = o + ((t(s) + t(s + 1)) + (t(s + 2) + t(s + 3))), l + ((pl[:, s] * e[:, s] + pl[:, s + 1] * e[:, s + 1]) + (pl[:, s + 2] * e[:, s + 2] + pl[:, s + 3] * e[:, s + 3]))
+        s += 4
+    for s in range(s, NS):
+        o, l = o + t(s), l + pl[:, s] * e[:, s]
+    return (o * (1.0 / l)[:, None]).reshape(-1), e
+
+
+@pytest.mark.parametrize("form", R.MERGE_FORMS)
+def test_merge_case_conditions(form):
+    """every case builds with its guards.  Exact family: the merged x is the integer x bit for bit in float32 in two orders of
+    summation and in fp64, dead weights are exactly 0 in float32, all magnitudes sum below 2^24, and live counts, places, 2^j and both
+    kinds of dead split vary between heads.  Probe family: |pm - max| <= 16, one dead split per head, B below half a bf16 ulp on
+    >= 98 % of the elements, and a plain float32 evaluation is inside the bound"""
+    nan = lambda t: bool(torch.isnan(t).all())
+    for c in [c for c in R.merge_cases() if c.inst == R.MERGE_INST[form] and (c.merge == "cmb") == (form == "cmb")]:
+        d = R.build(c)
+        H, NS, K = c.K // 128, c.NS, c.K
+        assert d.x.shape == (K,) and nan(d.x) and d.pm.shape == (H, NS) == d.pl.shape and d.po.shape == (H, NS, 128)
+        for buf, t, pad in ((d.pm_buf, d.pm, R.PAD), (d.pl_buf, d.pl, R.PAD), (d.po_buf, d.po, 128)):
+            assert buf.dtype == R.F32 and buf.numel() == t.numel() + pad and nan(buf[t.numel():]) and torch.equal(R.bits(buf[:t.numel()]), R.bits(t.reshape(-1)))
+        Wb = d.W.view(c.N + 1, c.ldw)
+        assert c.ldw == K + 8 and nan(Wb[:, K:]) and nan(Wb[c.N])
+        if c.res:
+            rb = d.res.view(2, c.res_bs)
+            assert nan(rb[:, c.nout:]) and nan(rb[1])
+        assert bool(torch.isfinite(d.po).all()) and bool(d.live.any(-1).all())
+        x64, B = R.merge_ref(c, d)
+        e = R.expected(c, d, rbf=False)
+        if c.mfam == "exact":
+            xi = d.xl[0]
+            assert torch.equal(x64, xi) and bool((xi == xi.round()).all()) and torch.equal(R.x_prime(c, d)[0][0], xi), c.name
+            for order in ("split", "four"):
+                x32, w = _merge32(d, order)
+                assert torch.equal(R.bits(x32), R.bits(xi.float())), (c.name, order)
+            assert bool((w[~d.live] == 0).all()) and bool((w[d.live] == 1).all()) and bool((d.po[~d.live].abs() == R.MRG_DEAD_PO).all())
+            live = d.live.double()
+            assert float((d.po.double().abs() * live[..., None]).sum(1).max()) < 2.0 ** 20 and float((d.pl.double() * live).sum(-1).max()) <= 2.0 ** 9
+            lsum = (d.pl.double() * live).sum(-1)
+            assert bool((torch.log2(lsum) == torch.log2(lsum).round()).all()) and bool((d.pl[d.live] >= 1).all())
+            assert torch.equal(e["y"].vals[e["y"].owned], (R.ref_acc(d, d.xl) + (d.rl if c.res else 0.0)).reshape(-1)), c.name
+            assert d.acc_max + (float(d.rl.abs().max()) if c.res else 0.0) < 2.0 ** 24
+            marker, far = ~d.live & (d.pm == R.MRG_DEAD_PM) & (d.pl == 0), ~d.live & (d.pm > -1e3) & (d.pl > 0)
+            assert bool((marker | far | d.live).all()) and (NS < 3 or H < 2 or (bool(marker.any()) and bool(far.any()))), c.name
+            if H >= 4 and NS >= 7:
+                L = d.live.sum(-1)
+                assert int(L.max()) == NS and int(L.min()) == 1 and lsum.unique().numel() >= 3 and L.unique().numel() >= 3
+                assert len({tuple(r.tolist()) for r in d.live[L < NS]}) >= min(4, int((L < NS).sum()) // 2), c.name     # places of their own
+        else:
+            dead = ~d.live
+            assert bool((dead.sum(-1) == 1).all()) and bool((d.pm[dead] == R.MRG_DEAD_PM).all()) and bool((d.pl[dead] == 0).all()) and bool((d.pl[d.live] > 0).all())
+            pmd = d.pm.double()
+            gap = torch.where(d.live, pmd.max(-1, keepdim=True).values - pmd, torch.zeros((), dtype=R.F64))
+            assert 0 <= float(gap.min()) and 15.99 < float(gap.max()) <= 16.0 and e["y"].owned.sum() == c.N
+            k = d.kpos
+            ref, Bk = x64[k], B[k]
+            h = R.bf16_ulp(ref) / 2
+            share = float((Bk < h).double().mean())
+            x32 = _merge32(d, "split")[0].double()[k]
+            ratio = float(((x32 - ref).abs() / Bk).max())
+            print(f"[gemv] {c.name}: B < half an ulp on {100 * share:.2f} % of the elements, largest B {float((Bk / h).max()):.2f} half ulps; float32 on the CPU: {ratio:.3f} B")
+            assert share >= 0.98 and ratio <= 1.0, c.name
+            assert torch.equal(e["y"].vals[e["y"].owned], R.rbf64(ref)), c.name
+            pos = set(k.tolist())
+            want = set(range(K)) if c.N >= K else {0, 1, 2, 3, 127, 128, K - 128, K - 4, K - 3, K - 2, K - 1} | set(range(4 * c.threads() - 4, 4 * c.threads() + 4))
+            assert want <= pos and len(pos) == min(c.N, K), c.name
+
+
+def test_merge_refusals():
+    """what usdm_gemv refuses before any launch with the mrg_* partials and with cmb_gran, by return code and message.  Where there
+    is a GPU every address is a real buffer that holds the launch and *skip is non-zero, should a refusal ever get lost"""
+    import ctypes
+    from usdm_amd import _lib
+    pool = torch.ones(1 << 21, dtype=torch.uint8, device="cuda") if torch.cuda.is_available() else None
+    p = 8 if pool is None else pool.data_ptr()
+
+    def refused(match, **kw):
+        a = dict(W=p, x=p, N=8, K=128, ldw=128, y32=p, skip=p, mrg_pm=p, mrg_pl=p, mrg_po=p, mrg_ns=2)
+        a.update(kw)
+        rc = _lib.lib.usdm_gemv(ctypes.byref(_lib.GemvArgs(**a)), ctypes.c_void_p(0))
+        msg = _lib.lib.usdm_last_error().decode()
+        assert rc == 2 and match in msg, (kw, rc, msg)
+
+    mrg, plain, cmb = "merged-attention input needs", "are for plain projections", "cmb_gran needs"
+    for kw in (dict(mrg_ns=0), dict(mrg_ns=65), dict(K=136, ldw=136), dict(norm_w=p), dict(x_delta=p), dict(mrg_pm=0), dict(mrg_pl=0)):
+        refused(mrg, **kw)
+    refused(plain, act=R.ACT_SWIGLU, N=32)
+    refused(plain, part_val=p, part_idx=p)
+    hand = dict(N=4096, cmb_gran=p, cmb_err=p)
+    for kw in (dict(N=37), dict(N=4080), dict(N=8192), dict(p2p=p, p2p_mode=1, residual=p, y16=p), dict(mrg_po=0), dict(act=R.ACT_SWIGLU, N=8192), dict(part_val=p, part_idx=p)):
+        refused(cmb, **dict(hand, **kw))
+    for kw in (dict(mrg_pm=0), dict(mrg_pl=0), dict(mrg_ns=0), dict(mrg_ns=65), dict(norm_w=p), dict(x_delta=p)):
+        refused(mrg, **dict(hand, **kw))

@@ -37,6 +37,12 @@ class Run:
             self.ksf, self.nt16 = R.ks_floats(c.N, c.K), R.cdiv(c.N, 16)
             cnt = torch.cat([torch.zeros(self.nt16, dtype=torch.int32), R.sentinel((4,), torch.int32)]).to(dev)
             self.ks = (R.sentinel((self.ksf + 64,), F32, dev), cnt)
+        self.mkw = {}
+        if c.merge:             # the merged-attention input; hand-off form: K / 2 granules, 16 more that no launch may touch, the error word
+            self.mkw["merge"] = (up(d.pm_buf), up(d.pl_buf), up(d.po_buf), c.NS)
+            if c.merge == "cmb":
+                self.gran, self.cmb_err = torch.empty(c.K // 2 + 16, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+                self.mkw["cmb"] = (self.gran, self.cmb_err)
 
     def sizes(self):
         c = self.c
@@ -62,8 +68,15 @@ class Run:
             else:               # (the twin of an usdm_gemv_fp8_mfma case: form 1 is what its form 0 must equal)
                 ops.gemv_batch(self.W, self.x, form=1 if (c.fmt == "fp8" and c.mfma and c.form == 0) else c.form, **bkw)
         else:
-            ops.gemv(self.W, self.x, x_delta=self.x_delta, x_out=out.get("x_out"), skip=self.skip, **kw)
+            if c.merge == "cmb":            # the tags are zero when the launch starts: the test clears them itself, every time
+                self.gran[:c.K // 2], self.gran[c.K // 2:] = 0, R.GRAN_TAIL
+                self.cmb_err.zero_()
+            ops.gemv(self.W, self.x, x_delta=self.x_delta, x_out=out.get("x_out"), skip=self.skip, **self.mkw, **kw)
         torch.cuda.synchronize()
+        if c.merge == "cmb":                # (self.granules: what the launch left in cmb_gran[K / 2])
+            self.granules = self.gran[:c.K // 2].cpu()
+            assert int(self.cmb_err.item()) == 0, f"{c.name}: cmb_err = {int(self.cmb_err.item())}"
+            assert bool((self.gran[c.K // 2:].cpu() == R.GRAN_TAIL).all()), f"{c.name}: granules written past cmb_gran[K / 2]"
         if c.ks:
             part, cnt = self.ks[0].cpu(), self.ks[1].cpu()
             assert int(cnt[:self.nt16].abs().sum()) == 0, f"{c.name}: tile counters not back at zero"
@@ -75,7 +88,7 @@ class Run:
         c = self.c
         pv = torch.empty(1, device=self.dev) if c.lm_head else None
         W = self.W if self.fmt == "bf16" else self.W.q        # (the launch selection does not depend on the format: the bf16 arguments)
-        a = ops.gemv(W, self.x, only_args=True, N=c.N, K=c.K, ldw=c.ldw, act=c.act, part_val=pv, part_idx=pv)
+        a = ops.gemv(W, self.x, only_args=True, N=c.N, K=c.K, ldw=c.ldw, act=c.act, part_val=pv, part_idx=pv, **self.mkw)
         return _lib.lib.usdm_gemv_threads(ctypes.byref(a))
 
 
@@ -205,8 +218,8 @@ def _probe(r):
 INF_TOL = float("inf")      # check_guard on the partials of a probe: only that nothing outside the owned ones is written
 
 
-def run_case(c, dev):
-    r = Run(c, dev)
+def run_case(c, dev, r=None):
+    r = Run(c, dev) if r is None else r
     if not c.nb:
         assert r.threads() == c.threads(), f"{c.name}: usdm_gemv_threads says {r.threads()}, the mirror {c.threads()}"
     if c.skip:
@@ -233,8 +246,8 @@ def run_case(c, dev):
     assert torch.equal(R.bits(r.x), x0), f"{c.name}: x changed"
 
 
-def _run_all(cases, dev, what):
-    worst = [v for v in (run_case(c, dev) for c in cases) if v is not None]
+def _run_all(cases, dev, what, run=run_case):
+    worst = [v for v in (run(c, dev) for c in cases) if v is not None]
     if worst:
         print(f"[gemv] {what}: worst {max(worst):.4f}")
 
