@@ -389,6 +389,33 @@ int usdm_dequant_mxfp4(const void* codes, int64_t ldw, const uint8_t* scales, in
                        int64_t ldo, usdm_stream_t stream);
 int usdm_sizeof_gemv_mxfp4_args(void);
 
+/* Lossless 13-bit image of a bf16 weight matrix (default on for the 7B's down_proj; usdm_amd/wpack.py is the one packer).  The
+ * exponent field of a weight matrix is almost constant, so a weight b (its 16 bits) is stored as its low byte b & 0xff, the 4-bit
+ * index ((b >> 8) & 0x7f) - base of its upper seven exponent bits, and its sign: 13 bits, rebuilt exactly in registers.  base is
+ * one value per matrix.  A row that holds a weight whose index is outside 0..15 (zeros, denormals, inf / NaN, ...) is marked in
+ * rowflag and streamed from the bf16 matrix instead, so the result never depends on the data.
+ * Layout: row r starts at planes + r * stride and is K / 2048 units of 3328 bytes; unit u covers elements 2048 u .. +2047, i.e.
+ * the four K iterations 4u .. 4u + 3 of the bf16 kernels, in which lane L owns elements e(i, k) = 2048 u + 512 i + 8 L + k:
+ *   bytes    0 .. 1023  low bytes: byte 16 L + 8 i + k of element e(i, k), i = 0, 1
+ *   bytes 1024 .. 2047  the same for i = 2, 3
+ *   bytes 2048 .. 3071  nibbles: dword 4 L + i holds in byte k (0..3) the index of e(i, k) in bits 3:0 and of e(i, k + 4) in 7:4
+ *   bytes 3072 .. 3327  signs: dword L holds the sign of e(i, k) at bit 8 (k & 3) + 7 - (2 i + (k >> 2))
+ * usdm_gemv_packed(args, pack) computes exactly usdm_gemv(args), bit for bit: where usdm_gemv would run the straight-line
+ * K = 14336 form (see usdm_gemv_args.resident) the unmarked rows stream the image; every other call is usdm_gemv itself. */
+typedef struct usdm_gemv_wpack {
+  const void* planes;        /* 16-byte aligned */
+  const uint8_t* rowflag;    /* [N rounded up to 4]: non-zero = the row streams from args->W (the packer's record; see marked) */
+  int64_t stride;            /* bytes between rows: a multiple of 16, >= K / 2048 * 3328 */
+  int32_t base;              /* 0 .. 112 */
+  int32_t units;             /* K / 2048 */
+  /* rowflag as bits (bit r of the array = row r is marked), the copy the kernel reads: a kernel argument, so no memory round trip
+   * stands in front of the first weight load.  At most 14336 rows. */
+  uint32_t marked[448];
+} usdm_gemv_wpack;
+int usdm_gemv_packed(const usdm_gemv_args* args, const usdm_gemv_wpack* pack, usdm_stream_t stream);
+int usdm_gemv_packs(const usdm_gemv_args* args);   /* 1 where usdm_gemv_packed streams the image of this projection */
+int usdm_sizeof_gemv_wpack(void);
+
 /* Device-resident greedy-decode state so that a decode step is replayable as one hipGraph. */
 typedef struct usdm_decode_state {
   int32_t* next_token;  /* [1] token fed to the next step                     */

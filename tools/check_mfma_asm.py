@@ -70,6 +70,85 @@ def audit(lines, i0, i1):
     return nload, bad
 
 
+def audit_paths(lines, i0, i1):
+    """audit() along the control-flow paths of a kernel with more than one body (gemv_stream_wpack_kernel: the packed and the bf16
+    rows).  The compiler merges the bodies' returns and the shared epilogue into blocks that are entered under FLAGS - scalar
+    register pairs it sets to the constants 0 and -1 (s_mov_b64) and tests as `s_and_b64 vcc, exec, flag` + s_cbranch_vccz / vccnz -
+    so a linear scan reads the epilogue as code under one body's ring, and a walk that takes both sides of those branches runs
+    from one body into the other.  This walk keeps the constant flags it has seen set: a branch on a known flag is followed one
+    way, every other conditional branch both ways; s_branch is followed, s_endpgm ends a path, a state is walked once.
+    -> (asm load instructions seen, [(line offset, code)] as audit())"""
+    label = {m.group(1): i for i in range(i0, i1) if (m := re.match(r"(\.LBB\d+_\d+):", lines[i]))}
+    seen, bad, loads = set(), {}, set()
+    stack = [(i0, (), (), None)]
+    while stack:
+        i, fifo, flags, vcc = stack.pop()    # flags: known constant s[a:b]; vcc: True = known non-zero, False = known zero
+        fifo, flags, inasm = list(fifo), dict(flags), False
+        while i < i1:
+            code = lines[i].split(";")[0]
+            if re.match(r"\.LBB\d+_\d+:", lines[i]):
+                key = (i, tuple(fifo), tuple(sorted(flags.items())), vcc)
+                if key in seen:
+                    break
+                seen.add(key)
+            if "ASMSTART" in lines[i]:
+                inasm = True
+            elif "ASMEND" in lines[i]:
+                inasm = False
+            elif inasm:
+                if LOAD.search(code):
+                    fifo.append(frozenset(regs(REG.findall(code)[0])))
+                    loads.add(i)
+                m = re.search(r"s_waitcnt vmcnt\((\d+)\)", code)
+                if m:
+                    fifo = trim(fifo, int(m.group(1)))
+            else:
+                used = set()
+                for tok in REG.findall(code):
+                    used |= regs(tok)
+                if any(used & f for f in fifo):
+                    bad[i - i0] = code.strip()
+                if re.search(r"\b(global|buffer|scratch|flat)_(load|store|atomic)", code):
+                    fifo.append(frozenset())
+                m = re.search(r"s_waitcnt.*vmcnt\((\d+)\)", code)
+                if m:
+                    fifo = trim(fifo, int(m.group(1)))
+                if "s_endpgm" in code:
+                    break
+                # the constant flags: what writes a scalar pair or vcc either sets a known constant or ends the knowledge
+                ops = re.match(r"\s*(\w+)\s+([^,\s]+)(?:,\s*([^,\s]+))?(?:,\s*([^,\s]+))?", code)
+                if ops and not ops.group(1).startswith(("s_cbranch", "s_branch", "s_cmp", "s_waitcnt", "s_nop", "s_barrier")):
+                    op, dst, a, b = ops.groups()
+                    if dst == "vcc" or op.startswith("v_cmp") and "_e64" not in op:
+                        known = op in ("s_and_b64", "s_andn2_b64") and a == "exec" and b in flags
+                        vcc = (bool(flags[b]) == (op == "s_and_b64")) if known else None    # (exec is not zero where a wave runs)
+                    elif dst in flags or (op == "s_mov_b64" and re.match(r"s\[\d+:\d+\]$", dst)):
+                        flags.pop(dst, None)
+                        if op == "s_mov_b64" and a in ("0", "-1"):
+                            flags[dst] = int(a)
+                    m2 = re.match(r"s\[(\d+):(\d+)\]$", dst) or re.match(r"s(\d+)()$", dst)
+                    if m2:      # a write that overlaps a flag pair under another name
+                        lo, hi = int(m2.group(1)), int(m2.group(2) or m2.group(1))
+                        for k in [k for k in flags if k != dst]:
+                            ka, kb = map(int, re.match(r"s\[(\d+):(\d+)\]", k).groups())
+                            if lo <= kb and ka <= hi:
+                                del flags[k]
+                m = re.match(r"\s*(s_branch|s_cbranch_\w+)\s+(\.LBB\d+_\d+)", code)
+                if m and m.group(1) == "s_branch":
+                    i = label[m.group(2)]
+                    continue
+                if m:
+                    taken = {"s_cbranch_vccz": vcc is not True, "s_cbranch_vccnz": vcc is not False}.get(m.group(1), True)
+                    falls = {"s_cbranch_vccz": vcc is not False, "s_cbranch_vccnz": vcc is not True}.get(m.group(1), True)
+                    if taken and falls:
+                        stack.append((label[m.group(2)], tuple(fifo), tuple(flags.items()), vcc))
+                    elif taken:
+                        i = label[m.group(2)]
+                        continue
+            i += 1
+    return len(loads), sorted(bad.items())
+
+
 def main(argv):
     lines = open(argv[1]).read().split("\n")
     rc = 0

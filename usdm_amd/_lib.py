@@ -26,6 +26,8 @@ lib.usdm_attn_decode_fp8.restype = C.c_int   # (the FP8 KV cache entry points: l
 lib.usdm_rope_cache_fp8.restype = C.c_int
 lib.usdm_gemv_mxfp4.restype = C.c_int        # (the MXFP4 entry points: likewise)
 lib.usdm_dequant_mxfp4.restype = C.c_int
+lib.usdm_gemv_packed.restype = C.c_int       # (the 13-bit weight image: likewise)
+lib.usdm_gemv_packs.restype = C.c_int
 lib.usdm_logprobs.restype = C.c_int          # (the log-probability entry points: likewise)
 lib.usdm_logprobs_seg.restype = C.c_int
 lib.usdm_prompt_logprobs.restype = C.c_int   # (the scoring entry points: likewise)

@@ -9,7 +9,8 @@
 //       gemv_rmsnorm8      gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain, engine (gemv_mfma_kernel keeps the text)
 //       gemv_glu_row       gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain
 //       gemv_swiglu_value  gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain, engine
-//       gemv_plain_value   gemv_kernel, gemv_stream_kernel, chain, engine (gemv_batch_kernel keeps the text)
+//       gemv_plain_value   gemv_kernel, gemv_stream_kernel, gemv_stream_wpack_kernel, chain, engine (gemv_batch_kernel keeps the text)
+//       gemv_wpack8        gemv_stream_wpack_kernel (the rebuild of eight bf16 weights from the 13-bit image)
 // The structural pieces of the bf16 batch-1 kernels (hand-counted loads, the RMSNorm reduction): gemv_pieces.h.
 // The launch selection and the argument checks of the launchers: gemv_launch.h.
 // A new weight format plugs in here: DESIGN.md section 8f.
@@ -53,6 +54,26 @@ __device__ __forceinline__ gemv_mx4 gemv_mx4_fmt(gemv_mx4 m) { return m; }
 constexpr int gemv_ring_depth(int NR, bool FP8, bool MX4) {
   const int bf16_depth = NR >= 8 ? 2 : NR >= 4 ? 4 : NR == 3 ? 5 : NR == 2 ? 8 : USDM_UNR1;
   return MX4 ? (NR >= 3 ? 2 : 4) : FP8 ? 2 * bf16_depth : bf16_depth;
+}
+
+// ---- the lossless 13-bit image of a bf16 matrix (usdm_gemv_wpack in usdm_hip.h; packer: usdm_amd/wpack.py).  A weight is its
+// low byte, a 4-bit index of its upper seven exponent bits above `base`, and its sign.  A row is cut into units of 2048 elements
+// = four K iterations; a unit is 3328 bytes: two planes of low bytes (lane L: 16 bytes = its pieces of iterations 0, 1 / 2, 3),
+// one of nibbles (lane L: one dword per iteration; byte k = element k in bits 3:0, element k + 4 in bits 7:4) and one of sign
+// dwords (lane L: the sign of element k of half j = 2 * iteration + (k >= 4) at bit 8 * (k & 3) + 7 - j).
+constexpr unsigned GEMV_WPACK_UNIT = 3328;
+// The eight bf16 weights of K iteration P (0..3) of a unit, as the bf16 kernels load them: lo0 / lo1 the low bytes of elements
+// 0..3 / 4..7, nib the iteration's nibbles, sgn the unit's signs, base4 = base in every byte
+template <int P>
+__device__ __forceinline__ u32x4 gemv_wpack8(unsigned lo0, unsigned lo1, unsigned nib, unsigned sgn, unsigned base4) {
+  const unsigned h0 = ((nib & 0x0f0f0f0fu) + base4) | ((sgn << (2 * P)) & 0x80808080u);          // high bytes of elements 0..3
+  const unsigned h1 = (((nib >> 4) & 0x0f0f0f0fu) + base4) | ((sgn << (2 * P + 1)) & 0x80808080u);   // ... of 4..7
+  u32x4 w;
+  w[0] = __builtin_amdgcn_perm(h0, lo0, 0x05010400u);   // (selector bytes 0..3: the low bytes, 4..7: the high bytes)
+  w[1] = __builtin_amdgcn_perm(h0, lo0, 0x07030602u);
+  w[2] = __builtin_amdgcn_perm(h1, lo1, 0x05010400u);
+  w[3] = __builtin_amdgcn_perm(h1, lo1, 0x07030602u);
+  return w;
 }
 
 // ---- per-item arithmetic that every kernel above must share bit for bit (a batched step = independent steps)

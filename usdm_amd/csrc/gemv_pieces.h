@@ -2,6 +2,7 @@
 //   * gemv_load16, gemv_early_loads: the hand-counted early loads of x and the RMSNorm weights
 //       gemv_kernel and gemv_resident_kernel (x + two weight pieces); gemv_stream_kernel (gemv_load16 twice: two pieces of x);
 //   * gemv_ring_load: the hand-counted ring load of the straight-line K loops - gemv_resident_kernel, gemv_stream_kernel;
+//   * gemv_unit_load: the hand-counted ring load of a unit of the 13-bit weight image - gemv_stream_wpack_kernel;
 //   * gemv_rms_rstd: the RMSNorm statistic over the waves of a workgroup - gemv_kernel, gemv_resident_kernel, the chain's stage_x.
 // None of them puts a run-time branch around a load that is issued before a counted wait: the wait-count pass drains the ring at
 // control-flow joins around loads (gemv_kernel's comments).
@@ -33,6 +34,17 @@ template <int IT>
 __device__ __forceinline__ void gemv_ring_load(u32x4& dst, const char* row, unsigned voff) {
   const unsigned vo = voff + (IT >> 2) * 4096u;
   asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(dst) : "v"(vo), "s"(row), "n"((IT & 3) * 1024) : "memory");
+}
+// Ring load of unit U (2048 elements = four K iterations) of a row of the 13-bit image (gemv_common.h): the lane's 16 bytes of each
+// of the two low-byte planes and of the nibble plane and its sign dword - four loads, in this order.  voff = lane * 16.
+struct gemv_wunit { u32x4 la, lb, nib; unsigned sgn; };
+template <int U>
+__device__ __forceinline__ void gemv_unit_load(gemv_wunit& d, const char* row, unsigned voff) {
+  const unsigned vo = voff + U * GEMV_WPACK_UNIT, vs = (voff >> 2) + U * GEMV_WPACK_UNIT;
+  asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(d.la) : "v"(vo), "s"(row) : "memory");
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:1024 nt" : "=v"(d.lb) : "v"(vo), "s"(row) : "memory");
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048 nt" : "=v"(d.nib) : "v"(vo), "s"(row) : "memory");
+  asm volatile("global_load_dword %0, %1, %2 offset:3072 nt" : "=v"(d.sgn) : "v"(vs), "s"(row) : "memory");
 }
 
 // ---- RMSNorm statistic of a workgroup of NWV waves: the threads' sums of squares over K elements reduced per wave, then over the

@@ -21,6 +21,12 @@
 #ifndef USDM_GEMV_DOWN_UNR
 #define USDM_GEMV_DOWN_UNR 8   // ring depth of gemv_stream_kernel (12 for A/B builds: 48 of its 128 VGPRs)
 #endif
+#ifndef USDM_GEMV_WPACK_RU
+#define USDM_GEMV_WPACK_RU 3   // units in flight per lane in gemv_stream_wpack_kernel (156 bytes; 2 and 4 for A/B builds)
+#endif
+#ifndef USDM_GEMV_WPACK_UB
+#define USDM_GEMV_WPACK_UB 12  // ring depth of its marked (bf16) rows
+#endif
 namespace {
 // ---------------------------------------------------------------------------------------------
 // GEMV: y = W x, W bf16 [N][ldw] row-major (the nn.Linear layout).
@@ -705,6 +711,107 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
   if (a.y32) a.y32[ob] = v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// gemv_stream_kernel over the lossless 13-bit image of the weights (usdm_gemv_wpack; gemv_common.h): the same grid, waves, rows,
+// prologue and epilogue, 13/16 of the bytes.  The ring holds RU units (a unit = four K iterations = four loads, 52 bytes per lane)
+// instead of 16-byte slots; a unit is consumed behind a wait that names the 4 * (RU - 1) younger loads, rebuilt piece by piece
+// into the bf16 pairs the bf16 kernel loads (gemv_wpack8) and refilled at once.  acc sees the same values in the same order:
+// identical bits.
+// A row the packer marked (a weight outside the 16-exponent window) streams from the bf16 matrix: a wave-uniform branch on the
+// row's flag, taken before any ring load is issued, into gemv_stream_kernel's text with a ring of UB slots.  (The text is
+// repeated here, not shared: gemv_stream_kernel's device code stays what it is.)  UB is deeper than that kernel's ring because
+// the marked row is 16/13 as long as its neighbours' and ends the launch if it falls behind them.  The two paths meet at wave_sum;
+// each has its own counted wait, skip return, x staging and barrier, so no branch sits around a load that a counted wait covers.
+// (The compiler merges the paths' returns and the epilogue into blocks entered under constant flags: tools/check_mfma_asm.py
+// audit_paths follows them.)
+// ---------------------------------------------------------------------------------------------
+template <int NIT, int RU, int UB>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void gemv_stream_wpack_kernel(const usdm_gemv_args a,
+                                                                                                        const usdm_gemv_wpack p) {
+  constexpr int NWV = 16, NTH = NWV * 64, K = NIT * 512, NU = NIT / 4;
+  static_assert(NIT % 4 == 0 && NU >= RU && RU >= 1 && NIT >= UB && UB >= 1 && K <= 2 * NTH * 8, "whole units; a full first ring");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* xs = (bf16_t*)smem;  // [K] bf16
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int skipv = a.skip ? *a.skip : 0;   // requested now, tested once the first ring is in flight
+  const int ob = blockIdx.x * NWV + wave;
+  const int urow = min((int)blockIdx.x * NWV + __builtin_amdgcn_readfirstlane(wave), a.N - 1);   // wave-uniform
+  // Is the row marked?  Read from the kernel arguments (a scalar load like every other argument), not from rowflag: the first
+  // memory access of a launch is its longest, and this test stands in front of the first weight load.
+  const bool marked = (p.marked[urow >> 5] >> (urow & 31)) & 1u;
+  const unsigned voff = lane * 16;
+  const bf16_t* rbase = a.residual ? (const bf16_t*)a.residual : (const bf16_t*)a.W;
+  const unsigned short resraw = rbase[min(ob, a.N - 1)];
+  const int i0 = tid * 8, i1 = i0 + NTH * 8;
+  const bf16_t* xp0 = (const bf16_t*)a.x + min(i0, K - 8);
+  const bf16_t* xp1 = (const bf16_t*)a.x + min(i1, K - 8);
+  float acc = 0.f;
+  // (both pieces of x are requested inside the paths: requested in front of the branch, the two counted waits that name them made
+  // the compiler copy their registers while the loads were in flight)
+  if (marked) {
+    // ---- a marked row: gemv_stream_kernel<NIT, UB>'s text
+    const char* wp = (const char*)((const bf16_t*)a.W + (int64_t)urow * a.ldw);
+    u32x4 x0, x1;
+    gemv_load16(x0, xp0);
+    gemv_load16(x1, xp1);
+    u32x4 ring[UB];
+    gemv_for<UB>([&](auto U) { gemv_ring_load<U.value>(ring[U.value], wp, voff); });
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(x0), "+v"(x1), "+s"(skipv) : "n"(UB));
+    if (skipv) return;
+    if (i0 < K) *(u32x4*)(xs + i0) = x0;
+    if (i1 < K) *(u32x4*)(xs + i1) = x1;
+    __syncthreads();
+    u32x4 xv = *(const u32x4*)(xs + lane * 8);
+    gemv_for<NIT>([&](auto IT) {
+      constexpr int it = decltype(IT)::value, u = it % UB;
+      constexpr int younger = it + UB < NIT ? UB - 1 : NIT - 1 - it;
+      const u32x4 xn = *(const u32x4*)(xs + (((it + 1) % NIT) * 64 + lane) * 8);
+      asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ring[u]) : "n"(younger) : "memory");
+      acc = dot8(ring[u], xv, acc);
+      if constexpr (it + UB < NIT) gemv_ring_load<it + UB>(ring[u], wp, voff);
+      xv = xn;
+    });
+  } else {
+    // ---- the packed row: RU units in flight
+    const char* pp = (const char*)p.planes + (int64_t)urow * p.stride;
+    const unsigned base4 = (unsigned)p.base * 0x01010101u;
+    u32x4 x0, x1;
+    gemv_load16(x0, xp0);
+    gemv_load16(x1, xp1);
+    gemv_wunit ring[RU];
+    gemv_for<RU>([&](auto U) { gemv_unit_load<U.value>(ring[U.value], pp, voff); });
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(x0), "+v"(x1), "+s"(skipv) : "n"(4 * RU));
+    if (skipv) return;
+    if (i0 < K) *(u32x4*)(xs + i0) = x0;
+    if (i1 < K) *(u32x4*)(xs + i1) = x1;
+    __syncthreads();
+    // the consumed unit's four loads are the oldest of the 4 * RU in flight; in the last RU units nothing is refilled and the
+    // count falls by four per consume.  x is read from LDS one iteration ahead, as in the bf16 loop.
+    u32x4 xv = *(const u32x4*)(xs + lane * 8);
+    gemv_for<NU>([&](auto UI) {
+      constexpr int un = decltype(UI)::value, s = un % RU;
+      constexpr int younger = un + RU < NU ? 4 * (RU - 1) : 4 * (NU - 1 - un);
+      gemv_wunit& r = ring[s];
+      asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r.la), "+v"(r.lb), "+v"(r.nib), "+v"(r.sgn) : "n"(younger) : "memory");
+      gemv_for<4>([&](auto PI) {
+        constexpr int P = decltype(PI)::value, it = 4 * un + P;
+        const u32x4 xn = *(const u32x4*)(xs + (((it + 1) % NIT) * 64 + lane) * 8);
+        const u32x4& lo = P < 2 ? r.la : r.lb;
+        acc = dot8(gemv_wpack8<P>(lo[2 * (P & 1)], lo[2 * (P & 1) + 1], r.nib[P], r.sgn, base4), xv, acc);
+        xv = xn;
+      });
+      if constexpr (un + RU < NU) gemv_unit_load<un + RU>(r, pp, voff);
+    });
+  }
+  acc = wave_sum(acc);
+
+  // ---- epilogue (gemv_kernel's plain form)
+  if (lane != 0 || ob >= a.N) return;
+  const float v = gemv_plain_value(acc, a.round_bf16, a.residual != nullptr, [&] { return bf2f(resraw); });
+  if (a.y16) ((bf16_t*)a.y16)[ob] = f2bf(v);
+  if (a.y32) a.y32[ob] = v;
+}
+
 // final arg-max over the per-block partials; advances the device-side decode state
 // (nseg segments of nparts partials per sequence, seg_stride apart: the tensor-parallel batched step gathers [rank][sequence][nparts])
 __global__ void argmax_final_kernel(const float* pv, const int* pi, int nparts, int nseg, int64_t seg_stride, usdm_decode_state st,
@@ -857,6 +964,28 @@ extern "C" int usdm_gemv(const usdm_gemv_args* pa, usdm_stream_t stream) {
   }
   return gemv_launch<GEMV_PLAIN, false, false, false, false>(a, st);
 }
+
+// 1 where usdm_gemv_packed streams the 13-bit image: where gemv_select names the straight-line form (a plain bf16 call, K = 14336)
+extern "C" int usdm_gemv_packs(const usdm_gemv_args* pa) { return gemv_select(*pa, false).stream ? 1 : 0; }
+
+extern "C" int usdm_gemv_packed(const usdm_gemv_args* pa, const usdm_gemv_wpack* pk, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->W && pa->x && pk && pk->planes && pk->rowflag, "usdm_gemv_packed: null args");
+  USDM_CHECK_ARG(pa->N <= 14336, "usdm_gemv_packed: at most 14336 rows (usdm_gemv_wpack.marked)");
+  if (!usdm_gemv_packs(pa)) return usdm_gemv(pa, stream);   // no packed form of this call: the bf16 kernels, the same bits
+  const usdm_gemv_args& a = *pa;
+  if (int rc = gemv_check_shape("usdm_gemv_packed", a, "input vector")) return rc;
+  if (int rc = gemv_check_outputs("usdm_gemv_packed", a)) return rc;
+  USDM_CHECK_ARG(pk->units == 7 && pk->units * 2048 == a.K && pk->stride % 16 == 0 && pk->stride >= (int64_t)pk->units * GEMV_WPACK_UNIT &&
+                     pk->base >= 0 && pk->base <= 112,
+                 "usdm_gemv_packed: the image must hold K / 2048 units of 3328 bytes per row, stride a multiple of 16, base 0..112");
+  USDM_CHECK_ARG(((uintptr_t)pk->planes & 15) == 0 && ((uintptr_t)pk->rowflag & 3) == 0, "usdm_gemv_packed: planes must be 16-byte, rowflag 4-byte aligned");
+  const gemv_sel s = gemv_select(a, false);
+  hipLaunchKernelGGL((gemv_stream_wpack_kernel<28, USDM_GEMV_WPACK_RU, USDM_GEMV_WPACK_UB>), dim3(s.grid), dim3(1024), (size_t)a.K * 2,
+                     (hipStream_t)stream, a, *pk);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int usdm_sizeof_gemv_wpack(void) { return (int)sizeof(usdm_gemv_wpack); }
 
 int usdm_gemv_fp8_batch_launch(const usdm_gemv_fp8_args* pa, hipStream_t st);   // llm_batch_k.hip: nb = 2..4
 

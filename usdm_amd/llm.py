@@ -32,6 +32,7 @@ then reuses its prefix on the single sequence too, reading the reused rows as th
 """
 import math
 import os
+import time
 from collections import namedtuple
 
 import torch
@@ -42,6 +43,7 @@ from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
 from .prefix import reusable_past
 from .quant import Fp8Weight, Mxfp4Weight, check_kv_cache_dtype
+from .wpack import PackedWeight
 from .slots import (CHUNK, NO_CANDIDATE_IDX, BeamSlots, DecodeSlots, SpecSequence, SpecSlots, TokenLogprobs, edit_buffers, logprob_buffers,
                     penalty_buffers, read_logprobs, seed_edits, seed_penalties, stop_block, stop_index)
 
@@ -250,8 +252,13 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
                  p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None, score_rows=256,
-                 enable_prefix_caching=False):
+                 enable_prefix_caching=False, weight_packing=None):
         check_quantization(quantization, fp8_matrix_cores)
+        # weight_packing (default on; USDM_WPACK=0 or False turns it off for A/B runs): the single-sequence decode step streams
+        # down_proj from a lossless 13-bit image of its bf16 weights (usdm_amd/wpack.py; identical bits, 13/16 of the bytes).  One GPU,
+        # plain bf16 weights and the 7B's down_proj shape only; the image is built at load, beside the bf16 matrix.
+        self.weight_packing = (os.environ.get("USDM_WPACK", "1") != "0") if weight_packing is None else bool(weight_packing)
+        self.wpack_report = None
         # enable_prefix_caching (vLLM's name; opt-in): batch slots reuse cached prompt rows (usdm_amd/prefix.py), and an
         # fp8-cache model reuses its prefix on the single sequence too.  Off: no index, no buffer and no plan of it is built.
         self.prefix_caching = bool(enable_prefix_caching)
@@ -482,8 +489,25 @@ class USDMForCausalLM:
         d = self.cfg["head_dim"]
         return 2 * self.cfg["num_hidden_layers"] * self.Hkv * ((d + 1) if self.kv8 else 2 * d)
 
+    def _pack_weights(self):
+        """The 13-bit images of the layers' down_proj matrices (weight_packing; the conditions: one GPU, plain bf16 weights, the
+        7B's shape N 4096 / K 14336 - where usdm_gemv has the straight-line form).  Each image verifies its own round trip
+        (wpack.PackedWeight.from_matrix raises otherwise).  wpack_report: per matrix the share of marked rows, the extra device
+        memory and the time the packing took."""
+        self.wpack_down = None
+        if not (self.weight_packing and self.tp_size == 1 and not self.tp_path and self.p2p is None and self.quantization is None
+                and self.cfg["hidden_size"] == 4096 and self.I == 14336):
+            return
+        t0 = time.perf_counter()
+        self.wpack_down = [PackedWeight.from_matrix(w["down"]) for w in self.W["layers"]]
+        torch.cuda.synchronize(self.device)
+        self.wpack_report = {"down_marked_share": [p.marked_share for p in self.wpack_down],
+                             "down_marked_rows": sum(len(p.marked_rows) for p in self.wpack_down),
+                             "extra_bytes": sum(p.nbytes for p in self.wpack_down), "seconds": time.perf_counter() - t0}
+
     # ------------------------------------------------------------------ buffers
     def _alloc(self):
+        self._pack_weights()
         c, dev = self.cfg, self.device
         L, d = c["num_hidden_layers"], c["head_dim"]
         bf = torch.bfloat16
@@ -733,7 +757,7 @@ class USDMForCausalLM:
         H, d = c["hidden_size"], c["head_dim"]
         return H, d, c["num_hidden_layers"], self.Hq, self.Hkv, self.I, (self.Hq + 2 * self.Hkv) * d
 
-    def _layers(self, rec, gemv, attn, h, qkv, ao, act, way, n=0, parts=None, h_alt=None, down_kw={}):
+    def _layers(self, rec, gemv, attn, h, qkv, ao, act, way, n=0, parts=None, h_alt=None, down_kw={}, down_wp=None):
         """The Mistral layers of every plan: this loop is the one statement of a layer's launch order.
         gemv(W, x, N=, K=, ...): the plan's projection launcher, in usdm_gemv's keywords (norm_w / eps: RMSNorm of x fused in front).
         attn(l): rope, cache and attention of layer l from qkv into ao; returns the keywords its hand-off adds to the o_proj launch.
@@ -782,7 +806,7 @@ class USDMForCausalLM:
             o_kw = attn(l) or {}
             land(w["o"], ao, Hq * d, 2 * l, **o_kw)
             proj(w["gu"], w["ln2"], 2 * I, act, ACT_SWIGLU)
-            land(w["down"], act, I, 2 * l + 1, **down_kw)
+            land(w["down"], act, I, 2 * l + 1, **down_kw, **({"wpack": down_wp[l]} if down_wp else {}))
         return h, pend
 
     def _prefill_rows(self, S, slot=None, past=0):
@@ -953,7 +977,9 @@ class USDMForCausalLM:
                 return None
             return dict(merge=mrg, cmb=(gran, self.cmb_err) if use_cmb else None)
 
-        h, pend = self._layers(rec, gemv, attn, h, qkv, ao, act, way, n=H, parts=parts, h_alt=h_alt)
+        # (down_wp: the 13-bit images of the down_proj matrices - this step only; a chained step keeps its bf16 phases)
+        h, pend = self._layers(rec, gemv, attn, h, qkv, ao, act, way, n=H, parts=parts, h_alt=h_alt,
+                               down_wp=self.wpack_down if way == "fused" else None)
         if chain:     # the last layer's chain has no next qkv to wait for
             flush()
         # (pend: the last down-projection's sum goes into the final norm + lm_head)

@@ -11,6 +11,10 @@ from . import _lib
 from ._lib import (BF16, F32, AttnVerifyArgs, AttnVerifyBatchArgs, SpecArgs, SpecBatchArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
+from .wpack import GemvWpack
+
+if lib.usdm_sizeof_gemv_wpack() != C_.sizeof(GemvWpack):
+    raise ImportError(f"ABI mismatch: usdm_gemv_wpack is {lib.usdm_sizeof_gemv_wpack()} bytes in the library, {C_.sizeof(GemvWpack)} in Python")
 
 
 def _stream():
@@ -249,13 +253,15 @@ def _fill_gemv(a, W, x, *, N, K, ldw=None, norm_w=None, eps=1e-5, act=0, round_b
 
 
 def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p_mode=0, merge=None, cmb=None, plan=None,
-         only_args=False, resident=None, **common):
+         only_args=False, resident=None, wpack=None, **common):
     """usdm_gemv: batch-1 weight-streaming GEMV (see include/usdm_hip.h; **common: the keywords of _fill_gemv).
     p2p: a usdm_amd.p2p.P2PComm (fused all-reduce).
     resident: usdm_gemv_args.resident (SwiGLU: 0 the launcher's choice, -1 one tile per workgroup, n > 0 resident on at most n
     workgroups; a plain K = 14336 projection: 0 the launcher's choice, -1 gemv_kernel, n > 0 the straight-line form at any N);
     None: USDM_GEMV_RESIDENT, else 0.
     only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
+    wpack: a wpack.PackedWeight of W (bf16 W only): usdm_gemv_packed, which streams the 13-bit image where usdm_gemv_packs says
+    the call has a packed form (down_proj's straight-line form) and is usdm_gemv everywhere else - identical bits either way.
     W a quant.Fp8Weight / quant.Mxfp4Weight: usdm_gemv_fp8 / usdm_gemv_mxfp4 (the plain single-GPU forms only; the library refuses
     the others)."""
     _need_cuda(x_delta, x_out, skip)
@@ -293,6 +299,16 @@ def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p
         f = GemvMxfp4Args()
         f.b.g, f.b.nb, f.scales, f.lds = a, 1, _ptr(W.s), W.s.shape[1]
         _go(plan, "usdm_gemv_mxfp4", lib.usdm_gemv_mxfp4, C_.byref(f))
+        return
+    if wpack is not None and not only_args and lib.usdm_gemv_packs(C_.byref(a)):
+        # the 13-bit image of W (usdm_amd.wpack): the same result from 13/16 of the bytes.  Recorded as usdm_gemv with the
+        # usdm_gemv_args first: a plan's GEMV launches are counted and grouped by that name and struct.
+        if not wpack.is_cuda or (wpack.N, wpack.K) != (a.N, a.K):
+            raise ValueError("usdm_gemv: wpack is the image of another matrix")
+        p = wpack.args()
+        if plan is not None:
+            plan.hold(wpack.planes, wpack.rowflag)
+        _go(plan, "usdm_gemv", lib.usdm_gemv_packed, C_.byref(a), C_.byref(p))
         return
     if only_args:
         return a
