@@ -389,6 +389,31 @@ int usdm_dequant_mxfp4(const void* codes, int64_t ldw, const uint8_t* scales, in
                        int64_t ldo, usdm_stream_t stream);
 int usdm_sizeof_gemv_mxfp4_args(void);
 
+/* The matrix-core form with MXFP4 weights (opt-in, 1..16 sequences).  It reads a SECOND image of the matrix, cut for waves that own
+ * contiguous K chunks of 32 (quant.Mxfp4Weight.with_matrix_core_image is the one packer): a row is K / 2 code bytes; for every quad Q
+ * of four consecutive chunks (128 elements, 64 bytes) 16-byte piece g (0..3) holds four dwords, dword j the 8 codes of elements
+ * 128 Q + 32 j + 8 g .. + 7, the earlier element of a byte in bits 3:0.  Lane (row r, g) of a wave so fetches its A fragments of four
+ * chunks with one 16-byte load (16 rows x 64 contiguous bytes per wave instruction), or dword j alone where a wave's share of K is
+ * no whole number of quads.  scales is plain [N][K / 32] e8m0 bytes: the dword at byte 4 Q of a row holds the scales of quad Q.
+ * ldc / lds: the row strides of codes / scales in bytes (ldc >= K / 2, a multiple of 16; lds >= K / 32, a multiple of 4); codes
+ * 16-byte, scales 4-byte aligned.  b.g.W and b.g.ldw are not read.
+ * b.nb 1..16, b.form 0 (K split over workgroups where b.ks_* allow it, as in usdm_gemv_batch) or 5 (no K split).  The codes are
+ * converted exactly to bf16 in registers (one scale per row and chunk) and the bf16 matrix-core arithmetic runs unchanged: the same
+ * tiles, rows per tile, K chunks per wave and their order, wave merge, K split with its slice-order merge and epilogues, so the result
+ * equals usdm_gemv_batch(form = 1, or 5) with the same ks_* arguments on W', bit for bit.  Supported: RMSNorm (K <= 4096), SwiGLU on
+ * packed gate/up rows, residual, plain; y16 only.  Refused (error, no fall-back): nb > 16, any other form, the lm_head mode
+ * (part_val / part_idx / ban / y32), p2p, mrg_* / cmb_gran, x_delta / x_out, misaligned pointers or strides, and every shape the
+ * bf16 matrix-core form refuses (K %% 256, the fused RMSNorm with K > 4096, more than 64 tiles per workgroup). */
+typedef struct usdm_gemv_mxfp4_mfma_args {
+  usdm_gemv_batch_args b;
+  const void* codes;         /* [N][ldc] bytes, the matrix-core image */
+  int64_t ldc;
+  const uint8_t* scales;     /* [N][lds] */
+  int64_t lds;
+} usdm_gemv_mxfp4_mfma_args;
+int usdm_gemv_mxfp4_mfma(const usdm_gemv_mxfp4_mfma_args* args, usdm_stream_t stream);
+int usdm_sizeof_gemv_mxfp4_mfma_args(void);
+
 /* Lossless 13-bit image of a bf16 weight matrix (default on for the 7B's down_proj; usdm_amd/wpack.py is the one packer).  The
  * exponent field of a weight matrix is almost constant, so a weight b (its 16 bits) is stored as its low byte b & 0xff, the 4-bit
  * index ((b >> 8) & 0x7f) - base of its upper seven exponent bits, and its sign: 13 bits, rebuilt exactly in registers.  base is

@@ -26,6 +26,7 @@ lib.usdm_attn_decode_fp8.restype = C.c_int   # (the FP8 KV cache entry points: l
 lib.usdm_rope_cache_fp8.restype = C.c_int
 lib.usdm_gemv_mxfp4.restype = C.c_int        # (the MXFP4 entry points: likewise)
 lib.usdm_dequant_mxfp4.restype = C.c_int
+lib.usdm_gemv_mxfp4_mfma.restype = C.c_int   # (the MXFP4 matrix-core form: likewise)
 lib.usdm_gemv_packed.restype = C.c_int       # (the 13-bit weight image: likewise)
 lib.usdm_gemv_packs.restype = C.c_int
 lib.usdm_logprobs.restype = C.c_int          # (the log-probability entry points: likewise)
@@ -179,6 +180,10 @@ class GemvFp8Args(C.Structure):
 
 class GemvMxfp4Args(C.Structure):
     _fields_ = [("b", GemvBatchArgs), ("scales", C.c_void_p), ("lds", C.c_int64)]
+
+
+class GemvMxfp4MfmaArgs(C.Structure):
+    _fields_ = [("b", GemvBatchArgs), ("codes", C.c_void_p), ("ldc", C.c_int64), ("scales", C.c_void_p), ("lds", C.c_int64)]
 
 
 class DecodeState(C.Structure):
@@ -340,6 +345,7 @@ def _selfcheck():
                       ("vb_solver", VbSolverArgs), ("gemv", GemvArgs), ("decode_state", DecodeState),
                       ("rope", RopeArgs), ("attn_decode", AttnDecodeArgs), ("sample", SampleArgs),
                       ("gemv_batch", GemvBatchArgs), ("gemv_fp8", GemvFp8Args), ("gemv_mxfp4", GemvMxfp4Args), ("p2p_dev", P2pDev),
+                      ("gemv_mxfp4_mfma", GemvMxfp4MfmaArgs),
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
                       ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs), ("beam", BeamArgs),
                       ("kv_reorder", KvReorderArgs), ("kv_expand", KvExpandArgs), ("attn_verify", AttnVerifyArgs), ("spec", SpecArgs),

@@ -26,6 +26,10 @@
 // FP8 weights (usdm_gemv_fp8_mfma, opt-in): the same kernel with an FP8 template flag - e4m3 bytes with a power-of-two scale per row,
 // converted exactly to bf16 in registers right before each MFMA; everything else is the bf16 form, so the result equals it on the
 // dequantized weights W' bit for bit.
+//
+// MXFP4 weights (usdm_gemv_mxfp4_mfma, opt-in): the same kernel again, selected by the type of its extra argument - a second image
+// of the codes, cut so that one 16-byte load is a lane's A fragments of four consecutive chunks, and one e8m0 scale per row and chunk;
+// converted exactly to bf16 right before each MFMA, equal to the bf16 form on W' bit for bit.
 #include "common.h"
 #include "../../include/usdm_hip.h"
 #include "gemv_common.h"
@@ -61,6 +65,16 @@ struct MfmaDev {
 constexpr int KS_K = 2048;  // K per workgroup of the split form: 8 waves x 8 chunks, one 8-load unit per tile and wave
 constexpr int KS_MAX = 8;   // slices (K <= 16384)
 
+// MXFP4 (usdm_gemv_mxfp4_mfma): the matrix-core image of the matrix (include/usdm_hip.h) is the one extra kernel argument of the
+// MX4 instantiations, which its TYPE selects: FP8 stays a bool and every bf16 / FP8 instantiation keeps its name.
+struct gemv_mx4mc { const uint8_t* codes; const uint8_t* scales; int64_t ldc, lds; };
+template <class... FMT> struct gemv_is_mx4mc { static constexpr bool value = false; };
+template <> struct gemv_is_mx4mc<gemv_mx4mc> { static constexpr bool value = true; };
+__device__ __forceinline__ const int8_t* gemv_row_exp(gemv_mx4mc) { return nullptr; }
+__device__ __forceinline__ gemv_mx4mc gemv_mx4mc_fmt() { return gemv_mx4mc{nullptr, nullptr, 0, 0}; }
+__device__ __forceinline__ gemv_mx4mc gemv_mx4mc_fmt(const int8_t*) { return gemv_mx4mc{nullptr, nullptr, 0, 0}; }
+__device__ __forceinline__ gemv_mx4mc gemv_mx4mc_fmt(gemv_mx4mc m) { return m; }
+
 __device__ __forceinline__ f32x4 mfma16(u32x4 w, u32x4 x, f32x4 acc) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
 }
@@ -83,6 +97,8 @@ __device__ __forceinline__ void ld_exp_asm(int& dst, const int8_t* p) {
 }
 template <int... I, class F>
 __device__ __forceinline__ void each_slot(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int... I, class F>      // f(slot) for the slots in order until one returns false
+__device__ __forceinline__ bool all_slots(std::integer_sequence<int, I...>, F&& f) { return (f(std::integral_constant<int, I>{}) && ...); }
 template <int WAIT, bool FIRST, class V>
 __device__ __forceinline__ void wait_mfma_asm(f32x4& acc, const V& w, const u32x4& x) {
   if constexpr (FIRST)
@@ -103,8 +119,11 @@ __device__ __forceinline__ void wait_mfma_asm(f32x4& acc, const V& w, const u32x
 // (fp8x8_to_bf16x8) hands the MFMA the bf16 fragments of W' = q * 2^e, so the result equals the bf16 form on W' bit for bit.
 template <bool HOLD, int CPWT, bool TRL, bool FP8 = false, class... FMT>
 __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT... fmt) {
-  static_assert(FP8 == (sizeof...(FMT) == 1), "FP8 takes the row exponents");
+  constexpr bool MX4 = gemv_is_mx4mc<FMT...>::value;
+  static_assert((FP8 || MX4) == (sizeof...(FMT) == 1) && !(FP8 && MX4), "FP8 takes the row exponents, MXFP4 its matrix-core image");
   static_assert(!FP8 || TRL || CPWT == 0, "FP8: the row-contiguous forms and the generic ones (the fragment-shaped form 3 is bf16 only)");
+  static_assert(!MX4 || (!TRL && (HOLD ? CPWT == 0 || CPWT == 8 || CPWT == 16 : CPWT == 0)), "MXFP4: the image is cut into fragments already");
+  constexpr bool KSPLIT = (TRL || MX4) && HOLD && CPWT == 8;     // the forms of the K split over workgroups
   const usdm_gemv_args& a = d.ba.g;
   const int cpw = CPWT > 0 ? CPWT : d.cpw;
   constexpr int MTG = TRL ? MTG_TRL : MTG_DEF;             // tiles per reduction group
@@ -253,13 +272,13 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
     }
     return (const u32x4*)(Wb + (int64_t)row * a.ldw + kofs + (int64_t)wave * (cpw * 32) + sub * 256 + lp * 8);
   };
-  int t0 = TRL ? -1 : next_tile(rem_ld), t1 = -1, t2 = -1;  // tile being multiplied, the next two (loads in flight / to be issued)
+  int t0 = (TRL || MX4) ? -1 : next_tile(rem_ld), t1 = -1, t2 = -1;  // tile being multiplied, the next two (loads in flight / to be issued)
   const wvec* wp0 = wbase(t0);
   const wvec* wp1 = wp0;
   const wvec* wp2 = wp0;
   float sc0 = 0.f, sc1 = 0.f, sc2 = 0.f;                    // FP8, generic forms: the scales of t0, t1, t2 for this lane's row
   if constexpr (FP8 && !TRL) sc0 = wscale(t0);
-  constexpr bool ASM_STREAM = HOLD && CPWT == CH && !USDM_MFMA_NO_ASM && !TRL;     // hand-counted loads (see the stream loop)
+  constexpr bool ASM_STREAM = HOLD && CPWT == CH && !USDM_MFMA_NO_ASM && !TRL && !MX4;     // hand-counted loads (see the stream loop)
   int ua = -1, ub = -1, uc = -1;                            // TRL: the tile being multiplied and the next two
   // TRL with streamed activations (K = 14336): units are numbered through the tiles, 7 per tile; (lt, ls) = the next unit to load
   int lt = -1, ls = 0;
@@ -297,13 +316,13 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   }
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
-    if (c < cpw && !TRL) {
+    if (c < cpw && !TRL && !MX4) {
       if constexpr (ASM_STREAM) ld_nt_asm(ring[c], wp0 + c * 4);
       else ring[c] = wload(wp0, c);
       if constexpr (!HOLD) rx[c] = xload(c);
     }
   }
-  if constexpr (HOLD && !TRL) {
+  if constexpr (HOLD && !TRL && !MX4) {
     t1 = next_tile(rem_ld);
     wp1 = wbase(t1);
 #pragma unroll
@@ -356,6 +375,46 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       tq8[decltype(Q)::value] = next_tile(rem_ld);
       ld_unit8(Q, tq8[decltype(Q)::value], 0);
     });
+  }
+
+  // ---- MXFP4 (usdm_gemv_mxfp4_mfma; the stream loop says what the image gives a lane), held activations: a unit = one tile's K slice
+  // of this wave, NQ quads = NQ 16-byte loads + NQ scale dwords, ND tiles in flight (K = 4096: 4 x 4 KiB per wave; K split: all <= 8
+  // tiles of the workgroup, 2 KiB each).  Six tiles of K = 4096 spill next to the 16 held activation fragments.  All loads are the compiler's (counted by its own s_waitcnt).  A unit whose
+  // tile does not exist loads ONE 16-byte piece of row 0 for the whole wave (a single request, a different quad for every wave) and
+  // the scale dword of that quad: inside the image, and every load of the loop stays unconditional.
+  const gemv_mx4mc m = gemv_mx4mc_fmt(fmt...);
+  const int kca = kofs / 32 + kc0;                          // this wave's first chunk in the row
+  const int phq = (int)((blockIdx.x * MW + wave) % (unsigned)(K / 128));      // the placeholder's quad of row 0
+  const bool quads = CPWT > 0 || (cpw & 3) == 0;            // else a quad would straddle two waves: dword loads (see the stream loop)
+  constexpr int NQ = CPWT > 0 ? CPWT / 4 : CH / 4;
+  constexpr int ND = CPWT == 8 ? 8 : 4;
+  using SlotsM = std::make_integer_sequence<int, ND>;
+  const int nq = cpw >> 2;
+  u32x4 cq[MX4 && HOLD ? ND : 1][NQ];
+  unsigned sq[MX4 && HOLD ? ND : 1][NQ];
+  int tm[ND];
+  auto ld_tile = [&](auto SLOT, int t) __attribute__((always_inline)) {
+    constexpr int s = decltype(SLOT)::value;
+    const int row = row_of(t, r16);
+    const uint8_t* cp = t < 0 ? m.codes + phq * 64 : m.codes + (int64_t)row * m.ldc + kca * 16 + g * 16;
+    const uint8_t* sp = t < 0 ? m.scales + phq * 4 : m.scales + (int64_t)row * m.lds + kca;
+    const int cs = t < 0 ? 0 : 64, ss = t < 0 ? 0 : 4;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q < nq) {
+        cq[s][q] = __builtin_nontemporal_load((const u32x4*)(cp + q * cs));
+        sq[s][q] = *(const unsigned*)(sp + q * ss);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);                      // units are issued in the order in which they are multiplied
+  };
+  if constexpr (MX4 && HOLD) {
+    if (quads) {
+      each_slot(SlotsM{}, [&](auto Q) __attribute__((always_inline)) {
+        tm[decltype(Q)::value] = next_tile(rem_ld);
+        ld_tile(Q, tm[decltype(Q)::value]);
+      });
+    }
   }
 
   TRM(1);
@@ -489,6 +548,25 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
     }
     old = __builtin_amdgcn_readfirstlane(old);
     if (old != d.ksplit - 1) return false;
+    if constexpr (MX4) {
+      // MXFP4: the same slices in the same order, read with the compiler's own loads (agent scope: past this XCD's L2, what sc1 asks
+      // for below), so that no MX4 instantiation holds a hand-counted load (tools/check_mfma_asm.py has nothing to audit in them)
+      asm volatile("" ::: "memory");                          // (the loads stay behind the counter's increment)
+      f32x4 p[KS_MAX];
+#pragma unroll
+      for (int k = 0; k < KS_MAX; ++k) {
+        const unsigned long long* q = (const unsigned long long*)(pp + min(k, d.ksplit - 1) * 256);
+        const unsigned long long lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        p[k] = f32x4{__builtin_bit_cast(float, (unsigned)lo), __builtin_bit_cast(float, (unsigned)(lo >> 32)),
+                     __builtin_bit_cast(float, (unsigned)hi), __builtin_bit_cast(float, (unsigned)(hi >> 32))};
+      }
+      s = p[0];
+#pragma unroll
+      for (int k = 1; k < KS_MAX; ++k)
+        if (k < d.ksplit) s += p[k];
+      return true;
+    }
     // all KS_MAX loads and their wait in ONE statement (slices that do not exist re-read the last one): nothing the compiler emits
     // can sit between a load and its wait
     f32x4 p[KS_MAX];
@@ -517,7 +595,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       f32x4 s = red[(slot * MW) * 64 + lane];
 #pragma unroll
       for (int w = 1; w < MW; ++w) s += red[(slot * MW + w) * 64 + lane];
-      if constexpr (TRL && HOLD && CPWT == 8) {
+      if constexpr (KSPLIT) {
         if (d.ksplit > 1 && !ks_merge(tl[slot], s)) continue;
       }
       epilogue(tl[slot], s);
@@ -536,7 +614,126 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   };
 
   // ---- stream
-  if constexpr (FP8 && TRL) {
+  if constexpr (MX4) {
+    // MXFP4 (usdm_gemv_mxfp4_mfma).  Lane (r16, g) owns the same 8 elements of every chunk as in bf16; the image stores them as one
+    // dword, the dwords of the four chunks of a quad side by side, so one 16-byte load fetches the lane's A fragments of a quad (a
+    // wave instruction: 16 rows x 64 contiguous bytes) and one dword load the quad's four scales.  Each fragment is converted with
+    // its own chunk's scale (mx4x8_to_bf16x8, exact) right before its MFMA, and a tile is ONE accumulation chain over the wave's
+    // chunks in ascending order, as in every bf16 variant: the result equals the bf16 form on W' bit for bit.
+    auto mul_quad = [&](f32x4 acc, const u32x4& c, unsigned s, const u32x4& x0, const u32x4& x1, const u32x4& x2, const u32x4& x3)
+                        __attribute__((always_inline)) -> f32x4 {
+      acc = mfma16(mx4x8_to_bf16x8<0>(c[0], s), x0, acc);
+      acc = mfma16(mx4x8_to_bf16x8<1>(c[1], s), x1, acc);
+      acc = mfma16(mx4x8_to_bf16x8<2>(c[2], s), x2, acc);
+      return mfma16(mx4x8_to_bf16x8<3>(c[3], s), x3, acc);
+    };
+    if (!quads) {
+      // a quad would straddle two waves (K = 512: 2 chunks per wave, K = 1792: 7): dword j of the quad's piece and the chunk's scale
+      // byte, one tile's loads at a time (no model shape comes here)
+      int t = next_tile(rem_cp);
+      while (t >= 0) {
+        const int row = row_of(t, r16);
+        const uint8_t* cp = m.codes + (int64_t)row * m.ldc + g * 16;
+        const uint8_t* sp = m.scales + (int64_t)row * m.lds + kca;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int c0 = 0; c0 < cpw; c0 += CH) {
+          unsigned cd[CH], sb[CH];
+          u32x4 xd[HOLD ? 1 : CH];
+#pragma unroll
+          for (int u = 0; u < CH; ++u) {
+            if (c0 + u < cpw) {
+              const int kc = kca + c0 + u;
+              cd[u] = *(const unsigned*)(cp + (kc >> 2) * 64 + (kc & 3) * 4);
+              sb[u] = sp[c0 + u];
+              if constexpr (!HOLD) xd[u] = xload(c0 + u);
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < CH; ++u) {
+            if (c0 + u < cpw) {
+              if constexpr (HOLD) acc = mfma16(mx4x8_to_bf16x8<0>(cd[u], sb[u]), xf[u], acc);      // (held: cpw <= CH, one pass)
+              else acc = mfma16(mx4x8_to_bf16x8<0>(cd[u], sb[u]), xd[u], acc);
+            }
+          }
+        }
+        finish_tile(t, acc);
+        t = next_tile(rem_cp);
+      }
+    } else if constexpr (HOLD) {
+      // held activations: the units of the first ND tiles are in flight since the prologue
+      auto mul_tile = [&](auto SLOT) __attribute__((always_inline)) -> f32x4 {
+        constexpr int s = decltype(SLOT)::value;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+          if (q < nq) acc = mul_quad(acc, cq[s][q], sq[s][q], xf[4 * q], xf[4 * q + 1], xf[4 * q + 2], xf[4 * q + 3]);
+        return acc;
+      };
+      if constexpr (KSPLIT) {
+        // K split over workgroups: at most MTG_TRL tiles per workgroup (host), reduced and merged after the stream, as in bf16
+        auto step = [&](auto SLOT) __attribute__((always_inline)) {
+          constexpr int s = decltype(SLOT)::value;
+          const int t = tm[s];
+          const f32x4 acc = mul_tile(SLOT);
+          tm[s] = next_tile(rem_ld);
+          ld_tile(SLOT, tm[s]);
+          if (t >= 0) {
+            red[(done * MW + wave) * 64 + lane] = acc;
+            if (tid == 0) tl[done] = t;
+            ++done;
+          }
+        };
+        while (tm[0] >= 0) each_slot(SlotsM{}, step);
+      } else {
+        auto step = [&](auto SLOT) __attribute__((always_inline)) -> bool {
+          constexpr int s = decltype(SLOT)::value;
+          const int t = tm[s];
+          if (t < 0) return false;
+          (void)next_tile(rem_cp);                            // (rem_cp = the tiles after this one: finish_tile's "more")
+          const f32x4 acc = mul_tile(SLOT);
+          tm[s] = next_tile(rem_ld);
+          ld_tile(SLOT, tm[s]);
+          finish_tile(t, acc);
+          return true;
+        };
+        while (all_slots(SlotsM{}, step)) {}
+      }
+    } else {
+      // activations streamed beside the weights (form 5 at K = 14336, any K > 4096 that is not split): a unit = one quad, its scale
+      // dword and its four activation fragments; a ring of DS units inside a tile, refilled DS quads ahead
+      constexpr int DS = 6;
+      const int nq = cpw >> 2;
+      u32x4 cq[DS], xq[DS][4];
+      unsigned sq[DS];
+      int t = next_tile(rem_cp);
+      while (t >= 0) {
+        const int row = row_of(t, r16);
+        const u32x4* cp = (const u32x4*)(m.codes + (int64_t)row * m.ldc + kca * 16 + g * 16);
+        const unsigned* sp = (const unsigned*)(m.scales + (int64_t)row * m.lds + kca);
+        auto ld_quad = [&](int u, int q) __attribute__((always_inline)) {
+          cq[u] = __builtin_nontemporal_load(cp + q * 4);
+          sq[u] = sp[q];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) xq[u][j] = xload(4 * q + j);
+        };
+#pragma unroll
+        for (int u = 0; u < DS; ++u)
+          if (u < nq) ld_quad(u, u);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int q0 = 0; q0 < nq; q0 += DS) {
+#pragma unroll
+          for (int u = 0; u < DS; ++u) {
+            if (q0 + u < nq) {
+              acc = mul_quad(acc, cq[u], sq[u], xq[u][0], xq[u][1], xq[u][2], xq[u][3]);
+              if (q0 + u + DS < nq) ld_quad(u, q0 + u + DS);
+            }
+          }
+        }
+        finish_tile(t, acc);
+        t = next_tile(rem_cp);
+      }
+    }
+  } else if constexpr (FP8 && TRL) {
     char* tb = smem + TB_OFF + wave * 8192;                 // this wave's transposition buffer: [16 rows][ROW8 bytes], piece ^ row
     // wait for unit q (the younger units stay in flight), its rows -> LDS; returns the scale of this lane's row
     auto take8 = [&](auto SLOT) __attribute__((always_inline)) -> float {
@@ -840,7 +1037,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
     }
   }
   TRM(4);
-  if (done % MTG || (TRL && HOLD && CPWT == 8 && done)) flush_group(false);
+  if (done % MTG || (KSPLIT && done)) flush_group(false);
 #ifdef USDM_MFMA_TRACE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   TRM(6);
@@ -868,6 +1065,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
     }
   }
 }
+
 }  // namespace
 
 #ifdef USDM_MFMA_TRACE
@@ -882,10 +1080,12 @@ extern "C" int64_t usdm_gemv_batch_ks_floats(int32_t N, int32_t K) {
 }
 
 namespace {
-// the matrix-core launch of usdm_gemv_batch (bf16) and usdm_gemv_fp8_mfma (FP8: fmt = the row exponents); both take the same
-// decisions (tiles, rows per tile, K split, variant) for the same shape
+// the matrix-core launch of usdm_gemv_batch (bf16), usdm_gemv_fp8_mfma (FP8: fmt = the row exponents) and usdm_gemv_mxfp4_mfma
+// (fmt = gemv_mx4mc; a.W / a.ldw stand in for a bf16 matrix of the same shape); all take the same decisions (tiles, rows per tile,
+// K split, K chunks per wave) for the same shape
 template <bool FP8, class... FMT>
 int mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st, const char* who, FMT... fmt) {
+  constexpr bool MX4 = gemv_is_mx4mc<FMT...>::value;
   const usdm_gemv_args& a = pa->g;
   USDM_CHECK_ARG(pa->nb >= 1 && pa->nb <= 16, "%s (matrix-core form): 1..16 sequences per step", who);
   USDM_CHECK_ARG(a.K % (MW * 32) == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && pa->x_bs % 8 == 0,
@@ -935,7 +1135,24 @@ int mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st, const char* who,
   USDM_CHECK_ARG(!lmh || pa->part_bs >= d.grid, "%s: part_bs must hold one partial per workgroup (%d)", who, d.grid);
   // K = 4096 (every RMSNorm-fed projection and o_proj of the 7B): row-contiguous loads re-cut through LDS; form 3 forces the
   // fragment-shaped loads there (A/B: tools/gemv_mfma_bench.py)
-  const bool trl = (hold ? d.cpw == 16 : d.cpw == 56) && pa->form != 3;
+  const bool trl = (hold ? d.cpw == 16 : d.cpw == 56) && pa->form != 3 && !MX4;
+  if constexpr (MX4) {      // the image is cut into fragments already: no re-cut through LDS; K = 4096 and the K split have CPWT forms
+    void (*kfn)(const MfmaDev, FMT...) = d.ksplit > 1 ? gemv_mfma_kernel<true, 8, false, false, FMT...>
+                                         : !hold      ? gemv_mfma_kernel<false, 0, false, false, FMT...>
+                                         : d.cpw == 16 ? gemv_mfma_kernel<true, 16, false, false, FMT...>
+                                                       : gemv_mfma_kernel<true, 0, false, false, FMT...>;
+    static bool mx_attr = false;
+    if (!mx_attr) {
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 8, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 0, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 0, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+      mx_attr = true;
+    }
+    hipLaunchKernelGGL(kfn, dim3(d.grid), dim3(MW * 64), LDS_BYTES, st, d, fmt...);
+    USDM_LAUNCH_CHECK();
+    return 0;
+  } else {
   if (d.ksplit > 1) {
     static bool ks_attr = false;
     if (!ks_attr) { (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 8, true, FP8, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL); ks_attr = true; }
@@ -972,6 +1189,7 @@ int mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st, const char* who,
   hipLaunchKernelGGL(kfn, dim3(d.grid), dim3(MW * 64), trl ? LDS_BYTES_TRL : LDS_BYTES, st, d, fmt...);
   USDM_LAUNCH_CHECK();
   return 0;
+  }
 }
 }  // namespace
 
@@ -992,3 +1210,26 @@ extern "C" int usdm_gemv_fp8_mfma(const usdm_gemv_fp8_args* pa, usdm_stream_t st
   USDM_CHECK_ARG(a.act != USDM_ACT_SWIGLU || a.N % 32 == 0, "usdm_gemv_fp8_mfma: swiglu needs N %% 32 == 0 (packed gate/up rows)");
   return mfma_launch<true>(&b, (hipStream_t)stream, "usdm_gemv_fp8_mfma", pa->row_exp);
 }
+
+extern "C" int usdm_gemv_mxfp4_mfma(const usdm_gemv_mxfp4_mfma_args* pa, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->codes && pa->scales && pa->b.g.x, "usdm_gemv_mxfp4_mfma: null args");
+  usdm_gemv_batch_args b = pa->b;
+  usdm_gemv_args& a = b.g;
+  USDM_CHECK_ARG(b.nb >= 1 && b.nb <= 16, "usdm_gemv_mxfp4_mfma: 1..16 sequences per step");
+  USDM_CHECK_ARG(b.form == 0 || b.form == 5, "usdm_gemv_mxfp4_mfma: form 0 (K split where ks_* allow it) or 5 (no K split)");
+  USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.mrg_pm && !a.mrg_pl && !a.cmb_gran && !a.x_delta && !a.x_out,
+                 "usdm_gemv_mxfp4_mfma: p2p / merged-attention input / cmb_gran / x_delta are not supported");
+  USDM_CHECK_ARG(!a.part_val && !a.part_idx && !a.ban && !a.y32, "usdm_gemv_mxfp4_mfma: the lm_head mode (part_val / ban / y32) is not supported with MXFP4 weights");
+  USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.K % (MW * 32) == 0, "usdm_gemv_mxfp4_mfma: bad N, or K not a multiple of %d", MW * 32);
+  USDM_CHECK_ARG(pa->ldc % 16 == 0 && pa->ldc >= a.K / 2 && pa->lds % 4 == 0 && pa->lds >= a.K / 32,
+                 "usdm_gemv_mxfp4_mfma: ldc (bytes) must be a multiple of 16 and hold K / 2, lds a multiple of 4 and hold K / 32");
+  USDM_CHECK_ARG(((uintptr_t)pa->codes & 15) == 0 && ((uintptr_t)pa->scales & 3) == 0 && ((uintptr_t)a.x & 15) == 0,
+                 "usdm_gemv_mxfp4_mfma: codes and x must be 16-byte, scales 4-byte aligned");
+  USDM_CHECK_ARG(a.y16, "usdm_gemv_mxfp4_mfma: no output (y16)");
+  USDM_CHECK_ARG(a.act != USDM_ACT_SWIGLU || a.N % 32 == 0, "usdm_gemv_mxfp4_mfma: swiglu needs N %% 32 == 0 (packed gate/up rows)");
+  a.W = pa->codes;      // (the kernel reads the image through its own argument; the launcher's shape checks see a [N][K] matrix)
+  a.ldw = a.K;
+  return mfma_launch<false>(&b, (hipStream_t)stream, "usdm_gemv_mxfp4_mfma", gemv_mx4mc{(const uint8_t*)pa->codes, pa->scales, pa->ldc, pa->lds});
+}
+
+extern "C" int usdm_sizeof_gemv_mxfp4_mfma_args(void) { return (int)sizeof(usdm_gemv_mxfp4_mfma_args); }

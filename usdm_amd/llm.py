@@ -19,7 +19,8 @@ matrices (qkv, o, gate/up, down, lm_head) are held as e4m3 with a power-of-two s
 model exactly the bf16 model with the dequantized weights W'; decode streams half the bytes (usdm_gemv_fp8), prefill dequantizes
 each matrix into one bf16 scratch right before its usdm_gemm.  Single GPU only.  quantization="mxfp4" (opt-in): the layers' matrices
 as OCP MXFP4 (e2m1, one power-of-two scale per 32 elements; 4.25 bits per weight, about 11.5 % relative weight error), the lm_head
-fp8; the same contract and the same structure (usdm_gemv_mxfp4, usdm_dequant_mxfp4), at most 4 sequences per decode step.
+fp8; the same contract and the same structure (usdm_gemv_mxfp4, usdm_dequant_mxfp4), at most 4 sequences per decode step
+unless mxfp4_matrix_cores=True (opt-in): a second image of the layers' codes, and steps of 5..16 sequences on usdm_gemv_mxfp4_mfma.
 KV cache: bf16 rows.  kv_cache_dtype="fp8" (opt-in, independent of `quantization`): every cached row (one token, one kv head) is
 held as e4m3 bytes + one power-of-two exponent (quant.quantize_kv_rows), written by usdm_rope_cache_fp8 / usdm_attn_decode_fp8.
 The model is then exactly the bf16-cache model whose decode steps read the round-tripped rows K', V'; a prompt's own prefill
@@ -95,13 +96,15 @@ QUANT_KEYS = ("qkv", "o", "gu", "down")    # the streamed matrices of a layer (q
 QUANTIZATIONS = (None, "fp8", "mxfp4")
 
 
-def check_quantization(quantization, fp8_matrix_cores):
-    """The values of the two weight-format arguments (USDMForCausalLM and serving.LLM take them)."""
+def check_quantization(quantization, fp8_matrix_cores, mxfp4_matrix_cores=False):
+    """The values of the weight-format arguments (USDMForCausalLM and serving.LLM take them)."""
     if quantization not in QUANTIZATIONS:
         raise ValueError(f"quantization={quantization!r}: supported are None (bf16), 'fp8' (e4m3 weights, power-of-two row scales) "
                          "and 'mxfp4' (e2m1 weights, one power-of-two scale per 32 elements; the lm_head stays fp8)")
     if fp8_matrix_cores and quantization != "fp8":
         raise ValueError("fp8_matrix_cores=True needs quantization='fp8'")
+    if mxfp4_matrix_cores and quantization != "mxfp4":
+        raise ValueError("mxfp4_matrix_cores=True needs quantization='mxfp4'")
 
 
 def stop_ids(eos_token_id):
@@ -215,15 +218,16 @@ class _Segments:
         return self.segs
 
 
-def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantization=None):
+def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantization=None, mxfp4_matrix_cores=False):
     """This rank's packed weights for tensor parallelism of degree `tp` (Megatron-style): q/k/v heads and MLP
     columns split by rank, o_proj/down_proj split along K (their outputs are partial sums), vocab rows split.
     quantization="fp8": every streamed matrix becomes a quant.Fp8Weight as soon as its layer is packed (rows quantized after the
     qkv concatenation and the gate/up packing; per-row scales do not depend on the row order), so at most one layer is ever held
     in bf16 next to the FP8 copy.  The embedding stays bf16, the norms f32.
     quantization="mxfp4": likewise with quant.Mxfp4Weight for qkv, o, gate/up and down (blocks of 32 run along K, so the row packing
-    only permutes rows of blocks); the lm_head shard is an Fp8Weight."""
-    qz = {"fp8": Fp8Weight.from_matrix, "mxfp4": Mxfp4Weight.from_matrix}.get(quantization, lambda t: t)
+    only permutes rows of blocks); the lm_head shard is an Fp8Weight.  mxfp4_matrix_cores: every Mxfp4Weight also holds its
+    matrix-core image (usdm_gemv_mxfp4_mfma), packed from the same codes."""
+    qz = {"fp8": Fp8Weight.from_matrix, "mxfp4": lambda t: Mxfp4Weight.from_matrix(t, matrix_cores=mxfp4_matrix_cores)}.get(quantization, lambda t: t)
     qz_head = Fp8Weight.from_matrix if quantization in ("fp8", "mxfp4") else (lambda t: t)
     d = cfg["head_dim"]
     Hq, Hkv, I = cfg["num_attention_heads"] // tp, cfg["num_key_value_heads"] // tp, cfg["intermediate_size"] // tp
@@ -252,8 +256,8 @@ def shard_weights(sd_get, cfg, rank, tp, device, dtype=torch.bfloat16, quantizat
 class USDMForCausalLM:
     def __init__(self, cfg, device, ctx_max=2048, tp_rank=0, tp_size=1, group=None, decode_splits=None, tp_segments=None, p2p=None,
                  p2p_fused=None, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None, score_rows=256,
-                 enable_prefix_caching=False, weight_packing=None):
-        check_quantization(quantization, fp8_matrix_cores)
+                 enable_prefix_caching=False, weight_packing=None, mxfp4_matrix_cores=False):
+        check_quantization(quantization, fp8_matrix_cores, mxfp4_matrix_cores)
         # weight_packing (default on; USDM_WPACK=0 or False turns it off for A/B runs): the single-sequence decode step streams
         # down_proj from a lossless 13-bit image of its bf16 weights (usdm_amd/wpack.py; identical bits, 13/16 of the bytes).  One GPU,
         # plain bf16 weights and the 7B's down_proj shape only; the image is built at load, beside the bf16 matrix.
@@ -285,6 +289,9 @@ class USDMForCausalLM:
         # fp8_matrix_cores (opt-in): decode steps of 5..16 sequences on the matrix cores (usdm_gemv_fp8_mfma) instead of groups of 4;
         # like bf16's matrix-core form they equal the oracle up to near-ties, not generate() bit for bit
         self.fp8_matrix_cores = bool(fp8_matrix_cores)
+        # mxfp4_matrix_cores (opt-in): likewise for mxfp4 (usdm_gemv_mxfp4_mfma); the layers' matrices then hold a second, matrix-core
+        # image of their codes (about as many bytes again)
+        self.mxfp4_matrix_cores = bool(mxfp4_matrix_cores)
         self.cfg = dict(cfg)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -404,7 +411,8 @@ class USDMForCausalLM:
     # ------------------------------------------------------------------ weights
     def _shard(self, sd_get):
         """Build this rank's packed weights from a getter name -> tensor (any device)."""
-        W = shard_weights(sd_get, self.cfg, self.tp_rank, self.tp_size, self.device, quantization=self.quantization)
+        W = shard_weights(sd_get, self.cfg, self.tp_rank, self.tp_size, self.device, quantization=self.quantization,
+                          mxfp4_matrix_cores=self.mxfp4_matrix_cores)
         assert (W["v0"], W["v1"]) == (self.v0, self.v1)
         return W
 
@@ -1073,11 +1081,13 @@ class USDMForCausalLM:
         on the matrix cores (K = 14336, n > 4): K split over workgroups, each holding its activation slice (usdm_gemv_batch ks_*); one
         scratch for all layers - the launches of a step are serial and each leaves the counters zero.  fp8_matrix_cores: the FP8
         projections of 5..16 rows on the matrix cores (usdm_gemv_fp8_mfma: the bf16 form's tiles, K split and epilogues, so the same ks
-        scratch); <= 4 keep the VALU FP8 form of gemv_batch."""
+        scratch); <= 4 keep the VALU FP8 form of gemv_batch.  mxfp4_matrix_cores: likewise, per weight (the lm_head of an mxfp4 model is fp8)."""
         H, Z = self.cfg["hidden_size"], lambda n, dt: rec.plan.hold(torch.zeros(n, device=self.device, dtype=dt))
         ksf = ops.gemv_batch_ks_floats(H, self.I) if n > 4 else 0
         ks = (Z(ksf, torch.float32), Z(-(-H // 16), torch.int32)) if ksf else None
         gemv_b = ops.gemv_fp8_mfma if (self.fp8_matrix_cores and n > 4) else ops.gemv_batch
+        if self.mxfp4_matrix_cores and n > 4:      # per weight: the layers' Mxfp4Weight on usdm_gemv_mxfp4_mfma, the fp8 lm_head on usdm_gemv_fp8_mfma
+            gemv_b = lambda W, x, **kw: (ops.gemv_mxfp4_mfma if isinstance(W, Mxfp4Weight) else ops.gemv_fp8_mfma)(W, x, **kw)
 
         def gemv(W, x, *, N, K, act=0, residual=None, y_bs=None, **kw):
             gemv_b(W, x, nb=n, N=N, K=K, x_bs=K, y_bs=(N // 2 if act else N) if y_bs is None else y_bs, res_bs=N if residual is not None else 0,
@@ -1196,12 +1206,10 @@ class USDMForCausalLM:
         8 waves in chunks of 32 (every projection's K must be a multiple of 256), else the 4 of the VALU form."""
         c = self.cfg
         ks = (c["hidden_size"], self.Hq * c["head_dim"], self.I)
-        if self.quantization == "mxfp4":        # usdm_gemv_mxfp4: the VALU form only
-            return 4
-        if self.quantization == "fp8":
-            if not self.fp8_matrix_cores:       # usdm_gemv_fp8: the VALU form only
-                return 4
-            # usdm_gemv_fp8_mfma refuses what the launcher cannot run: K % 256, the fused RMSNorm with K > 4096, more than 64
+        if self.quantization in ("fp8", "mxfp4"):
+            if not (self.fp8_matrix_cores if self.quantization == "fp8" else self.mxfp4_matrix_cores):
+                return 4                        # usdm_gemv_fp8 / usdm_gemv_mxfp4: the VALU form only
+            # usdm_gemv_fp8_mfma / usdm_gemv_mxfp4_mfma refuse what the launcher cannot run: K % 256, the fused RMSNorm with K > 4096, more than 64
             # lm_head tiles of 16 rows per workgroup
             fits = all(k % 256 == 0 for k in ks) and c["hidden_size"] <= 4096 and -(-(self.v1 - self.v0) // 16) <= 64 * 256
             return self.MAX_BATCH if fits else 4

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnVerifyArgs, AttnVerifyBatchArgs, SpecArgs, SpecBatchArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnVerifyArgs, AttnVerifyBatchArgs, SpecArgs, SpecBatchArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, GemvMxfp4MfmaArgs, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 from .wpack import GemvWpack
@@ -774,6 +774,20 @@ def gemv_fp8_mfma(W, x, *, plan=None, **kw):
     f = GemvFp8Args()
     f.b, f.row_exp = gemv_batch(W.q, x, **dict(kw, only_args=True)), _ptr(W.e)
     _go(plan, "usdm_gemv_fp8_mfma", lib.usdm_gemv_fp8_mfma, C_.byref(f))
+
+
+def gemv_mxfp4_mfma(W, x, *, plan=None, **kw):
+    """usdm_gemv_mxfp4_mfma: the matrix-core form (nb <= 16) on a quant.Mxfp4Weight that holds the matrix-core image
+    (Mxfp4Weight.from_matrix(w, matrix_cores=True) / with_matrix_core_image()), opt-in.  Keywords as gemv_batch; form 0 (K split
+    where ks is given) or 5 (no split); y16 only.  Equals gemv_batch(W.dequantize(), ..., form=1 or 5) bit for bit; NOT bit-identical
+    with the VALU form that gemv_batch runs on an Mxfp4Weight (nb <= 4)."""
+    if not isinstance(W, Mxfp4Weight) or not W.has_matrix_core_image:
+        raise TypeError("gemv_mxfp4_mfma takes a quant.Mxfp4Weight that holds the matrix-core image (matrix_cores=True)")
+    _need_cuda(W.mq, W.ms)
+    f = GemvMxfp4MfmaArgs()
+    f.b = gemv_batch(W, x, **dict(kw, only_args=True))
+    f.codes, f.ldc, f.scales, f.lds = _ptr(W.mq), W.mq.stride(0), _ptr(W.ms), W.ms.stride(0)
+    _go(plan, "usdm_gemv_mxfp4_mfma", lib.usdm_gemv_mxfp4_mfma, C_.byref(f))
 
 
 def dequant_fp8(W, out, plan=None):

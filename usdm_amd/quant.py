@@ -175,22 +175,49 @@ def dequantize_mxfp4(codes, scales):
     return torch.ldexp(v, (scales.float() - 127.0)[:, :, None]).view(N, K).to(torch.bfloat16)
 
 
+MX_QUAD = 128         # elements of a row that the matrix-core image interleaves (four K chunks of 32 of one MFMA wave)
+
+
+def _mc_swap(byts, N, K):
+    """code bytes [N][K / 2]: linear dword 16 Q + 4 j + g (elements 128 Q + 32 j + 8 g ..+7) <-> dword 16 Q + 4 g + j (its own inverse)"""
+    return byts.view(N, K // MX_QUAD, 4, 4, 4).permute(0, 1, 3, 2, 4).reshape(N, K // 2)
+
+
 class Mxfp4Weight:
     """A quantized matrix as the kernels take it: q uint8 [N][Kp / 2] packed codes and s uint8 [N][Kp / 32] scale bytes, Kp = K
-    rounded up to whole groups of 2048 (zero codes, scale bytes 127).  ops.gemv / ops.gemv_batch dispatch on this type."""
-    __slots__ = ("q", "s", "N", "K")
+    rounded up to whole groups of 2048 (zero codes, scale bytes 127).  ops.gemv / ops.gemv_batch dispatch on this type.
+    Only when asked (matrix_cores=True, or with_matrix_core_image()) it also holds a second image of the same logical matrix for
+    usdm_gemv_mxfp4_mfma (ops.gemv_mxfp4_mfma), whose waves own contiguous K chunks: mq uint8 [N][K / 2], where 16-byte piece g of
+    the quad Q of four chunks holds four dwords, dword j the codes of elements 128 Q + 32 j + 8 g ..+7 (the earlier element in bits
+    3:0, as in q), and ms uint8 [N][K / 32], the plain scale bytes.  No padding; K % 128 == 0.  The VALU kernels and
+    usdm_dequant_mxfp4 never read it; it costs K / 2 + K / 32 more bytes per row."""
+    __slots__ = ("q", "s", "N", "K", "mq", "ms")
 
-    def __init__(self, q, s, K):
+    def __init__(self, q, s, K, mq=None, ms=None):
         Kp = -(-K // MX_GROUP) * MX_GROUP
         if q.dtype != torch.uint8 or s.dtype != torch.uint8 or q.dim() != 2 or K % MX_BLOCK or q.shape[1] != Kp // 2 \
                 or s.shape != (q.shape[0], Kp // MX_BLOCK):
             raise ValueError("Mxfp4Weight: q uint8 [N][Kp / 2] and s uint8 [N][Kp / 32], Kp = K (a multiple of 32) rounded up to 2048")
         self.q, self.s = q.contiguous(), s.contiguous()
         self.N, self.K = q.shape[0], K
+        if (mq is None) != (ms is None):
+            raise ValueError("Mxfp4Weight: the matrix-core image is mq AND ms")
+        if mq is not None and (K % MX_QUAD or mq.dtype != torch.uint8 or ms.dtype != torch.uint8 or mq.shape != (self.N, K // 2)
+                               or ms.shape != (self.N, K // MX_BLOCK) or mq.stride(1) != 1 or ms.stride(1) != 1):
+            raise ValueError("Mxfp4Weight: mq uint8 [N][K / 2] and ms uint8 [N][K / 32], K a multiple of 128")
+        self.mq, self.ms = mq, ms
+
+    @staticmethod
+    def _pack_mc(codes, scales):
+        N, K = codes.shape
+        if K % MX_QUAD:
+            raise ValueError("Mxfp4Weight: the matrix-core image needs K to be a multiple of 128")
+        byts = codes[:, 0::2] | (codes[:, 1::2] << 4)
+        return _mc_swap(byts, N, K).contiguous(), scales.contiguous()
 
     @classmethod
-    def from_codes(cls, codes, scales):
-        """Pack the logical (codes [N][K], scales [N][K/32]) of quantize_mxfp4 into the kernels' layout."""
+    def from_codes(cls, codes, scales, matrix_cores=False):
+        """Pack the logical (codes [N][K], scales [N][K/32]) of quantize_mxfp4 into the kernels' layout (matrix_cores: both images)."""
         N, K = codes.shape
         G = -(-K // MX_GROUP)
         c = torch.zeros(N, G * MX_GROUP, dtype=torch.uint8, device=codes.device)
@@ -202,14 +229,29 @@ class Mxfp4Weight:
         sc[:, :K // MX_BLOCK] = scales
         # block 64 g + 16 i + b -> byte 64 g + 4 b + i
         s = sc.view(N, G, 4, 16).permute(0, 1, 3, 2).reshape(N, G * MX_GROUP // MX_BLOCK)
-        return cls(q, s, K)
+        return cls(q, s, K, *(cls._pack_mc(codes, scales) if matrix_cores else ()))
 
     @classmethod
-    def from_matrix(cls, w):
-        return cls.from_codes(*quantize_mxfp4(w))
+    def from_matrix(cls, w, matrix_cores=False):
+        return cls.from_codes(*quantize_mxfp4(w), matrix_cores=matrix_cores)
 
-    def unpack(self):
-        """-> the logical (codes uint8 [N][K], scales uint8 [N][K/32])."""
+    @property
+    def has_matrix_core_image(self):
+        return self.mq is not None
+
+    def with_matrix_core_image(self):
+        """Build the matrix-core image (from the first one) if it is not there yet; returns self."""
+        if self.mq is None:
+            self.mq, self.ms = self._pack_mc(*self.unpack())
+        return self
+
+    def unpack(self, matrix_cores=False):
+        """-> the logical (codes uint8 [N][K], scales uint8 [N][K/32]); matrix_cores: read from the matrix-core image."""
+        if matrix_cores:
+            if self.mq is None:
+                raise ValueError("Mxfp4Weight.unpack: this matrix holds no matrix-core image")
+            byts = _mc_swap(self.mq.contiguous(), self.N, self.K)
+            return torch.stack((byts & 15, byts >> 4), dim=2).view(self.N, self.K).contiguous(), self.ms.contiguous()
         N, G = self.N, self.q.shape[1] * 2 // MX_GROUP
         byts = self.q.view(N, G, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(N, G * MX_GROUP // 2)
         c = torch.stack((byts & 15, byts >> 4), dim=2).view(N, G * MX_GROUP)
@@ -231,6 +273,11 @@ class Mxfp4Weight:
     def nbytes(self):
         """bytes one pass over the matrix streams (packed codes + scale bytes, padding included)"""
         return self.q.numel() + self.s.numel()
+
+    @property
+    def nbytes_matrix_cores(self):
+        """bytes one pass over the matrix-core image streams (0 without it)"""
+        return 0 if self.mq is None else self.N * (self.K // 2 + self.K // MX_BLOCK)
 
     def data_ptr(self):
         return self.q.data_ptr()

@@ -227,15 +227,16 @@ class LLM:
 
     def __init__(self, model, tokenizer=None, download_dir=None, gpu_memory_utilization=0.9, max_model_len=None, device="cuda",
                  dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None,
-                 enable_prefix_caching=False, speculative_config=None, **unused):
+                 enable_prefix_caching=False, speculative_config=None, mxfp4_matrix_cores=False, **unused):
         # max_num_seqs (vllm's name): sequences decoded per step, 1..16.  <= 4: the VALU batch kernel (per slot bit-identical with the
         # single-request path); above: the matrix-core form (usdm_gemv_batch form 1)
         self.max_slots = max(1, min(int(max_num_seqs), MAX_SLOTS))
         # quantization (vllm's name): None = bf16, "fp8" = e4m3 weights with power-of-two row scales (usdm_amd/quant.py); the
         # FP8 model decodes at most 4 sequences per step (its max_batch()) unless fp8_matrix_cores (opt-in) runs steps of 5..16
         # sequences on the matrix cores (usdm_gemv_fp8_mfma)
-        # "mxfp4" = e2m1 weights with one power-of-two scale per 32 elements (fp8 lm_head): at most 4 sequences per step
-        check_quantization(quantization, fp8_matrix_cores)
+        # "mxfp4" = e2m1 weights with one power-of-two scale per 32 elements (fp8 lm_head): at most 4 sequences per step unless
+        # mxfp4_matrix_cores (opt-in) runs steps of 5..16 sequences on the matrix cores (usdm_gemv_mxfp4_mfma, a second image of the codes)
+        check_quantization(quantization, fp8_matrix_cores, mxfp4_matrix_cores)
         # kv_cache_dtype (vllm's name): None / "bf16", or "fp8" = e4m3 cache rows with one power-of-two scale per (token, kv head)
         kvd = check_kv_cache_dtype(kv_cache_dtype)
         if isinstance(model, USDMForCausalLM):
@@ -247,6 +248,8 @@ class LLM:
                                  f"quantization={model.quantization!r}")
             if fp8_matrix_cores and not model.fp8_matrix_cores:
                 raise ValueError("fp8_matrix_cores=True, but the model object was loaded with fp8_matrix_cores=False")
+            if mxfp4_matrix_cores and not model.mxfp4_matrix_cores:
+                raise ValueError("mxfp4_matrix_cores=True, but the model object was loaded with mxfp4_matrix_cores=False")
             if enable_prefix_caching and not model.prefix_caching:
                 raise ValueError("enable_prefix_caching=True, but the model object was loaded with enable_prefix_caching=False")
             self.llm = model
@@ -258,7 +261,8 @@ class LLM:
                 tokenizer = AutoTokenizer.from_pretrained(path, local_files_only=True)
             ctx = min(int(max_model_len or getattr(tokenizer, "model_max_length", 4096) or 4096), 8192)
             self.llm = USDMForCausalLM.from_pretrained(path, device=device, ctx_max=ctx, quantization=quantization,
-                                                       fp8_matrix_cores=fp8_matrix_cores, kv_cache_dtype=kv_cache_dtype,
+                                                       fp8_matrix_cores=fp8_matrix_cores, mxfp4_matrix_cores=mxfp4_matrix_cores,
+                                                       kv_cache_dtype=kv_cache_dtype,
                                                        enable_prefix_caching=enable_prefix_caching)
         if isinstance(tokenizer, str):
             from transformers import AutoTokenizer
