@@ -340,6 +340,23 @@ typedef struct usdm_gemv_batch_args {
 int64_t usdm_gemv_batch_ks_floats(int32_t N, int32_t K);   /* 0: this shape is not split */
 int usdm_gemv_batch(const usdm_gemv_batch_args* args, usdm_stream_t stream);
 
+/* What the matrix-core launcher decides for a shape, asked on the host (no HIP call, no device needed): the one selection that
+ * usdm_gemv_batch (forms 1 / 3 / 5), usdm_gemv_fp8_mfma and usdm_gemv_mxfp4_mfma launch from.
+ * flags: bit 0 SwiGLU, bit 1 fused RMSNorm, bit 2 lm_head mode, bit 3 ks_part / ks_cnt given.  form: as usdm_gemv_batch_args.form.
+ * fmt: 0 bf16, 1 FP8, 2 MXFP4.  Returns 0 and fills *out, or non-zero with usdm_last_error() for a shape the launcher refuses. */
+typedef struct usdm_gemv_mfma_plan {
+  int32_t hold, cpwt, trl;   /* the kernel variant: activations held in registers; K chunks per wave as a constant (0: any); row-contiguous
+                                loads re-cut through LDS */
+  int32_t rt;                /* rows per tile */
+  int32_t ksplit;            /* K slices over workgroups (1: not split) */
+  int32_t ntiles, nout;
+  int32_t cpw;               /* K chunks of 32 per wave */
+  int32_t grid, kwg;         /* workgroups; workgroups that share the tiles of a K slice (= grid when not split) */
+  int32_t lds_bytes;
+} usdm_gemv_mfma_plan;
+int usdm_gemv_mfma_select(int32_t N, int32_t K, int32_t flags, int32_t form, int32_t fmt, usdm_gemv_mfma_plan* out);
+int usdm_sizeof_gemv_mfma_plan(void);
+
 /* Weight-only FP8 decode GEMV (opt-in, usdm_amd/quant.py): b.g.W holds OCP e4m3fn bytes [N][ldw] (row-major, ldw in elements =
  * bytes, a multiple of 8) and row r is scaled by 2^row_exp[r].  Every dequantized weight q * 2^e is a bf16 value, and the kernels
  * convert it exactly in registers and then run the bf16 arithmetic unchanged: the result equals usdm_gemv (nb = 1) or the VALU

@@ -186,6 +186,10 @@ class GemvMxfp4MfmaArgs(C.Structure):
     _fields_ = [("b", GemvBatchArgs), ("codes", C.c_void_p), ("ldc", C.c_int64), ("scales", C.c_void_p), ("lds", C.c_int64)]
 
 
+class GemvMfmaPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("hold", "cpwt", "trl", "rt", "ksplit", "ntiles", "nout", "cpw", "grid", "kwg", "lds_bytes")]
+
+
 class DecodeState(C.Structure):
     _fields_ = [
         ("next_token", C.c_void_p), ("out_tokens", C.c_void_p), ("step", C.c_void_p), ("pos", C.c_void_p),
@@ -357,6 +361,8 @@ def _selfcheck():
         raise ImportError("ABI mismatch: usdm_penalty_params")
     if lib.usdm_sizeof_logit_edit_params() != C.sizeof(LogitEditParams):
         raise ImportError("ABI mismatch: usdm_logit_edit_params")
+    if lib.usdm_sizeof_gemv_mfma_plan() != C.sizeof(GemvMfmaPlan):
+        raise ImportError("ABI mismatch: usdm_gemv_mfma_plan")
 
 
 _selfcheck()

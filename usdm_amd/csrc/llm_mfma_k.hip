@@ -16,7 +16,7 @@
 // o_proj; the RMSNorm with HF's rounding points is applied to the held fragments in the prologue, under the first weight loads), or
 // streams beside the weights (down_proj, K = 14336, one tile per workgroup).  Tiles (16 rows; 12 where that balances the 256 CUs
 // better; SwiGLU: 8 gate + 8 up rows of the same 8 features) are dealt round-robin to the workgroups; a wave keeps the loads of two
-// tiles (16 x 16 B per lane) in flight.  The 16 partial sums per output are added in wave order through LDS (deterministic), then
+// tiles (16 x 16 B per lane) in flight.  The 8 partial sums per output are added in wave order through LDS (deterministic), then
 // the batch-1 kernels' epilogues: bf16 rounding points of HF, residual add, SwiGLU, ban-masked arg-max partials + logits.
 //
 // Per sequence the result is NOT bit-identical to usdm_gemv: the K partition and the MFMA's internal summation order differ (f32
@@ -30,6 +30,12 @@
 // MXFP4 weights (usdm_gemv_mxfp4_mfma, opt-in): the same kernel again, selected by the type of its extra argument - a second image
 // of the codes, cut so that one 16-byte load is a lane's A fragments of four consecutive chunks, and one e8m0 scale per row and chunk;
 // converted exactly to bf16 right before each MFMA, equal to the bf16 form on W' bit for bit.
+//
+// The shape of this file (a new format or schedule: DESIGN.md 8f).  Helpers: slot aliases, drain, recut_store / recut_frag, next_unit.
+// gemv_mfma_kernel: tiles and ban mask; row_of and the load bases; the first loads of the live stream; RMSNorm; the services a stream
+// hands tiles to (epilogue, ks_merge, flush_group, finish_tile, keep_tile); the streams - quads (MXFP4), re-cut FP8, re-cut bf16, ring,
+// pairs - one `if constexpr` branch each (as five structs every instantiation left class A / B: profiles/gemv_mfma_split.txt); the
+// final flush; the lm_head partials.  Host: mfma_select, USDM_MFMA_VARIANTS (the one list of instantiations), launch_one.
 #include "common.h"
 #include "../../include/usdm_hip.h"
 #include "gemv_common.h"
@@ -95,10 +101,60 @@ __device__ __forceinline__ void ld_nt_asm(V& dst, const V* p) {
 __device__ __forceinline__ void ld_exp_asm(int& dst, const int8_t* p) {
   asm volatile("global_load_sbyte %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
 }
+// ---- slots of a ring of registers: compile-time indices, so that every register array is indexed by constants
+template <int I> using slot = std::integral_constant<int, I>;
+using Q0 = slot<0>; using Q1 = slot<1>; using Q2 = slot<2>; using Q3 = slot<3>;
+template <int N> using slots = std::make_integer_sequence<int, N>;
 template <int... I, class F>
-__device__ __forceinline__ void each_slot(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+__device__ __forceinline__ void each_slot(std::integer_sequence<int, I...>, F&& f) { (f(slot<I>{}), ...); }
 template <int... I, class F>      // f(slot) for the slots in order until one returns false
-__device__ __forceinline__ bool all_slots(std::integer_sequence<int, I...>, F&& f) { return (f(std::integral_constant<int, I>{}) && ...); }
+__device__ __forceinline__ bool all_slots(std::integer_sequence<int, I...>, F&& f) { return (f(slot<I>{}) && ...); }
+
+// drain: loads for tiles that do not exist may still be in flight into load registers; the wait for everything in one statement,
+// then every load register named after it, which keeps the compiler from reusing any of them before the wait has executed
+template <class V> __device__ __forceinline__ void name_reg(const V& v) { asm volatile("" ::"v"(v) : "memory"); }
+template <class V, int N> __device__ __forceinline__ void name_reg(const V (&v)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) name_reg(v[i]);
+}
+template <class... R> __device__ __forceinline__ void drain(const R&... regs) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  (name_reg(regs), ...);
+}
+
+// ---- re-cut of row-contiguous loads into MFMA fragments through a wave's LDS buffer [16 rows][ROWB bytes], 16-byte piece ^ row
+// (conflict-free both ways).  ROWB: bytes of a row per unit (512, or FP8's 256); a load instruction covers 1024 / ROWB rows.
+// the landed loads of a unit -> the buffer, by rows
+template <int ROWB, int NL>
+__device__ __forceinline__ void recut_store(char* tb, int lane, const u32x4 (&u)[NL]) {
+  constexpr int RPI = 1024 / ROWB;
+  static_assert(NL == 16 / RPI, "a unit is 16 rows");
+  const int lrow = lane / (64 / RPI), lp = lane % (64 / RPI);      // row (of the instruction's RPI) and 16-byte piece this lane loaded
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {
+    const int r = RPI * i + lrow;
+    *(u32x4*)(tb + r * ROWB + ((lp ^ r) << 4)) = u[i];
+  }
+}
+// chunk c of lane (r16, g)'s row: its 8 weights as V (16 bytes of bf16, 8 of e4m3)
+template <int ROWB, class V>
+__device__ __forceinline__ V recut_frag(const char* tb, int r16, int g, int c) {
+  if constexpr (sizeof(V) == 16) return *(const V*)(tb + r16 * ROWB + (((4 * c + g) ^ r16) << 4));
+  else return *(const V*)(tb + r16 * ROWB + (((2 * c + (g >> 1)) ^ r16) << 4) + (g & 1) * 8);      // (one formula in bytes left class A)
+}
+
+// ---- streamed units: K slices longer than the held activations are multiplied in units numbered through the tiles, UPT per tile
+// and wave; (t, s) is a unit, next_unit moves to the following one (true: it is the first of the next tile)
+struct unit_pos { int t, s; };
+template <int UPT, class NEXT>
+__device__ __forceinline__ bool next_unit(unit_pos& u, NEXT&& next) {
+  if (++u.s == UPT) {
+    u.s = 0;
+    u.t = next();
+    return true;
+  }
+  return false;
+}
 template <int WAIT, bool FIRST, class V>
 __device__ __forceinline__ void wait_mfma_asm(f32x4& acc, const V& w, const u32x4& x) {
   if constexpr (FIRST)
@@ -192,14 +248,18 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   // CLAMPED to existing ones instead of masked: they only feed output rows / columns that the epilogue never stores, and every load
   // below stays unconditional (uniform control flow, one 64-bit base + immediates per tile).
   const int kc0 = wave * cpw;                             // first K chunk of this wave (host: K %% (MW * 32) == 0)
+  // the row of W behind A-row r of tile t (t < 0: row 0): the one place that knows how tiles are cut
+  auto row_of = [&](int t, int r) -> int {
+    if (t < 0) return 0;
+    if (glu) return gemv_glu_row(min(t * 8 + (r & 7), d.nout - 1), r >= 8);
+    return min(t * d.rt + r, a.N - 1);
+  };
   auto wbase = [&](int t) -> const wvec* {
+    // (row_of's text with the clamp of t < 0 INSIDE the SwiGLU row, which this base has always had - a lane of the up half reads row
+    // 16 then; through row_of plus that case the ring and pair instantiations, the hand-counted one among them, left class A / B)
     int row;
-    if (glu) {
-      const int f = t < 0 ? 0 : min(t * 8 + (r16 & 7), d.nout - 1);
-      row = (f >> 4) * 32 + (f & 15) + (r16 >= 8 ? 16 : 0);
-    } else {
-      row = t < 0 ? 0 : min(t * d.rt + r16, a.N - 1);
-    }
+    if (glu) row = gemv_glu_row(t < 0 ? 0 : min(t * 8 + (r16 & 7), d.nout - 1), r16 >= 8);
+    else row = t < 0 ? 0 : min(t * d.rt + r16, a.N - 1);
     if (t < 0 && K >= 2048) {
       // No such tile: the stream loop's loads stay unconditional (uniform wait counts), but they must cost nothing - 64 bytes of the
       // activation vector per instruction (one request instead of sixteen), a different line for every wave so that no L2 channel
@@ -213,15 +273,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   auto wload = [&](const wvec* base, int c) -> wvec {
     return __builtin_nontemporal_load(base + c * 4);
   };
-  // FP8: the A-row r of tile t (t < 0: row 0), its scale for this lane's row r16, and the bf16 fragment of 8 loaded bytes
-  auto row_of = [&](int t, int r) -> int {
-    if (t < 0) return 0;
-    if (glu) {
-      const int f = min(t * 8 + (r & 7), d.nout - 1);
-      return (f >> 4) * 32 + (f & 15) + (r >= 8 ? 16 : 0);
-    }
-    return min(t * d.rt + r, a.N - 1);
-  };
+  // FP8: the scale of tile t for this lane's row r16, and the bf16 fragment of 8 loaded bytes
   auto wscale = [&](int t) -> float {
     if constexpr (FP8) return fp8_row_scale(rexp[row_of(t, r16)]);
     else return 0.f;
@@ -262,15 +314,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   const int lrow = lane >> 5, lp = lane & 31;              // row (of a pair) and 16-byte piece this lane loads
   auto unit_ptr = [&](int t, int sub, int i) -> const u32x4* {
     if (t < 0) return (const u32x4*)a.x + ((blockIdx.x * MW + wave) & 7) * 4 + (lane & 3) + i * 32;      // placeholder: 64 B of x (see wbase)
-    const int r = 2 * i + lrow;                            // A-row of the tile
-    int row;
-    if (glu) {
-      const int f = min(t * 8 + (r & 7), d.nout - 1);
-      row = (f >> 4) * 32 + (f & 15) + (r >= 8 ? 16 : 0);
-    } else {
-      row = min(t * d.rt + r, a.N - 1);
-    }
-    return (const u32x4*)(Wb + (int64_t)row * a.ldw + kofs + (int64_t)wave * (cpw * 32) + sub * 256 + lp * 8);
+    return (const u32x4*)(Wb + (int64_t)row_of(t, 2 * i + lrow) * a.ldw + kofs + (int64_t)wave * (cpw * 32) + sub * 256 + lp * 8);
   };
   int t0 = (TRL || MX4) ? -1 : next_tile(rem_ld), t1 = -1, t2 = -1;  // tile being multiplied, the next two (loads in flight / to be issued)
   const wvec* wp0 = wbase(t0);
@@ -280,8 +324,8 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   if constexpr (FP8 && !TRL) sc0 = wscale(t0);
   constexpr bool ASM_STREAM = HOLD && CPWT == CH && !USDM_MFMA_NO_ASM && !TRL && !MX4;     // hand-counted loads (see the stream loop)
   int ua = -1, ub = -1, uc = -1;                            // TRL: the tile being multiplied and the next two
-  // TRL with streamed activations (K = 14336): units are numbered through the tiles, 7 per tile; (lt, ls) = the next unit to load
-  int lt = -1, ls = 0;
+  // TRL with streamed activations (K = 14336): units are numbered through the tiles, 7 per tile; lu = the next unit to load
+  unit_pos lu{-1, 0};
   constexpr int UPT = CPWT / 8;                             // units per tile and wave
   auto ld_unit_x = [&](auto SLOT, int t, int sub) __attribute__((always_inline)) {
     constexpr int q = decltype(SLOT)::value;
@@ -290,11 +334,11 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
 #pragma unroll
     for (int c = 0; c < 8; ++c) ld_nt_asm(X[q][c], xbase + (sub * 8 + c) * 4);
   };
-  auto adv_unit = [&]() { if (++ls == UPT) { ls = 0; lt = next_tile(rem_ld); } };
+  auto adv_unit = [&]() { next_unit<UPT>(lu, [&]() { return next_tile(rem_ld); }); };
   if constexpr (!FP8 && TRL && !HOLD) {
-    lt = next_tile(rem_ld);
-    ld_unit_x(std::integral_constant<int, 0>{}, lt, ls); adv_unit();
-    ld_unit_x(std::integral_constant<int, 1>{}, lt, ls); adv_unit();
+    lu.t = next_tile(rem_ld);
+    ld_unit_x(Q0{}, lu.t, lu.s); adv_unit();
+    ld_unit_x(Q1{}, lu.t, lu.s); adv_unit();
   }
   int tq[4] = {-1, -1, -1, -1};                             // K-split form: the tiles whose single unit sits in slots 0 .. 3
   if constexpr (!FP8 && TRL && HOLD && CPWT == 8) {
@@ -345,7 +389,6 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   constexpr int NL8 = 16 / RPI8;                            // weight loads per unit
   constexpr int NR8 = CPWT == 8 ? 8 : 3;                    // units in flight
   constexpr int LPU8 = NL8 + 1 + (HOLD ? 0 : 8);            // loads per unit
-  using Slots8 = std::make_integer_sequence<int, NR8>;
   u32x4 U8[FP8 && TRL ? NR8 : 1][NL8];
   int E8[FP8 && TRL ? NR8 : 1];
   u32x4 X8[FP8 && TRL && !HOLD ? NR8 : 1][8];
@@ -367,11 +410,11 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
     }
   };
   if constexpr (FP8 && TRL && !HOLD) {
-    lt = next_tile(rem_ld);
-    each_slot(Slots8{}, [&](auto Q) __attribute__((always_inline)) { ld_unit8(Q, lt, ls); adv_unit(); });
+    lu.t = next_tile(rem_ld);
+    each_slot(slots<NR8>{}, [&](auto Q) __attribute__((always_inline)) { ld_unit8(Q, lu.t, lu.s); adv_unit(); });
   }
   if constexpr (FP8 && TRL && HOLD) {
-    each_slot(Slots8{}, [&](auto Q) __attribute__((always_inline)) {
+    each_slot(slots<NR8>{}, [&](auto Q) __attribute__((always_inline)) {
       tq8[decltype(Q)::value] = next_tile(rem_ld);
       ld_unit8(Q, tq8[decltype(Q)::value], 0);
     });
@@ -388,7 +431,6 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   const bool quads = CPWT > 0 || (cpw & 3) == 0;            // else a quad would straddle two waves: dword loads (see the stream loop)
   constexpr int NQ = CPWT > 0 ? CPWT / 4 : CH / 4;
   constexpr int ND = CPWT == 8 ? 8 : 4;
-  using SlotsM = std::make_integer_sequence<int, ND>;
   const int nq = cpw >> 2;
   u32x4 cq[MX4 && HOLD ? ND : 1][NQ];
   unsigned sq[MX4 && HOLD ? ND : 1][NQ];
@@ -410,7 +452,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
   };
   if constexpr (MX4 && HOLD) {
     if (quads) {
-      each_slot(SlotsM{}, [&](auto Q) __attribute__((always_inline)) {
+      each_slot(slots<ND>{}, [&](auto Q) __attribute__((always_inline)) {
         tm[decltype(Q)::value] = next_tile(rem_ld);
         ld_tile(Q, tm[decltype(Q)::value]);
       });
@@ -532,7 +574,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       if (a.y32) a.y32[(int64_t)b * d.ba.y_bs + n] = x;
     }
   };
-  // the tiles of a group are summed over the 16 waves in wave order (wave w < ng takes tile slot w) and finished
+  // the tiles of a group are summed over the 8 waves in wave order (wave w < ng takes tile slot w) and finished
   int done = 0;
   // K split over workgroups: this workgroup's partial tile goes to ks_part[t][slice] as write-through stores (the merging workgroup
   // may sit on another XCD, whose L2 is not coherent with ours); once they are acknowledged, one relaxed increment of the tile's
@@ -612,6 +654,16 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
 #endif
     if (done % MTG == 0) flush_group(rem_cp != 0ull);
   };
+  // ... of a stream that keeps all its (at most MTG) tiles for ONE flush after it (the K split, the straight-line part); t < 0: no tile
+  auto keep_tile = [&](int t, f32x4 acc) __attribute__((always_inline)) {
+    if (t < 0) return;
+    red[(done * MW + wave) * 64 + lane] = acc;
+    if (tid == 0) tl[done] = t;
+    ++done;
+#ifdef USDM_MFMA_TRACE
+    if (done == 1) TRM(3);
+#endif
+  };
 
   // ---- stream
   if constexpr (MX4) {
@@ -677,13 +729,9 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
           const f32x4 acc = mul_tile(SLOT);
           tm[s] = next_tile(rem_ld);
           ld_tile(SLOT, tm[s]);
-          if (t >= 0) {
-            red[(done * MW + wave) * 64 + lane] = acc;
-            if (tid == 0) tl[done] = t;
-            ++done;
-          }
+          keep_tile(t, acc);
         };
-        while (tm[0] >= 0) each_slot(SlotsM{}, step);
+        while (tm[0] >= 0) each_slot(slots<ND>{}, step);
       } else {
         auto step = [&](auto SLOT) __attribute__((always_inline)) -> bool {
           constexpr int s = decltype(SLOT)::value;
@@ -696,7 +744,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
           finish_tile(t, acc);
           return true;
         };
-        while (all_slots(SlotsM{}, step)) {}
+        while (all_slots(slots<ND>{}, step)) {}
       }
     } else {
       // activations streamed beside the weights (form 5 at K = 14336, any K > 4096 that is not split): a unit = one quad, its scale
@@ -743,35 +791,27 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       if constexpr (NL8 == 8) asm volatile("" : "+v"(U8[q][4]), "+v"(U8[q][5]), "+v"(U8[q][6]), "+v"(U8[q][7]));
       if constexpr (!HOLD)
         asm volatile("" : "+v"(X8[q][0]), "+v"(X8[q][1]), "+v"(X8[q][2]), "+v"(X8[q][3]), "+v"(X8[q][4]), "+v"(X8[q][5]), "+v"(X8[q][6]), "+v"(X8[q][7]));
-#pragma unroll
-      for (int i = 0; i < NL8; ++i) {
-        const int r = RPI8 * i + lrow8;
-        *(u32x4*)(tb + r * ROW8 + ((lp8 ^ r) << 4)) = U8[q][i];
-      }
+      recut_store<ROW8>(tb, lane, U8[q]);
       return fp8_row_scale(E8[q]);
     };
-    // chunk c of this lane's row as bf16: 8 bytes of piece 2 c + g / 2, converted just before the MFMA
+    // chunk c of this lane's row as bf16, converted just before the MFMA
     auto frag8 = [&](int c, float s) __attribute__((always_inline)) -> u32x4 {
-      const int p = 2 * c + (g >> 1);
-      return fp8x8_to_bf16x8(*(const u32x2*)(tb + r16 * ROW8 + ((p ^ r16) << 4) + (g & 1) * 8), s);
+      return fp8x8_to_bf16x8(recut_frag<ROW8, u32x2>(tb, r16, g, c), s);
     };
-    using Q0 = std::integral_constant<int, 0>; using Q1 = std::integral_constant<int, 1>; using Q2 = std::integral_constant<int, 2>;
     if constexpr (!HOLD) {
       // streamed activations (K = 14336): units numbered through the tiles, 7 per tile, in slot n % 3; the tile's chain runs over
       // its units in order, as in bf16
-      int ct = next_tile(rem_cp), cs = 0;
+      unit_pos cu{next_tile(rem_cp), 0};
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       auto unit = [&](auto SLOT) __attribute__((always_inline)) -> bool {
         constexpr int q = decltype(SLOT)::value;
-        if (ct < 0) return false;
+        if (cu.t < 0) return false;
         const float s = take8(SLOT);
 #pragma unroll
         for (int c = 0; c < 8; ++c) acc = mfma16(frag8(c, s), X8[q][c], acc);
-        ld_unit8(SLOT, lt, ls); adv_unit();
-        if (++cs == UPT) {
-          cs = 0;
-          const int t = ct;
-          ct = next_tile(rem_cp);
+        ld_unit8(SLOT, lu.t, lu.s); adv_unit();
+        const int t = cu.t;
+        if (next_unit<UPT>(cu, [&]() { return next_tile(rem_cp); })) {
           finish_tile(t, acc);
           acc = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -790,13 +830,9 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < 8; ++c) acc = mfma16(frag8(c, s), xf[c], acc);
-        if (t >= 0) {
-          red[(done * MW + wave) * 64 + lane] = acc;
-          if (tid == 0) tl[done] = t;
-          ++done;
-        }
+        keep_tile(t, acc);
       };
-      while (tq8[0] >= 0) each_slot(Slots8{}, unit);
+      while (tq8[0] >= 0) each_slot(slots<NR8>{}, unit);
     } else {
       // K = 4096: one unit = one tile; refilled with the tile three further on
       auto tile8 = [&](auto SLOT) __attribute__((always_inline)) -> bool {
@@ -815,54 +851,36 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       };
       while (tile8(Q0{}) && tile8(Q1{}) && tile8(Q2{})) {}
     }
-    // drain: loads for tiles that do not exist may still be in flight; naming every load register after the wait keeps the compiler
-    // from reusing any of them before it
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int q = 0; q < NR8; ++q) {
-      asm volatile("" ::"v"(U8[q][0]), "v"(U8[q][1]), "v"(U8[q][2]), "v"(U8[q][3]), "v"(E8[q]) : "memory");
-      if constexpr (NL8 == 8) asm volatile("" ::"v"(U8[q][4]), "v"(U8[q][5]), "v"(U8[q][6]), "v"(U8[q][7]) : "memory");
-      if constexpr (!HOLD)
-        asm volatile("" ::"v"(X8[q][0]), "v"(X8[q][1]), "v"(X8[q][2]), "v"(X8[q][3]), "v"(X8[q][4]), "v"(X8[q][5]), "v"(X8[q][6]), "v"(X8[q][7]) : "memory");
-    }
+    if constexpr (HOLD) drain(U8, E8);
+    else drain(U8, E8, X8);
   } else if constexpr (TRL && !HOLD) {
     char* tb = smem + TB_OFF + wave * 8192;
-    int ct = next_tile(rem_cp), cs = 0;                     // the unit being multiplied
+    unit_pos cu{next_tile(rem_cp), 0};                      // the unit being multiplied
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     // one unit: its 16 loads have landed (the 32 younger ones stay in flight), rows -> LDS, fragments <- LDS, 8 MFMAs against the
     // unit's own activation fragments, then the slot is refilled with the unit three further on
     auto unit = [&](auto SLOT) __attribute__((always_inline)) -> bool {
       constexpr int q = decltype(SLOT)::value;
-      if (ct < 0) return false;
+      if (cu.t < 0) return false;
       asm volatile("s_waitcnt vmcnt(%8)" : "+v"(U[q][0]), "+v"(U[q][1]), "+v"(U[q][2]), "+v"(U[q][3]), "+v"(U[q][4]), "+v"(U[q][5]), "+v"(U[q][6]), "+v"(U[q][7])
                    : "n"((NR - 1) * 16) : "memory");
       asm volatile("" : "+v"(X[q][0]), "+v"(X[q][1]), "+v"(X[q][2]), "+v"(X[q][3]), "+v"(X[q][4]), "+v"(X[q][5]), "+v"(X[q][6]), "+v"(X[q][7]));
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int r = 2 * i + lrow;
-        *(u32x4*)(tb + r * 512 + ((lp ^ r) << 4)) = U[q][i];
-      }
+      recut_store<512>(tb, lane, U[q]);
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const u32x4 f = *(const u32x4*)(tb + r16 * 512 + (((4 * c + g) ^ r16) << 4));
+        const u32x4 f = recut_frag<512, u32x4>(tb, r16, g, c);
         acc = mfma16(f, X[q][c], acc);
       }
-      ld_unit_x(SLOT, lt, ls); adv_unit();
-      if (++cs == UPT) {
-        cs = 0;
-        const int t = ct;
-        ct = next_tile(rem_cp);
+      ld_unit_x(SLOT, lu.t, lu.s); adv_unit();
+      const int t = cu.t;
+      if (next_unit<UPT>(cu, [&]() { return next_tile(rem_cp); })) {
         finish_tile(t, acc);
         acc = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       return true;
     };
-    using Q0 = std::integral_constant<int, 0>; using Q1 = std::integral_constant<int, 1>;
     while (unit(Q0{}) && unit(Q1{})) {}
-    asm volatile("s_waitcnt vmcnt(0)" ::"v"(U[0][0]), "v"(U[0][1]), "v"(U[0][2]), "v"(U[0][3]), "v"(U[0][4]), "v"(U[0][5]), "v"(U[0][6]), "v"(U[0][7]),
-                 "v"(U[1][0]), "v"(U[1][1]), "v"(U[1][2]), "v"(U[1][3]), "v"(U[1][4]), "v"(U[1][5]), "v"(U[1][6]), "v"(U[1][7]) : "memory");
-    asm volatile("" ::"v"(X[0][0]), "v"(X[0][1]), "v"(X[0][2]), "v"(X[0][3]), "v"(X[0][4]), "v"(X[0][5]), "v"(X[0][6]), "v"(X[0][7]),
-                 "v"(X[1][0]), "v"(X[1][1]), "v"(X[1][2]), "v"(X[1][3]), "v"(X[1][4]), "v"(X[1][5]), "v"(X[1][6]), "v"(X[1][7]) : "memory");
+    drain(U, X);
   } else if constexpr (TRL && CPWT == 8) {
     // K split over workgroups: ONE unit per tile and wave (16 rows x 512 bytes of this wave's 256 K), four tiles in flight; tile n
     // sits in slot n % 4 and is refilled with tile n + 4 as soon as its rows are in LDS
@@ -874,36 +892,20 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       const int t = tq[q];
       asm volatile("s_waitcnt vmcnt(%8)" : "+v"(U[q][0]), "+v"(U[q][1]), "+v"(U[q][2]), "+v"(U[q][3]), "+v"(U[q][4]), "+v"(U[q][5]), "+v"(U[q][6]), "+v"(U[q][7])
                    : "n"((NR - 1) * 8) : "memory");
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int r = 2 * i + lrow;
-        *(u32x4*)(tb + r * 512 + ((lp ^ r) << 4)) = U[q][i];
-      }
+      recut_store<512>(tb, lane, U[q]);
       tq[q] = next_tile(rem_ld);
 #pragma unroll
       for (int i = 0; i < 8; ++i) ld_nt_asm(U[q][i], unit_ptr(tq[q], 0, i));
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const u32x4 f = *(const u32x4*)(tb + r16 * 512 + (((4 * c + g) ^ r16) << 4));
+        const u32x4 f = recut_frag<512, u32x4>(tb, r16, g, c);
         acc = mfma16(f, xf[c], acc);
       }
-      if (t >= 0) {
-        red[(done * MW + wave) * 64 + lane] = acc;           // at most MTG tiles per workgroup (host): reduced and merged after the stream,
-        if (tid == 0) tl[done] = t;                          // when the load registers are free for the merge's partials
-        ++done;
-#ifdef USDM_MFMA_TRACE
-        if (done == 1) TRM(3);
-#endif
-      }
+      keep_tile(t, acc);      // at most MTG tiles per workgroup (host): reduced and merged after the stream, when the load registers are free
     };
-    using Q0 = std::integral_constant<int, 0>; using Q1 = std::integral_constant<int, 1>;
-    using Q2 = std::integral_constant<int, 2>; using Q3 = std::integral_constant<int, 3>;
     while (tq[0] >= 0) { unit(Q0{}); unit(Q1{}); unit(Q2{}); unit(Q3{}); }
-    asm volatile("s_waitcnt vmcnt(0)" ::"v"(U[0][0]), "v"(U[0][1]), "v"(U[0][2]), "v"(U[0][3]), "v"(U[0][4]), "v"(U[0][5]), "v"(U[0][6]), "v"(U[0][7]),
-                 "v"(U[1][0]), "v"(U[1][1]), "v"(U[1][2]), "v"(U[1][3]), "v"(U[1][4]), "v"(U[1][5]), "v"(U[1][6]), "v"(U[1][7]),
-                 "v"(U[2][0]), "v"(U[2][1]), "v"(U[2][2]), "v"(U[2][3]), "v"(U[2][4]), "v"(U[2][5]), "v"(U[2][6]), "v"(U[2][7]) : "memory");
-    asm volatile("" ::"v"(U[3][0]), "v"(U[3][1]), "v"(U[3][2]), "v"(U[3][3]), "v"(U[3][4]), "v"(U[3][5]), "v"(U[3][6]), "v"(U[3][7]) : "memory");
+    drain(U);
   } else if constexpr (TRL) {
     char* tb = smem + TB_OFF + wave * 8192;                 // this wave's transposition buffer: [16 rows][32 pieces of 16 B], piece ^ row
     // one unit: wait for its 8 loads (the 24 younger ones stay in flight), rows -> LDS, refill the registers with the same unit of the
@@ -915,20 +917,15 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       constexpr int q = decltype(SLOT)::value, sub = decltype(SUB)::value;
       asm volatile("s_waitcnt vmcnt(%8)" : "+v"(U[q][0]), "+v"(U[q][1]), "+v"(U[q][2]), "+v"(U[q][3]), "+v"(U[q][4]), "+v"(U[q][5]), "+v"(U[q][6]), "+v"(U[q][7])
                    : "n"((NR - 1) * 8) : "memory");
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int r = 2 * i + lrow;
-        *(u32x4*)(tb + r * 512 + ((lp ^ r) << 4)) = U[q][i];
-      }
+      recut_store<512>(tb, lane, U[q]);
 #pragma unroll
       for (int i = 0; i < 8; ++i) ld_nt_asm(U[q][i], unit_ptr(tnext, 1 - sub, i));
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const u32x4 f = *(const u32x4*)(tb + r16 * 512 + (((4 * c + g) ^ r16) << 4));
+        const u32x4 f = recut_frag<512, u32x4>(tb, r16, g, c);
         acc = mfma16(f, xf[sub * 8 + c], acc);
       }
     };
-    using Q0 = std::integral_constant<int, 0>; using Q1 = std::integral_constant<int, 1>; using Q2 = std::integral_constant<int, 2>;
     // one tile at ring phase P (its halves sit in slots 2 P % 3 and (2 P + 1) % 3); false after the last tile
     auto ttile = [&](auto S0, auto S1) __attribute__((always_inline)) -> bool {
       if (ua < 0) return false;
@@ -941,11 +938,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       return true;
     };
     while (ttile(Q0{}, Q1{}) && ttile(Q2{}, Q0{}) && ttile(Q1{}, Q2{})) {}
-    // drain: placeholder loads for tiles that do not exist may still be in flight into U; naming all 24 registers keeps the compiler
-    // from reusing any of them before the wait has executed
-    asm volatile("s_waitcnt vmcnt(0)" ::"v"(U[0][0]), "v"(U[0][1]), "v"(U[0][2]), "v"(U[0][3]), "v"(U[0][4]), "v"(U[0][5]), "v"(U[0][6]), "v"(U[0][7]),
-                 "v"(U[1][0]), "v"(U[1][1]), "v"(U[1][2]), "v"(U[1][3]), "v"(U[1][4]), "v"(U[1][5]), "v"(U[1][6]), "v"(U[1][7]),
-                 "v"(U[2][0]), "v"(U[2][1]), "v"(U[2][2]), "v"(U[2][3]), "v"(U[2][4]), "v"(U[2][5]), "v"(U[2][6]), "v"(U[2][7]) : "memory");
+    drain(U);
   } else if constexpr (HOLD) {
     // one tile at ring phase P (its chunk c sits in slot (16 P + c) % 24); returns false after the last tile
     auto tile_phase = [&](auto P, auto STATIC) __attribute__((always_inline)) -> bool {
@@ -973,9 +966,7 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       }
       if constexpr (stat) {                                  // straight-line part: at most MTG tiles, no flush in between
         asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc));     // the last MFMA's result before the compiler's own code reads it
-        red[(done * MW + wave) * 64 + lane] = acc;
-        if (tid == 0) tl[done] = t0;
-        ++done;
+        keep_tile(t0, acc);
       } else {
         finish_tile(t0, acc);
       }
@@ -985,7 +976,6 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       if constexpr (FP8) { sc0 = sc1; sc1 = sc2; sc2 = wscale(t2); }
       return true;
     };
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
     if constexpr (ASM_STREAM) {
       // The first 12 tiles (every production launch has at most 11 per workgroup) as STRAIGHT-LINE code with hand-counted loads.
       // Left to the compiler, the wait-count pass puts vmcnt(7) in front of the first eight MFMAs of every tile - in the looped AND in
@@ -995,20 +985,19 @@ __global__ __launch_bounds__(MW * 64) void gemv_mfma_kernel(const MfmaDev d, FMT
       static_assert(MTG >= 12 || TRL, "the straight-line part must fit one reduction group");
       using T = std::true_type;
       do {
-        if (!tile_phase(I0{}, T{})) break; if (!tile_phase(I1{}, T{})) break; if (!tile_phase(I2{}, T{})) break;
-        if (!tile_phase(I0{}, T{})) break; if (!tile_phase(I1{}, T{})) break; if (!tile_phase(I2{}, T{})) break;
-        if (!tile_phase(I0{}, T{})) break; if (!tile_phase(I1{}, T{})) break; if (!tile_phase(I2{}, T{})) break;
-        if (!tile_phase(I0{}, T{})) break; if (!tile_phase(I1{}, T{})) break; if (!tile_phase(I2{}, T{})) break;
+        if (!tile_phase(Q0{}, T{})) break; if (!tile_phase(Q1{}, T{})) break; if (!tile_phase(Q2{}, T{})) break;
+        if (!tile_phase(Q0{}, T{})) break; if (!tile_phase(Q1{}, T{})) break; if (!tile_phase(Q2{}, T{})) break;
+        if (!tile_phase(Q0{}, T{})) break; if (!tile_phase(Q1{}, T{})) break; if (!tile_phase(Q2{}, T{})) break;
+        if (!tile_phase(Q0{}, T{})) break; if (!tile_phase(Q1{}, T{})) break; if (!tile_phase(Q2{}, T{})) break;
       } while (false);
-      // drain: loads for tiles that do not exist (row 0) may still be in flight into ring registers; naming all 24 as inputs keeps
-      // the compiler from reusing any of them before the wait has executed
+      // (not drain(ring): naming the 24 registers behind the wait instead of in it gave this instantiation one more s_nop - class C)
       asm volatile("s_waitcnt vmcnt(0)" ::"v"(ring[0]), "v"(ring[1]), "v"(ring[2]), "v"(ring[3]), "v"(ring[4]), "v"(ring[5]), "v"(ring[6]), "v"(ring[7]),
                    "v"(ring[8]), "v"(ring[9]), "v"(ring[10]), "v"(ring[11]), "v"(ring[12]), "v"(ring[13]), "v"(ring[14]), "v"(ring[15]),
                    "v"(ring[16]), "v"(ring[17]), "v"(ring[18]), "v"(ring[19]), "v"(ring[20]), "v"(ring[21]), "v"(ring[22]), "v"(ring[23])
                    : "memory");
     }
     using F = std::false_type;
-    while (tile_phase(I0{}, F{}) && tile_phase(I1{}, F{}) && tile_phase(I2{}, F{})) {}
+    while (tile_phase(Q0{}, F{}) && tile_phase(Q1{}, F{}) && tile_phase(Q2{}, F{})) {}
   } else {
     // activations streamed beside the weights (K slices longer than CH chunks: down_proj): a ring of CH (weight, activation) pairs,
     // each refilled CH chunks ahead as soon as it has been multiplied
@@ -1080,134 +1069,147 @@ extern "C" int64_t usdm_gemv_batch_ks_floats(int32_t N, int32_t K) {
 }
 
 namespace {
-// the matrix-core launch of usdm_gemv_batch (bf16), usdm_gemv_fp8_mfma (FP8: fmt = the row exponents) and usdm_gemv_mxfp4_mfma
-// (fmt = gemv_mx4mc; a.W / a.ldw stand in for a bf16 matrix of the same shape); all take the same decisions (tiles, rows per tile,
-// K split, K chunks per wave) for the same shape
-template <bool FP8, class... FMT>
-int mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st, const char* who, FMT... fmt) {
-  constexpr bool MX4 = gemv_is_mx4mc<FMT...>::value;
-  const usdm_gemv_args& a = pa->g;
-  USDM_CHECK_ARG(pa->nb >= 1 && pa->nb <= 16, "%s (matrix-core form): 1..16 sequences per step", who);
-  USDM_CHECK_ARG(a.K % (MW * 32) == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && pa->x_bs % 8 == 0,
-                 "%s (matrix-core form): K %% %d, ldw %% 8, x stride %% 8", who, MW * 32);
-  const bool glu = a.act == USDM_ACT_SWIGLU, lmh = a.part_val != nullptr;
-  MfmaDev d;
-  d.ba = *pa;
-  d.nchunks = a.K / 32;
-  d.cpw = cdiv(d.nchunks, MW);
-  const bool hold = d.cpw <= CH;
-  USDM_CHECK_ARG(!a.norm_w || (hold && a.K <= GAM_FLOATS && a.K % 4 == 0), "%s (matrix-core form): the fused RMSNorm needs K <= 4096", who);
-  USDM_CHECK_ARG(!lmh || (a.part_idx && !glu), "%s: lm_head partial buffers", who);
-  USDM_CHECK_ARG(!glu || a.N % 32 == 0, "%s (matrix-core form): swiglu needs N %% 32 == 0 (packed gate/up rows)", who);   // (else the last up rows lie past W)
-  d.nout = glu ? a.N / 2 : a.N;
-  d.rt = 16;
-  d.ksplit = 1;
-  const int64_t ksf = usdm_gemv_batch_ks_floats(a.N, a.K);
-  if (ksf && pa->ks_part && pa->ks_cnt && !glu && !lmh && !a.norm_w && pa->form != 3 && pa->form != 5) {
-    USDM_CHECK_ARG(pa->ks_part_floats >= ksf && (((uintptr_t)pa->ks_part) & 15) == 0, "%s: ks_part must hold %lld floats (16-byte aligned)", who, (long long)ksf);
-    d.ksplit = a.K / KS_K;
-    if (cdiv(cdiv(a.N, 16), min(256 / d.ksplit, cdiv(a.N, 16))) > MTG_TRL) d.ksplit = 1;      // one reduction group per workgroup
+enum { MFMA_BF16 = 0, MFMA_FP8 = 1, MFMA_MX4 = 2 };
+// floats of ks_part if the launch may split K over workgroups (given the ks_* buffers), else 0
+int64_t mfma_ks_floats(int N, int K, bool glu, bool norm, bool lmh, int form) {
+  return !glu && !lmh && !norm && form != 3 && form != 5 ? usdm_gemv_batch_ks_floats(N, K) : 0;
+}
+
+// The matrix-core launch selection: tiles, rows per tile, K split, K chunks per wave, grid and kernel variant of a shape - the same
+// decisions for usdm_gemv_batch (bf16), usdm_gemv_fp8_mfma and usdm_gemv_mxfp4_mfma.  Host only (usdm_gemv_mfma_select asks it where
+// there is no device); refuses, with the launcher's message, the shapes the launcher refuses.
+int mfma_select(const char* who, int N, int K, bool glu, bool norm, bool lmh, bool ks_given, int form, int fmt, usdm_gemv_mfma_plan& p) {
+  USDM_CHECK_ARG(K % (MW * 32) == 0, "%s (matrix-core form): K %% %d, ldw %% 8, x stride %% 8", who, MW * 32);
+  p.cpw = cdiv(K / 32, MW);
+  const bool hold = p.cpw <= CH;
+  USDM_CHECK_ARG(!norm || (hold && K <= GAM_FLOATS && K % 4 == 0), "%s (matrix-core form): the fused RMSNorm needs K <= 4096", who);
+  USDM_CHECK_ARG(!glu || N % 32 == 0, "%s (matrix-core form): swiglu needs N %% 32 == 0 (packed gate/up rows)", who);   // (else the last up rows lie past W)
+  p.nout = glu ? N / 2 : N;
+  p.rt = 16;
+  p.ksplit = 1;
+  if (ks_given && mfma_ks_floats(N, K, glu, norm, lmh, form)) {
+    p.ksplit = K / KS_K;
+    if (cdiv(cdiv(N, 16), min(256 / p.ksplit, cdiv(N, 16))) > MTG_TRL) p.ksplit = 1;      // one reduction group per workgroup
   }
   if (glu) {
-    d.ntiles = cdiv(d.nout, 8);
+    p.ntiles = cdiv(p.nout, 8);
   } else if (lmh) {
-    d.ntiles = cdiv(a.N, 16);
+    p.ntiles = cdiv(N, 16);
   } else {
     // rows per tile: 16, or 12 / 8 where that shortens the longest workgroup (N = 6144: 384 tiles of 16 = 2 rounds of 16 rows, 512
     // tiles of 12 = 2 rounds of 12)
     int best = 1 << 30;
     for (int rt : {16, 12, 8}) {
-      const int nt = cdiv(a.N, rt), per = cdiv(nt, nt < 256 ? nt : 256) * rt;
-      if (per < best) { best = per; d.rt = rt; }
+      const int nt = cdiv(N, rt), per = cdiv(nt, nt < 256 ? nt : 256) * rt;
+      if (per < best) { best = per; p.rt = rt; }
     }
-    d.ntiles = cdiv(a.N, d.rt);
+    p.ntiles = cdiv(N, p.rt);
   }
-  d.grid = d.ntiles < 256 ? d.ntiles : 256;
-  d.kwg = d.grid;
-  if (d.ksplit > 1) {      // 16-row tiles; 256 / ksplit workgroups per slice, each with every kwg-th tile
-    d.rt = 16;
-    d.ntiles = cdiv(a.N, 16);
-    d.kwg = min(256 / d.ksplit, d.ntiles);
-    d.grid = d.kwg * d.ksplit;
-    d.cpw = KS_K / 32 / MW;
+  p.grid = p.ntiles < 256 ? p.ntiles : 256;
+  p.kwg = p.grid;
+  if (p.ksplit > 1) {      // 16-row tiles; 256 / ksplit workgroups per slice, each with every kwg-th tile
+    p.rt = 16;
+    p.ntiles = cdiv(N, 16);
+    p.kwg = min(256 / p.ksplit, p.ntiles);
+    p.grid = p.kwg * p.ksplit;
+    p.cpw = KS_K / 32 / MW;
   }
-  USDM_CHECK_ARG(cdiv(d.ntiles, d.kwg) <= 64, "%s (matrix-core form): N too large (more than 64 tiles per workgroup)", who);
-  USDM_CHECK_ARG(!lmh || pa->part_bs >= d.grid, "%s: part_bs must hold one partial per workgroup (%d)", who, d.grid);
-  // K = 4096 (every RMSNorm-fed projection and o_proj of the 7B): row-contiguous loads re-cut through LDS; form 3 forces the
-  // fragment-shaped loads there (A/B: tools/gemv_mfma_bench.py)
-  const bool trl = (hold ? d.cpw == 16 : d.cpw == 56) && pa->form != 3 && !MX4;
-  if constexpr (MX4) {      // the image is cut into fragments already: no re-cut through LDS; K = 4096 and the K split have CPWT forms
-    void (*kfn)(const MfmaDev, FMT...) = d.ksplit > 1 ? gemv_mfma_kernel<true, 8, false, false, FMT...>
-                                         : !hold      ? gemv_mfma_kernel<false, 0, false, false, FMT...>
-                                         : d.cpw == 16 ? gemv_mfma_kernel<true, 16, false, false, FMT...>
-                                                       : gemv_mfma_kernel<true, 0, false, false, FMT...>;
-    static bool mx_attr = false;
-    if (!mx_attr) {
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 8, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 0, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 0, false, false, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      mx_attr = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3(d.grid), dim3(MW * 64), LDS_BYTES, st, d, fmt...);
-    USDM_LAUNCH_CHECK();
-    return 0;
-  } else {
-  if (d.ksplit > 1) {
-    static bool ks_attr = false;
-    if (!ks_attr) { (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 8, true, FP8, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL); ks_attr = true; }
-    hipLaunchKernelGGL((gemv_mfma_kernel<true, 8, true, FP8, FMT...>), dim3(d.grid), dim3(MW * 64), LDS_BYTES_TRL, st, d, fmt...);
-    USDM_LAUNCH_CHECK();
-    return 0;
-  }
-  void (*kfn)(const MfmaDev, FMT...);
-  static bool attr_done = false;
-  if constexpr (FP8) {      // (the fragment-shaped variants of K = 4096 / 14336 are form 3 only: bf16)
-    kfn = trl ? (hold ? gemv_mfma_kernel<true, 16, true, true, FMT...> : gemv_mfma_kernel<false, 56, true, true, FMT...>)
-              : (hold ? gemv_mfma_kernel<true, 0, false, true, FMT...> : gemv_mfma_kernel<false, 0, false, true, FMT...>);
-    if (!attr_done) {
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, true, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, true, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 0, false, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 0, false, true, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      attr_done = true;
-    }
-  } else {
-    kfn = trl ? (hold ? gemv_mfma_kernel<true, 16, true> : gemv_mfma_kernel<false, 56, true>)
-              : hold ? (d.cpw == 16 ? gemv_mfma_kernel<true, 16, false> : gemv_mfma_kernel<true, 0, false>)
-                     : (d.cpw == 56 ? gemv_mfma_kernel<false, 56, false> : gemv_mfma_kernel<false, 0, false>);
-    if (!attr_done) {
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_TRL);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<true, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 56, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemv_mfma_kernel<false, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      attr_done = true;
-    }
-  }
-  hipLaunchKernelGGL(kfn, dim3(d.grid), dim3(MW * 64), trl ? LDS_BYTES_TRL : LDS_BYTES, st, d, fmt...);
+  USDM_CHECK_ARG(cdiv(p.ntiles, p.kwg) <= 64, "%s (matrix-core form): N too large (more than 64 tiles per workgroup)", who);
+  // The variant.  K = 4096 (every RMSNorm-fed projection and o_proj of the 7B) and K = 14336: K chunks per wave as a constant and
+  // row-contiguous loads re-cut through LDS; form 3 forces the fragment-shaped loads there (A/B: tools/gemv_mfma_bench.py).  MXFP4:
+  // the image is cut into fragments already - no re-cut, constants for K = 4096 and the K split only.
+  const bool mx4 = fmt == MFMA_MX4, fixed = p.ksplit == 1 && p.cpw == (hold ? 16 : 56);
+  p.hold = hold || p.ksplit > 1;
+  p.trl = !mx4 && (p.ksplit > 1 || (fixed && form != 3));
+  p.cpwt = p.ksplit > 1 ? 8 : fixed && !(mx4 && !hold) ? p.cpw : 0;
+  if (fmt == MFMA_FP8 && !p.trl) p.cpwt = 0;      // (FP8 has no fragment-shaped variant with constant chunks: they are form 3, bf16 only)
+  p.lds_bytes = p.trl ? LDS_BYTES_TRL : LDS_BYTES;
+  return 0;
+}
+
+// Every instantiation of gemv_mfma_kernel, named here and nowhere else: X(HOLD, CPWT, TRL, format).  A new format or schedule adds
+// its lines here; mfma_select is what picks among them.
+#define USDM_MFMA_VARIANTS(X)                                                                                          \
+  X(true, 0, false, MFMA_BF16) X(true, 16, false, MFMA_BF16) X(true, 16, true, MFMA_BF16) X(true, 8, true, MFMA_BF16)   \
+  X(false, 0, false, MFMA_BF16) X(false, 56, false, MFMA_BF16) X(false, 56, true, MFMA_BF16)                            \
+  X(true, 0, false, MFMA_FP8) X(true, 16, true, MFMA_FP8) X(true, 8, true, MFMA_FP8)                                    \
+  X(false, 0, false, MFMA_FP8) X(false, 56, true, MFMA_FP8)                                                            \
+  X(true, 0, false, MFMA_MX4) X(true, 16, false, MFMA_MX4) X(true, 8, false, MFMA_MX4) X(false, 0, false, MFMA_MX4)
+
+// sets the dynamic-LDS limit of its own instantiation once (a function-local static: initialised once under any number of host
+// threads) and launches it
+template <bool HOLD, int CPWT, bool TRL, bool FP8, class... FMT>
+int launch_one(const MfmaDev& d, hipStream_t st, FMT... fmt) {
+  constexpr int lds = TRL ? LDS_BYTES_TRL : LDS_BYTES;
+  static const hipError_t attr =
+      hipFuncSetAttribute((const void*)gemv_mfma_kernel<HOLD, CPWT, TRL, FP8, FMT...>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  (void)attr;
+  hipLaunchKernelGGL((gemv_mfma_kernel<HOLD, CPWT, TRL, FP8, FMT...>), dim3(d.grid), dim3(MW * 64), lds, st, d, fmt...);
   USDM_LAUNCH_CHECK();
   return 0;
+}
+
+// the matrix-core launch of usdm_gemv_batch (bf16), usdm_gemv_fp8_mfma (FP8: fmt = the row exponents) and usdm_gemv_mxfp4_mfma
+// (fmt = gemv_mx4mc; a.W / a.ldw stand in for a bf16 matrix of the same shape): checks the buffers, asks mfma_select, launches
+template <bool FP8, class... FMT>
+int mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st, const char* who, FMT... fmt) {
+  constexpr int FMT_ID = gemv_is_mx4mc<FMT...>::value ? MFMA_MX4 : FP8 ? MFMA_FP8 : MFMA_BF16;
+  const usdm_gemv_args& a = pa->g;
+  USDM_CHECK_ARG(pa->nb >= 1 && pa->nb <= 16, "%s (matrix-core form): 1..16 sequences per step", who);
+  USDM_CHECK_ARG(a.K % (MW * 32) == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && pa->x_bs % 8 == 0,
+                 "%s (matrix-core form): K %% %d, ldw %% 8, x stride %% 8", who, MW * 32);
+  const bool glu = a.act == USDM_ACT_SWIGLU, lmh = a.part_val != nullptr;
+  USDM_CHECK_ARG(!lmh || (a.part_idx && !glu), "%s: lm_head partial buffers", who);
+  usdm_gemv_mfma_plan p;
+  if (const int rc = mfma_select(who, a.N, a.K, glu, a.norm_w != nullptr, lmh, pa->ks_part && pa->ks_cnt, pa->form, FMT_ID, p)) return rc;
+  if (pa->ks_part && pa->ks_cnt) {
+    const int64_t ksf = mfma_ks_floats(a.N, a.K, glu, a.norm_w != nullptr, lmh, pa->form);
+    USDM_CHECK_ARG(!ksf || (pa->ks_part_floats >= ksf && (((uintptr_t)pa->ks_part) & 15) == 0), "%s: ks_part must hold %lld floats (16-byte aligned)", who, (long long)ksf);
   }
+  USDM_CHECK_ARG(!lmh || pa->part_bs >= p.grid, "%s: part_bs must hold one partial per workgroup (%d)", who, p.grid);
+  MfmaDev d;
+  d.ba = *pa;
+  d.ntiles = p.ntiles; d.rt = p.rt; d.cpw = p.cpw; d.nchunks = a.K / 32; d.grid = p.grid; d.nout = p.nout;
+  d.ksplit = p.ksplit; d.kwg = p.kwg;
+#define USDM_MFMA_CASE(HOLD, CPWT, TRL, F)                                         \
+  if constexpr (F == FMT_ID)                                                       \
+    if (p.hold == HOLD && p.cpwt == CPWT && p.trl == TRL) return launch_one<HOLD, CPWT, TRL, FP8, FMT...>(d, st, fmt...);
+  USDM_MFMA_VARIANTS(USDM_MFMA_CASE)
+#undef USDM_MFMA_CASE
+  usdm_set_error("%s: no instantiation for hold %d, %d chunks per wave, re-cut %d", __FILE__, p.hold, p.cpwt, p.trl);      // a mistake in mfma_select
+  return 1;
+}
+
+// the argument checks the two quantized entry points share
+int mfma_check_quantized(const char* who, const usdm_gemv_batch_args& b) {
+  const usdm_gemv_args& a = b.g;
+  USDM_CHECK_ARG(b.nb >= 1 && b.nb <= 16, "%s: 1..16 sequences per step", who);
+  USDM_CHECK_ARG(b.form == 0 || b.form == 5, "%s: form 0 (K split where ks_* allow it) or 5 (no K split)", who);
+  USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.mrg_pm && !a.mrg_pl && !a.cmb_gran && !a.x_delta && !a.x_out,
+                 "%s: p2p / merged-attention input / cmb_gran / x_delta are not supported", who);
+  USDM_CHECK_ARG(a.act != USDM_ACT_SWIGLU || a.N % 32 == 0, "%s: swiglu needs N %% 32 == 0 (packed gate/up rows)", who);
+  return 0;
 }
 }  // namespace
 
 // called by usdm_gemv_batch (llm_batch_k.hip) for 5..16 sequences, or when the caller forces the matrix-core form
 int usdm_gemv_mfma_launch(const usdm_gemv_batch_args* pa, hipStream_t st) { return mfma_launch<false>(pa, st, "usdm_gemv_batch"); }
 
+extern "C" int usdm_gemv_mfma_select(int32_t N, int32_t K, int32_t flags, int32_t form, int32_t fmt, usdm_gemv_mfma_plan* out) {
+  USDM_CHECK_ARG(out && N > 0 && K > 0 && fmt >= MFMA_BF16 && fmt <= MFMA_MX4 && (flags & ~15) == 0 && !((flags & 1) && (flags & 4)),
+                 "usdm_gemv_mfma_select: null plan, bad N / K / flags, or fmt not 0 (bf16), 1 (FP8), 2 (MXFP4)");
+  return mfma_select("usdm_gemv_mfma_select", N, K, flags & 1, flags & 2, flags & 4, flags & 8, form, fmt, *out);
+}
+extern "C" int usdm_sizeof_gemv_mfma_plan(void) { return (int)sizeof(usdm_gemv_mfma_plan); }
+
 extern "C" int usdm_gemv_fp8_mfma(const usdm_gemv_fp8_args* pa, usdm_stream_t stream) {
   USDM_CHECK_ARG(pa && pa->b.g.W && pa->b.g.x && pa->row_exp, "usdm_gemv_fp8_mfma: null args");
   const usdm_gemv_batch_args& b = pa->b;
   const usdm_gemv_args& a = b.g;
-  USDM_CHECK_ARG(b.nb >= 1 && b.nb <= 16, "usdm_gemv_fp8_mfma: 1..16 sequences per step");
-  USDM_CHECK_ARG(b.form == 0 || b.form == 5, "usdm_gemv_fp8_mfma: form 0 (K split where ks_* allow it) or 5 (no K split)");
-  USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.mrg_pm && !a.mrg_pl && !a.cmb_gran && !a.x_delta && !a.x_out,
-                 "usdm_gemv_fp8_mfma: p2p / merged-attention input / cmb_gran / x_delta are not supported");
+  if (const int rc = mfma_check_quantized("usdm_gemv_fp8_mfma", b)) return rc;
   USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.ldw % 16 == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.x & 15) == 0,
                  "usdm_gemv_fp8_mfma: bad N/K, or W / ldw / x not 16-byte aligned");
   USDM_CHECK_ARG(a.y16 || a.y32 || a.part_val, "usdm_gemv_fp8_mfma: no output");
-  USDM_CHECK_ARG(a.act != USDM_ACT_SWIGLU || a.N % 32 == 0, "usdm_gemv_fp8_mfma: swiglu needs N %% 32 == 0 (packed gate/up rows)");
   return mfma_launch<true>(&b, (hipStream_t)stream, "usdm_gemv_fp8_mfma", pa->row_exp);
 }
 
@@ -1215,10 +1217,7 @@ extern "C" int usdm_gemv_mxfp4_mfma(const usdm_gemv_mxfp4_mfma_args* pa, usdm_st
   USDM_CHECK_ARG(pa && pa->codes && pa->scales && pa->b.g.x, "usdm_gemv_mxfp4_mfma: null args");
   usdm_gemv_batch_args b = pa->b;
   usdm_gemv_args& a = b.g;
-  USDM_CHECK_ARG(b.nb >= 1 && b.nb <= 16, "usdm_gemv_mxfp4_mfma: 1..16 sequences per step");
-  USDM_CHECK_ARG(b.form == 0 || b.form == 5, "usdm_gemv_mxfp4_mfma: form 0 (K split where ks_* allow it) or 5 (no K split)");
-  USDM_CHECK_ARG(!a.p2p && !a.p2p_mode && !a.mrg_po && !a.mrg_pm && !a.mrg_pl && !a.cmb_gran && !a.x_delta && !a.x_out,
-                 "usdm_gemv_mxfp4_mfma: p2p / merged-attention input / cmb_gran / x_delta are not supported");
+  if (const int rc = mfma_check_quantized("usdm_gemv_mxfp4_mfma", b)) return rc;
   USDM_CHECK_ARG(!a.part_val && !a.part_idx && !a.ban && !a.y32, "usdm_gemv_mxfp4_mfma: the lm_head mode (part_val / ban / y32) is not supported with MXFP4 weights");
   USDM_CHECK_ARG(a.N > 0 && a.K > 0 && a.K % (MW * 32) == 0, "usdm_gemv_mxfp4_mfma: bad N, or K not a multiple of %d", MW * 32);
   USDM_CHECK_ARG(pa->ldc % 16 == 0 && pa->ldc >= a.K / 2 && pa->lds % 4 == 0 && pa->lds >= a.K / 32,
@@ -1226,7 +1225,6 @@ extern "C" int usdm_gemv_mxfp4_mfma(const usdm_gemv_mxfp4_mfma_args* pa, usdm_st
   USDM_CHECK_ARG(((uintptr_t)pa->codes & 15) == 0 && ((uintptr_t)pa->scales & 3) == 0 && ((uintptr_t)a.x & 15) == 0,
                  "usdm_gemv_mxfp4_mfma: codes and x must be 16-byte, scales 4-byte aligned");
   USDM_CHECK_ARG(a.y16, "usdm_gemv_mxfp4_mfma: no output (y16)");
-  USDM_CHECK_ARG(a.act != USDM_ACT_SWIGLU || a.N % 32 == 0, "usdm_gemv_mxfp4_mfma: swiglu needs N %% 32 == 0 (packed gate/up rows)");
   a.W = pa->codes;      // (the kernel reads the image through its own argument; the launcher's shape checks see a [N][K] matrix)
   a.ldw = a.K;
   return mfma_launch<false>(&b, (hipStream_t)stream, "usdm_gemv_mxfp4_mfma", gemv_mx4mc{(const uint8_t*)pa->codes, pa->scales, pa->ldc, pa->lds});

@@ -39,7 +39,7 @@ from collections import namedtuple
 import torch
 
 from . import ops
-from ._lib import ACT_SWIGLU
+from ._lib import ACT_SWIGLU, UsdmError
 from .graph import GraphedPlan, GraphedSegments
 from .plancache import LRU
 from .prefix import reusable_past
@@ -1202,18 +1202,23 @@ class USDMForCausalLM:
     MAX_BATCH = 16      # sequences per decode step (usdm_gemv_batch: VALU form up to 4, matrix-core form up to 16)
 
     def max_batch(self):
-        """Sequences one decode step can take with THIS model's (per-rank) shapes: 16 on the matrix-core form, which splits K over
-        8 waves in chunks of 32 (every projection's K must be a multiple of 256), else the 4 of the VALU form."""
-        c = self.cfg
-        ks = (c["hidden_size"], self.Hq * c["head_dim"], self.I)
+        """Sequences one decode step can take with THIS model's (per-rank) shapes: 16 where the matrix-core launcher takes every
+        projection and the lm_head shard (its own answer: ops.gemv_mfma_select), else the 4 of the VALU form."""
+        H, d, _, Hq, _, I, nq = self._dims()
+        fmt = "bf16"
         if self.quantization in ("fp8", "mxfp4"):
             if not (self.fp8_matrix_cores if self.quantization == "fp8" else self.mxfp4_matrix_cores):
                 return 4                        # usdm_gemv_fp8 / usdm_gemv_mxfp4: the VALU form only
-            # usdm_gemv_fp8_mfma / usdm_gemv_mxfp4_mfma refuse what the launcher cannot run: K % 256, the fused RMSNorm with K > 4096, more than 64
-            # lm_head tiles of 16 rows per workgroup
-            fits = all(k % 256 == 0 for k in ks) and c["hidden_size"] <= 4096 and -(-(self.v1 - self.v0) // 16) <= 64 * 256
-            return self.MAX_BATCH if fits else 4
-        return self.MAX_BATCH if all(k % 256 == 0 for k in ks) else 4
+            fmt = self.quantization
+        # (N, K, mode, format) of qkv, o_proj, gate/up, down_proj and the lm_head shard (fp8 in an mxfp4 model) as _layers launches them
+        shapes = ((nq, H, dict(norm=True), fmt), (H, Hq * d, {}, fmt), (2 * I, H, dict(norm=True, glu=True), fmt), (H, I, dict(ks=True), fmt),
+                  (self.v1 - self.v0, H, dict(norm=True, lm_head=True), "fp8" if fmt == "mxfp4" else fmt))
+        try:
+            for N, K, mode, f in shapes:
+                ops.gemv_mfma_select(N, K, form=1 if f == "bf16" else 0, fmt=f, **mode)
+        except UsdmError:
+            return 4
+        return self.MAX_BATCH
 
     @torch.no_grad()
     def generate_batch(self, input_ids_list, max_new_tokens, bad_words_ids=None, eos_token_id=None, min_new_tokens=0, group=None,

@@ -815,6 +815,19 @@ def gemv_batch_ks_floats(N, K):
     return int(lib.usdm_gemv_batch_ks_floats(C_.c_int32(N), C_.c_int32(K)))
 
 
+GEMV_MFMA_FMT = {"bf16": 0, "fp8": 1, "mxfp4": 2}
+
+
+def gemv_mfma_select(N, K, *, glu=False, norm=False, lm_head=False, ks=False, form=1, fmt="bf16"):
+    """usdm_gemv_mfma_select: what the matrix-core launcher decides for this shape (host only, no device needed) -> the
+    usdm_gemv_mfma_plan as a dict; UsdmError with the launcher's message for a shape it refuses."""
+    p = _lib.GemvMfmaPlan()
+    flags = int(bool(glu)) | int(bool(norm)) << 1 | int(bool(lm_head)) << 2 | int(bool(ks)) << 3
+    _lib.check(lib.usdm_gemv_mfma_select(C_.c_int32(N), C_.c_int32(K), C_.c_int32(flags), C_.c_int32(form),
+                                         C_.c_int32(GEMV_MFMA_FMT[fmt]), C_.byref(p)), "usdm_gemv_mfma_select")
+    return {n: getattr(p, n) for n, _ in p._fields_}
+
+
 def attn_decode(qkv, pos, cos, sin, kcache, vcache, pm, pl, po, out, *, Hq, Hkv, ctx_max, NS, scale, counters=None, batch=0,
                 qkv_bs=0, out_bs=0, cache_bs=0, skip=None, defer_merge=False, window=0, cmb_gran=None, kv8=None, exp_bs=0, plan=None):
     """usdm_attn_decode; kv8=(kexp, vexp): usdm_attn_decode_fp8 on uint8 e4m3 caches (cache_bs in bytes, exp_bs between the
