@@ -104,14 +104,17 @@ typedef struct usdm_gemm_args {
   const float* ln_stats; int32_t ln_nt, ln_mode, ln_C; float ln_eps;
   const float* ln_c; const float* ln_gamma; const float* ln_beta;
   int32_t* ln_guard; float ln_guard_ratio;
-  /* 0: the launcher picks the tile from the shape (measured heuristics, csrc/gemm.hip); t + 1: force tile t (benchmarks and the
-   * tile-equivalence tests; the Python wrapper fills it from USDM_GEMM_TILE so the library itself reads no environment per launch) */
+  /* 0: the launcher picks the tile from the shape (measured heuristics, csrc/gemm.hip gemm_select); t + 1: force tile t, a row of
+   * USDM_GEMM_TILES in csrc/gemm.hip (benchmarks and the tile-equivalence tests; the Python wrapper fills it from USDM_GEMM_TILE
+   * so the library itself reads no environment per launch) */
   int32_t tile_sel;
 } usdm_gemm_args;
 
 int usdm_gemm(const usdm_gemm_args* args, usdm_stream_t stream);
-int usdm_gemm_tile_for(const usdm_gemm_args* args); /* the tile usdm_gemm would pick (12..14 = ping-pong tiles: the only ones with the
-                                                        stats_out / ln_mode epilogues), < 0 for invalid arguments; launches nothing */
+int usdm_gemm_tile_for(const usdm_gemm_args* args); /* the tile usdm_gemm would pick (the ping-pong rows of the table are the only ones
+                                                        with the stats_out / ln_mode epilogues), < 0 for invalid arguments; launches nothing */
+int usdm_gemm_tile_info(int tile, int dtype, int32_t* out); /* out[8] = BM, BN, waves, DMA, LDS stages, chunks per stage, ping-pong, 0
+                                                                of row `tile`; refuses a tile that does not exist for `dtype`; host only */
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm / RMSNorm over channels of [rows][C] activations (one wave per row).

@@ -204,7 +204,25 @@ def make_process_unit():
     save("process_unit.npz", **outs)
 
 
+def make_gemm_tiles(lib_path):
+    """Which tile usdm_gemm's heuristic chooses (usdm_gemm_tile_for: host only, nothing is launched), asked of the library at lib_path
+    - one built from the commit BEFORE a change of csrc/gemm.hip's launcher, never the one under test - over the grid below in the
+    order of tests/test_gemm_exact_cpu.py tile_queries: one int8 per query, refusals as their negative code."""
+    import ctypes
+    from tests.test_gemm_exact_cpu import tile_sweep
+    # the sizes on either side of every threshold of the chain, plus the rows of DESIGN.md's GEMM tables (499, 1100, 1118, 2236, 4096)
+    M = (1, 16, 33, 64, 100, 128, 129, 200, 256, 300, 384, 499, 512, 600, 768, 1000, 1100, 1118, 1500, 2048, 2236, 3000, 4096, 4472, 8192,
+         20000, 60000)
+    N = (24, 48, 64, 65, 128, 192, 256, 512, 768, 1024, 2048, 3072, 4096, 6144, 14336, 28672, 42003)
+    Kc = (32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 14336)
+    tile = tile_sweep(ctypes.CDLL(os.path.abspath(lib_path)), M, N, Kc)
+    save("gemm_tiles.npz", M=np.array(M, dtype=np.int32), N=np.array(N, dtype=np.int32), Kc=np.array(Kc, dtype=np.int32), tile=tile)
+
+
 if __name__ == "__main__":
+    if "--gemm-tiles" in sys.argv:      # --gemm-tiles PATH/libusdm_hip.so
+        make_gemm_tiles(sys.argv[sys.argv.index("--gemm-tiles") + 1])
+        sys.exit(0)
     if "--only-variant" in sys.argv:
         make_bigvgan_variant()
         sys.exit(0)

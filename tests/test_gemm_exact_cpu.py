@@ -1,6 +1,6 @@
 """The reference, the inputs and the bounds of tests/test_gemm_exact_gpu.py, checked without a GPU: the reference against
 torch.nn.functional on the very inputs of the GPU cases, the exactness bound, the recorded activation constants, the guards, and the
-host side of usdm_gemm (refusals and usdm_gemm_tile_for)."""
+host side of usdm_gemm (refusals, usdm_gemm_tile_for, the tile table and the recorded tile choice)."""
 import ctypes as C_
 
 import pytest
@@ -334,3 +334,73 @@ def test_usdm_gemm_tile_for_reports_the_tile_that_runs():
         big = dict(M=M, N=N, Kc=K, lda=K, ldw=K, rowsA=M, ldc=N)
         assert tile_for(dtype=_lib.BF16, **big) >= 12 and tile_for(dtype=_lib.F32, **big) < 12
     assert sorted(R.TILES) == list(range(15)) and len(R.DT_TILES) == 27
+
+
+def test_tile_table_matches_the_mirror():
+    """usdm_gemm_tile_info against R.TILES / R.DT_TILES, all 15 ids and both dtypes: the GPU tests choose their K values below, at and
+    above the pipeline depth from that mirror"""
+    from usdm_amd import _lib
+    # the mirror's loader names as (waves, DMA, LDS stages, 64-byte chunks per stage, ping-pong)
+    loaders = {"reg": (4, 0, 2, 2, 0), "reg8": (8, 0, 2, 2, 0), "dma2": (4, 1, 2, 2, 0), "dma3": (4, 1, 3, 2, 0), "dma4": (4, 1, 4, 2, 0),
+               "dma4x1": (4, 1, 4, 1, 0), "pp": (8, 1, 3, 2, 1)}
+    out = (C_.c_int32 * 8)()
+    for dtype, dt in ((_lib.BF16, BF), (_lib.F32, F32)):
+        for t in range(15):
+            rc = _lib.lib.usdm_gemm_tile_info(t, dtype, out)
+            assert (rc == 0) == ((dt, t) in R.DT_TILES), (dt, t, rc)
+            if rc:
+                assert rc == 2 and b"usdm_gemm_tile_info" in _lib.lib.usdm_last_error()
+                continue
+            BM, BN, loader, _ = R.TILES[t]
+            assert list(out) == [BM, BN, *loaders[loader], 0], (t, list(out))
+    for t, dtype in ((-1, 0), (15, 0), (0, 2)):
+        assert _lib.lib.usdm_gemm_tile_info(t, dtype, out) == 2
+
+
+# ---- which tile the heuristic chooses: recorded from the library of the commit before the launcher was split into gemm_check /
+#      gemm_select / gemm_reroute (tests/golden/make_golden.py make_gemm_tiles), replayed here against the library under test
+TILE_VARIANTS = ("plain", "batch 2", "batch 8", "split_k 2", "split_k 4", "transposed", "3 taps", "7 taps", "2 sources along K", "head split")
+CHOSEN = {BF: (0, 1, 2, 4, 5, 6, 8, 10, 12, 13, 14), F32: (0, 1, 2, 4, 5, 6, 10, 11)}       # every tile the heuristic can choose
+
+
+def tile_queries(Ms, Ns, Kcs):
+    """(dtype, M, N, Kc, variant, keywords of _args) of every query of the grid, in the fixture's order"""
+    for dt in (BF, F32):
+        for M in Ms:
+            for N in Ns:
+                for Kc in Kcs:
+                    base = dict(dtype=0 if dt == BF else 1, M=M, N=N, Kc=Kc, lda=Kc, ldw=Kc, rowsA=M, ldc=N)
+                    split = dict(c_split_stride=M * N)
+                    variants = (dict(), dict(batch=2), dict(batch=8), dict(split, split_k=2), dict(split, split_k=4), dict(transpose_out=1),
+                                dict(taps=3, ldw=3 * Kc, a_row_step=1), dict(taps=7, ldw=7 * Kc, a_row_step=1),
+                                dict(taps=2, ldw=2 * Kc, a_tap_stride=64),
+                                dict(epi=1, C32=0, qkv_q=PTR, qkv_k=PTR, qkv_v=PTR, qkv_S=M, qkv_Spad=M, qkv_D=64, qkv_H=N // 192))
+                    for name, kw in zip(TILE_VARIANTS, variants):
+                        if name != "head split" or N % 192 == 0:
+                            yield dt, M, N, Kc, name, dict(base, **kw)
+
+
+def tile_sweep(lib, Ms, Ns, Kcs):
+    """int8 per query of tile_queries: the tile usdm_gemm_tile_for names, or the negative refusal code"""
+    import numpy as np
+    return np.array([lib.usdm_gemm_tile_for(C_.byref(_args(**kw))) for *_, kw in tile_queries(Ms, Ns, Kcs)], dtype=np.int8)
+
+
+def test_tile_choice_is_the_recorded_one():
+    """the heuristic's choice on 2 dtypes x 27 M x 17 N x 10 Kc x 10 launch forms, refusals included, is the recorded one entry for entry"""
+    import os
+    import numpy as np
+    from usdm_amd import _lib
+    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_tiles.npz"))
+    axes = [[int(v) for v in d[k]] for k in ("M", "N", "Kc")]
+    want, got = d["tile"], tile_sweep(_lib.lib, *axes)
+    assert want.dtype == np.int8 and want.shape == got.shape and want.size > 80000
+    half = want.size // 2
+    for dt, part in ((BF, want[:half]), (F32, want[half:])):
+        assert sorted(set(part[part >= 0].tolist())) == list(CHOSEN[dt]), (R.dt_name(dt), "the grid no longer reaches every tile the heuristic chooses")
+    assert 0 < int((want < 0).sum()) < want.size // 50 and set(want[want < 0].tolist()) == {-2}
+    bad = np.nonzero(got != want)[0]
+    if bad.size:
+        q = list(tile_queries(*axes))
+        first = [(R.dt_name(q[i][0]), *q[i][1:5], f"recorded {int(want[i])}, got {int(got[i])}") for i in bad[:5]]
+        raise AssertionError(f"{bad.size} of {want.size} tile choices differ from the recorded ones, first: {first}")

@@ -21,6 +21,7 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)      # (global: the experimental library resolves usdm_set_error here)
 lib.usdm_last_error.restype = C.c_char_p
 lib.usdm_gemv_batch_ks_floats.restype = C.c_int64
+lib.usdm_gemm_tile_info.restype = C.c_int    # (the tile table's query: resolving it here makes a stale library fail at import)
 lib.usdm_gemv_fp8_mfma.restype = C.c_int     # (the FP8 matrix-core form; resolving it here makes a stale library fail at import)
 lib.usdm_attn_decode_fp8.restype = C.c_int   # (the FP8 KV cache entry points: likewise)
 lib.usdm_rope_cache_fp8.restype = C.c_int

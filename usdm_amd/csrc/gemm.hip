@@ -18,7 +18,7 @@
 //   * loader variants of the same kernel: register-staged (above), LDS-DMA with 2-4 stages, and - for the
 //     big single-tap bf16 GEMMs (Voicebox QKV / FFN, LLM prefill) - the 8-wave PING-PONG loop on 256x128,
 //     288x128 and 128x128 tiles at one workgroup per CU ("8-wave ping-pong loop" below; selection in
-//     usdm_gemm; measurements in profiles/r02_gemm_ablation.txt sections 3-4).
+//     gemm_select; measurements in profiles/r02_gemm_ablation.txt sections 3-4).
 #include "common.h"
 #include "../../include/usdm_hip.h"
 #include <stdlib.h>
@@ -54,6 +54,30 @@ struct GemmDev {
   int tiles_m, tiles_n;
 };
 
+// THE tile table: every instantiation of gemm_kernel, one row per id (usdm_gemm_args.tile_sel - 1, USDM_GEMM_TILE, what
+// usdm_gemm_tile_for returns).  The dispatch, the reroutes and usdm_gemm_tile_info are generated from it; f32 runs the rows that are not PP.
+//   id, BM, BN, NWM, NWN, DMA, NST, NCH, PP   (template parameters of gemm_kernel, see there)
+#define USDM_GEMM_TILES(X)                                                                                              \
+  X(0, 128, 128, 2, 2, false, 2, 2, false)  /* register-staged loaders: every operand and epilogue */                 \
+  X(1, 128, 64, 2, 2, false, 2, 2, false)                                                                               \
+  X(2, 64, 64, 2, 2, false, 2, 2, false)                                                                                \
+  X(3, 128, 128, 2, 4, false, 2, 2, false)  /* ... with 8 waves */                                                     \
+  X(4, 128, 128, 2, 2, true, 2, 2, false)   /* LDS-DMA, 2 stages */                                                    \
+  X(5, 64, 64, 2, 2, true, 2, 2, false)                                                                                 \
+  X(6, 128, 64, 2, 2, true, 2, 2, false)                                                                                \
+  X(7, 64, 64, 2, 2, true, 3, 2, false)     /* deeper DMA pipelines */                                                  \
+  X(8, 64, 64, 2, 2, true, 4, 2, false)                                                                                 \
+  X(9, 128, 128, 2, 2, true, 4, 1, false)                                                                               \
+  X(10, 128, 64, 2, 2, true, 3, 2, false)                                                                               \
+  X(11, 128, 128, 2, 2, true, 3, 2, false)                                                                              \
+  X(12, 256, 128, 4, 2, true, 3, 2, true)   /* 8-wave ping-pong loop, one workgroup per CU */                          \
+  X(13, 288, 128, 2, 4, true, 3, 2, true)                                                                               \
+  X(14, 128, 128, 4, 2, true, 3, 2, true)   /* the same loop on a 128x128 tile (wave tile 32x64) */
+
+// tile geometries the transposed store loops cover (transpose_out, V^T tiles of the head-split epilogue): the kernel compiles those
+// loops for them alone, gemm_reroute sends such outputs to another row
+__host__ __device__ constexpr bool gemm_tr_ok(int BM, int BN, int NTH) { return NTH % (BM / 4) == 0 && BN % (NTH / (BM / 4)) == 0; }
+
 // compile-time loop: every accumulator index below is a constant, so nothing can fall into scratch
 template <int N, typename F, int... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
@@ -67,6 +91,20 @@ __device__ __forceinline__ void static_for(F&& f) {
 // LDS image of one operand stage: [sub-chunk 0..1][row][4 pieces of 16 B], piece index XOR f(row).
 __device__ __forceinline__ int swz(int row) { return (-(row >> 2)) & 3; }
 
+// output (and residual) row of row m + r of batch bz; with m = the tile's first row the 64-bit part of the sum is wave-uniform
+__device__ __forceinline__ int64_t out_row(const usdm_gemm_args& a, int bz, int m, int r = 0) {
+  return ((int64_t)bz * a.c_bstride + m + r) * a.c_row_mul + a.c_row_off;
+}
+
+// the scalar epilogues (transposed outputs, ragged or unaligned columns): one residual value, f32 or bf16; one output, f32 and / or bf16
+__device__ __forceinline__ float res1(const void* resid, int res_dtype, int64_t ri) {
+  return (res_dtype == USDM_F32) ? ((const float*)resid)[ri] : bf2f(((const bf16_t*)resid)[ri]);
+}
+__device__ __forceinline__ void store1(float* C32p, void* C16, int64_t oi, float x) {
+  if (C32p) C32p[oi] = x;
+  if (C16) ((bf16_t*)C16)[oi] = f2bf(x);
+}
+
 __device__ __forceinline__ float silu_mul(float g, float u, bool rbf) {
   if (rbf) {
     g = round_bf(g); u = round_bf(u);
@@ -79,8 +117,10 @@ __device__ __forceinline__ float silu_mul(float g, float u, bool rbf) {
 // debugging aid (tools/gemm_trace.py): per-workgroup phase timestamps (100 MHz wall clock) + hardware ids
 __device__ unsigned long long g_gemm_trace[8192 * 8];
 #define TR(i) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_gemm_trace[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
+#define TR_END() do { TR(6); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TR(5); } while (0)   // stores issued / stores retired
 #else
 #define TR(i) do { } while (0)
+#define TR_END() do { } while (0)
 #endif
 
 // bias of this thread's epilogue columns -> registers (SwiGLU: gate / up), per-column bias of the transposed epilogues -> LDS.
@@ -608,9 +648,9 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
   const bool rbf = a.round_bf16 != 0;
   const bool is_qkv = a.epi == USDM_EPI_QKV_HEADS;
 
-  constexpr bool TR_OK = NTH % (BM / 4) == 0 && BN % (NTH / (BM / 4)) == 0;   // tile geometries the transposed store loops cover
+  constexpr bool TR_OK = gemm_tr_ok(BM, BN, NTH);
   if (tr_mode) {
-    if constexpr (!TR_OK) return;   // (the launcher routes transposed outputs to the other tiles: usdm_gemm, sel == 13)
+    if constexpr (!TR_OK) return;   // (the launcher routes transposed outputs to the other tiles: gemm_reroute)
     // ---- transposed mode: the accumulator fragment of a lane is 4 consecutive rows of one column, i.e. one float4 of the
     // transposed tile; the store loop then reads float4s along m without bank conflicts (a strided read of the row-major
     // tile was 8-way conflicted: 10 us per 128x128 V tile)
@@ -672,11 +712,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
           }
         }
       }
-#ifdef USDM_GEMM_TRACE
-      TR(6);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      TR(5);
-#endif
+      TR_END();
       return;
     }
     constexpr int R4 = BM / 4, CPI = NTH / R4, NIT2 = BN / CPI;
@@ -684,7 +720,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
     const int m = m0 + r4;
     const int mv = (a.M - m) < 4 ? (a.M - m) : 4;
     if (mv > 0) {
-      const int64_t row = ((int64_t)bz * a.c_bstride + m) * a.c_row_mul + a.c_row_off;
+      const int64_t row = out_row(a, bz, m);
       float4 cv = *(const float4*)(ct + c0 * CSTT + r4);
 #pragma unroll 2
       for (int it = 0; it < NIT2; ++it) {
@@ -706,21 +742,15 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
           const int64_t rw = row + (int64_t)e * a.c_row_mul;
           float x = v[e];
           if (resid) {
-            const int64_t ri = rw * a.ldr + gcol + n;
-            x += (a.res_dtype == USDM_F32) ? ((const float*)resid)[ri] : bf2f(((const bf16_t*)resid)[ri]);
+            x += res1(resid, a.res_dtype, rw * a.ldr + gcol + n);
             if (rbf) x = round_bf(x);
           }
           const int64_t oi = (int64_t)(gcol + n) * a.ldc + rw;
-          if (C32p) C32p[oi] = x;
-          if (a.C16) ((bf16_t*)a.C16)[oi] = f2bf(x);
+          store1(C32p, a.C16, oi, x);
         }
       }
     }
-#ifdef USDM_GEMM_TRACE
-    TR(6);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TR(5);
-#endif
+    TR_END();
     return;
   }
 
@@ -752,7 +782,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = silu_mul(a.alpha * gt[e] + bv[e], a.alpha * up[e] + bu[e], rbf);
-        const int64_t row = ((int64_t)bz * a.c_bstride + m) * a.c_row_mul + a.c_row_off;
+        const int64_t row = out_row(a, bz, m);
         const int64_t oi = row * a.ldc + (gcol >> 1) + nout;
         if (C32p) st_out((float4*)(C32p + oi), make_float4(o[0], o[1], o[2], o[3]));
         if (a.C16) { uint2 p; p.x = pack_bf2(o[0], o[1]); p.y = pack_bf2(o[2], o[3]); st_out((uint2*)((bf16_t*)a.C16 + oi), p); }
@@ -822,7 +852,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
     }
   } else if (wide_gelu) {
     const int64_t rstep = (int64_t)RPI8 * a.c_row_mul;
-    int64_t row = ((int64_t)bz * a.c_bstride + m0 + er8) * a.c_row_mul + a.c_row_off;
+    int64_t row = out_row(a, bz, m0, er8);
     const f32x2_t b01 = {bv[0], bv[1]}, b23 = {bv[2], bv[3]}, b45 = {bu[0], bu[1]}, b67 = {bu[2], bu[3]};
     f32x2_t lc01 = {0.f, 0.f}, lc23 = {0.f, 0.f}, lc45 = {0.f, 0.f}, lc67 = {0.f, 0.f};
     if (a.ln_mode == 1) {
@@ -853,7 +883,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
     // the feed-forward GELU epilogue of the one-workgroup-per-CU tiles: nothing overlaps it there, so it is written for VALU
     // throughput (two values per instruction, no per-element dispatch)
     const int64_t rstep = (int64_t)RPI * a.c_row_mul;
-    int64_t row = ((int64_t)bz * a.c_bstride + m0 + er) * a.c_row_mul + a.c_row_off;
+    int64_t row = out_row(a, bz, m0, er);
     const f32x2_t b01 = {bv[0], bv[1]}, b23 = {bv[2], bv[3]};
     f32x2_t lc01 = {0.f, 0.f}, lc23 = {0.f, 0.f};
     if (a.ln_mode == 1) { const float4 c4 = *(const float4*)(a.ln_c + gcol + n); lc01 = f32x2_t{c4.x, c4.y}; lc23 = f32x2_t{c4.z, c4.w}; }
@@ -881,7 +911,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
     // 88 KB and ran out of the instruction cache); the next row's LDS read is issued under this row's math
     const bool has_res = resid != nullptr;
     const int64_t rstep = (int64_t)RPI * a.c_row_mul;
-    int64_t row = ((int64_t)bz * a.c_bstride + m0 + er) * a.c_row_mul + a.c_row_off;
+    int64_t row = out_row(a, bz, m0, er);
     float4 cv = *(const float4*)(ct + er * CST + ec);
 #pragma unroll 2
     for (int it = 0; it < NIT; ++it, row += rstep) {
@@ -920,7 +950,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
     static_assert(NIT % NB == 0, "epilogue batches");
     const bool has_res = resid != nullptr;
     const int64_t rstep = (int64_t)RPI * a.c_row_mul;
-    int64_t row = ((int64_t)bz * a.c_bstride + m0 + er) * a.c_row_mul + a.c_row_off;
+    int64_t row = out_row(a, bz, m0, er);
     // folded LayerNorm, residual form (ln_mode 2): the residual rows are un-normalised x; LN(x) = x * (rstd gamma) - (rstd mean) gamma + beta
     float lg[4] = {0.f, 0.f, 0.f, 0.f}, lb[4] = {0.f, 0.f, 0.f, 0.f};
     const bool ln_res = PP && a.ln_mode == 2 && has_res;
@@ -996,41 +1026,51 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(const GemmDev g) {
     for (int it = 0; it < NIT; ++it) {
       const int r = er + it * RPI, m = m0 + r;
       if (m >= a.M) break;
-      const int64_t row = ((int64_t)bz * a.c_bstride + m) * a.c_row_mul + a.c_row_off;
+      const int64_t row = out_row(a, bz, m);
       for (int e = 0; e < nv; ++e) {
         float x = a.alpha * ct[r * CST + ec + e] + bv[e];
         if (rbf) x = round_bf(x);
         x = act_fn(x);
         if (resid) {
-          const int64_t ri = row * a.ldr + gcol + n + e;
-          x += (a.res_dtype == USDM_F32) ? ((const float*)resid)[ri] : bf2f(((const bf16_t*)resid)[ri]);
+          x += res1(resid, a.res_dtype, row * a.ldr + gcol + n + e);
           if (rbf) x = round_bf(x);
         }
         const int64_t oi = row * a.ldc + gcol + n + e;
-        if (C32p) C32p[oi] = x;
-        if (a.C16) ((bf16_t*)a.C16)[oi] = f2bf(x);
+        store1(C32p, a.C16, oi, x);
       }
     }
   }
-#ifdef USDM_GEMM_TRACE
-  TR(6);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  TR(5);
-#endif
+  TR_END();
 }
 
 #undef USDM_GEMM_FETCH_BIAS
 
-template <typename T, int BM, int BN, int NWM = 2, int NWN = 2, bool DMA = false, int NST = 2, int NCH = 2, bool PP = false>
+template <int BM, int BN, int NWM, int NWN, bool DMA, int NST, int NCH, bool PP>
 int launch(const usdm_gemm_args& a, hipStream_t st) {
   GemmDev g;
   g.a = a;
   g.tiles_m = cdiv(a.M, BM);
   g.tiles_n = cdiv(a.N, BN);
   dim3 grid(g.tiles_m * g.tiles_n, 1, a.groups * a.batch * (a.split_k > 1 ? a.split_k : 1));
-  hipLaunchKernelGGL((gemm_kernel<T, BM, BN, NWM, NWN, DMA, NST, NCH, PP>), grid, dim3(NWM * NWN * 64), 0, st, g);
+  if (a.dtype == USDM_BF16) hipLaunchKernelGGL((gemm_kernel<bf16_t, BM, BN, NWM, NWN, DMA, NST, NCH, PP>), grid, dim3(NWM * NWN * 64), 0, st, g);
+  else if constexpr (!PP) hipLaunchKernelGGL((gemm_kernel<float, BM, BN, NWM, NWN, DMA, NST, NCH, PP>), grid, dim3(NWM * NWN * 64), 0, st, g);
   USDM_LAUNCH_CHECK();
   return 0;
+}
+
+struct GemmTile { int id, BM, BN, NWM, NWN; bool DMA; int NST, NCH; bool PP; };
+#define X(id, BM, BN, NWM, NWN, DMA, NST, NCH, PP) {id, BM, BN, NWM, NWN, DMA, NST, NCH, PP},
+constexpr GemmTile kTiles[] = {USDM_GEMM_TILES(X)};   // (indexed by id: static_assert below)
+#undef X
+constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
+constexpr int kTileAny = 2;   // 64x64, register-staged: every dtype, operand and epilogue
+constexpr bool tile_tr_ok(const GemmTile& t) { return gemm_tr_ok(t.BM, t.BN, t.NWM * t.NWN * 64); }
+
+template <class P>
+int find_tile(P pred) {   // first row of the table with the property, or -1
+  for (const GemmTile& t : kTiles)
+    if (pred(t)) return t.id;
+  return -1;
 }
 
 }  // namespace
@@ -1041,10 +1081,10 @@ extern "C" int usdm_dbg_gemm_trace(unsigned long long* host, int n) {
 }
 #endif
 
-// validation + tile choice (+ launch unless tile_out: usdm_gemm_tile_for)
-static int gemm_impl(const usdm_gemm_args* pa, usdm_stream_t stream, int* tile_out) {
-  USDM_CHECK_ARG(pa != nullptr, "usdm_gemm: null args");
-  usdm_gemm_args a = *pa;
+static_assert([] { for (int i = 0; i < kNumTiles; ++i) if (kTiles[i].id != i) return false; return true; }(), "kTiles is indexed by id");
+
+// the defaults of the optional fields, then the refusals
+static int gemm_check(usdm_gemm_args& a) {
   if (a.groups <= 0) a.groups = 1;
   if (a.batch <= 0) a.batch = 1;
   if (a.taps <= 0) a.taps = 1;
@@ -1077,106 +1117,121 @@ static int gemm_impl(const usdm_gemm_args* pa, usdm_stream_t stream, int* tile_o
     USDM_CHECK_ARG(a.qkv_q && a.qkv_k && a.qkv_v && a.N == 3 * a.qkv_H * a.qkv_D && (a.qkv_H * a.qkv_D) % 64 == 0 && a.qkv_S > 0 && a.qkv_Spad >= a.qkv_S &&
                        a.qkv_D % 4 == 0 && !a.transpose_out && !a.residual && a.groups == 1 && a.batch == 1,
                    "usdm_gemm: bad qkv epilogue args");
-  hipStream_t st = (hipStream_t)stream;
-  // tile selection, measured on MI355X (profiles/r01_gemm_tiles.txt, profiles/r01_gemm_ablation.txt)
-  const int64_t z = (int64_t)a.groups * a.batch * (a.split_k > 1 ? a.split_k : 1);
-  const int64_t t128 = (int64_t)cdiv(a.M, 128) * cdiv(a.N, 128) * z;
-  const int64_t t12864 = (int64_t)cdiv(a.M, 128) * cdiv(a.N, 64) * z;
-  int sel;  // 0-2: register-staged 128x128 / 128x64 / 64x64; 4-6: the same tiles with 2-stage LDS-DMA; 7-11: deeper DMA pipelines; 12-13: ping-pong
-  // Single-tap GEMMs (Linear layers): chosen from tools/vb_gemm_bench.py (the Voicebox layer's GEMMs over cold weights) and
-  // tools/bench_gemm_tiles.py, see profiles/r01_gemm_ablation.txt.
-  constexpr int heur = 1;
+  return 0;
+}
+
+// what the ping-pong loop reads besides a single tap: sources concatenated along K (a step of 64 never straddles two of them)
+static bool pp_taps(int taps, int a_row_step, int Kc) { return taps == 1 || (a_row_step == 0 && Kc % 64 == 0); }
+
+// The tile for a shape, measured on MI355X (profiles/r01_gemm_tiles.txt, profiles/r01_gemm_ablation.txt); z = groups x batch x K
+// splits.  tests/golden/gemm_tiles.npz records what it answers (tests/test_gemm_exact_cpu.py test_tile_choice_is_the_recorded_one).
+static int gemm_select(int dtype, int M, int N, int Kc, int taps, int a_row_step, int split_k, int64_t z, bool transpose_out, int epi) {
+  const int64_t t128 = (int64_t)cdiv(M, 128) * cdiv(N, 128) * z;
+  const int64_t t12864 = (int64_t)cdiv(M, 128) * cdiv(N, 64) * z;
   // Big single-tap bf16 GEMMs: the 8-wave ping-pong tiles (256x128, or 288x128 when that saves a round of workgroups) at one
   // workgroup per CU, 1.2-2x the 128x128 tile on the Voicebox and LLM-prefill shapes (profiles/r02_gemm_ablation.txt section 4)
-  const int64_t t12 = (int64_t)cdiv(a.M, 256) * cdiv(a.N, 128) * z, t13 = (int64_t)cdiv(a.M, 288) * cdiv(a.N, 128) * z;
-  const bool pp_taps = a.taps == 1 || (a.a_row_step == 0 && a.Kc % 64 == 0);      // single tap, or sources concatenated along K
-  const bool pp_ok = heur == 1 && a.dtype == USDM_BF16 && pp_taps && a.N > 64 && t12 >= 96 && a.Kc / (a.split_k > 1 ? a.split_k : 1) >= 256 &&
-                     (int64_t)cdiv(a.M, 256) * 256 * 2 <= (int64_t)a.M * 3;      // (= rows256_ok below)
+  // (K-concatenated sources included: the skip Linear 31.1 -> 25.7 us, r03_vb_ablation.txt 8)
+  const int64_t t12 = (int64_t)cdiv(M, 256) * cdiv(N, 128) * z, t13 = (int64_t)cdiv(M, 288) * cdiv(N, 128) * z;
+  const bool pp = dtype == USDM_BF16 && pp_taps(taps, a_row_step, Kc) && N > 64 && Kc / (split_k > 1 ? split_k : 1) >= 256;
   // ... and its 128x128 form where the big tiles would leave half the CUs idle (96-256 tiles of 128x128, one per CU)
-  const int64_t t14 = (int64_t)cdiv(a.M, 128) * cdiv(a.N, 128) * z;
   // (also where 256-row tiles would be mostly padding: the 33 - 100 row prefills of a reused prefix stream gate/up's 235 MB through
   // 224 such tiles at 4.1 TB/s, 57 us against 67 - 90 on the 128x64 tile; profiles/r04_prefill_small.log)
-  const bool rows256_ok = (int64_t)cdiv(a.M, 256) * 256 * 2 <= (int64_t)a.M * 3;
-  const bool pp_small = heur == 1 && a.dtype == USDM_BF16 && pp_taps && a.N > 64 &&   // (K-concatenated sources included: the skip Linear 31.1 -> 25.7 us, r03_vb_ablation.txt 8)
-                        (t12 < 128 || !rows256_ok) && t14 >= 96 && t14 <= 256 &&
-                        a.Kc / (a.split_k > 1 ? a.split_k : 1) >= 256;
-  if (pp_small) sel = 14;
-  else if (pp_ok) {
+  const bool rows256_ok = (int64_t)cdiv(M, 256) * 256 * 2 <= (int64_t)M * 3;
+  if (pp && (t12 < 128 || !rows256_ok) && t128 >= 96 && t128 <= 256) return 14;
+  if (pp && t12 >= 96 && rows256_ok) {
     const int64_t c12 = cdiv(t12, 256) * 256, c13 = cdiv(t13, 256) * 288;     // rounds x rows per tile
-    sel = (!a.transpose_out && a.epi == USDM_EPI_PLAIN && c13 < c12) ? 13 : 12;
+    return (!transpose_out && epi == USDM_EPI_PLAIN && c13 < c12) ? 13 : 12;
   }
-  else if (a.N <= 64) sel = (a.dtype != USDM_F32 && cdiv(a.M, 128) * z >= 448) ? 1 : 2;   // (f32: the 64x64 tile is 7 - 17 % faster on BigVGAN's 24 / 48-channel stages, profiles/r04_bigvgan_conv_tiles.log)
-  else if (heur == 1 && a.taps == 1) {
-    if (a.split_k > 1 && t128 >= 224 && t128 <= 512) sel = 4;          // split-K partials filling one round of the big tile
-    else if (t128 >= 640) sel = 4;                                     // many rounds of the big tile
-    else if (a.Kc >= 8192 && t128 >= 128 && t128 <= 256) sel = 11;     // one deep-K tile per CU: 3-stage DMA pipeline
-    else if (a.Kc >= 2048 && t12864 >= 256) sel = 10;                  // deep K, few tiles: 128x64, 3 stages
-    else if (t128 >= 400 && t128 <= 512) sel = 4;                      // exactly one round of 2 workgroups per CU
-    else if (a.N >= 2048 && t12864 >= 768) sel = 6;
+  if (N <= 64) return (dtype != USDM_F32 && cdiv(M, 128) * z >= 448) ? 1 : 2;   // (f32: the 64x64 tile is 7 - 17 % faster on BigVGAN's 24 / 48-channel stages, profiles/r04_bigvgan_conv_tiles.log)
+  // Single-tap GEMMs (Linear layers): chosen from tools/vb_gemm_bench.py (the Voicebox layer's GEMMs over cold weights) and
+  // tools/bench_gemm_tiles.py, see profiles/r01_gemm_ablation.txt.
+  if (taps == 1) {
+    if (split_k > 1 && t128 >= 224 && t128 <= 512) return 4;       // split-K partials filling one round of the big tile
+    if (t128 >= 640) return 4;                                     // many rounds of the big tile
+    if (Kc >= 8192 && t128 >= 128 && t128 <= 256) return 11;       // one deep-K tile per CU: 3-stage DMA pipeline
+    if (Kc >= 2048 && t12864 >= 256) return 10;                    // deep K, few tiles: 128x64, 3 stages
+    if (t128 >= 400 && t128 <= 512) return 4;                      // exactly one round of 2 workgroups per CU
+    if (N >= 2048 && t12864 >= 768) return 6;
     // few tiles: weight streaming through a handful of CUs is latency-bound - the 64x64 tile with FOUR DMA stages in flight (short
     // 7B prefills: qkv / o 52 -> 27 us, down 169 -> 84 us; f32 shapes measure the same on 2 and 4 stages and keep the 2-stage tile)
-    else sel = (a.dtype == USDM_BF16 && a.Kc >= 1024) ? 8 : 5;
+    return (dtype == USDM_BF16 && Kc >= 1024) ? 8 : 5;
   }
   // multi-tap operands (convolutions): register-staged loaders (the DMA path recomputes the tap row shift per K-step)
-  else if (t128 >= 640) sel = (a.taps == 1) ? 4 : 0;
-  else if (a.N >= 4096 && t12864 >= 448) sel = 1;
-  else sel = 2;
+  if (t128 >= 640) return 0;
+  if (N >= 4096 && t12864 >= 448) return 1;
+  return 2;
+}
+
+// The tile that runs: the caller's override, then the rows that do not serve this operand, epilogue or dtype hand over to one that does.
+static int gemm_reroute(const usdm_gemm_args& a, int sel) {
   if (a.tile_sel > 0) sel = (a.tile_sel & 0xff) - 1;   // benchmarking / test override (usdm_gemm_args.tile_sel; ops.gemm fills it from USDM_GEMM_TILE)
-  if (a.taps != 1 && sel >= 4 && !(sel >= 12 && pp_taps)) sel = (sel == 6 || sel == 10) ? 1 : ((sel == 5 || sel == 7 || sel == 8) ? 2 : 0);   // DMA tiles are single-tap
-  if (sel == 13 && (a.transpose_out || a.epi != USDM_EPI_PLAIN)) sel = 12;   // the 288-row tiles have row-major epilogues only
-  if (a.dtype == USDM_F32 && sel >= 12) sel = 2;      // the ping-pong tiles are bf16 only (reachable through tile_sel alone): report the 64x64 tile that runs
-  if (!tile_out && (a.stats_out || a.ln_mode)) {      // folded LayerNorm: implemented in the epilogues of the ping-pong tiles only (see usdm_gemm_args)
-    USDM_CHECK_ARG(sel >= 12 && sel <= 14 && a.dtype == USDM_BF16 && a.epi == USDM_EPI_PLAIN && !a.transpose_out && !a.round_bf16 &&
-                       a.N % 128 == 0 && a.groups == 1 && (a.ldc & 3) == 0,
-                   "usdm_gemm: stats_out / ln_mode need a bf16 GEMM on the ping-pong tiles with a row-major epilogue and N %% 128 == 0 (tile %d)", sel);
-    USDM_CHECK_ARG(!a.stats_out || (a.act == USDM_ACT_NONE && a.split_k <= 1), "usdm_gemm: stats_out needs a plain, unsplit epilogue");
-    USDM_CHECK_ARG(a.ln_mode == 0 || (a.ln_stats && a.ln_nt > 0 && a.ln_nt <= 64 && a.ln_C > 0 && a.ln_C == a.ln_nt * 128),
-                   "usdm_gemm: ln_stats / ln_nt / ln_C (the producer's tiles are 128 columns wide)");
-    USDM_CHECK_ARG(!a.ln_guard || a.ln_guard_ratio > 0.f, "usdm_gemm: ln_guard needs ln_guard_ratio > 0");
-    USDM_CHECK_ARG(a.ln_mode != 1 || (a.ln_c && a.act == USDM_ACT_GELU && a.C16 && !a.C32 && !a.residual && a.alpha == 1.0f && a.split_k <= 1),
-                   "usdm_gemm: ln_mode 1 is the GELU bf16-out epilogue (no residual, alpha 1)");
-    USDM_CHECK_ARG(a.ln_mode != 2 || (a.ln_gamma && a.ln_beta && a.residual && a.res_dtype == USDM_F32 && a.act == USDM_ACT_NONE && (a.ldr & 3) == 0),
-                   "usdm_gemm: ln_mode 2 needs an f32 residual, gamma / beta and a plain epilogue");
-    USDM_CHECK_ARG(a.ln_mode >= 0 && a.ln_mode <= 2, "usdm_gemm: ln_mode");
+  if (sel < 0 || sel >= kNumTiles) return kTileAny;    // (no such row)
+  // multi-tap operands: the LDS-DMA rows are single-tap (the ping-pong rows also take sources concatenated along K); the register-staged
+  // row of the same size runs, 128x128 where there is none
+  if (a.taps != 1 && kTiles[sel].DMA && !(kTiles[sel].PP && pp_taps(a.taps, a.a_row_step, a.Kc))) {
+    const GemmTile& t = kTiles[sel];
+    sel = find_tile([&](const GemmTile& r) { return !r.DMA && r.BM == t.BM && r.BN == t.BN; });
+    if (sel < 0) sel = find_tile([](const GemmTile& r) { return !r.DMA && r.BM == 128 && r.BN == 128; });
   }
+  // outputs whose fast axis is m: a row without the transposed store loops (288x128) hands over to the first row with the same
+  // pipeline and width that has them (256x128)
+  if ((a.transpose_out || a.epi != USDM_EPI_PLAIN) && !tile_tr_ok(kTiles[sel])) {
+    const GemmTile& t = kTiles[sel];
+    sel = find_tile([&](const GemmTile& r) { return r.PP == t.PP && r.DMA == t.DMA && r.NST == t.NST && r.BN == t.BN && tile_tr_ok(r); });
+  }
+  if (a.dtype == USDM_F32 && kTiles[sel].PP) sel = kTileAny;   // the ping-pong tiles are bf16 only (reachable through tile_sel alone): report the 64x64 tile that runs
+  return sel;
+}
+
+// folded LayerNorm: implemented in the epilogues of the ping-pong tiles only (see usdm_gemm_args)
+static int gemm_check_ln(const usdm_gemm_args& a, int sel) {
+  if (!a.stats_out && !a.ln_mode) return 0;
+  USDM_CHECK_ARG(kTiles[sel].PP && a.dtype == USDM_BF16 && a.epi == USDM_EPI_PLAIN && !a.transpose_out && !a.round_bf16 &&
+                     a.N % 128 == 0 && a.groups == 1 && (a.ldc & 3) == 0,
+                 "usdm_gemm: stats_out / ln_mode need a bf16 GEMM on the ping-pong tiles with a row-major epilogue and N %% 128 == 0 (tile %d)", sel);
+  USDM_CHECK_ARG(!a.stats_out || (a.act == USDM_ACT_NONE && a.split_k <= 1), "usdm_gemm: stats_out needs a plain, unsplit epilogue");
+  USDM_CHECK_ARG(a.ln_mode == 0 || (a.ln_stats && a.ln_nt > 0 && a.ln_nt <= 64 && a.ln_C > 0 && a.ln_C == a.ln_nt * 128),
+                 "usdm_gemm: ln_stats / ln_nt / ln_C (the producer's tiles are 128 columns wide)");
+  USDM_CHECK_ARG(!a.ln_guard || a.ln_guard_ratio > 0.f, "usdm_gemm: ln_guard needs ln_guard_ratio > 0");
+  USDM_CHECK_ARG(a.ln_mode != 1 || (a.ln_c && a.act == USDM_ACT_GELU && a.C16 && !a.C32 && !a.residual && a.alpha == 1.0f && a.split_k <= 1),
+                 "usdm_gemm: ln_mode 1 is the GELU bf16-out epilogue (no residual, alpha 1)");
+  USDM_CHECK_ARG(a.ln_mode != 2 || (a.ln_gamma && a.ln_beta && a.residual && a.res_dtype == USDM_F32 && a.act == USDM_ACT_NONE && (a.ldr & 3) == 0),
+                 "usdm_gemm: ln_mode 2 needs an f32 residual, gamma / beta and a plain epilogue");
+  USDM_CHECK_ARG(a.ln_mode >= 0 && a.ln_mode <= 2, "usdm_gemm: ln_mode");
+  return 0;
+}
+
+// validation + tile choice (+ launch unless tile_out: usdm_gemm_tile_for, which skips only the folded-LayerNorm rules)
+static int gemm_impl(const usdm_gemm_args* pa, usdm_stream_t stream, int* tile_out) {
+  USDM_CHECK_ARG(pa != nullptr, "usdm_gemm: null args");
+  usdm_gemm_args a = *pa;
+  if (const int rc = gemm_check(a)) return rc;
+  const int64_t z = (int64_t)a.groups * a.batch * (a.split_k > 1 ? a.split_k : 1);
+  const int sel = gemm_reroute(a, gemm_select(a.dtype, a.M, a.N, a.Kc, a.taps, a.a_row_step, a.split_k, z, a.transpose_out != 0, a.epi));
   if (tile_out) { *tile_out = sel; return 0; }
-  if (a.dtype == USDM_BF16) {
-    if (sel == 3) return launch<bf16_t, 128, 128, 2, 4>(a, st);
-    if (sel == 4) return launch<bf16_t, 128, 128, 2, 2, true>(a, st);
-    if (sel == 5) return launch<bf16_t, 64, 64, 2, 2, true>(a, st);
-    if (sel == 6) return launch<bf16_t, 128, 64, 2, 2, true>(a, st);
-    if (sel == 7) return launch<bf16_t, 64, 64, 2, 2, true, 3, 2>(a, st);
-    if (sel == 8) return launch<bf16_t, 64, 64, 2, 2, true, 4, 2>(a, st);
-    if (sel == 9) return launch<bf16_t, 128, 128, 2, 2, true, 4, 1>(a, st);
-    if (sel == 10) return launch<bf16_t, 128, 64, 2, 2, true, 3, 2>(a, st);
-    if (sel == 11) return launch<bf16_t, 128, 128, 2, 2, true, 3, 2>(a, st);
-    if (sel == 12) return launch<bf16_t, 256, 128, 4, 2, true, 3, 2, true>(a, st);   // 8-wave ping-pong loop, one workgroup per CU
-    if (sel == 13) return launch<bf16_t, 288, 128, 2, 4, true, 3, 2, true>(a, st);   // row-major epilogues only
-    if (sel == 14) return launch<bf16_t, 128, 128, 4, 2, true, 3, 2, true>(a, st);   // the same loop on a 128x128 tile (wave tile 32x64)
-    if (sel == 0) return launch<bf16_t, 128, 128>(a, st);
-    if (sel == 1) return launch<bf16_t, 128, 64>(a, st);
-    return launch<bf16_t, 64, 64>(a, st);
-  } else {
-    if (sel == 3) return launch<float, 128, 128, 2, 4>(a, st);
-    if (sel == 4) return launch<float, 128, 128, 2, 2, true>(a, st);
-    if (sel == 5) return launch<float, 64, 64, 2, 2, true>(a, st);
-    if (sel == 6) return launch<float, 128, 64, 2, 2, true>(a, st);
-    if (sel == 7) return launch<float, 64, 64, 2, 2, true, 3, 2>(a, st);
-    if (sel == 8) return launch<float, 64, 64, 2, 2, true, 4, 2>(a, st);
-    if (sel == 9) return launch<float, 128, 128, 2, 2, true, 4, 1>(a, st);
-    if (sel == 10) return launch<float, 128, 64, 2, 2, true, 3, 2>(a, st);
-    if (sel == 11) return launch<float, 128, 128, 2, 2, true, 3, 2>(a, st);
-    if (sel == 0) return launch<float, 128, 128>(a, st);
-    if (sel == 1) return launch<float, 128, 64>(a, st);
-    return launch<float, 64, 64>(a, st);
-  }
+  if (const int rc = gemm_check_ln(a, sel)) return rc;
+#define X(id, BM, BN, NWM, NWN, DMA, NST, NCH, PP) \
+  if (sel == id) return launch<BM, BN, NWM, NWN, DMA, NST, NCH, PP>(a, (hipStream_t)stream);
+  USDM_GEMM_TILES(X)
+#undef X
+  return 2;   // (gemm_reroute returns rows of the table only)
 }
 
 extern "C" int usdm_gemm(const usdm_gemm_args* pa, usdm_stream_t stream) { return gemm_impl(pa, stream, nullptr); }
-// The tile usdm_gemm would run these arguments on (12 - 14: the ping-pong tiles, the only ones with the folded-LayerNorm epilogues),
+// The tile usdm_gemm would run these arguments on (the PP rows of USDM_GEMM_TILES: the only ones with the folded-LayerNorm epilogues),
 // or a negative number if the arguments are invalid: lets a caller decide BEFORE building a plan whether stats_out / ln_mode apply.
 extern "C" int usdm_gemm_tile_for(const usdm_gemm_args* pa) {
   int tile = -1;
   const int rc = gemm_impl(pa, nullptr, &tile);
   return rc == 0 ? tile : -rc;
+}
+// Row `tile` of USDM_GEMM_TILES as out[8] = BM, BN, waves, DMA, LDS stages, 64-byte chunks per stage, PP, 0; refuses an id outside the
+// table and a row that does not run `dtype`.  Host only.
+extern "C" int usdm_gemm_tile_info(int tile, int dtype, int32_t* out) {
+  USDM_CHECK_ARG(out != nullptr && (dtype == USDM_BF16 || dtype == USDM_F32), "usdm_gemm_tile_info: bad dtype %d or null out", dtype);
+  USDM_CHECK_ARG(tile >= 0 && tile < kNumTiles && !(dtype == USDM_F32 && kTiles[tile].PP), "usdm_gemm_tile_info: no tile %d for dtype %d", tile, dtype);
+  const GemmTile& t = kTiles[tile];
+  const int32_t v[8] = {t.BM, t.BN, t.NWM * t.NWN, t.DMA, t.NST, t.NCH, t.PP, 0};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return 0;
 }
