@@ -143,8 +143,17 @@ int usdm_norm(const usdm_norm_args* args, usdm_stream_t stream);
  * Fused anti-aliased SnakeBeta: Activation1d(SnakeBeta) of the reference in one pass
  * (vocoder/alias_free_torch/act.py:23-28, resample.py:25-33, filter.py:86-95,
  *  vocoder/activations.py:107-120).  x is channels-last f32 [T][ldx]; channels >= Creal are padding
- * and are written as zero.  fup/fdn: the 12 Kaiser-sinc taps of kaiser_sinc_filter1d(0.25,0.3,12)
- * (filter.py:28-57) computed on the host.  L: time steps per thread (0 = choose).
+ * and are written as zero (their x, alpha and beta are never used).  fup/fdn: the 12 Kaiser-sinc taps
+ * of kaiser_sinc_filter1d(0.25,0.3,12) (filter.py:28-57) computed on the host.  The production taps are
+ * symmetric, but the fields are not interchangeable with their reverse.  Orientation: fup[] are the
+ * weights of conv_transpose1d(stride 2), fdn[] the weights of conv1d(stride 2) (a correlation):
+ *   u[2m]   = 2 * sum_{i=-2..3} fup[5+2i] * x~[m-i]
+ *   u[2m+1] = 2 * sum_{i=-3..2} fup[6+2i] * x~[m-i]           x~[k] = x[clamp(k, 0, T-1)]
+ *   v[n]    = u[n] + 1/(b + 1e-9) * sin(u[n] * a)^2           a, b = alpha, beta (exp() of them if logscale)
+ *   o[t]    = sum_{j=0..11} fdn[j] * v~[2t-5+j]               v~[n] = v[clamp(n, 0, 2T-1)]
+ * L: time steps per thread (0 = choose); the result does not depend on it.
+ * Alignment: the kernel moves channel pairs, so C, ldx and ldo are even, x and out32 are 8-byte aligned
+ * and out16 is 4-byte aligned; anything else is refused.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct usdm_snake_args {
   const float* x; int64_t ldx;

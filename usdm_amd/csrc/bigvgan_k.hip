@@ -165,6 +165,9 @@ extern "C" int usdm_aa_snake(const usdm_snake_args* pa, usdm_stream_t stream) {
   USDM_CHECK_ARG(a.T > 0 && a.C > 0 && a.C % 2 == 0 && a.Creal <= a.C, "usdm_aa_snake: bad T/C");
   USDM_CHECK_ARG(a.ldx % 2 == 0 && a.ldo % 2 == 0, "usdm_aa_snake: strides must be even");
   USDM_CHECK_ARG(a.out32 || a.out16, "usdm_aa_snake: no output");
+  // the kernel moves channel pairs: float2 loads of x, float2 stores to out32, one packed 32-bit store to out16
+  USDM_CHECK_ARG((uintptr_t)a.x % 8 == 0 && (uintptr_t)a.out32 % 8 == 0 && (uintptr_t)a.out16 % 4 == 0,
+                 "usdm_aa_snake: x and out32 must be 8-byte aligned, out16 4-byte aligned");
   if (a.L <= 0) {
     a.L = 32;
     const int64_t cols = cdiv(a.C, 32);
