@@ -6,7 +6,8 @@
 // `seed` with the device-side step counter as counter, so a (seed, step) pair always gives the same token.
 //
 // One workgroup of 1024 threads, a handful of passes over the V logits (L2-resident, 168 KB at V = 42003):
-//   top-k  : radix select (4 x 8 bits) of the k-th largest key with integer histograms;
+//   top-k  : radix select (4 x 8 bits) of the k-th largest key with integer histograms; ties at the k-th rank are kept, and -0.0
+//            counts as +0.0 there, as in HF's `scores < kth`;
 //   top-p  : radix select over the ascending exp(x - max) keys with FIXED-POINT mass histograms (u64 LDS atomics are
 //            associative, so the kept set does not depend on thread scheduling); ties are kept or dropped as a block;
 //   min-p  : HF MinPLogitsWarper / vLLM: ids with p_i < min_p * p_max are dropped, by raising the top-p stage's key threshold;
@@ -73,6 +74,9 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
     a.min_p = (a.dev_params->min_p >= 0.f && a.dev_params->min_p <= 1.0f) ? a.dev_params->min_p : 0.f;   // (NaN fails both)
   }
   const float invT = 1.0f / a.temperature;   // HF divides; x / T and x * (1 / T) differ by <= 1 ulp, below the logits' bf16 grain
+  // the scaled logit as every stage sees it.  -0.0 becomes +0.0: HF's `scores < kth` compares values, to which the two zeros are
+  // equal, while fkey orders -0.0 one key below +0.0 and would drop the -0.0 entries of a zero tie block at the k-th rank
+  auto SC = [&](float lg) -> float { const float x = lg * invT; return x == 0.f ? 0.f : x; };
   const logits_row_view rv{seg_stride, seg_len, seg_magic};
   auto LG = [&](int i) -> float { return row_at<SEG>(a.logits, i, rv); };
   auto each = [&](auto&& f) {   // f(i, logit of i) for i = tid, tid + NT, ... < V
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
       if (tid < 256) hist[tid] = 0;
       __syncthreads();
       each([&](int, float lg) {
-        const unsigned k = fkey(lg * invT);
+        const unsigned k = fkey(SC(lg));
         if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255], 1ull);
       });
       __syncthreads();
@@ -111,12 +115,12 @@ __global__ __launch_bounds__(NT) void sample_final_kernel(usdm_sample_args a, us
   // ---- softmax numerators over the top-k survivors
   float m = -INFINITY;
   each([&](int, float lg) {
-    const float x = lg * invT;
+    const float x = SC(lg);
     if (fkey(x) >= kth) m = fmaxf(m, x);
   });
   m = block_max(m, sred);
   auto El = [&](float lg) -> float {   // exp(x - max) of a top-k survivor, 0 otherwise (banned = -inf -> 0)
-    const float x = lg * invT;
+    const float x = SC(lg);
     return (fkey(x) >= kth) ? __expf(x - m) : 0.f;
   };
   auto Ei = [&](int i) -> float { return El(LG(i)); };
