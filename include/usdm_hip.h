@@ -469,6 +469,18 @@ typedef struct usdm_gemv_wpack {
 int usdm_gemv_packed(const usdm_gemv_args* args, const usdm_gemv_wpack* pack, usdm_stream_t stream);
 int usdm_gemv_packs(const usdm_gemv_args* args);   /* 1 where usdm_gemv_packed streams the image of this projection */
 int usdm_sizeof_gemv_wpack(void);
+/* The same image of an interleaved gate/up matrix (a SwiGLU call: N rows = blocks of 16 gate + 16 up rows, N / 2 outputs).  The
+ * byte layout per ROW is the one above, K = 4096 = 2 units; planes, rowflag, stride, base and units mean what they mean above, with
+ * rowflag still one byte per weight row.  Only `marked` differs: bit o of the array = OUTPUT o is marked, i.e. its gate row
+ * 32 (o >> 4) + (o & 15) or its up row (that + 16) holds a weight outside the window; at most 14336 outputs.  A wave of the kernel
+ * that owns a marked output streams its rows from the bf16 matrix.
+ * usdm_gemv_packed_glu(args, pack) computes exactly usdm_gemv(args), bit for bit.  usdm_gemv_packs_glu is 1 where it streams the
+ * image: where usdm_gemv would run the straight-line resident form of gate/up - a plain bf16 SwiGLU call, no x_delta, K = 4096 and
+ * two tiles on every resident workgroup (see usdm_gemv_args.resident; the device is asked how many it holds, so the query needs
+ * one where the rest applies).  Every other call is usdm_gemv itself.  Refused: units != 2, a stride below 2 * 3328 or no multiple
+ * of 16, planes not 16-byte aligned, base outside 0..112, N / 2 > 14336. */
+int usdm_gemv_packed_glu(const usdm_gemv_args* args, const usdm_gemv_wpack* pack, usdm_stream_t stream);
+int usdm_gemv_packs_glu(const usdm_gemv_args* args);
 
 /* Device-resident greedy-decode state so that a decode step is replayable as one hipGraph. */
 typedef struct usdm_decode_state {

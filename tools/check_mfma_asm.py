@@ -77,17 +77,20 @@ def audit_paths(lines, i0, i1):
     so a linear scan reads the epilogue as code under one body's ring, and a walk that takes both sides of those branches runs
     from one body into the other.  This walk keeps the constant flags it has seen set: a branch on a known flag is followed one
     way, every other conditional branch both ways; s_branch is followed, s_endpgm ends a path, a state is walked once.
+    A flag is also tested as `s_and_saveexec_b64 saved, flag` + s_cbranch_execz / execnz (gemv_resident_wpack_kernel: the skip
+    return enters the merged last store that way, under a zero flag): exec is then known to be zero until it is written again.
     -> (asm load instructions seen, [(line offset, code)] as audit())"""
     label = {m.group(1): i for i in range(i0, i1) if (m := re.match(r"(\.LBB\d+_\d+):", lines[i]))}
     seen, bad, loads = set(), {}, set()
-    stack = [(i0, (), (), None)]
+    stack = [(i0, (), (), None, False)]
     while stack:
-        i, fifo, flags, vcc = stack.pop()    # flags: known constant s[a:b]; vcc: True = known non-zero, False = known zero
+        # flags: known constant s[a:b]; vcc: True = known non-zero, False = known zero; execz: exec is known to be zero
+        i, fifo, flags, vcc, execz = stack.pop()
         fifo, flags, inasm = list(fifo), dict(flags), False
         while i < i1:
             code = lines[i].split(";")[0]
             if re.match(r"\.LBB\d+_\d+:", lines[i]):
-                key = (i, tuple(fifo), tuple(sorted(flags.items())), vcc)
+                key = (i, tuple(fifo), tuple(sorted(flags.items())), vcc, execz)
                 if key in seen:
                     break
                 seen.add(key)
@@ -119,6 +122,8 @@ def audit_paths(lines, i0, i1):
                 ops = re.match(r"\s*(\w+)\s+([^,\s]+)(?:,\s*([^,\s]+))?(?:,\s*([^,\s]+))?", code)
                 if ops and not ops.group(1).startswith(("s_cbranch", "s_branch", "s_cmp", "s_waitcnt", "s_nop", "s_barrier")):
                     op, dst, a, b = ops.groups()
+                    if dst == "exec" or "saveexec" in op:
+                        execz = op == "s_and_saveexec_b64" and flags.get(a) == 0
                     if dst == "vcc" or op.startswith("v_cmp") and "_e64" not in op:
                         known = op in ("s_and_b64", "s_andn2_b64") and a == "exec" and b in flags
                         vcc = (bool(flags[b]) == (op == "s_and_b64")) if known else None    # (exec is not zero where a wave runs)
@@ -138,10 +143,12 @@ def audit_paths(lines, i0, i1):
                     i = label[m.group(2)]
                     continue
                 if m:
-                    taken = {"s_cbranch_vccz": vcc is not True, "s_cbranch_vccnz": vcc is not False}.get(m.group(1), True)
-                    falls = {"s_cbranch_vccz": vcc is not False, "s_cbranch_vccnz": vcc is not True}.get(m.group(1), True)
+                    taken = {"s_cbranch_vccz": vcc is not True, "s_cbranch_vccnz": vcc is not False,
+                             "s_cbranch_execnz": not execz}.get(m.group(1), True)
+                    falls = {"s_cbranch_vccz": vcc is not False, "s_cbranch_vccnz": vcc is not True,
+                             "s_cbranch_execz": not execz}.get(m.group(1), True)
                     if taken and falls:
-                        stack.append((label[m.group(2)], tuple(fifo), tuple(flags.items()), vcc))
+                        stack.append((label[m.group(2)], tuple(fifo), tuple(flags.items()), vcc, execz))
                     elif taken:
                         i = label[m.group(2)]
                         continue

@@ -30,6 +30,8 @@ lib.usdm_dequant_mxfp4.restype = C.c_int
 lib.usdm_gemv_mxfp4_mfma.restype = C.c_int   # (the MXFP4 matrix-core form: likewise)
 lib.usdm_gemv_packed.restype = C.c_int       # (the 13-bit weight image: likewise)
 lib.usdm_gemv_packs.restype = C.c_int
+lib.usdm_gemv_packed_glu.restype = C.c_int   # (its gate/up form: likewise)
+lib.usdm_gemv_packs_glu.restype = C.c_int
 lib.usdm_logprobs.restype = C.c_int          # (the log-probability entry points: likewise)
 lib.usdm_logprobs_seg.restype = C.c_int
 lib.usdm_prompt_logprobs.restype = C.c_int   # (the scoring entry points: likewise)

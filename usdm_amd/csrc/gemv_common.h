@@ -7,10 +7,11 @@
 //       gemv_sumsq8        gemv_kernel, gemv_resident_kernel, chain, engine (gemv_batch_kernel keeps the text, see there;
 //                          gemv_mfma_kernel's statistic is another expression on purpose)
 //       gemv_rmsnorm8      gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain, engine (gemv_mfma_kernel keeps the text)
-//       gemv_glu_row       gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain
-//       gemv_swiglu_value  gemv_kernel, gemv_resident_kernel, gemv_batch_kernel, chain, engine
+//       gemv_glu_row       gemv_kernel, gemv_resident_kernel, gemv_resident_wpack_kernel, gemv_batch_kernel, chain
+//       gemv_swiglu_value  gemv_kernel, gemv_resident_kernel, gemv_resident_wpack_kernel, gemv_batch_kernel, chain, engine
 //       gemv_plain_value   gemv_kernel, gemv_stream_kernel, gemv_stream_wpack_kernel, chain, engine (gemv_batch_kernel keeps the text)
-//       gemv_wpack8        gemv_stream_wpack_kernel (the rebuild of eight bf16 weights from the 13-bit image)
+//       gemv_wpack8        gemv_stream_wpack_kernel, gemv_resident_wpack_kernel (the rebuild of eight bf16 weights from the
+//                          13-bit image)
 // The structural pieces of the bf16 batch-1 kernels (hand-counted loads, the RMSNorm reduction): gemv_pieces.h.
 // The launch selection and the argument checks of the launchers: gemv_launch.h.
 // A new weight format plugs in here: DESIGN.md section 8f.

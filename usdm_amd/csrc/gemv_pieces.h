@@ -1,9 +1,13 @@
 // Structural pieces of the bf16 batch-1 decode GEMVs of llm_k.hip, one text each (the arithmetic pieces: gemv_common.h).
 //   * gemv_load16, gemv_early_loads: the hand-counted early loads of x and the RMSNorm weights
-//       gemv_kernel and gemv_resident_kernel (x + two weight pieces); gemv_stream_kernel (gemv_load16 twice: two pieces of x);
-//   * gemv_ring_load: the hand-counted ring load of the straight-line K loops - gemv_resident_kernel, gemv_stream_kernel;
-//   * gemv_unit_load: the hand-counted ring load of a unit of the 13-bit weight image - gemv_stream_wpack_kernel;
-//   * gemv_rms_rstd: the RMSNorm statistic over the waves of a workgroup - gemv_kernel, gemv_resident_kernel, the chain's stage_x.
+//       gemv_kernel, gemv_resident_kernel and gemv_resident_wpack_kernel (x + two weight pieces); gemv_stream_kernel and
+//       gemv_stream_wpack_kernel (gemv_load16 twice: two pieces of x);
+//   * gemv_ring_load: the hand-counted ring load of the straight-line K loops - gemv_resident_kernel, gemv_stream_kernel and the
+//       marked rows of the two packed kernels;
+//   * gemv_unit_load: the hand-counted ring load of a unit of the 13-bit weight image - gemv_stream_wpack_kernel,
+//       gemv_resident_wpack_kernel;
+//   * gemv_rms_rstd: the RMSNorm statistic over the waves of a workgroup - gemv_kernel, gemv_resident_kernel,
+//       gemv_resident_wpack_kernel, the chain's stage_x.
 // None of them puts a run-time branch around a load that is issued before a counted wait: the wait-count pass drains the ring at
 // control-flow joins around loads (gemv_kernel's comments).
 // What stays text in its kernels, because as a function it compiled to other device code in gemv_kernel (tools/isa_diff.py

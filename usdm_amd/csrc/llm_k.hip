@@ -27,6 +27,9 @@
 #ifndef USDM_GEMV_WPACK_UB
 #define USDM_GEMV_WPACK_UB 12  // ring depth of its marked (bf16) rows
 #endif
+#ifndef USDM_GEMV_GU_WPACK_RU
+#define USDM_GEMV_GU_WPACK_RU 4   // units in flight per lane in gemv_resident_wpack_kernel (208 bytes; 5 and 6 for A/B builds)
+#endif
 namespace {
 // ---------------------------------------------------------------------------------------------
 // GEMV: y = W x, W bf16 [N][ldw] row-major (the nn.Linear layout).
@@ -812,6 +815,183 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
   if (a.y32) a.y32[ob] = v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// gemv_resident_kernel<2, 7, 2, 8> (gate/up of the 7B: two tiles per workgroup, K = 4096) over the lossless 13-bit image of the
+// interleaved gate/up matrix: the same grid, tile-to-workgroup assignment, rows (gemv_glu_row), prologue and epilogue, 13/16 of
+// the bytes.  A row is two units (gemv_unit_load); a wave's 2 tiles x 2 units x 4 rows are ONE straight-line sequence of 16 units,
+// unit s = (tile, unit of the row, row) in that order, so that acc[j] sees its row's iterations 0..7 in order, each as
+// dot8(gemv_wpack8<P>(...), the x piece of the iteration, acc[j]) - identical bits - and the four rows of a step share the four x
+// pieces of its iterations (16 VGPRs, replaced piece by piece under the step's last row).  The ring holds RU units, hand-counted:
+// a unit is consumed behind a wait that names the 4 * (RU - 1) younger loads and its slot is refilled at once with unit s + RU,
+// which in the last RU units of tile 0 is a unit of tile 1 - the ring does not drain at the seam and the epilogue of tile 0 runs
+// with tile 1's units in flight.  In the last RU units nothing is refilled and the count falls by four per consume.
+// The image's marked bit o says that the gate row or the up row of OUTPUT o holds a weight outside the window.  A wave whose four
+// outputs (two per tile) have a bit set streams both its tiles from the bf16 matrix: a wave-uniform branch on the bits (kernel
+// arguments, no memory round trip), taken before any ring load, into gemv_resident_kernel's straight-line text (repeated here, not
+// shared: that kernel's device code stays what it is).  Each path has its own early loads, counted waits, skip return, x staging
+// and barriers, so no branch sits around a load that a counted wait covers; the paths meet at the end of the kernel.
+// ---------------------------------------------------------------------------------------------
+template <int RU>
+__global__ __launch_bounds__(7 * 64) __attribute__((amdgpu_waves_per_eu(4))) void gemv_resident_wpack_kernel(const usdm_gemv_args a,
+                                                                                                          const usdm_gemv_wpack p) {
+  constexpr int RW = 2, NWV = 7, TPW = 2, NIT = 8;
+  constexpr int NTH = NWV * 64, NR = 2 * RW, TILE = NWV * RW;
+  constexpr int UNR = gemv_ring_depth(NR, false, false);   // the marked waves' ring: gemv_resident_kernel's
+  constexpr int NU = NIT / 4, NSEQ = TPW * NU * NR;         // units per row; units of a wave
+  static_assert(RU >= 1 && RU <= NSEQ && NIT >= UNR && NIT % UNR == 0, "a full first ring; slot u = iteration u of every tile");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* xs = (bf16_t*)smem;  // [K] bf16
+  __shared__ float red[NWV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int skipv = a.skip ? *a.skip : 0;
+  const int K = a.K;           // NIT * 512 (the launcher)
+  const int Kpad = (K + 511) & ~511;
+  const int uwave = __builtin_amdgcn_readfirstlane(wave);   // the row bases are wave-uniform: scalar registers, one lane offset
+  // weight row j of this wave in tile t (rows past N re-read the last row, never stored)
+  auto row_of = [&](int t, int j) -> int {
+    const int r = gemv_glu_row((blockIdx.x + t * gridDim.x) * TILE + uwave * RW + (j % RW), j >= RW);
+    return r < a.N ? r : a.N - 1;
+  };
+  // Is one of the wave's outputs marked?  Its two outputs of a tile are an even / odd pair: two neighbouring bits of one word.
+  unsigned mk = 0u;
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    const int o = (blockIdx.x + t * gridDim.x) * TILE + uwave * RW;
+    if (2 * o < a.N) mk |= (p.marked[o >> 5] >> (o & 31)) & 3u;
+  }
+  const unsigned voff = lane * 16;
+  const int i0 = tid * 8;
+  // x into LDS, RMS-normalised where asked (gemv_resident_kernel's staging), once per workgroup, under the first ring
+  auto stage = [&](u32x4 x0, u32x4 ge0v, u32x4 ge1v) {
+    const float4 ge0 = __builtin_bit_cast(float4, ge0v), ge1 = __builtin_bit_cast(float4, ge1v);
+    const bf16_t* xg = (const bf16_t*)a.x;
+    const int iloop = i0 + NTH * 8;
+    if (a.norm_w) {
+      float ss = 0.f;
+      if (i0 < K) ss = gemv_sumsq8(x0, ss);
+      for (int i = iloop; i < K; i += NTH * 8) ss = gemv_sumsq8(*(const u32x4*)(xg + i), ss);
+      const float rstd = gemv_rms_rstd<NWV>(ss, red, K, a.eps);
+      if (i0 < Kpad) *(u32x4*)(xs + i0) = i0 < K ? gemv_rmsnorm8(x0, rstd, ge0, ge1) : u32x4{0, 0, 0, 0};
+      for (int i = iloop; i < Kpad; i += NTH * 8) {
+        u32x4 o = {0, 0, 0, 0};
+        if (i < K) o = gemv_rmsnorm8(*(const u32x4*)(xg + i), rstd, *(const float4*)(a.norm_w + i), *(const float4*)(a.norm_w + i + 4));
+        *(u32x4*)(xs + i) = o;
+      }
+    } else {
+      if (i0 < Kpad) *(u32x4*)(xs + i0) = i0 < K ? x0 : u32x4{0, 0, 0, 0};
+      for (int i = iloop; i < Kpad; i += NTH * 8) {
+        u32x4 v = {0, 0, 0, 0};
+        if (i < K) v = *(const u32x4*)(xg + i);
+        *(u32x4*)(xs + i) = v;
+      }
+    }
+    __syncthreads();
+  };
+  // the epilogue of tile t (gemv_resident_kernel's), run with the next tile's ring in flight
+  auto finish = [&](int t, float (&acc)[NR]) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) acc[j] = wave_sum(acc[j]);
+    if (lane == 0) {
+      const int ob = (blockIdx.x + t * gridDim.x) * TILE + wave * RW;
+#pragma unroll
+      for (int j = 0; j < RW; ++j) {
+        const int o = ob + j;
+        if (2 * o >= a.N) continue;
+        const float r = gemv_swiglu_value(acc[j], acc[j + RW], a.round_bf16);
+        if (a.y16) ((bf16_t*)a.y16)[o] = f2bf(r);
+        if (a.y32) a.y32[o] = r;
+      }
+    }
+  };
+  float acc[NR];
+  if (mk) {
+    // ---- a marked wave: gemv_resident_kernel<2, 7, 2, 8>'s text over the bf16 rows of both tiles
+    const char* wp[NR];
+    const char* wn[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) wp[j] = (const char*)((const bf16_t*)a.W + (int64_t)row_of(0, j) * a.ldw);
+    u32x4 x0 = {0u, 0u, 0u, 0u}, ge0v = x0, ge1v = x0;
+    gemv_early_loads(a, i0, K, x0, ge0v, ge1v);
+    u32x4 ring[NR][UNR];
+    gemv_for<UNR>([&](auto U) { gemv_for<NR>([&](auto J) { gemv_ring_load<U.value>(ring[J.value][U.value], wp[J.value], voff); }); });
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(x0), "+v"(ge0v), "+v"(ge1v) : "n"(UNR * NR));
+    if (skipv) return;
+    stage(x0, ge0v, ge1v);
+    u32x4 xv = *(const u32x4*)(xs + lane * 8);
+    gemv_for<TPW>([&](auto T) {
+      constexpr int t = decltype(T)::value;
+      constexpr bool has_next = t + 1 < TPW;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        acc[j] = 0.f;
+        wn[j] = has_next ? (const char*)((const bf16_t*)a.W + (int64_t)row_of(t + 1, j) * a.ldw) : wp[j];
+      }
+      gemv_for<NIT>([&](auto IT) {
+        constexpr int it = decltype(IT)::value, u = it % UNR;
+        constexpr bool refill = it + UNR < NIT || has_next;
+        const u32x4 xn = *(const u32x4*)(xs + (((it + 1) % NIT) * 64 + lane) * 8);
+        gemv_for<NR>([&](auto J) {
+          constexpr int j = decltype(J)::value;
+          constexpr int younger = refill ? NR * UNR - 1 : NR * UNR - 1 - ((it - (NIT - UNR)) * NR + j);
+          asm volatile("s_waitcnt vmcnt(%1)" : "+v"(ring[j][u]) : "n"(younger) : "memory");
+          acc[j] = dot8(ring[j][u], xv, acc[j]);
+          if constexpr (it + UNR < NIT) gemv_ring_load<it + UNR>(ring[j][u], wp[j], voff);
+          else if constexpr (has_next) gemv_ring_load<u>(ring[j][u], wn[j], voff);
+        });
+        xv = xn;
+      });
+      finish(t, acc);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) wp[j] = wn[j];
+    });
+  } else {
+    // ---- the packed rows: RU units in flight, unit s = row s % NR, unit (s / NR) % NU of the row, tile s / (NR * NU)
+    const char* pp[TPW][NR];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t)
+#pragma unroll
+      for (int j = 0; j < NR; ++j) pp[t][j] = (const char*)p.planes + (int64_t)row_of(t, j) * p.stride;
+    const unsigned base4 = (unsigned)p.base * 0x01010101u;
+    u32x4 x0 = {0u, 0u, 0u, 0u}, ge0v = x0, ge1v = x0;
+    gemv_early_loads(a, i0, K, x0, ge0v, ge1v);
+    gemv_wunit ring[RU];
+    gemv_for<RU>([&](auto S) {
+      constexpr int s = decltype(S)::value;
+      gemv_unit_load<(s / NR) % NU>(ring[s], pp[s / (NR * NU)][s % NR], voff);
+    });
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(x0), "+v"(ge0v), "+v"(ge1v) : "n"(4 * RU));
+    if (skipv) return;
+    stage(x0, ge0v, ge1v);
+    // the lane's x pieces of the step's four iterations; under the step's last row each is replaced, once used, by the piece of
+    // the next step (the asm statements are compiler barriers: read in front of the next step they would wait there)
+    u32x4 xq[4];
+#pragma unroll
+    for (int P = 0; P < 4; ++P) xq[P] = *(const u32x4*)(xs + (P * 64 + lane) * 8);
+    gemv_for<TPW>([&](auto T) {
+      constexpr int t = decltype(T)::value;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) acc[j] = 0.f;
+      gemv_for<NU>([&](auto UI) {
+        constexpr int un = decltype(UI)::value;
+        gemv_for<NR>([&](auto J) {
+          constexpr int j = decltype(J)::value, s = (t * NU + un) * NR + j, s2 = s + RU;
+          constexpr int younger = s2 < NSEQ ? 4 * (RU - 1) : 4 * (NSEQ - 1 - s);
+          gemv_wunit& r = ring[s % RU];
+          asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r.la), "+v"(r.lb), "+v"(r.nib), "+v"(r.sgn) : "n"(younger) : "memory");
+          gemv_for<4>([&](auto PI) {
+            constexpr int P = decltype(PI)::value;
+            const u32x4& lo = P < 2 ? r.la : r.lb;
+            acc[j] = dot8(gemv_wpack8<P>(lo[2 * (P & 1)], lo[2 * (P & 1) + 1], r.nib[P], r.sgn, base4), xq[P], acc[j]);
+            if constexpr (j == NR - 1) xq[P] = *(const u32x4*)(xs + ((4 * ((un + 1) % NU) + P) * 64 + lane) * 8);
+          });
+          if constexpr (s2 < NSEQ) gemv_unit_load<(s2 / NR) % NU>(r, pp[s2 / (NR * NU)][s2 % NR], voff);
+        });
+      });
+      finish(t, acc);
+    });
+  }
+}
+
 // final arg-max over the per-block partials; advances the device-side decode state
 // (nseg segments of nparts partials per sequence, seg_stride apart: the tensor-parallel batched step gathers [rank][sequence][nparts])
 __global__ void argmax_final_kernel(const float* pv, const int* pi, int nparts, int nseg, int64_t seg_stride, usdm_decode_state st,
@@ -860,7 +1040,8 @@ __global__ void residual_add_kernel(bf16_t* h, const float* delta, int n) {
 }  // namespace
 
 // Workgroups of `kern` the current device holds at once (the occupancy query x its CUs), remembered for the last kernel, device
-// and LDS size asked about
+// and LDS size asked about (WHO: one memory per asker, so that the bf16 and the packed gate/up launches of a step keep theirs)
+template <int WHO = 0>
 static int gemv_resident_count(const void* kern, int nth, size_t lds, int* out) {
   static thread_local const void* c_kern = nullptr;
   static thread_local int c_dev = -1, c_n = 0;
@@ -878,6 +1059,13 @@ static int gemv_resident_count(const void* kern, int nth, size_t lds, int* out) 
   return 0;
 }
 
+// Where the selection's (2, GLU, 7) row runs in its STRAIGHT-LINE resident form: two tiles on every workgroup of `grid`, K = 4096,
+// no x_delta.  The one statement of that choice: gemv_launch_resident reads it for the bf16 kernel, gemv_packed_glu_grid for the
+// packed one.
+static bool gemv_straight_form(const usdm_gemv_args& a, int ntiles, int grid) {
+  return !a.x_delta && a.K == 8 * 512 && ntiles == 2 * grid;
+}
+
 // The resident form of the selection's (2, GLU, 7) row: *launched = false where one tile per workgroup is all there is to run
 // (every tile already resident, or x_delta) and the one-tile kernel takes the launch.
 static int gemv_launch_resident(const usdm_gemv_args& a, const gemv_sel& s, size_t lds, hipStream_t st, bool* launched) {
@@ -891,7 +1079,7 @@ static int gemv_launch_resident(const usdm_gemv_args& a, const gemv_sel& s, size
   if (int rc = gemv_resident_count((const void*)straight, NWV * 64, lds, &n)) return rc;
   int grid = min(min(n, s.res), ntiles);
   if (grid == ntiles) return 0;
-  if (a.K == 8 * 512 && ntiles == 2 * grid) {
+  if (gemv_straight_form(a, ntiles, grid)) {
     hipLaunchKernelGGL(straight, dim3(grid), dim3(NWV * 64), lds, st, a);
   } else {
     if (int rc = gemv_resident_count((const void*)generic, NWV * 64, lds, &n)) return rc;
@@ -982,6 +1170,44 @@ extern "C" int usdm_gemv_packed(const usdm_gemv_args* pa, const usdm_gemv_wpack*
   const gemv_sel s = gemv_select(a, false);
   hipLaunchKernelGGL((gemv_stream_wpack_kernel<28, USDM_GEMV_WPACK_RU, USDM_GEMV_WPACK_UB>), dim3(s.grid), dim3(1024), (size_t)a.K * 2,
                      (hipStream_t)stream, a, *pk);
+  USDM_LAUNCH_CHECK();
+  return 0;
+}
+// The packed gate/up form: *grid = the grid on which gemv_resident_wpack_kernel runs the call, 0 where the call has no packed form.
+// That is exactly where gemv_launch_resident launches the straight-line bf16 instantiation: a plain bf16 SwiGLU call on the
+// selection's resident row, in the straight-line form on the grid of the kernel that is launched (the occupancy question is asked
+// about the packed kernel; what needs no device is tested first, so that every other call is answered without one).
+static int gemv_packed_glu_grid(const usdm_gemv_args& a, int* grid) {
+  *grid = 0;
+  const gemv_sel s = gemv_select(a, false);
+  if (!(s.glu && s.rw == 2 && s.nwv == 7 && s.res > 0) || a.x_out || a.K != 8 * 512 || a.x_delta) return 0;
+  int n = 0;
+  if (int rc = gemv_resident_count<1>((const void*)gemv_resident_wpack_kernel<USDM_GEMV_GU_WPACK_RU>, 7 * 64, (size_t)a.K * 2, &n)) return rc;
+  const int g = min(min(n, s.res), s.grid);
+  if (gemv_straight_form(a, s.grid, g)) *grid = g;
+  return 0;
+}
+
+// 1 where usdm_gemv_packed_glu streams the 13-bit image (0 also where the device cannot be asked: such a launch fails anyway)
+extern "C" int usdm_gemv_packs_glu(const usdm_gemv_args* pa) {
+  int grid = 0;
+  return pa && gemv_packed_glu_grid(*pa, &grid) == 0 && grid > 0 ? 1 : 0;
+}
+
+extern "C" int usdm_gemv_packed_glu(const usdm_gemv_args* pa, const usdm_gemv_wpack* pk, usdm_stream_t stream) {
+  USDM_CHECK_ARG(pa && pa->W && pa->x && pk && pk->planes && pk->rowflag, "usdm_gemv_packed_glu: null args");
+  USDM_CHECK_ARG(pa->act == USDM_ACT_SWIGLU && pa->N / 2 <= 14336, "usdm_gemv_packed_glu: a SwiGLU call of at most 14336 outputs (usdm_gemv_wpack.marked)");
+  const usdm_gemv_args& a = *pa;
+  int grid = 0;
+  if (int rc = gemv_packed_glu_grid(a, &grid)) return rc;
+  if (!grid) return usdm_gemv(pa, stream);   // no packed form of this call: the bf16 kernels, the same bits
+  if (int rc = gemv_check_shape("usdm_gemv_packed_glu", a, "input vector")) return rc;
+  if (int rc = gemv_check_outputs("usdm_gemv_packed_glu", a)) return rc;
+  USDM_CHECK_ARG(pk->units == 2 && pk->stride % 16 == 0 && pk->stride >= (int64_t)2 * GEMV_WPACK_UNIT && pk->base >= 0 && pk->base <= 112,
+                 "usdm_gemv_packed_glu: the image must hold 2 units of 3328 bytes per row, stride a multiple of 16, base 0..112");
+  USDM_CHECK_ARG(((uintptr_t)pk->planes & 15) == 0 && ((uintptr_t)pk->rowflag & 3) == 0,
+                 "usdm_gemv_packed_glu: planes must be 16-byte, rowflag 4-byte aligned");
+  hipLaunchKernelGGL((gemv_resident_wpack_kernel<USDM_GEMV_GU_WPACK_RU>), dim3(grid), dim3(7 * 64), (size_t)a.K * 2, (hipStream_t)stream, a, *pk);
   USDM_LAUNCH_CHECK();
   return 0;
 }

@@ -259,9 +259,11 @@ class USDMForCausalLM:
                  enable_prefix_caching=False, weight_packing=None, mxfp4_matrix_cores=False):
         check_quantization(quantization, fp8_matrix_cores, mxfp4_matrix_cores)
         # weight_packing (default on; USDM_WPACK=0 or False turns it off for A/B runs): the single-sequence decode step streams
-        # down_proj from a lossless 13-bit image of its bf16 weights (usdm_amd/wpack.py; identical bits, 13/16 of the bytes).  One GPU,
-        # plain bf16 weights and the 7B's down_proj shape only; the image is built at load, beside the bf16 matrix.
+        # down_proj and gate/up from lossless 13-bit images of their bf16 weights (usdm_amd/wpack.py; identical bits, 13/16 of the
+        # bytes).  One GPU, plain bf16 weights and the 7B's MLP shapes only; the images are built at load, beside the bf16 matrices.
+        # USDM_WPACK_GU=0: down_proj only (A/B runs of the gate/up image).
         self.weight_packing = (os.environ.get("USDM_WPACK", "1") != "0") if weight_packing is None else bool(weight_packing)
+        self.weight_packing_gu = self.weight_packing and os.environ.get("USDM_WPACK_GU", "1") != "0"
         self.wpack_report = None
         # enable_prefix_caching (vLLM's name; opt-in): batch slots reuse cached prompt rows (usdm_amd/prefix.py), and an
         # fp8-cache model reuses its prefix on the single sequence too.  Off: no index, no buffer and no plan of it is built.
@@ -499,10 +501,12 @@ class USDMForCausalLM:
 
     def _pack_weights(self):
         """The 13-bit images of the layers' down_proj matrices (weight_packing; the conditions: one GPU, plain bf16 weights, the
-        7B's shape N 4096 / K 14336 - where usdm_gemv has the straight-line form).  Each image verifies its own round trip
-        (wpack.PackedWeight.from_matrix raises otherwise).  wpack_report: per matrix the share of marked rows, the extra device
-        memory and the time the packing took."""
-        self.wpack_down = None
+        7B's shape N 4096 / K 14336 - where usdm_gemv has the straight-line form) and, under the same conditions and unless
+        USDM_WPACK_GU=0, of their interleaved gate/up matrices (N 28672 / K 4096).  Each image verifies its own round trip
+        (wpack.PackedWeight.from_matrix raises otherwise).  wpack_report: per down_proj matrix the share of marked rows, the extra
+        device memory and the time the packing took; the gu_* keys say the same of the gate/up images (marked OUTPUTS: a gate or an
+        up row marked), the other keys keep their down_proj-only meaning."""
+        self.wpack_down = self.wpack_gu = None
         if not (self.weight_packing and self.tp_size == 1 and not self.tp_path and self.p2p is None and self.quantization is None
                 and self.cfg["hidden_size"] == 4096 and self.I == 14336):
             return
@@ -512,6 +516,12 @@ class USDMForCausalLM:
         self.wpack_report = {"down_marked_share": [p.marked_share for p in self.wpack_down],
                              "down_marked_rows": sum(len(p.marked_rows) for p in self.wpack_down),
                              "extra_bytes": sum(p.nbytes for p in self.wpack_down), "seconds": time.perf_counter() - t0}
+        if self.weight_packing_gu:
+            t0 = time.perf_counter()
+            self.wpack_gu = [PackedWeight.from_matrix(w["gu"], glu=True) for w in self.W["layers"]]
+            torch.cuda.synchronize(self.device)
+            self.wpack_report.update({"gu_marked_outputs": [len(p.marked_outputs) for p in self.wpack_gu],
+                                      "gu_extra_bytes": sum(p.nbytes for p in self.wpack_gu), "gu_seconds": time.perf_counter() - t0})
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self):
@@ -765,7 +775,7 @@ class USDMForCausalLM:
         H, d = c["hidden_size"], c["head_dim"]
         return H, d, c["num_hidden_layers"], self.Hq, self.Hkv, self.I, (self.Hq + 2 * self.Hkv) * d
 
-    def _layers(self, rec, gemv, attn, h, qkv, ao, act, way, n=0, parts=None, h_alt=None, down_kw={}, down_wp=None):
+    def _layers(self, rec, gemv, attn, h, qkv, ao, act, way, n=0, parts=None, h_alt=None, down_kw={}, down_wp=None, gu_wp=None):
         """The Mistral layers of every plan: this loop is the one statement of a layer's launch order.
         gemv(W, x, N=, K=, ...): the plan's projection launcher, in usdm_gemv's keywords (norm_w / eps: RMSNorm of x fused in front).
         attn(l): rope, cache and attention of layer l from qkv into ao; returns the keywords its hand-off adds to the o_proj launch.
@@ -782,12 +792,12 @@ class USDMForCausalLM:
         H, d, _, Hq, Hkv, I, nq = self._dims()
         eps, h0, pend = self.cfg["rms_norm_eps"], h, None
 
-        def proj(W, ln, N, out, a=0):
+        def proj(W, ln, N, out, a=0, **kw):
             nonlocal h, pend
             if pend is None:
-                return gemv(W, h, N=N, K=H, norm_w=ln, eps=eps, act=a, y16=out)
+                return gemv(W, h, N=N, K=H, norm_w=ln, eps=eps, act=a, y16=out, **kw)
             nxt = h_alt if h is h0 else h0
-            gemv(W, h, N=N, K=H, norm_w=ln, eps=eps, act=a, y16=out, x_delta=pend, x_out=nxt)
+            gemv(W, h, N=N, K=H, norm_w=ln, eps=eps, act=a, y16=out, x_delta=pend, x_out=nxt, **kw)
             h, pend = nxt, None
 
         def land(W, x, K, site, **kw):
@@ -813,7 +823,7 @@ class USDMForCausalLM:
             proj(w["qkv"], w["ln1"], nq, qkv)
             o_kw = attn(l) or {}
             land(w["o"], ao, Hq * d, 2 * l, **o_kw)
-            proj(w["gu"], w["ln2"], 2 * I, act, ACT_SWIGLU)
+            proj(w["gu"], w["ln2"], 2 * I, act, ACT_SWIGLU, **({"wpack": gu_wp[l]} if gu_wp else {}))
             land(w["down"], act, I, 2 * l + 1, **down_kw, **({"wpack": down_wp[l]} if down_wp else {}))
         return h, pend
 
@@ -985,9 +995,10 @@ class USDMForCausalLM:
                 return None
             return dict(merge=mrg, cmb=(gran, self.cmb_err) if use_cmb else None)
 
-        # (down_wp: the 13-bit images of the down_proj matrices - this step only; a chained step keeps its bf16 phases)
+        # (down_wp, gu_wp: the 13-bit images of the down_proj and gate/up matrices - this step only; a chained step keeps its bf16
+        # phases)
         h, pend = self._layers(rec, gemv, attn, h, qkv, ao, act, way, n=H, parts=parts, h_alt=h_alt,
-                               down_wp=self.wpack_down if way == "fused" else None)
+                               down_wp=self.wpack_down if way == "fused" else None, gu_wp=self.wpack_gu if way == "fused" else None)
         if chain:     # the last layer's chain has no next qkv to wait for
             flush()
         # (pend: the last down-projection's sum goes into the final norm + lm_head)

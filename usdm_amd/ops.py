@@ -262,6 +262,8 @@ def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p
     only_args=True: return the filled usdm_gemv_args instead of launching (a phase of usdm_gemv_chain).
     wpack: a wpack.PackedWeight of W (bf16 W only): usdm_gemv_packed, which streams the 13-bit image where usdm_gemv_packs says
     the call has a packed form (down_proj's straight-line form) and is usdm_gemv everywhere else - identical bits either way.
+    A SwiGLU call takes the image of the interleaved gate/up matrix (PackedWeight.from_matrix(W, glu=True)) through
+    usdm_gemv_packed_glu / usdm_gemv_packs_glu in the same way (gate/up's straight-line resident form).
     W a quant.Fp8Weight / quant.Mxfp4Weight: usdm_gemv_fp8 / usdm_gemv_mxfp4 (the plain single-GPU forms only; the library refuses
     the others)."""
     _need_cuda(x_delta, x_out, skip)
@@ -300,15 +302,17 @@ def gemv(W, x, *, x_delta=None, x_out=None, skip=None, p2p=None, p2p_site=0, p2p
         f.b.g, f.b.nb, f.scales, f.lds = a, 1, _ptr(W.s), W.s.shape[1]
         _go(plan, "usdm_gemv_mxfp4", lib.usdm_gemv_mxfp4, C_.byref(f))
         return
-    if wpack is not None and not only_args and lib.usdm_gemv_packs(C_.byref(a)):
+    glu = a.act == _lib.ACT_SWIGLU
+    packs, packed = (lib.usdm_gemv_packs_glu, lib.usdm_gemv_packed_glu) if glu else (lib.usdm_gemv_packs, lib.usdm_gemv_packed)
+    if wpack is not None and not only_args and packs(C_.byref(a)):
         # the 13-bit image of W (usdm_amd.wpack): the same result from 13/16 of the bytes.  Recorded as usdm_gemv with the
         # usdm_gemv_args first: a plan's GEMV launches are counted and grouped by that name and struct.
-        if not wpack.is_cuda or (wpack.N, wpack.K) != (a.N, a.K):
+        if not wpack.is_cuda or (wpack.N, wpack.K, wpack.glu) != (a.N, a.K, glu):
             raise ValueError("usdm_gemv: wpack is the image of another matrix")
         p = wpack.args()
         if plan is not None:
             plan.hold(wpack.planes, wpack.rowflag)
-        _go(plan, "usdm_gemv", lib.usdm_gemv_packed, C_.byref(a), C_.byref(p))
+        _go(plan, "usdm_gemv", packed, C_.byref(a), C_.byref(p))
         return
     if only_args:
         return a

@@ -1,4 +1,4 @@
-"""Lossless 13-bit image of a bf16 weight matrix for the batch-1 decode GEMVs (default on for the 7B's down_proj).
+"""Lossless 13-bit image of a bf16 weight matrix for the batch-1 decode GEMVs (default on for the 7B's down_proj and gate/up).
 
 The exponent field of a weight matrix is almost constant: of the 8 exponent bits of a bf16 weight the upper seven take, for all but
 a few weights in a hundred million, one of 16 neighbouring values.  A weight with the 16 bits b is therefore stored as
@@ -18,6 +18,11 @@ iterations i = 0..3, and every plane is contiguous over the lanes:
     bytes 2048 .. 3071   nibbles: dword 4 L + i, byte k (0..3) = index of e(i, k) | index of e(i, k + 4) << 4
     bytes 3072 .. 3327   signs: dword L, the sign of e(i, k) at bit 8 (k & 3) + 7 - (2 i + (k >> 2))
 so that the kernel needs no per-weight shift.  Packing runs once at load, with torch ops on the device the matrix is on.
+
+The interleaved gate/up matrix of a SwiGLU projection (blocks of 16 gate + 16 up rows; PackedWeight.from_matrix(w, glu=True)) is
+packed row by row in the same layout.  Its kernel works on OUTPUTS - a wave streams the gate and the up rows of its outputs
+together - so the bitmap in the kernel argument is per output there: output o is marked when its gate row or its up row is
+(glu_row; csrc/gemv_common.h gemv_glu_row).
 """
 import ctypes as C
 
@@ -25,7 +30,12 @@ import torch
 
 UNIT_ELEMS = 2048
 UNIT_BYTES = 3328
-MAX_ROWS = 14336      # rows the kernel argument's bitmap of marked rows covers
+MAX_ROWS = 14336      # rows (glu: outputs) the kernel argument's bitmap of marked rows covers
+
+
+def glu_row(o, up):
+    """Weight row of SwiGLU output o in the interleaved gate/up matrix (csrc/gemv_common.h gemv_glu_row)."""
+    return (o >> 4) * 32 + (o & 15) + (16 if up else 0)
 
 
 def _i16(w):
@@ -98,23 +108,28 @@ class GemvWpack(C.Structure):
 
 class PackedWeight:
     """The image of one matrix as ops.gemv(..., wpack=) takes it.  from_matrix verifies its own round trip - unpack(pack(W)) == W
-    on the raw bits of every unmarked row - and raises if that fails."""
-    __slots__ = ("planes", "rowflag", "base", "N", "K", "marked_rows")
+    on the raw bits of every unmarked row - and raises if that fails.  glu: the interleaved gate/up matrix of a SwiGLU call;
+    marked_outputs are then the outputs whose gate or up row is marked (the bits of args().marked), else None."""
+    __slots__ = ("planes", "rowflag", "base", "N", "K", "marked_rows", "glu", "marked_outputs")
 
-    def __init__(self, planes, rowflag, base, K):
-        self.planes, self.rowflag, self.base, self.K = planes, rowflag, int(base), K
+    def __init__(self, planes, rowflag, base, K, glu=False):
+        self.planes, self.rowflag, self.base, self.K, self.glu = planes, rowflag, int(base), K, bool(glu)
         self.N = planes.shape[0]
-        if self.N > MAX_ROWS:
-            raise ValueError(f"wpack: at most {MAX_ROWS} rows")
+        if glu and self.N % 32:
+            raise ValueError("wpack: a gate/up matrix has a multiple of 32 rows")
+        if (self.N // 2 if glu else self.N) > MAX_ROWS:
+            raise ValueError(f"wpack: at most {MAX_ROWS} {'outputs' if glu else 'rows'}")
         self.marked_rows = torch.nonzero(rowflag[:self.N]).flatten().tolist()
+        # rows [block][gate | up][16] -> outputs [block][16]: glu_row's formula
+        self.marked_outputs = torch.nonzero(rowflag[:self.N].view(-1, 2, 16).amax(dim=1).flatten()).flatten().tolist() if glu else None
 
     @classmethod
-    def from_matrix(cls, w):
+    def from_matrix(cls, w, glu=False):
         planes, flag, base = pack(w)
         ok = (unpack(planes, base, w.shape[1]) == _i16(w)).all(dim=1) | (flag[:w.shape[0]] != 0)
         if not bool(ok.all()):
             raise RuntimeError("wpack: the packed image does not reproduce the matrix")
-        return cls(planes, flag, base, w.shape[1])
+        return cls(planes, flag, base, w.shape[1], glu)
 
     @property
     def is_cuda(self):
@@ -132,6 +147,6 @@ class PackedWeight:
         a = GemvWpack()
         a.planes, a.rowflag = C.c_void_p(self.planes.data_ptr()), C.c_void_p(self.rowflag.data_ptr())
         a.stride, a.base, a.units = self.planes.shape[1], self.base, self.K // UNIT_ELEMS
-        for r in self.marked_rows:
+        for r in (self.marked_outputs if self.glu else self.marked_rows):
             a.marked[r >> 5] |= 1 << (r & 31)
         return a
