@@ -905,6 +905,40 @@ int usdm_spec_commit_batch(const usdm_spec_batch_args* args, const usdm_decode_s
                            void* h_out_bf16, usdm_stream_t stream);
 int usdm_sizeof_spec_batch_args(void);
 
+/* Speculative decoding for SAMPLED requests: the picks of the n * T rows of a verify step, drawn instead of
+ * arg-maxed.  One launch, one workgroup of 1024 threads per row; row r = b * T + i belongs to sequence / slot b and reads
+ * logits + r * logits_bs (f32 [V], banned ids = -inf).  It draws as usdm_sample_final does - the same text - with the knobs of
+ * dev_params[b] (sanitised as there) and the Philox counter (unsigned)(step[b] + i): picks[r] is the LOCAL id that
+ * usdm_sample_final commits (minus id_offset) for that row, those knobs and step[b] + i, bit for bit - top_k == 1 takes the lowest
+ * id among ties, a row without mass the arg-max of its finite logits, else id 0.  The token at a position is therefore a function
+ * of (its logits row, the knobs, the seed, the position) and of nothing else, which is what makes "draw, accept the draft iff it
+ * equals the draw" exact and independent of the drafts.
+ * Nothing else is written: no commit, no embedding row, no state word.  done != NULL and done[b] != 0: sequence b's workgroups return
+ * at once and its picks keep their old values.  So does row i >= 1 unless drafts[b][1 .. i] are all >= 0: the accept loop of the
+ * commit stops at the first draft that is -1 and never reads such a pick.
+ * Refused: T outside 1 .. 8, n < 1, n * T > 16, V outside 1 .. 2^20, logits_bs < V with more than one row, a NULL logits,
+ * dev_params, step, drafts or picks. */
+typedef struct usdm_spec_sample_args {
+  const float* logits; int64_t logits_bs;      /* [n * T][logits_bs] */
+  int32_t V, T, n;
+  const usdm_sample_params* dev_params;        /* [n] device */
+  const int32_t* step;                         /* [n] device: the decode state's */
+  const int32_t* done;                         /* [n] device or NULL */
+  const int32_t* drafts;                       /* [n][8] device: the ids fed as rows 1 .. T-1 */
+  int32_t* picks;                              /* [n * T] device */
+} usdm_spec_sample_args;
+int usdm_spec_sample(const usdm_spec_sample_args* args, usdm_stream_t stream);
+int usdm_sizeof_spec_sample_args(void);
+
+/* usdm_spec_commit / usdm_spec_commit_batch from GIVEN picks: picks [T] (batch: [B * T], slot b's at b * T) are the rows' LOCAL ids
+ * (usdm_spec_sample's), g_i = picks[i] + st->id_offset, in place of the arg-max of the partials - part_val / part_idx / nparts are
+ * not read.  Everything behind the pick - accept, stop ids, min_new, the limit, the counters, the proposal, the T embedding rows,
+ * propose_only, done - is the same text as the arg-max forms'.  Refused: what those refuse, and picks == NULL unless propose_only. */
+int usdm_spec_commit_picks(const usdm_spec_args* args, const int32_t* picks, const usdm_decode_state* st, const void* embed_table_bf16,
+                           int32_t Hd, void* h_out_bf16, usdm_stream_t stream);
+int usdm_spec_commit_batch_picks(const usdm_spec_batch_args* args, const int32_t* picks, const usdm_decode_state* st,
+                                 const void* embed_table_bf16, int32_t Hd, void* h_out_bf16, usdm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * One-shot peer-to-peer all-reduce for the tensor-parallel decode step (replaces the single-GPU
  * model.generate of src/inference.py:116-123 when the 7B is sharded over the 8 GPUs of a node).  Messages are 4096 f32

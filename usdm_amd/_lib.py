@@ -48,6 +48,9 @@ lib.usdm_attn_verify.restype = C.c_int       # (the speculative-decoding entry p
 lib.usdm_spec_commit.restype = C.c_int
 lib.usdm_attn_verify_batch.restype = C.c_int
 lib.usdm_spec_commit_batch.restype = C.c_int
+lib.usdm_spec_sample.restype = C.c_int       # (sampled speculation: the rows' draws and the commit from given picks)
+lib.usdm_spec_commit_picks.restype = C.c_int
+lib.usdm_spec_commit_batch_picks.restype = C.c_int
 _exp = None
 
 
@@ -338,6 +341,13 @@ class SpecBatchArgs(C.Structure):
     _fields_ = [("s", SpecArgs), ("slot_lo", C.c_int32), ("n", C.c_int32)]
 
 
+class SpecSampleArgs(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p), ("logits_bs", C.c_int64), ("V", C.c_int32), ("T", C.c_int32), ("n", C.c_int32),
+        ("dev_params", C.c_void_p), ("step", C.c_void_p), ("done", C.c_void_p), ("drafts", C.c_void_p), ("picks", C.c_void_p),
+    ]
+
+
 def check(rc, what=""):
     if rc != 0:
         raise UsdmError(f"{what} failed (rc={rc}): {lib.usdm_last_error().decode()}")
@@ -356,7 +366,8 @@ def _selfcheck():
                       ("attn_decode_fp8", AttnDecodeFp8Args), ("rope_fp8", RopeFp8Args), ("logprob", LogprobArgs),
                       ("penalty", PenaltyArgs), ("logit_edit", LogitEditArgs), ("prompt_logprob", PromptLogprobArgs), ("beam", BeamArgs),
                       ("kv_reorder", KvReorderArgs), ("kv_expand", KvExpandArgs), ("attn_verify", AttnVerifyArgs), ("spec", SpecArgs),
-                      ("attn_verify_batch", AttnVerifyBatchArgs), ("spec_batch", SpecBatchArgs)):
+                      ("attn_verify_batch", AttnVerifyBatchArgs), ("spec_batch", SpecBatchArgs),
+                      ("spec_sample", SpecSampleArgs)):
         n = getattr(lib, f"usdm_sizeof_{name}" if name in ("decode_state", "p2p_dev") else f"usdm_sizeof_{name}_args")()
         if n != C.sizeof(cls):
             raise ImportError(f"ABI mismatch: usdm_{name}_args is {n} bytes in the library, {C.sizeof(cls)} in Python")

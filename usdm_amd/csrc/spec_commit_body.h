@@ -1,7 +1,9 @@
 // The body of the speculative commit kernels (spec_k.hip), included as text into spec_commit_kernel (one sequence) and
 // spec_commit_batch_kernel (one workgroup per slot): expects `a` (usdm_spec_args) and `st` (usdm_decode_state) of ONE sequence, the
 // embedding table E, Hd and that sequence's h_out rows.  Text and not a device function so that the single-sequence kernel compiles
-// to the code it had before the batch kernel existed (profiles/spec_batch_isa_diff.txt).
+// to the code it had before the batch kernel existed (profiles/spec_batch_isa_diff.txt).  SPEC_GIVEN_PICKS defined around the
+// include (the *_picks kernels): the pick stage reads `picks`, this sequence's T local ids, instead of arg-maxing
+// the partials; everything behind it is the same text.
   __shared__ float sv[256];
   __shared__ int si[256];
   __shared__ int s_g[SP_TMAX], s_d[SP_TMAX];
@@ -9,6 +11,11 @@
   const int tid = threadIdx.x, T = a.T;
   if (st.done && st.done[0]) return;
   if (!a.propose_only) {
+#ifdef SPEC_GIVEN_PICKS
+    // ---- picks: given as local ids (usdm_spec_sample's draws), `picks` of this sequence's T rows
+    if (tid < T) s_g[tid] = picks[tid] + st.id_offset;
+    __syncthreads();
+#else
     // ---- picks: row i's arg-max over its partials, usdm_argmax_final's reduction
     for (int i = 0; i < T; ++i) {
       const float* pv = a.part_val + (int64_t)i * a.nparts;
@@ -24,6 +31,7 @@
       if (tid == 0) s_g[i] = (si[0] == PICK_NO_ID ? 0 : si[0]) + st.id_offset;
       __syncthreads();
     }
+#endif
     // ---- accept and commit (one thread: at most 8 tokens)
     if (tid == 0) {
       const int s0 = st.step[0];

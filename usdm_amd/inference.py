@@ -80,7 +80,7 @@ def _bad(name, *a, **k):
 def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, tokenizer, output_path,
            reference_mel=None, n_timesteps=50, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
            min_p=0.0, logit_bias=None, no_repeat_ngram_size=0, num_beams=None, num_speculative_tokens=None, prompt_lookup_max=3,
-           prompt_lookup_min=1):
+           prompt_lookup_min=1, speculative_sampling=False):
     """src/inference.py:48-89.  logprobs=K (0 .. 20): the LLM also computes per-token log-probabilities (USDMForCausalLM.generate) and the
     cumulative log-probability of each of the three rounds goes to stderr; nothing else changes.
     repetition_penalty / presence_penalty / frequency_penalty: passed to all three rounds (USDMForCausalLM.generate; on the device).
@@ -89,7 +89,9 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
     hypothesis, HF's defaults length_penalty = 1 and early_stopping = False); its score goes to stderr.  Not with the knobs above.
     num_speculative_tokens=k (1 .. 7): the three rounds run speculative greedy decoding with n-gram drafts
     (USDMForCausalLM.generate(num_speculative_tokens=k, prompt_lookup_max, prompt_lookup_min)); steps, drafts and accepted drafts of
-    each round go to stderr.  Not with the knobs above or num_beams."""
+    each round go to stderr.  Not with the knobs above or num_beams.
+    speculative_sampling=True (with num_speculative_tokens): the rounds run the SAMPLED speculative step
+    (USDMForCausalLM.generate(speculative_sampling=True)), on which their top_k = 1 picks give the same ids and min_p is allowed."""
     bad_words_ids_unit2text = _bad("u2t", 32000, 42003)
     bad_words_ids_text2text = _bad("t2t", 32002, 42003)
     bad_words_ids_text2unit = _bad("t2u", 0, 32002, exclude=[28705])
@@ -109,7 +111,7 @@ def sample(user_path, reference_path, model, unit_extractor, voicebox, vocoder, 
                              repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                              min_p=min_p, logit_bias=logit_bias, no_repeat_ngram_size=no_repeat_ngram_size,
                              num_speculative_tokens=num_speculative_tokens, prompt_lookup_max=prompt_lookup_max,
-                             prompt_lookup_min=prompt_lookup_min)
+                             prompt_lookup_min=prompt_lookup_min, **(dict(speculative_sampling=True) if speculative_sampling else {}))
         if model.last_spec_stats is not None:
             st = model.last_spec_stats
             print(f"{name}: {st['steps']} speculative steps, {st['drafted']} drafts, {st['accepted']} accepted", file=sys.stderr)
@@ -247,15 +249,21 @@ def main(argv=None):
                              "or --kv_cache_dtype fp8.")
     parser.add_argument('--prompt_lookup_max', type=int, default=3, help="Longest n-gram the draft lookup matches (1 .. 16).")
     parser.add_argument('--prompt_lookup_min', type=int, default=1, help="Shortest n-gram the draft lookup matches.")
+    parser.add_argument('--speculative_sampling', action='store_true',
+                        help="With --num_speculative_tokens: verify the drafts on the sampled speculative step, whose picks are drawn with "
+                             "each position's own Philox counter (the ids of a fixed seed do not depend on the drafts).  Lifts the error "
+                             "with --min_p; the others stay.")
     args = parser.parse_args(argv)
     from .llm import check_edits, check_min_p, check_penalties
-    from .spec import check_spec_args, check_spec_call
+    from .spec import check_spec_args, check_spec_call, check_speculative_sampling
     try:
-        if check_spec_args(args.num_speculative_tokens, args.prompt_lookup_max, args.prompt_lookup_min) is not None:
+        spec = check_spec_args(args.num_speculative_tokens, args.prompt_lookup_max, args.prompt_lookup_min)
+        check_speculative_sampling(args.speculative_sampling, spec is not None)
+        if spec is not None:
             try:
                 check_spec_call(False, args.logprobs, check_penalties(args.repetition_penalty, args.presence_penalty, args.frequency_penalty),
                                 check_edits(parse_logit_bias(args.logit_bias), args.no_repeat_ngram_size), args.min_p, None, args.num_beams,
-                                False, args.kv_cache_dtype == "fp8")
+                                False, args.kv_cache_dtype == "fp8", speculative_sampling=args.speculative_sampling)
             except NotImplementedError as e:
                 raise ValueError(str(e)) from None
         check_num_beams(args)
@@ -275,7 +283,7 @@ def main(argv=None):
                repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty,
                min_p=args.min_p, logit_bias=logit_bias, no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams,
                num_speculative_tokens=args.num_speculative_tokens, prompt_lookup_max=args.prompt_lookup_max,
-               prompt_lookup_min=args.prompt_lookup_min)
+               prompt_lookup_min=args.prompt_lookup_min, speculative_sampling=args.speculative_sampling)
     except Exception as e:       # the reference swallows sampling errors the same way (src/inference.py:131-134)
         print(f"Error while sampling: {e}")
         return 1

@@ -1147,14 +1147,17 @@ class USDMForCausalLM:
         return segs if (tp or beam is not None) else segs[0]
 
     # ------------------------------------------------------------------ speculative greedy decoding (the states: usdm_amd/slots.py)
-    def _build_spec_step(self, state, T):
+    def _build_spec_step(self, state, T, sampled=False):
         """One speculative step of a slots.SpecState: its n sequences x T rows each (row b * T + i: sequence b's token at position
         pos[b] + i - the token to continue from and T - 1 drafts) through _layers with the batched projections of _build_decode_batch
         over n * T rows (weights streamed once; <= 4 rows on the VALU form, bit-identical per row with the single step, 5 .. 16 on the
         matrix cores), the state's verify attention on its caches (SpecSequence: usdm_attn_verify, every cached row read once for all
         rows; SpecSlots: usdm_attn_verify_batch), the lm_head in batched arg-max mode, the state's commit (usdm_spec_commit /
         usdm_spec_commit_batch).  Sequences with done != 0 are skipped by the attention and the commit.  One plan, one graph per
-        state and T."""
+        state, T and sampled.
+        sampled: the lm_head also materialises the rows' f32 logits (y32, as the sampled batched step and beam search
+        do), usdm_spec_sample draws row i of sequence b with b's knobs at the counter step[b] + i - the token the plain sampled call
+        draws at that position from that row - and the commit takes those picks in place of the arg-max."""
         dev, bf = self.device, torch.bfloat16
         H, d, L, Hq, Hkv, I, nq = self._dims()
         n = state.n * T
@@ -1173,6 +1176,12 @@ class USDMForCausalLM:
                        window=self.window, plan=rec.plan)
 
         self._layers(rec, gemv, attn, h, qkv, ao, act, "fused", n=n * H, down_kw=dict(ks=ks))
+        if sampled:
+            gemv(self.W["lm_head"], h, N=self.v1 - self.v0, K=H, norm_w=self.W["norm"], eps=self.cfg["rms_norm_eps"], ban=self.ban,
+                 y32=state.sample_rows(T)["logits"], part_val=r["pv"], part_idx=r["pi"], idx_offset=self.v0, part_bs=self.nparts, y_bs=self.Vloc)
+            state.sample(T, rec.plan)
+            state.commit(T, rec.plan, sampled=True)
+            return rec.finish()[0]
         gemv(self.W["lm_head"], h, N=self.v1 - self.v0, K=H, norm_w=self.W["norm"], eps=self.cfg["rms_norm_eps"], ban=self.ban,
              part_val=r["pv"], part_idx=r["pi"], idx_offset=self.v0, part_bs=self.nparts, y_bs=0)
         state.commit(T, rec.plan)
@@ -1196,17 +1205,19 @@ class USDMForCausalLM:
         """Sequences per speculative step with k drafts each: the rows of a step shared out in slots of k + 1"""
         return self.max_batch() // (k + 1)
 
-    def _generate_spec_group(self, ids_list, limits, spec, scripts, bad_words_ids, eos_token_id, min_new_tokens):
+    def _generate_spec_group(self, ids_list, limits, spec, scripts, bad_words_ids, eos_token_id, min_new_tokens, samplings=None):
         """A group of 2 .. max_batch() // (k + 1) sequences on the speculative slots: per-slot prefill, then the step of B x (k + 1)
-        rows replayed in chunks (SpecSlots.serve).  -> (the sequences, their dict(steps=, drafted=, accepted=))"""
+        rows replayed in chunks (SpecSlots.serve).  samplings (a list: per sequence the slot's knobs or None = greedy): the sampled
+        step.  -> (the sequences, their dict(steps=, drafted=, accepted=))"""
         k, lookup_max, lookup_min = spec
         ss = self.spec_slots(len(ids_list))
         self.load_ban(bad_words_ids)
         ss.set_lookup(lookup_max, lookup_min, scripts is not None)
         stops = stop_ids(eos_token_id)
-        reqs = [dict(ids=ids[0], limit=lim, stops=stops, min_new=min_new_tokens, script=None if scripts is None else scripts[b])
+        reqs = [dict(ids=ids[0], limit=lim, stops=stops, min_new=min_new_tokens, script=None if scripts is None else scripts[b],
+                     sampling=None if samplings is None else samplings[b])
                 for b, (ids, lim) in enumerate(zip(ids_list, limits))]
-        res, _ = ss.serve(reqs, k + 1)
+        res, _ = ss.serve(reqs, k + 1, sampled=samplings is not None)
         outs = [torch.cat([ids[0], torch.tensor(toks, dtype=torch.long, device=ids.device)]).unsqueeze(0) for ids, (toks, _) in zip(ids_list, res)]
         return outs, [st for _, st in res]
 
@@ -1234,7 +1245,8 @@ class USDMForCausalLM:
     @torch.no_grad()
     def generate_batch(self, input_ids_list, max_new_tokens, bad_words_ids=None, eos_token_id=None, min_new_tokens=0, group=None,
                        logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, logit_bias=None,
-                       no_repeat_ngram_size=0, num_speculative_tokens=None, prompt_lookup_max=3, prompt_lookup_min=1, _spec_script=None):
+                       no_repeat_ngram_size=0, num_speculative_tokens=None, prompt_lookup_max=3, prompt_lookup_min=1, _spec_script=None,
+                       speculative_sampling=False, do_sample=False, temperature=1.0, top_k=None, top_p=1.0, seed=None):
         """Greedy generation of several utterances in lockstep (the serving-side batching of inference_vllm.py:109-125): up to
         `group` (default 16) sequences per step, longer lists run in groups.  Each prompt is prefilled on its own; every decode
         step then streams the weights once for the whole group.  Groups of <= 4 run on the VALU kernel and equal generate() per
@@ -1257,9 +1269,16 @@ class USDMForCausalLM:
         they equal generate(num_speculative_tokens=k) bit for bit, above they are equal up to near-ties (the matrix cores).
         max_new_tokens may then be a list with one value per sequence.  self.last_spec_stats = [dict(steps=, drafted=, accepted=)] per
         sequence.  _spec_script (tests, tools/spec_batch_rate.py): one script per sequence.  Refused as in generate()
-        (spec.check_spec_call), and (NotImplementedError) groups of two or more on a model built with enable_prefix_caching=True."""
-        from .spec import check_spec_args, check_spec_call
+        (spec.check_spec_call), and (NotImplementedError) groups of two or more on a model built with enable_prefix_caching=True.
+        speculative_sampling=True (with num_speculative_tokens=k; DESIGN.md 8k-3, see generate()): the groups run the SAMPLED
+        speculative step, every slot with its own knobs and seed - do_sample, temperature, top_k, top_p, seed and min_p are then one
+        value for all sequences or a list with one per sequence (seed None: drawn as generate() draws it).  A sequence with do_sample
+        False or top_k == 1 is greedy inside the step (top_k = 1).  For a fixed seed a sequence's ids depend neither on the drafts nor
+        on its neighbours; at B * (k + 1) <= 4 rows they equal generate(..., speculative_sampling=True) of that sequence bit for bit.
+        Without the flag the sampling arguments are refused (ValueError): these picks are greedy."""
+        from .spec import check_spec_args, check_spec_call, check_speculative_sampling
         spec = check_spec_args(num_speculative_tokens, prompt_lookup_max, prompt_lookup_min)
+        spec_sampled = check_speculative_sampling(speculative_sampling, spec is not None)
         lpk = check_logprobs(logprobs)
         n = len(input_ids_list)
         pens = [check_penalties(*k) for k in zip(*(_per_sequence(k, n) for k in (repetition_penalty, presence_penalty, frequency_penalty)))]
@@ -1267,10 +1286,17 @@ class USDMForCausalLM:
             check_min_p(v)
         V = self.cfg["vocab_size"]
         edits = [check_edits(lb, ng, V) for lb, ng in zip(_per_sequence(logit_bias, n), _per_sequence(no_repeat_ngram_size, n))]
+        knobs = [_per_sequence(v, n) for v in (do_sample, temperature, top_k, top_p, seed)]
+        if not spec_sampled and (any(knobs[0]) or any(t != 1.0 for t in knobs[1]) or any(k is not None for k in knobs[2])
+                                 or any(p != 1.0 for p in knobs[3]) or any(s is not None for s in knobs[4])):
+            raise ValueError("generate_batch picks greedily: do_sample / temperature / top_k / top_p / seed need num_speculative_tokens "
+                             "with speculative_sampling=True")
         if spec is not None:
             check_spec_call(False, lpk, next((p for p in pens if p is not None), None), next((e for e in edits if e is not None), None),
-                            any(_per_sequence(min_p, n)), tensor_parallel=self.tp_path, kv_cache_fp8=self.kv8)
-            return self._generate_batch_spec(input_ids_list, max_new_tokens, spec, _spec_script, bad_words_ids, eos_token_id, min_new_tokens, group)
+                            any(_per_sequence(min_p, n)), tensor_parallel=self.tp_path, kv_cache_fp8=self.kv8, speculative_sampling=spec_sampled)
+            samplings = [self._slot_sampling(*k) for k in zip(*knobs, _per_sequence(min_p, n))] if spec_sampled else None
+            return self._generate_batch_spec(input_ids_list, max_new_tokens, spec, _spec_script, bad_words_ids, eos_token_id, min_new_tokens, group,
+                                             samplings)
         group = self.max_batch() if group is None else max(1, min(int(group), self.max_batch()))
         outs, self.last_logprobs = [], (None if lpk is None else [])
         for g0 in range(0, n, group):
@@ -1278,8 +1304,27 @@ class USDMForCausalLM:
                                          pens[g0:g0 + group], edits[g0:g0 + group])
         return outs
 
-    def _generate_batch_spec(self, ids_list, max_new_tokens, spec, scripts, bad_words_ids, eos_token_id, min_new_tokens, group=None):
-        """generate_batch(num_speculative_tokens=k): the groups of spec_group(k) sequences; a group of one is generate()'s call"""
+    def _slot_sampling(self, do_sample, temperature, top_k, top_p, seed, min_p):
+        """One sequence's knobs of a sampled speculative group -> (temperature, top_k, top_p, seed, min_p) for its slot's sampler
+        block, or None where it is greedy (do_sample False or top_k == 1), checked and seeded as generate() does it"""
+        if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0):
+            raise ValueError(f"top_k must be None or an integer >= 0 (0 = off), got {top_k!r}")
+        if not do_sample:
+            if temperature != 1.0 or top_p != 1.0:
+                raise ValueError("temperature / top_p only apply with do_sample=True")
+            return None
+        if top_k == 1:
+            return None
+        if not (temperature > 0) or not (0 < top_p <= 1):
+            raise ValueError("temperature must be > 0 and top_p in (0, 1]")
+        if seed is None:
+            seed = self._agree_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
+        return (temperature, int(top_k or 0), top_p, seed, min_p)
+
+    def _generate_batch_spec(self, ids_list, max_new_tokens, spec, scripts, bad_words_ids, eos_token_id, min_new_tokens, group=None,
+                             samplings=None):
+        """generate_batch(num_speculative_tokens=k): the groups of spec_group(k) sequences; a group of one is generate()'s call.
+        samplings (speculative_sampling=True): per sequence _slot_sampling's value; the groups then run the sampled step."""
         k, lookup_max, lookup_min = spec
         n = len(ids_list)
         self._check_spec_shape(k)
@@ -1300,12 +1345,17 @@ class USDMForCausalLM:
                 outs += [ids.clone() for ids in grp]
                 stats += [dict(steps=0, drafted=0, accepted=0) for _ in grp]
             elif len(grp) == 1:
+                one = {} if samplings is None else dict(speculative_sampling=True)
+                if samplings is not None and samplings[g0] is not None:
+                    t, tk, tp_, sd, mp = samplings[g0]
+                    one.update(do_sample=True, temperature=t, top_k=tk or None, top_p=tp_, seed=sd, min_p=mp)
                 outs.append(self.generate(grp[0], max_new_tokens=limits[0], bad_words_ids=bad_words_ids, eos_token_id=eos_token_id,
                                           min_new_tokens=min_new_tokens, num_speculative_tokens=k, prompt_lookup_max=lookup_max,
-                                          prompt_lookup_min=lookup_min, _spec_script=None if sc is None else sc[0]))
+                                          prompt_lookup_min=lookup_min, _spec_script=None if sc is None else sc[0], **one))
                 stats.append(self.last_spec_stats)
             else:
-                res, st = self._generate_spec_group(grp, limits, spec, sc, bad_words_ids, eos_token_id, min_new_tokens)
+                res, st = self._generate_spec_group(grp, limits, spec, sc, bad_words_ids, eos_token_id, min_new_tokens,
+                                                    None if samplings is None else samplings[g0:g0 + size])
                 outs, stats = outs + res, stats + st
         self.last_spec_stats = stats
         return outs
@@ -1439,11 +1489,13 @@ class USDMForCausalLM:
         gen = torch.tensor(seqs, dtype=torch.long, device=input_ids.device).view(n, -1)
         return torch.cat([input_ids[0].expand(n, -1), gen], 1)
 
-    def _generate_spec(self, input_ids, ids_host, max_new, spec, script, dev_eos, eos, min_new):
+    def _generate_spec(self, input_ids, ids_host, max_new, spec, script, dev_eos, eos, min_new, sampled=False, on_step=None):
         """The decode loop of generate(num_speculative_tokens=k) behind the prefill: the captured step is replayed in chunks and the
         host reads step / done after each, since a replay emits 1 .. k + 1 tokens.  A chunk never holds more replays than the
         remaining tokens could need at k + 1 per step, so no replay runs past the limit by the host's doing; replays past a
-        device-side stop change nothing."""
+        device-side stop change nothing.  sampled: the step whose picks are drawn.  on_step (tests; sampled only):
+        every chunk is ONE replay and on_step(dict(step=, drafts=, rows=, picks=)) gets host copies of the step word and the drafts
+        the replay started from and of the T logits rows and picks it left."""
         k, lookup_max, lookup_min = spec
         T = k + 1
         if self._spec is None:
@@ -1452,7 +1504,15 @@ class USDMForCausalLM:
         sp.seed(0, input_ids[0], max_new, script)
         sp.set_lookup(lookup_max, lookup_min, script is not None)
         sp.propose(T, 0)
-        step = sp.spec_step(T)
+        step = sp.spec_step(T, sampled)
+        if on_step is not None and not sampled:
+            raise ValueError("_spec_on_step records logits rows, which only the sampled speculative step materialises")
+
+        def recorded():      # one replay, its inputs and rows copied out
+            rows = sp.sample_rows(T)
+            before = dict(step=int(self.st_step.item()), drafts=sp.drafts[0, :T].tolist())
+            step.run()
+            on_step(dict(before, rows=rows["logits"].cpu().clone(), picks=rows["picks"].tolist()))
         while True:
             produced = min(int(self.st_step.item()), max_new)      # host sync point
             toks = self.st_out[:produced].tolist()
@@ -1462,6 +1522,9 @@ class USDMForCausalLM:
                 break
             if produced >= max_new or int(self.st_done.item()):
                 break
+            if on_step is not None:
+                recorded()
+                continue
             for _ in range(max(1, min(CHUNK, -(-(max_new - produced) // T)))):
                 step.run()
         if self.reuse_prefix:   # committed rows only: the prompt and every emitted token that was fed back and accepted
@@ -1540,7 +1603,7 @@ class USDMForCausalLM:
                  _logits_hook=None, logprobs=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0,
                  logit_bias=None, no_repeat_ngram_size=0, num_beams=None, num_return_sequences=None, length_penalty=1.0,
                  early_stopping=False, pad_token_id=None, _beam_keep_rows=False, _beam_on_step=None, num_speculative_tokens=None,
-                 prompt_lookup_max=3, prompt_lookup_min=1, _spec_script=None, **unused):
+                 prompt_lookup_max=3, prompt_lookup_min=1, _spec_script=None, speculative_sampling=False, _spec_on_step=None, **unused):
         """Generation with the call shape of src/inference.py:63-83.  Greedy when do_sample is False or top_k == 1 (what the
         reference passes: arg-max of the ban-masked logits).  Otherwise temperature / top-k / top-p sampling on the device
         (usdm_sample_final).  `seed` keys its Philox stream; seed=None draws a fresh one from torch's global CPU generator,
@@ -1579,9 +1642,17 @@ class USDMForCausalLM:
         _spec_script (tests, tools/spec_rate.py): an int sequence / tensor whose entry j replaces the lookup as the draft for output j.
         Not combined with (NotImplementedError): sampling with top_k != 1, logprobs, the penalties, logit_bias / no_repeat_ngram_size,
         min_p, _logits_hook, num_beams > 1, tensor parallelism, kv_cache_dtype="fp8".  Cache rows behind the committed position are
-        dead; prefix reuse after the call counts committed rows only."""
-        from .spec import check_spec_args, check_spec_call
+        dead; prefix reuse after the call counts committed rows only.
+        speculative_sampling=True (with num_speculative_tokens=k; default False: everything above holds as it stands): speculation for
+        SAMPLED calls.  The step materialises its k + 1 logits rows, usdm_spec_sample draws row i with the call's
+        knobs and seed at the Philox counter of ITS position - the token the plain sampled call draws there - and a draft is accepted
+        iff it equals that draw.  The output distribution is the plain sampled call's, and for a fixed seed the ids do not depend on
+        the drafts.  do_sample with top_k != 1 and min_p are then allowed; a greedy call runs on the same step with top_k = 1 (the ids
+        of the greedy speculative call).  Still refused: logprobs, the penalties, logit_bias / no_repeat_ngram_size, _logits_hook,
+        num_beams > 1, tensor parallelism, kv_cache_dtype="fp8".  _spec_on_step (tests): see _generate_spec."""
+        from .spec import check_spec_args, check_spec_call, check_speculative_sampling
         spec = check_spec_args(num_speculative_tokens, prompt_lookup_max, prompt_lookup_min)
+        spec_sampled = check_speculative_sampling(speculative_sampling, spec is not None)
         lpk = check_logprobs(logprobs)
         pen = check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         min_p = check_min_p(min_p)
@@ -1590,7 +1661,8 @@ class USDMForCausalLM:
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("input_ids must be a LongTensor of shape [1, L] (batch 1, as the reference calls it)")
         if spec is not None:
-            check_spec_call(bool(do_sample) and top_k != 1, lpk, pen, edt, min_p, _logits_hook, num_beams, self.tp_path, self.kv8)
+            check_spec_call(bool(do_sample) and top_k != 1, lpk, pen, edt, min_p, _logits_hook, num_beams, self.tp_path, self.kv8,
+                            speculative_sampling=spec_sampled)
             self._check_spec_shape(spec[0])
         if num_beams is not None and num_beams != 1:
             from .beam import check_beam_args, check_beam_call
@@ -1627,7 +1699,7 @@ class USDMForCausalLM:
         else:
             if (temperature != 1.0 or top_p != 1.0) and not do_sample:
                 raise ValueError("temperature / top_p only apply with do_sample=True")
-        kind = step_kind(sampling, lpk, pen is not None, edt is not None)
+        kind = step_kind(sampling or spec_sampled, lpk, pen is not None, edt is not None)      # (sampled speculation: the prefill's pick is the sampler's)
         if kind.sampling and not sampling:      # greedy on the sampling step: top_k = 1
             ops.set_sample_params(self.sample_params, 1.0, 1, 1.0, 0)
         max_new_tokens = self._max_new(input_ids.shape[1], max_new_tokens, max_length)
@@ -1638,7 +1710,8 @@ class USDMForCausalLM:
                                           logprobs=lpk, penalties=pen, edits=edt)
         self._run_segs(segs)  # prefill + first token
         if spec is not None:
-            return self._generate_spec(input_ids, ids_host, max_new_tokens, spec, _spec_script, dev_eos, stop_ids(eos_token_id), min_new_tokens)
+            return self._generate_spec(input_ids, ids_host, max_new_tokens, spec, _spec_script, dev_eos, stop_ids(eos_token_id), min_new_tokens,
+                                       sampled=spec_sampled, on_step=_spec_on_step)
         if kind not in self._decodes:      # a plan / graph of its own per kind (the hooked step has host code inside: never captured)
             self._decodes[kind] = self._graphed(self._build_decode(*kind), enabled=False if kind.sampling == "hook" else None)
         self._decode = self._decodes[kind]

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (BF16, F32, AttnVerifyArgs, AttnVerifyBatchArgs, SpecArgs, SpecBatchArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, GemvMxfp4MfmaArgs, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
+from ._lib import (BF16, F32, AttnVerifyArgs, AttnVerifyBatchArgs, SpecArgs, SpecBatchArgs, SpecSampleArgs, BeamArgs, KvExpandArgs, KvReorderArgs, AttnArgs, AttnDecodeArgs, AttnDecodeFp8Args, RopeFp8Args, DecodeState, GemmArgs, GemvArgs, GemvBatchArgs, GemvFp8Args, GemvMxfp4Args, GemvMxfp4MfmaArgs, LogitEditArgs, LogprobArgs, NormArgs, PenaltyArgs, PromptLogprobArgs, RopeArgs, SampleArgs, SnakeArgs,
                    VbInputArgs, VbSolverArgs, check, lib)
 from .quant import Fp8Weight, Mxfp4Weight
 from .wpack import GemvWpack
@@ -904,24 +904,47 @@ def _spec_args(a, part_val, part_idx, nparts, T, drafts, limit, prompt, prompt_l
 
 
 def spec_commit(part_val, part_idx, nparts, st, *, T, drafts, limit, prompt, prompt_len, params, counters, V, script=None, embed, h_out, Hd,
-                propose_only=False, plan=None):
-    """usdm_spec_commit: pick, accept, commit, propose and embed at the end of a speculative step (propose_only: after the prefill)."""
-    _need_cuda(part_val, part_idx, drafts, limit, prompt, prompt_len, params, counters, script, embed, h_out)
+                propose_only=False, picks=None, plan=None):
+    """usdm_spec_commit: pick, accept, commit, propose and embed at the end of a speculative step (propose_only: after the prefill).
+    picks (int32 [T], local ids): usdm_spec_commit_picks - the rows' picks are given (usdm_spec_sample) and the partials not read."""
+    _need_cuda(part_val, part_idx, picks, drafts, limit, prompt, prompt_len, params, counters, script, embed, h_out)
     a = SpecArgs()
     _spec_args(a, part_val, part_idx, nparts, T, drafts, limit, prompt, prompt_len, prompt.numel(), params, counters, V, script, propose_only)
+    if picks is not None:
+        _go(plan, "usdm_spec_commit_picks", lib.usdm_spec_commit_picks, C_.byref(a), _ptr(picks), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
+        return
     _go(plan, "usdm_spec_commit", lib.usdm_spec_commit, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
 
 
 def spec_commit_batch(part_val, part_idx, nparts, st, *, T, drafts, limit, prompt, prompt_len, params, counters, V, script=None, embed, h_out, Hd,
-                      slot_lo=0, n=None, propose_only=False, plan=None):
+                      slot_lo=0, n=None, propose_only=False, picks=None, plan=None):
     """usdm_spec_commit_batch: usdm_spec_commit on the slots [slot_lo, slot_lo + n) (default: all) of the batched state st (st.batch = B
     slots): part_val / part_idx [B*T][nparts], drafts [B][8], limit / prompt_len [B], prompt [B][prompt_max], script [B][max_out] or
-    None, counters [B][3], params [4] shared, h_out [B*T][Hd]."""
-    _need_cuda(part_val, part_idx, drafts, limit, prompt, prompt_len, params, counters, script, embed, h_out)
+    None, counters [B][3], params [4] shared, h_out [B*T][Hd].  picks (int32 [B*T], local ids): usdm_spec_commit_batch_picks."""
+    _need_cuda(part_val, part_idx, picks, drafts, limit, prompt, prompt_len, params, counters, script, embed, h_out)
     a = SpecBatchArgs()
     _spec_args(a.s, part_val, part_idx, nparts, T, drafts, limit, prompt, prompt_len, prompt.shape[-1], params, counters, V, script, propose_only)
     a.slot_lo, a.n = slot_lo, st.batch - slot_lo if n is None else n
+    if picks is not None:
+        _go(plan, "usdm_spec_commit_batch_picks", lib.usdm_spec_commit_batch_picks, C_.byref(a), _ptr(picks), C_.byref(st), _ptr(embed), C_.c_int32(Hd),
+            _ptr(h_out))
+        return
     _go(plan, "usdm_spec_commit_batch", lib.usdm_spec_commit_batch, C_.byref(a), C_.byref(st), _ptr(embed), C_.c_int32(Hd), _ptr(h_out))
+
+
+def spec_sample(logits, picks, *, T, n, dev_params, step, drafts, done=None, V=None, plan=None):
+    """usdm_spec_sample: the draws of the n * T rows of a sampled speculative step.  logits f32 [n * T][>= V], dev_params [n][24]
+    (sample_params_tensor), step [n], done [n] or None, drafts [n][8], picks int32 [n * T]: picks[b * T + i] = the local id
+    usdm_sample_final commits for that row with slot b's knobs at step[b] + i; rows of a done slot or behind a -1 draft are skipped."""
+    _need_cuda(logits, picks, dev_params, step, drafts, done)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < n * T:
+        raise ValueError("spec_sample: logits must be float32 [n * T][>= V] with unit inner stride")
+    if picks.dtype != torch.int32 or picks.numel() < n * T or drafts.numel() < n * SPEC_MAX_T or step.numel() < n or (done is not None and done.numel() < n) or dev_params.numel() < n * C_.sizeof(_lib.SampleParams):
+        raise ValueError("spec_sample: picks [n * T] int32, drafts [n][8], step [n] and dev_params [n][24] are required")
+    a = SpecSampleArgs()
+    a.logits, a.logits_bs, a.V, a.T, a.n = _ptr(logits), logits.stride(0), logits.shape[-1] if V is None else V, T, n
+    a.dev_params, a.step, a.done, a.drafts, a.picks = _ptr(dev_params), _ptr(step), _ptr(done), _ptr(drafts), _ptr(picks)
+    _go(plan, "usdm_spec_sample", lib.usdm_spec_sample, C_.byref(a))
 
 
 def residual_add(h, delta, n, plan=None):

@@ -225,6 +225,8 @@ class LLM:
     """`LLM(model='naver-ai/USDM-DailyTalk', download_dir=cache)` as in inference_vllm.py:105 (hub names resolve inside
     download_dir), or `LLM(model=<USDMForCausalLM>, tokenizer=<tokenizer>)` around objects that are already loaded."""
 
+    spec_sampling = False      # speculative_config's "speculative_sampling" (DESIGN.md 8k-3); off unless __init__ reads it from the config
+
     def __init__(self, model, tokenizer=None, download_dir=None, gpu_memory_utilization=0.9, max_model_len=None, device="cuda",
                  dtype="bfloat16", max_num_seqs=MAX_SLOTS, quantization=None, fp8_matrix_cores=False, kv_cache_dtype=None,
                  enable_prefix_caching=False, speculative_config=None, mxfp4_matrix_cores=False, **unused):
@@ -280,9 +282,11 @@ class LLM:
         # speculative_config (vLLM's name and shape): {"method": "ngram", "num_speculative_tokens": k, "prompt_lookup_max": ..,
         # "prompt_lookup_min": ..} - greedy requests with a static mask run on the speculative step: two or more of a group share the
         # speculative slots (slots.SpecSlots), one that is alone runs generate(num_speculative_tokens=k);
-        # everything else runs as without the option
-        from .spec import check_spec_call, check_speculative_config
+        # everything else runs as without the option.  "speculative_sampling": True makes sampled requests, min_p
+        # included, eligible too: a group with one of them runs the sampled speculative step (its greedy members with top_k = 1)
+        from .spec import check_spec_call, check_speculative_config, config_speculative_sampling
         self.spec = check_speculative_config(speculative_config)
+        self.spec_sampling = config_speculative_sampling(speculative_config)
         if self.spec is not None:
             check_spec_call(tensor_parallel=self.llm.tp_path, kv_cache_fp8=self.llm.kv8)
             if self.spec[0] + 1 > self.llm.max_batch():
@@ -291,6 +295,8 @@ class LLM:
             # slots (counted in batched_requests too), spec_max_active: the most of them decoding in one step;
             # spec_steps / spec_drafted / spec_accepted: per-sequence steps, drafts fed and drafts accepted of both
             self.stats.update(spec_requests=0, spec_steps=0, spec_drafted=0, spec_accepted=0, spec_batched_requests=0, spec_max_active=0)
+            if self.spec_sampling:      # sampled requests served on a speculative step, alone or through the slots
+                self.stats.update(spec_sampled_requests=0)
         self._next_id = 0
 
     def get_tokenizer(self):
@@ -462,8 +468,11 @@ class LLM:
         sampled = not sp.greedy
         if sampled:
             kw.update(do_sample=True, temperature=sp.temperature, top_p=sp.top_p, top_k=(sp.top_k if sp.top_k > 0 else None), seed=r["seed"])
-        if self._spec_eligible(r):        # a plain greedy request served alone: the speculative step
+        if self._spec_eligible(r):        # a plain greedy request served alone: the speculative step (sampled, with the flag: its sampled variant)
             k, lmax, lmin = self.spec
+            if sampled or (self.spec_sampling and sp.min_p):      # (a greedy request with min_p: eligible with the flag only, top_k = 1)
+                kw.update(speculative_sampling=True)
+                self.stats["spec_sampled_requests"] += int(sampled)
             out = llm.generate(ban_mask=r["mask"], num_speculative_tokens=k, prompt_lookup_max=lmax, prompt_lookup_min=lmin, **kw)
             st = llm.last_spec_stats
             self.stats["spec_requests"] += 1
@@ -492,10 +501,11 @@ class LLM:
 
     # ------------------------------------------------------------------ speculative decoding: who, and the slots
     def _spec_eligible(self, r):
-        """speculative_config is on and the request is plain greedy with a static mask: no logprobs, min_p, penalties or edits"""
+        """speculative_config is on and the request is plain greedy with a static mask: no logprobs, min_p, penalties or edits.  With
+        speculative_sampling in the config a sampled request, with or without min_p, is eligible too."""
         sp = r["sp"]
-        return (self.spec is not None and r["mask"] is not None and sp.greedy and sp.logprobs is None and not sp.min_p
-                and sp.penalties is None and sp.edits is None)
+        return (self.spec is not None and r["mask"] is not None and ((sp.greedy and not sp.min_p) or self.spec_sampling)
+                and sp.logprobs is None and sp.penalties is None and sp.edits is None)
 
     def _spec_slot_count(self):
         """Slots of the batched speculative step: the rows of a step shared out in slots of k + 1, at most max_num_seqs; 0 = off (no
@@ -519,9 +529,14 @@ class LLM:
         ss = llm.spec_slots(self._spec_slot_count())
         llm.load_ban(ban_mask=grp[0]["mask"])
         ss.set_lookup(lmax, lmin, False)
-        reqs = [dict(ids=torch.tensor(r["ids"], dtype=torch.long), limit=r["max_new"], stops=r["stops"], min_new=r["sp"].min_tokens) for r in grp]
-        res, max_active = ss.serve(reqs, k + 1)
+        knobs = lambda r: None if r["sp"].greedy else (r["sp"].temperature, max(r["sp"].top_k, 0), r["sp"].top_p, r["seed"], r["sp"].min_p)
+        reqs = [dict(ids=torch.tensor(r["ids"], dtype=torch.long), limit=r["max_new"], stops=r["stops"], min_new=r["sp"].min_tokens,
+                     sampling=knobs(r)) for r in grp]
+        n_sampled = sum(q["sampling"] is not None for q in reqs)      # one sampled request -> the whole group runs the sampled step
+        res, max_active = ss.serve(reqs, k + 1, sampled=n_sampled > 0)
         st = self.stats
+        if n_sampled:
+            st["spec_sampled_requests"] += n_sampled
         st["batched_requests"] += len(grp)
         st["spec_batched_requests"] += len(grp)
         st["spec_max_active"] = max(st["spec_max_active"], max_active)

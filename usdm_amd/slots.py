@@ -287,7 +287,10 @@ class SpecState:
     T = k + 1 the n * T rows the step runs on (h, the arg-max partials), the captured step (model._build_spec_step) and the
     one-sequence propose_only launches.  A holder adds where its sequences live, as the step's two launches that differ:
     attn(l, qkv, pm, pl, po, ao, **shape), the verify attention of layer l on its caches, and commit(T, plan, b, propose_only), the
-    commit over all its sequences (b = None) or sequence b alone, on its decode state."""
+    commit over all its sequences (b = None) or sequence b alone, on its decode state.
+    Sampled requests: per T also the rows' f32 logits and their picks (sample_rows), a second captured step under
+    (T, "sampled"), and from the holder sample_block(), its sequences' usdm_sample_params [n][24], and step_words(), their step and
+    done words, which usdm_spec_sample reads."""
 
     def __init__(self, model, n=1):
         i32 = lambda *s, v=0: torch.full(s, v, dtype=torch.int32, device=model.device)
@@ -305,18 +308,38 @@ class SpecState:
                                 pi=torch.full((rows, m.nparts), NO_CANDIDATE_IDX, dtype=torch.int32, device=m.device))
         return self.rows[T]
 
-    def commit_words(self, T):
-        """What both commit launches take besides their decode state: the rows' partials and the words above"""
-        m, r = self.model, self.spec_rows(T)
+    def sample_rows(self, T):
+        """What the SAMPLED step with T rows per sequence adds (allocated at first use): the rows' f32 logits
+        [n*T][Vloc], which the lm_head materialises, and their picks [n*T], usdm_spec_sample's draws"""
+        r = self.spec_rows(T)
+        if "logits" not in r:
+            m, rows = self.model, self.n * T
+            r["logits"] = torch.zeros(rows, m.Vloc, dtype=torch.float32, device=m.device)
+            r["picks"] = torch.zeros(rows, dtype=torch.int32, device=m.device)
+        return r
+
+    def commit_words(self, T, sampled=False):
+        """What both commit launches take besides their decode state: the rows' partials (sampled: their picks too) and the words above"""
+        m, r = self.model, self.sample_rows(T) if sampled else self.spec_rows(T)
         return (r["pv"], r["pi"], m.nparts), dict(T=T, drafts=self.drafts, limit=self.limit, prompt=self.prompt, prompt_len=self.prompt_len,
                                                   params=self.params, counters=self.counters, V=m.cfg["vocab_size"], script=self.script,
-                                                  embed=m.W["embed"], h_out=r["h"], Hd=m.cfg["hidden_size"])
+                                                  embed=m.W["embed"], h_out=r["h"], Hd=m.cfg["hidden_size"],
+                                                  **(dict(picks=r["picks"]) if sampled else {}))
 
-    def spec_step(self, T):
-        """The replayable speculative step of the n sequences x T rows (built and captured at first use)"""
-        if T not in self.spec_steps:
-            self.spec_steps[T] = self.model._graphed(self.model._build_spec_step(self, T))
-        return self.spec_steps[T]
+    def sample(self, T, plan):
+        """usdm_spec_sample over the n * T logits rows of the sampled step: row b * T + i drawn with sequence b's knobs (the holder's
+        sample_block(): [n][24]) at the holder's step[b] + i, sequences that are done and rows behind a -1 draft skipped"""
+        r, (step, done) = self.sample_rows(T), self.step_words()
+        ops.spec_sample(r["logits"], r["picks"], T=T, n=self.n, dev_params=self.sample_block(), step=step, done=done, drafts=self.drafts,
+                        V=self.model.v1 - self.model.v0, plan=plan)
+
+    def spec_step(self, T, sampled=False):
+        """The replayable speculative step of the n sequences x T rows (built and captured at first use); sampled: the variant
+        whose picks are drawn (usdm_spec_sample), a graph of its own under the key (T, "sampled")"""
+        key = (T, "sampled") if sampled else T
+        if key not in self.spec_steps:
+            self.spec_steps[key] = self.model._graphed(self.model._build_spec_step(self, T, sampled))
+        return self.spec_steps[key]
 
     def set_lookup(self, lookup_max, lookup_min, use_script):
         self.params.copy_(torch.tensor([lookup_max, lookup_min, int(bool(use_script)), 0], dtype=torch.int32))
@@ -356,12 +379,20 @@ class SpecSequence(SpecState):
         m = self.model
         ops.attn_verify(qkv, m.st_pos, m.cos, m.sin, m.kcache[l], m.vcache[l], *bufs, skip=m.st_done, **kw)
 
-    def commit(self, T, plan, b=None, propose_only=False):
-        """usdm_spec_commit over the T rows: the end of the step, or (propose_only) the first drafts and the first T input rows"""
-        m, (parts, words) = self.model, self.commit_words(T)
+    def commit(self, T, plan, b=None, propose_only=False, sampled=False):
+        """usdm_spec_commit over the T rows: the end of the step, or (propose_only) the first drafts and the first T input rows;
+        sampled: usdm_spec_commit_picks on the rows' draws"""
+        m, (parts, words) = self.model, self.commit_words(T, sampled)
         st = ops.decode_state(m.st_next, m.st_out, m.st_step, m.st_pos, advance_pos=True, done=m.st_done, eos=m.st_eos)
         ops.spec_commit(*parts, st, **words, propose_only=propose_only, plan=plan)
         plan.hold(st)
+
+    def sample_block(self):
+        """The call's knobs and seed: the single sequence's sampler block, which generate() writes and the prefill's pick reads"""
+        return self.model.sample_params.view(1, -1)
+
+    def step_words(self):
+        return self.model.st_step, self.model.st_done
 
 
 class SpecSlots(DecodeSlots, SpecState):
@@ -386,21 +417,33 @@ class SpecSlots(DecodeSlots, SpecState):
         ops.attn_verify_batch(qkv, self.pos, m.cos, m.sin, self.kc[0, l], self.vc[0, l], *bufs, B=self.B, cache_bs=self.kc.stride(0),
                               skip=self.done, **kw)
 
-    def commit(self, T, plan, b=None, propose_only=False):
+    def sample_block(self):
+        """Per-slot knobs and seeds: the slots' sampler blocks, which admit() writes and a slot's prefill pick reads"""
+        return self.sp
+
+    def step_words(self):
+        return self.step, self.done
+
+    def commit(self, T, plan, b=None, propose_only=False, sampled=False):
         """usdm_spec_commit_batch over all slots or (b) slot b alone: the end of the step, or (propose_only) an admitted slot's first
-        drafts and input rows"""
-        parts, words = self.commit_words(T)
+        drafts and input rows; sampled: usdm_spec_commit_batch_picks on the rows' draws"""
+        parts, words = self.commit_words(T, sampled)
         st = ops.decode_state(self.nxt, self.out, self.step, self.pos, advance_pos=True, batch=self.B, done=self.done, eos=self.eos)
         st.max_out = self.model.max_out
         lo, n = (0, None) if b is None else (b, 1)
         ops.spec_commit_batch(*parts, st, **words, slot_lo=lo, n=n, propose_only=propose_only, plan=plan)
         plan.hold(st)
 
-    def admit_spec(self, b, ids, T, limit, stops=(), min_new=0, script=None):
+    def admit_spec(self, b, ids, T, limit, stops=(), min_new=0, script=None, sampled=False, sampling=None):
         """Admit a prompt (ids [L]) into slot b: DecodeSlots.admit's per-slot prefill, whose pick is committed as step 1, then the
         slot's stop block (the host checks every id anyway), its speculative words (seed), done = 0, and its first drafts and input
-        rows (propose)."""
-        self.admit(b, ids, self.kind)
+        rows (propose).  sampled (the slots run the sampled step): the prefill is the sampling kind's, so the first
+        token is usdm_sample_final's draw at counter 0 with the slot's knobs - sampling = (temperature, top_k, top_p, seed, min_p), or
+        None: a greedy request, which carries top_k = 1."""
+        if sampled:
+            self.admit(b, ids, self.kind._replace(sampling=True), sampling=sampling or GREEDY_KNOBS)
+        else:
+            self.admit(b, ids, self.kind)
         self.eos[b] = stop_block(stops, min_new)[0]
         self.seed(b, ids, limit, script)
         self.done[b] = 0
@@ -410,19 +453,20 @@ class SpecSlots(DecodeSlots, SpecState):
         """Slot b has no request: every launch of the step leaves it alone"""
         self.done[b] = 1
 
-    def serve(self, requests, T, stops_of=None):
+    def serve(self, requests, T, stops_of=None, sampled=False):
         """Run `requests` - dicts with ids [L] (a tensor), limit (tokens to emit, <= ctx_max - L and max_out), stops (a set), min_new
-        and optionally script - through the slots with turnover: a finished slot is refilled from the queue at the next scheduling
+        and optionally script and (sampled: the sampled step; a request without is greedy inside it) sampling = (temperature, top_k,
+        top_p, seed, min_p) - through the slots with turnover: a finished slot is refilled from the queue at the next scheduling
         point.  The captured step is replayed in chunks; the host reads step / done / out at each scheduling point and never
         runs more replays than the slot with the most tokens left needs at one token per step.  Replays past a slot's device-side
         stop change nothing of that slot.  -> ([(tokens, dict(steps=, drafted=, accepted=)) per request], most slots active at once)"""
-        step = self.spec_step(T)
+        step = self.spec_step(T, sampled)
         queue, slots, results, max_active = deque(enumerate(requests)), [None] * self.B, [None] * len(requests), 0
         while queue or any(s is not None for s in slots):
             for b in range(self.B):
                 if slots[b] is None and queue:
                     i, r = queue.popleft()
-                    self.admit_spec(b, r["ids"], T, r["limit"], r["stops"], r["min_new"], r.get("script"))
+                    self.admit_spec(b, r["ids"], T, r["limit"], r["stops"], r["min_new"], r.get("script"), sampled, r.get("sampling"))
                     slots[b] = (i, r)
             active = [b for b in range(self.B) if slots[b] is not None]
             max_active = max(max_active, len(active))
